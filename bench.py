@@ -11,6 +11,10 @@ Prints ONE JSON line (rank 0).
 
 `value` / `ms_per_step` / `dtype` are the STRICT fp32 policy: every conv -- forward, data gradient, weight gradient --
 on PSEG_PREC_FP32 (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulate), the reference's own arithmetic.
+A plain run does only that: set-up, W warm-up steps, the K timed steps, the outputs (--dump-outputs DIR) and the line.
+--dump-outputs DIR writes what the last timed step handed its caller, as float32 / float64 .npy files (see dump_outputs).
+Everything below is measured only with --full (without it `other_policies`, `other_configs`, `roofline` and
+`cpu_baseline` are null and the N>1 line has no `multi_gpu`):
 `other_policies` carries the same K timed steps, measured in the same process right after, under the opt-in policies:
 `half` (= train.py -mp: fp16 storage, one fp16 MFMA pass, fp32 master weights, dynamic loss scaling -- with its own
 roofline objects: the dominant conv class against the 2.5 PF dense fp16 peak and the BatchNorm passes against HBM), and
@@ -63,6 +67,11 @@ def parse():
     ap.add_argument('--batch', type=int, default=16, help='images per GPU (BASELINE.json configs[2]: 16)')
     ap.add_argument('--size', type=int, default=512)
     ap.add_argument('--classes', type=int, default=21)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure the other policies (--also), the other configurations (--configs), '
+                         'the roofline step, the CPU baseline and (N>1) the collectives-skipped re-timing')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='write what the last timed step computed to DIR/<name>.npy (see dump_outputs)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--cpu-batch', type=int, default=2)
@@ -71,10 +80,10 @@ def parse():
     ap.add_argument('--configs', default='hrnet,unet',
                     help='N=1: after the headline, time the other single-GPU BASELINE.json configurations (configs[4] HRNet 512x512 '
                          'B=8, configs[1] UNet 256x256 B=8; fp32 and -mp) with a default-constructed Trainer -> "other_configs".  '
-                         'Skipped when --also is empty (profiling runs) or this is ""')
+                         'Only with --full; skipped when --also is empty (profiling runs) or this is ""')
     ap.add_argument('--only-config', default='', help=argparse.SUPPRESS)     # (child process of --configs: one configuration, JSON out)
     ap.add_argument('--also', default='half,mixed,limb',
-                    help='comma-separated policies measured after the headline in the same process (N=1 only; "" = none)')
+                    help='comma-separated policies measured after the headline in the same process (--full, N=1 only; "" = none)')
     return ap.parse_args()
 
 
@@ -332,6 +341,31 @@ def timed_config(name, steps, device):
     return res
 
 
+DUMP_SAMPLE = 4 << 20       # elements kept of each flat arena: 16 MB in float32
+
+
+def dump_outputs(out_dir, trainer, loss):
+    """What the last timed step handed its caller, for comparing two builds output for output: the loss it returned
+    (loss.npy, float64), the parameters after its SGD update and the gradients it computed (params.npy / grads.npy: the flat
+    fp32 arenas, or a fixed seeded sample of DUMP_SAMPLE sorted indices when larger), and the BatchNorm running statistics
+    (bn_stats.npy: every floating-point buffer of the model, flattened, in module order).  Under 64 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(flat):
+        if flat.numel() <= DUMP_SAMPLE:
+            return flat
+        g = torch.Generator(device='cpu').manual_seed(0)
+        idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+        return flat[idx.to(flat.device)]
+
+    arrays = {'loss': loss.detach().double().reshape(1),
+              'params': sample(trainer.arena.params.detach()),
+              'grads': sample(trainer.arena.grads.detach()),
+              'bn_stats': torch.cat([b.detach().float().reshape(-1) for b in trainer.model.buffers() if b.is_floating_point()])}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a.cpu().numpy())
+
 
 def main():
     args = parse()
@@ -387,6 +421,8 @@ def main():
         dt = tt.item()
     loss_val = loss.item()
     headline_mode = trainer.step_mode()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, loss)
 
     def timed_policy(name):
         """K timed steps under another conv policy, same process, same model / batch (N=1 only)."""
@@ -404,7 +440,7 @@ def main():
         return {'value': args.batch * args.steps / d, 'unit': 'images/sec', 'ms_per_step': d / args.steps * 1e3,
                 'steps': args.steps, 'dtype': DTYPES[name], 'loss': ls.item(), 'step_mode': mode}
 
-    # ---- N > 1: make the run explain itself.  Nobody can rehearse the 8-GPU case (the builder's boxes have one GPU and RCCL
+    # ---- N > 1, --full: make the run explain itself.  Nobody can rehearse the 8-GPU case (the test machines have one GPU and RCCL
     # refuses two ranks on one device), so the line records who took part and what the exchange cost:
     #   ranks_seen / distinct_devices / devices -- every rank's device name, PCI address and uuid, all-gathered
     #   exchange        -- bucket count / sizes, all-reduce vs reduce-scatter + all-gather (PSEG_EXCHANGE), native RCCL binding
@@ -413,7 +449,7 @@ def main():
     #                      side stream and joins still run; gradients stay local): step - step_nocomm is the part of the
     #                      exchange that backward did not hide
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         props = torch.cuda.get_device_properties(device)
         mine = {'rank': rank, 'local_rank': local_rank, 'name': props.name,
                 'pci': '%04x:%02x:%02x' % (getattr(props, 'pci_domain_id', 0), getattr(props, 'pci_bus_id', 0),
@@ -451,11 +487,11 @@ def main():
                          'IS the first N>1 execution over RCCL'}
 
     others = None
-    if world == 1 and rank == 0 and args.also:
+    if args.full and world == 1 and rank == 0 and args.also:
         others = {n: timed_policy(n) for n in args.also.split(',') if n and n != args.precision}
 
     other_configs = None
-    if world == 1 and rank == 0 and args.also and args.configs:
+    if args.full and world == 1 and rank == 0 and args.also and args.configs:
         # each in a process of its own: the Trainer of a replayed configuration lays out its streams (and with them the
         # hardware queues its lanes land on) as `python train.py` would, not behind the streams this process already has
         import subprocess
@@ -545,7 +581,8 @@ def main():
         return roof, hbm
 
     roof = roof_hbm = None
-    if not args.no_roofline and rank != 0:
+    roofline = args.full and not args.no_roofline
+    if roofline and rank != 0:
         # the metered extra steps are full training steps with their gradient all-reduce: every rank takes part
         overlap, ops.OVERLAP_WGRAD = ops.OVERLAP_WGRAD, False
         graph_mode, trainer.graph = trainer.graph, False
@@ -553,7 +590,7 @@ def main():
         trainer.train_batch(x, t)
         ops.OVERLAP_WGRAD = overlap
         trainer.graph = graph_mode
-    if not args.no_roofline and rank == 0:
+    if roofline and rank == 0:
         roof, roof_hbm = measure_roofline(args.precision)
         if roof_hbm is not None:
             roof['batchnorm_passes'] = roof_hbm
@@ -575,7 +612,7 @@ def main():
         barrier()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     if rank == 0:

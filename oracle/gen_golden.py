@@ -38,6 +38,7 @@ sys.path.insert(0, REPO)
 
 from oracle import blocks as oblocks  # noqa: E402
 from oracle import fill  # noqa: E402
+from oracle import golden  # noqa: E402
 from oracle import margins  # noqa: E402
 
 OUT = os.path.join(REPO, 'tests', 'golden')
@@ -150,7 +151,7 @@ def gen_aspp_small():
     m.eval()
     with torch.no_grad():
         d['y_eval'] = np_(m(x))
-    np.savez_compressed(os.path.join(OUT, 'aspp_small.npz'), **d)
+    golden.save(OUT, 'aspp_small', d)
     return d
 
 
@@ -225,7 +226,7 @@ def gen_deeplab_head():
     d.update(nd)
     d.update(grads_digest(m))
     d.update(bn_buffers(m))
-    np.savez_compressed(os.path.join(OUT, 'deeplab_head.npz'), **d)
+    golden.save(OUT, 'deeplab_head', d)
     return d
 
 
@@ -258,7 +259,7 @@ def gen_unet_head():
         d['df%d' % i] = np_(feats[i].grad)
     d.update(grads_digest(m))
     d.update(bn_buffers(m))
-    np.savez_compressed(os.path.join(OUT, 'unet_head.npz'), **d)
+    golden.save(OUT, 'unet_head', d)
     return d
 
 
@@ -287,7 +288,7 @@ def gen_hrnet_small():
     m.eval()
     with torch.no_grad():
         d['out_eval'] = np_(m(x))
-    np.savez_compressed(os.path.join(OUT, 'hrnet_small.npz'), **d)
+    golden.save(OUT, 'hrnet_small', d)
     return d
 
 

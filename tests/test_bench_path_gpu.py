@@ -127,15 +127,15 @@ def test_trainer_step_at_config2_matches_the_bridge_path(policy):
 
 
 def test_bench_line_carries_the_other_configurations():
-    """`python bench.py` as the driver runs it at N = 1 (two steps here): ONE JSON line with the contract's keys, the roofline
+    """`python bench.py --full` at N = 1 (two steps here): ONE JSON line with the contract's keys, the roofline
     object, and `other_configs` -- BASELINE.json configs[4] (HRNet) and configs[1] (UNet) under fp32 and -mp, each timed in a
     process of its own with a default-constructed Trainer that must have chosen the replay by itself."""
     import json
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(repo, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
-                        '--also', 'half'], capture_output=True, text=True, timeout=600, cwd=repo)
+    r = subprocess.run([sys.executable, os.path.join(repo, 'bench.py'), '--full', '--steps', '2', '--warmup', '1',
+                        '--no-cpu-baseline', '--also', 'half'], capture_output=True, text=True, timeout=600, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith('{')]
     assert len(lines) == 1
@@ -154,3 +154,32 @@ def test_bench_line_carries_the_other_configurations():
             assert 'error' not in e, e
             assert e['ms_per_step'] > 0 and e['replayed'] is True and e['lane_executor']['lanes'] >= 2, (name, pol, e)
     assert oc['hrnet']['half']['lane_executor']['lanes'] >= 4
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """`python bench.py` without --full (two steps here): ONE JSON line with the headline keys and nothing measured beyond
+    them, and --dump-outputs writes the last timed step's loss, parameters, gradients and BatchNorm statistics as finite
+    float32 / float64 arrays, the loss equal to the one in the line, under 64 MB in all."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / 'outputs'
+    r = subprocess.run([sys.executable, os.path.join(repo, 'bench.py'), '--steps', '2', '--warmup', '1', '--dump-outputs',
+                        str(out)], capture_output=True, text=True, timeout=600, cwd=repo)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['steps'] == 2 and d['warmup'] == 1 and d['dtype'] == 'f32' and d['higher_is_better'] is True
+    assert d['value'] > 0 and abs(d['value'] - 16 * 1e3 / d['ms_per_step']) <= 1e-6 * d['value']
+    assert d['other_policies'] is None and d['other_configs'] is None and d['roofline'] is None and d['cpu_baseline'] is None
+    arrays = {f.stem: np.load(f) for f in out.glob('*.npy')}
+    assert set(arrays) == {'loss', 'params', 'grads', 'bn_stats'}
+    assert sum(f.stat().st_size for f in out.glob('*.npy')) <= 64 << 20
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), name
+    assert float(arrays['loss'][0]) == pytest.approx(d['config']['loss'], rel=1e-6)
+    assert arrays['grads'].any() and arrays['params'].any()

@@ -157,7 +157,7 @@ def test_bench_two_rank_rehearsal():
     env = dict(os.environ, PSEG_BENCH_REHEARSAL='1', PSEG_EXCHANGE='rs_ag')
     env.pop('PSEG_FORCE_REDUCER', None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
-           '127.0.0.1', '--master-port', str(_free_port()), os.path.join(repo, 'bench.py'), '--gpus', '2', '--steps', '2',
+           '127.0.0.1', '--master-port', str(_free_port()), os.path.join(repo, 'bench.py'), '--full', '--gpus', '2', '--steps', '2',
            '--warmup', '1', '--batch', '2', '--size', '128']
     r = subprocess.run(cmd, cwd=repo, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -187,7 +187,7 @@ def test_bench_four_rank_rehearsal():
     env = dict(os.environ, PSEG_BENCH_REHEARSAL='1', PSEG_EXCHANGE='allreduce')
     env.pop('PSEG_FORCE_REDUCER', None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '4', '--master-addr',
-           '127.0.0.1', '--master-port', str(_free_port()), os.path.join(repo, 'bench.py'), '--gpus', '4', '--steps', '2',
+           '127.0.0.1', '--master-port', str(_free_port()), os.path.join(repo, 'bench.py'), '--full', '--gpus', '4', '--steps', '2',
            '--warmup', '1', '--batch', '2', '--size', '128']
     r = subprocess.run(cmd, cwd=repo, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]

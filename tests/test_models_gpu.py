@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import fill
+from oracle import golden
 from oracle import loss as oloss
 from oracle import margins
 from oracle import models as omodels
@@ -41,7 +42,7 @@ def rel(a, b):
 
 
 def load(golden_dir, name):
-    return dict(np.load(os.path.join(golden_dir, name + '.npz')))
+    return golden.load(golden_dir, name)
 
 
 def apply_case_nudges(golden_dir, key, module, at_least=20):

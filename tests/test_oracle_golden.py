@@ -6,13 +6,13 @@ import os
 import numpy as np
 import torch
 
-from oracle import fill, loss as oloss, margins, models as omodels
+from oracle import fill, golden, loss as oloss, margins, models as omodels
 
 RTOL, ATOL = 1e-5, 1e-6  # same torch ops in a different composition order: fp32 round-off only
 
 
 def _load(golden_dir, name):
-    return dict(np.load(os.path.join(golden_dir, name + '.npz')))
+    return golden.load(golden_dir, name)
 
 
 def _close(a, b, rtol=RTOL, atol=ATOL):

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" && export TMPDIR=/tmp
 TAG=${1:-r04}
 O=gpurun_out
-python3 bench.py > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench_n1.err || { echo bench failed; tail -5 $O/${TAG}_bench_n1.err; exit 1; }
+python3 bench.py --full > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench_n1.err || { echo bench failed; tail -5 $O/${TAG}_bench_n1.err; exit 1; }
 echo "bench done"
 prof() {   # name, policy, env...
   name=$1; pol=$2; shift 2
