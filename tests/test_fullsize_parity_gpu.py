@@ -309,7 +309,7 @@ def test_fullsize_step_every_call_strict(fp32_policy, name):
     so this is where "the train-mode step at the benchmark size equals the reference's arithmetic" is decided; the composition
     (which tensor feeds which call) is pinned by the whole-model tests at 128x128 and by the forward quantities above."""
     import time
-    from opcheck import OpCheck
+    from opcheck import ALLOW_BRIDGE, OpCheck
     from pytorch_segmentation_amd import models
     from pytorch_segmentation_amd.utils import compute_loss
     hip_cls, nc, S, B, key = {'deeplabv3plus': (models.DeepLabV3Plus, 21, 512, 16, 'cfg2t'),
@@ -338,7 +338,10 @@ def test_fullsize_step_every_call_strict(fp32_policy, name):
           % (name, S, S, B, len(oc.calls), time.time() - t0,
              ', '.join('%s x%d %.1e' % (k, v[0], v[1]) for k, v in sorted(kinds.items()))))
     assert len(oc.calls) > 400
-    for need in ('conv2d_fwd', 'conv2d_dgrad', 'conv2d_wgrad', 'bn_act_fwd', 'bn_act_bwd.dy', 'bn_finalize', 'ce.dlogits'):
+    for need in ('conv2d_fwd', 'conv2d_dgrad', 'conv2d_wgrad', 'bn_act_fwd', 'bn_act_bwd.dy', 'bn_finalize', 'ce.dlogits',
+                 'transpose_filters'):
         assert need in kinds, need
+    print('unchecked launches: %s' % oc.census)
+    assert oc.unchecked() == ALLOW_BRIDGE['fp32'], oc.census
     bad = [(op, err, info) for op, err, info in oc.calls if not err < 1e-4]
     assert not bad, bad[:8]

@@ -391,7 +391,7 @@ def test_full_model_step_every_call_strict(pseg, name):
     inside the 1e-3 contract.  A 1 % systematic error in any mid-network data or weight gradient fails this by two
     orders of magnitude; which tensor feeds which call is pinned by the whole-model tests around this one.
     Why not simply max-norm on the final parameter gradients: see test_full_model_backward_frozen_bn."""
-    from opcheck import OpCheck
+    from opcheck import ALLOW_BRIDGE, OpCheck
     from pytorch_segmentation_amd import models
     from pytorch_segmentation_amd.utils import compute_loss
     hip_cls, ref, nc, S, B = {
@@ -421,6 +421,8 @@ def test_full_model_step_every_call_strict(pseg, name):
     assert len(oc.calls) > 100
     for need in ('conv2d_fwd', 'conv2d_dgrad', 'conv2d_wgrad', 'bn_act_fwd', 'bn_act_bwd.dy', 'bn_finalize', 'ce.dlogits'):
         assert need in kinds, need
+    print('unchecked launches: %s' % oc.census)
+    assert oc.unchecked() == ALLOW_BRIDGE[pseg.policy], oc.census
     bad = [(op, err, info) for op, err, info in oc.calls if not err < tol]
     assert not bad, bad[:8]
 
