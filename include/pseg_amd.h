@@ -59,7 +59,7 @@ extern "C" {
 #define PSEG_ACT_RELU6 2
 
 /* bumped whenever an existing prototype changes incompatibly; pseg_abi_version() returns the value the library was built with */
-#define PSEG_ABI_VERSION 11
+#define PSEG_ABI_VERSION 12
 int pseg_abi_version(void);
 const char* pseg_last_error(void);
 /* The PSEG_CONV_* / PSEG_WGRAD_* planning overrides are read from the environment once, at the first launch;
@@ -429,6 +429,30 @@ int pseg_ce_upsampled_fwd_bwd(const float* logits_lr, int ld, int B, int h, int 
 int pseg_scale_inplace(float* x, int64_t n, const float* gscale, void* stream);
 int pseg_argmax(const float* logits, int B, int C, int64_t HW, int64_t* mask, void* stream);
 int pseg_confusion(const int64_t* pred, const int64_t* target, int64_t n, int C, int64_t* counters, void* stream);
+
+/* ------------------------------------------------------------------ batched inference (csrc/infer.hip)
+ * The host passes of the reference's inference (utils/inference.py:10-22: cv2.resize, /255, softmax, cv2.resize of the
+ * probabilities to each photo's size, argmax) on the device, for a ragged batch of photos.  `table` is a device array of
+ * B records of three int64 {offset, H, W}: photo (or output image) b is H x W.  Records whose extent leaves the buffer
+ * (offset + H*W*elements > capacity, H or W outside [1, 65535]) are skipped on the device -- nothing is read or written
+ * for them -- so validate the table on the host.
+ *
+ * pseg_image_preprocess: src holds B uint8 HWC 3-channel photos back to back (photo b at byte table[b].offset, src_bytes
+ *   in all); out is the fp32 NCHW model input [B,3,oh,ow]: out[b,c,y,x] = (v - mean_c) / std_c, v = the photo resampled
+ *   with INTER_LINEAR geometry (= F.interpolate bilinear, align_corners=False, no antialias: source coordinate
+ *   (d + 0.5) * in/out - 0.5 clamped at 0, upper tap clamped to in - 1) in fp32 and rounded to 8 bits half up,
+ *   saturated; correctly rounded fp32 division.  bgr != 0: the photo's channels are B, G, R (cv2.imread) and are swapped
+ *   to RGB on load.  A photo already at oh x ow gives exactly CocoDataset.post_fetch_fn's input.
+ * pseg_seg_decode: logits fp32 NCHW [B,C,h,w] (what every model returns); for each b, mask[table[b].offset + y*W + x] =
+ *   argmax_c bilinear(softmax_c(logits[b]), (H, W), align_corners=False)[c, y, x] as uint8, first index on ties;
+ *   npix_total = the mask buffer's size in bytes.  rgb (nullable, 3 * npix_total bytes) receives lut[3*mask .. 3*mask+2]
+ *   at 3 * (offset + y*W + x); lut = 256 x 3 bytes, given with rgb.  1 <= C <= 256.  The softmax is evaluated once per
+ *   source pixel of a tile (tiles share a one-pixel halo); no full-resolution C-channel tensor exists anywhere.
+ */
+int pseg_image_preprocess(const uint8_t* src, int64_t src_bytes, const int64_t* table, int B, int bgr, float mean0, float mean1,
+                          float mean2, float std0, float std1, float std2, float* out, int oh, int ow, void* stream);
+int pseg_seg_decode(const float* logits, int B, int C, int h, int w, const int64_t* table, int64_t npix_total, uint8_t* mask,
+                    uint8_t* rgb, const uint8_t* lut, void* stream);
 
 /* ------------------------------------------------------------------ optimiser (flat parameter arena)
  * One launch over the whole arena; grad_scale folds the 1/world_size of the data-parallel mean

@@ -1,0 +1,80 @@
+#!/usr/bin/python3
+"""Inference entry point with the reference's flags (reference inference.py:41-58) on the MI355X HIP path.
+
+    python3 inference.py data/samples outputs --weights weights.pth [-s W H] [-nc N] [-bs N] [--model ...] [-mp]
+                         [--norm dataset|reference]
+
+Every file of img_dir whose extension is in IMG_EXT (case-sensitive, as the reference) is segmented, in name order, and
+written to output_dir as <name>.png in VOC colours.  Photos are decoded with PIL (RGB); resizing, normalisation, softmax,
+the resize of the probabilities to each photo's size and the argmax run on the device (utils/inference.py), -bs photos
+per batch.  Unlike the reference, output_dir is created but never emptied: deleting a directory the user names is not
+something an inference tool should do.  --show is accepted and ignored (the reference never used it either).
+"""
+import argparse
+import os
+import os.path as osp
+
+import numpy as np
+import torch
+from PIL import Image
+
+from pytorch_modules.utils import IMG_EXT
+from pytorch_segmentation_amd.models import DeepLabV3Plus, HRNet, UNet
+from pytorch_segmentation_amd.utils.datasets import VOC_COLORMAP, _warn_ignored
+from pytorch_segmentation_amd.utils.inference import NORMS, inference
+
+MODELS = {'deeplabv3plus': DeepLabV3Plus, 'unet': UNet, 'hrnet': HRNet}
+# VOC_COLORMAP rows are [b, g, r] for cv2.imwrite (reference inference.py:35-37); PIL writes RGB
+PALETTE_RGB = np.ascontiguousarray(VOC_COLORMAP[:, ::-1])
+
+
+def list_images(img_dir):
+    return sorted(n for n in os.listdir(img_dir) if osp.splitext(n)[1] in IMG_EXT)
+
+
+def load_image(path):
+    return np.asarray(Image.open(path).convert('RGB'), dtype=np.uint8)
+
+
+def run(img_dir, output_dir, img_size, num_classes, weights, show=False, model_name='deeplabv3plus', batch_size=1,
+        half=False, norm='dataset'):
+    if show:
+        _warn_ignored('--show', 'the reference accepts it and never displays anything either')
+    os.makedirs(output_dir, exist_ok=True)
+    model = MODELS[model_name](num_classes)
+    state_dict = torch.load(weights, map_location='cpu')
+    model.load_state_dict(state_dict['model'])
+    model = model.cuda()
+    model.eval()
+    names = list_images(img_dir)
+    for i in range(0, len(names), max(1, batch_size)):
+        batch = names[i:i + max(1, batch_size)]
+        imgs = [load_image(osp.join(img_dir, n)) for n in batch]
+        _, colored = inference(model, imgs, tuple(img_size), norm=norm, bgr=False, half=half, colors=PALETTE_RGB)
+        for name, seg in zip(batch, colored):
+            Image.fromarray(seg).save(osp.join(output_dir, osp.splitext(name)[0] + '.png'))
+        print('%d/%d' % (min(i + batch_size, len(names)), len(names)), flush=True)
+    return names
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument('img_dir', type=str)
+    parser.add_argument('output_dir', type=str)
+    parser.add_argument('-s', '--img_size', type=int, nargs=2, default=[320, 320])
+    parser.add_argument('-nc', '--num-classes', type=int, default=2)
+    parser.add_argument('--weights', type=str, default='weights/best.pt')
+    parser.add_argument('--show', action='store_true', help='accepted and ignored')
+    parser.add_argument('--model', choices=sorted(MODELS), default='deeplabv3plus')
+    parser.add_argument('-bs', '--batch-size', type=int, default=1)
+    parser.add_argument('-mp', '--mix_precision', action='store_true', help='half-precision forward')
+    parser.add_argument('--norm', choices=sorted(NORMS), default='dataset',
+                        help="'dataset': the training loader's mean/std (default); 'reference': /255 as the reference")
+    opt = parser.parse_args(argv)
+    print(opt)
+    run(opt.img_dir, opt.output_dir, opt.img_size, opt.num_classes, opt.weights, opt.show, opt.model, opt.batch_size,
+        opt.mix_precision, opt.norm)
+
+
+if __name__ == '__main__':
+    main()

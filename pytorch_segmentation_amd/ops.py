@@ -1206,6 +1206,42 @@ def argmax(logits):
     return mask
 
 
+def image_preprocess(src, table, oh, ow, mean, std, bgr):
+    """Ragged batch of uint8 HWC photos -> fp32 NCHW model input [B,3,oh,ow] (pseg_image_preprocess).  src: flat uint8
+    device tensor, photos back to back; table: int64 device tensor [B,3] of {byte offset, H, W} (validated by the caller)."""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
+    assert table.device == src.device and table.dtype == torch.int64 and table.is_contiguous() and table.dim() == 2
+    assert table.shape[1] == 3 and len(mean) == 3 and len(std) == 3
+    B = table.shape[0]
+    out = torch.empty(B, 3, oh, ow, dtype=torch.float32, device=src.device)
+    _lib.call('pseg_image_preprocess', src.data_ptr(), src.numel(), table.data_ptr(), B, int(bool(bgr)),
+              *[float(m) for m in mean], *[float(v) for v in std], out.data_ptr(), oh, ow, _stream())
+    return out
+
+
+def seg_decode(logits, table, npix_total, lut=None, out=None):
+    """NCHW fp32 logits [B,C,h,w] -> per-image uint8 masks argmax_c(bilinear(softmax_c(logits))) at each image's own
+    size (pseg_seg_decode), packed in one flat uint8 tensor of npix_total bytes at the offsets of table (int64 device
+    tensor [B,3] of {pixel offset, H, W}); with lut (uint8 [256,3] on the device) also the flat [npix_total,3] colours.
+    out (optional): one uint8 device tensor of npix_total (x 4 with lut) bytes that receives the mask, then the colours.
+    -> (mask, rgb or None)."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
+    assert table.device == logits.device and table.dtype == torch.int64 and table.is_contiguous()
+    assert table.shape == (logits.shape[0], 3)
+    B, C, h, w = logits.shape
+    nbytes = npix_total * (1 if lut is None else 4)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
+    assert out.device == logits.device and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == nbytes
+    mask, rgb = out[:npix_total], None
+    if lut is not None:
+        assert lut.device == logits.device and lut.dtype == torch.uint8 and lut.is_contiguous() and lut.shape == (256, 3)
+        rgb = out[npix_total:].view(npix_total, 3)
+    _lib.call('pseg_seg_decode', logits.data_ptr(), B, C, h, w, table.data_ptr(), npix_total, mask.data_ptr(), _ptr(rgb),
+              _ptr(lut), _stream())
+    return mask, rgb
+
+
 def confusion(pred, target, counters):
     """counters: int64 [3][C] (tp, fn, fp), accumulated in place."""
     assert pred.dtype == torch.int64 and target.dtype == torch.int64 and counters.dtype == torch.int64

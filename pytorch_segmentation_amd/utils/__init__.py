@@ -1,6 +1,9 @@
+from .datasets import VOC_COLORMAP, voc_colormap
 from .dist import GradReducer, all_reduce_counters, broadcast_buffers
 from .loss import compute_loss, compute_metrics, predict_mask, update_class_counts
+from .inference import inference
 from .trainer import Fetcher, FlatOptimizer, Trainer
 
 __all__ = ['compute_loss', 'compute_metrics', 'predict_mask', 'update_class_counts', 'GradReducer',
-           'all_reduce_counters', 'broadcast_buffers', 'Fetcher', 'FlatOptimizer', 'Trainer']
+           'all_reduce_counters', 'broadcast_buffers', 'Fetcher', 'FlatOptimizer', 'Trainer', 'inference', 'voc_colormap',
+           'VOC_COLORMAP']

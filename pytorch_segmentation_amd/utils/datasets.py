@@ -24,6 +24,25 @@ MEAN = (123.675, 116.28, 103.53)
 STD = (58.395, 57.12, 57.375)
 
 
+def voc_colormap(N=256):
+    """The PASCAL VOC palette exactly as the reference builds it (utils/datasets.py:128-143): row i = [b, g, r], the byte
+    order cv2.imwrite expects, so a written PNG shows the standard VOC RGB colours (class 1 -> (128, 0, 0))."""
+    cmap = np.zeros((N, 3), dtype=np.uint8)
+    for i in range(N):
+        r = g = b = 0
+        c = i
+        for j in range(8):
+            r |= ((c >> 0) & 1) << (7 - j)
+            g |= ((c >> 1) & 1) << (7 - j)
+            b |= ((c >> 2) & 1) << (7 - j)
+            c >>= 3
+        cmap[i, :] = [b, g, r]
+    return cmap
+
+
+VOC_COLORMAP = voc_colormap(32)     # classes >= 32 are drawn black (reference inference.py:33-35)
+
+
 _WARNED = set()
 
 

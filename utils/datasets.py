@@ -1,2 +1,3 @@
-"""`from utils.datasets import CocoDataset, CocoInstance` -- the reference's import path (train.py:15, test.py:10)."""
-from pytorch_segmentation_amd.utils.datasets import CocoDataset, CocoInstance  # noqa: F401
+"""`from utils.datasets import CocoDataset, CocoInstance, VOC_COLORMAP` -- the reference's import path (train.py:15, test.py:10,
+inference.py:13)."""
+from pytorch_segmentation_amd.utils.datasets import VOC_COLORMAP, CocoDataset, CocoInstance, voc_colormap  # noqa: F401
