@@ -1,6 +1,7 @@
 """Every kernel call of one half-precision (`-mp`) training step at full size, against fp64.
 
-BASELINE.json configs[2] (DeepLabV3+ R50, 21 classes, 512x512, batch 16) and configs[4] (HRNet, 21 classes, 512x512, batch 8)
+BASELINE.json configs[2] (DeepLabV3+ R50, 21 classes, 512x512, batch 16), configs[4] (HRNet, 21 classes, 512x512, batch 8) and
+configs[1] (UNet on MobileNetV2, 2 classes, 256x256, batch 8: the depthwise kernels above their launch cap, ReLU6)
 under Trainer(mixed_precision=True): the explicit step `bench.py` and `train.py -mp` run (Trainer._fwd_loss_bwd), with the fp16
 filter copies, the loss-scaled entry into the fp16 network and, for DeepLabV3+, the fused low-resolution loss.  At 128x128 the
 planner picks other kernels and tiles than here (256x128 tiles on eight waves, the XCD remap of 2048-block grids, the
@@ -28,8 +29,12 @@ from test_half_models_gpu import CALL_TOL, F32_CALL_TOL
 
 pytestmark = pytest.mark.gpu
 
-CASES = [('deeplabv3plus', 21, 512, 16, 'cfg2h'), ('hrnet', 21, 512, 8, 'cfg4h')]
-F32_OPS = ('conv2d_wgrad', 'conv2d_wgrad.ch', 'bn_finalize', 'bn_act_bwd.dgamma', 'bn_act_bwd.dbeta')
+CASES = [('deeplabv3plus', 21, 512, 16, 'cfg2h'), ('hrnet', 21, 512, 8, 'cfg4h'), ('unet', 2, 256, 8, 'cfg1h')]
+# UNet's every-call run at 128x128, batch 4 (tests/test_half_models_gpu.py) records 1260 figures, 47 of them 'bn_running_stats'
+# (reported only by the fused small-tensor BatchNorm launch: 35 at 256x256); the other 1213 are the same at every size
+UNET_CALLS_128 = 1260 - 47
+F32_OPS = ('conv2d_wgrad', 'conv2d_wgrad.ch', 'dwconv_wgrad', 'dwconv_wgrad.ch', 'bn_finalize', 'bn_act_bwd.dgamma',
+           'bn_act_bwd.dbeta')
 CE_UP_TOL = {'ce_upsampled.loss': 1e-5, 'ce_upsampled.count': 0.5, 'ce_upsampled.bad': 0.5, 'ce_upsampled.dlogits': 2e-5}
 
 
@@ -48,8 +53,8 @@ def test_fullsize_half_step_every_call(monkeypatch, name, nc, S, B, key):
     from pytorch_segmentation_amd.utils import Trainer
     if name == 'hrnet':
         monkeypatch.setenv('PSEG_DEFER_SLABS', '1')         # read when the Trainer is built
-    hip_cls = {'deeplabv3plus': models.DeepLabV3Plus, 'hrnet': models.HRNet}[name]
-    ref = {'deeplabv3plus': omodels.DeepLabV3Plus, 'hrnet': omodels.HRNet}[name](nc)
+    hip_cls = {'deeplabv3plus': models.DeepLabV3Plus, 'hrnet': models.HRNet, 'unet': models.UNet}[name]
+    ref = {'deeplabv3plus': omodels.DeepLabV3Plus, 'hrnet': omodels.HRNet, 'unet': omodels.UNet}[name](nc)
     fill.fill_module_(ref, key)
     m = hip_cls(nc)
     m.load_state_dict(ref.state_dict())
@@ -83,13 +88,21 @@ def test_fullsize_half_step_every_call(monkeypatch, name, nc, S, B, key):
     print('  launches checked: %s' % dict(sorted(oc.checked.items())))
     print('  launches unchecked: %s' % dict(sorted(oc.census.items())))
 
-    assert len(oc.calls) > 400
+    if name == 'unet':
+        assert sum(1 for op, _, _ in oc.calls if op != 'bn_running_stats') >= UNET_CALLS_128
+    else:
+        assert len(oc.calls) > 400
     need = ['conv2d_fwd', 'conv2d_dgrad', 'conv2d_wgrad', 'bn_act_fwd', 'bn_act_bwd.dy', 'bn_finalize', 'act_to',
             'prepare_half']
     if name == 'deeplabv3plus':
         need += ['ce_upsampled.loss', 'ce_upsampled.count', 'ce_upsampled.bad', 'ce_upsampled.dlogits']
-    else:
+    elif name == 'hrnet':
         need += ['ce.loss', 'ce.dlogits']
+    else:                       # UNet: the one model on the depthwise kernels and on ReLU6 in the fused BatchNorm kernels
+        need += ['dwconv_fwd', 'dwconv_dgrad', 'dwconv_wgrad']
+        assert any(op.startswith('ce') for op in kinds), sorted(kinds)
+        for op in ('bn_act_fwd', 'bn_act_bwd.dy'):
+            assert any(o == op and ' act2 ' in info + ' ' for o, _, info in oc.calls), op + ' act2'
     for op in need:
         assert op in kinds, op
     # the fp16 filter copies every forward conv and data gradient of the step read were checked bit for bit

@@ -300,12 +300,21 @@ def test_config4_hrnet_512_batch8_train_step_vs_oracle(fp32_policy):
     trh.close()
 
 
-@pytest.mark.parametrize('name', ['deeplabv3plus', 'hrnet'])
+# The every-call run of UNet at 128x128, batch 4 (tests/test_models_gpu.py::test_full_model_step_every_call_strict[fp32-unet])
+# records 1088 figures; 47 of them are 'bn_running_stats', which only the fused small-tensor BatchNorm launch reports (which
+# layers take it depends on the tensor size: 35 at 256x256).  The other 1041 belong to the model's layers and are the same at
+# every size: that is UNet's floor here.
+UNET_CALLS_128 = 1088 - 47
+
+
+@pytest.mark.parametrize('name', ['deeplabv3plus', 'hrnet', 'unet'])
 def test_fullsize_step_every_call_strict(fp32_policy, name):
     """The strict form of full-size parity: EVERY kernel call of one real training step of configs[2] (DeepLabV3+ 512x512 B=16:
     ~570 calls) / configs[4] (HRNet 512x512 B=8: ~1000 calls) -- the headline's own shapes, grids, plan tiles, pixel strides, concat
     slices and accumulate flags -- recomputed on the CPU in fp64 from the call's own device inputs (tests/opcheck.py) and held to
-    1e-4 in max-norm, no outlier allowance.  Independent of the graph's conditioning (each call is judged on its actual inputs),
+    1e-4 in max-norm, no outlier allowance.  configs[1] (UNet, 2 classes, 256x256 B=8) the same way: the one model that reaches the
+    depthwise kernels (above their launch cap at this size: the first depthwise layer has ~1 M work items), ReLU6 in the fused
+    BatchNorm kernels and the MobileNetV2 shapes -- all four must be among the checked kinds.  Independent of the graph's conditioning (each call is judged on its actual inputs),
     so this is where "the train-mode step at the benchmark size equals the reference's arithmetic" is decided; the composition
     (which tensor feeds which call) is pinned by the whole-model tests at 128x128 and by the forward quantities above."""
     import time
@@ -313,8 +322,9 @@ def test_fullsize_step_every_call_strict(fp32_policy, name):
     from pytorch_segmentation_amd import models
     from pytorch_segmentation_amd.utils import compute_loss
     hip_cls, nc, S, B, key = {'deeplabv3plus': (models.DeepLabV3Plus, 21, 512, 16, 'cfg2t'),
-                              'hrnet': (models.HRNet, 21, 512, 8, 'cfg4t')}[name]
-    ref = {'deeplabv3plus': omodels.DeepLabV3Plus, 'hrnet': omodels.HRNet}[name](nc)
+                              'hrnet': (models.HRNet, 21, 512, 8, 'cfg4t'),
+                              'unet': (models.UNet, 2, 256, 8, 'cfg1t')}[name]
+    ref = {'deeplabv3plus': omodels.DeepLabV3Plus, 'hrnet': omodels.HRNet, 'unet': omodels.UNet}[name](nc)
     fill.fill_module_(ref, key)
     m = hip_cls(nc)
     m.load_state_dict(ref.state_dict())
@@ -337,10 +347,18 @@ def test_fullsize_step_every_call_strict(fp32_policy, name):
     print('full-size every-call check [%s %dx%d B=%d]: %d calls in %.0f s; worst per op: %s'
           % (name, S, S, B, len(oc.calls), time.time() - t0,
              ', '.join('%s x%d %.1e' % (k, v[0], v[1]) for k, v in sorted(kinds.items()))))
-    assert len(oc.calls) > 400
+    if name == 'unet':
+        assert sum(1 for op, _, _ in oc.calls if op != 'bn_running_stats') >= UNET_CALLS_128
+    else:
+        assert len(oc.calls) > 400
     for need in ('conv2d_fwd', 'conv2d_dgrad', 'conv2d_wgrad', 'bn_act_fwd', 'bn_act_bwd.dy', 'bn_finalize', 'ce.dlogits',
                  'transpose_filters'):
         assert need in kinds, need
+    if name == 'unet':
+        for need in ('dwconv_fwd', 'dwconv_dgrad', 'dwconv_wgrad'):
+            assert need in kinds and need + '.ch' in kinds, need
+        for need in ('bn_act_fwd', 'bn_act_bwd.dy'):      # ReLU6 (act == 2) in the fused BatchNorm kernels, both directions
+            assert any(op == need and ' act2 ' in info + ' ' for op, _, info in oc.calls), need + ' act2'
     print('unchecked launches: %s' % oc.census)
     assert oc.unchecked() == ALLOW_BRIDGE['fp32'], oc.census
     bad = [(op, err, info) for op, err, info in oc.calls if not err < 1e-4]
