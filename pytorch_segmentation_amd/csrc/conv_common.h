@@ -836,6 +836,84 @@ static bool dil_geom(DilGeom& g, int Ho, int Wo, int Hi, int Wi, int taps_h, int
   return true;
 }
 
+// A conv as a gather GEMM, fp32 or fp16: M rows (pixels of the Ho x Wo row space) x N columns, contraction over
+// K = taps_h * taps_w * Cin gathered from the Hi x Wi source.
+struct GatherGeom {
+  long long M;
+  int N, K, Cin, Hi, Wi, Ho, Wo, taps_h, taps_w, s_out, s_in, dstep, off0;
+};
+
+// Order of the GEMM rows (GatherConvParams::row_perm and the fields that go with it) and whether dead taps are skipped.
+struct RowOrder {
+  int skip_taps, row_perm, patch_w, patch_hw, patches_per_row, xcd_remap;
+};
+
+// can_skip / can_parity: what the number format adds to the conditions for skipping the padding taps of a dilated conv / for
+// the parity order of a stride-2 data gradient (whole K-steps per tap; fp32: no split-K; fp16: not on the 128x128 tile).
+static RowOrder gather_row_order(const GatherGeom& g, const FwdPlan& pl, bool can_skip, bool can_parity) {
+  RowOrder o{0, 0, 1, 1, 1, cfg().conv_noxcd == 0 ? 1 : 0};
+  const int taps = g.taps_h * g.taps_w;
+  const int adil = g.dstep < 0 ? -g.dstep : g.dstep;
+  const bool skipping = taps <= 32 && cfg().conv_noskip == 0;
+  o.skip_taps = (can_skip && skipping && adil >= 4 && taps > 1) ? 1 : 0;
+  // 1x1, unit stride: GEMM row m is pixel m of the source (set_gather_geometry presents the tensor as a 1 x M image)
+  if (g.K == g.Cin && g.s_out == 1 && g.s_in == 1 && g.off0 == 0 && g.Hi == g.Ho && g.Wi == g.Wo) o.row_perm = 3;
+  if (pl.patch_w > 0 && o.skip_taps) {
+    o.row_perm = 2;
+    o.patch_w = pl.patch_w;
+    o.patch_hw = pl.patch_h * pl.patch_w;
+    o.patches_per_row = g.Wo / pl.patch_w;
+  }
+  if (pl.banded && o.skip_taps) {
+    o.row_perm = 4;
+    o.xcd_remap = 2;     // the descending-cost order is the schedule (band_makespan)
+  }
+  // stride-2 data gradient (s_in == 2): parity-homogeneous tiles + tap skipping (needs whole tiles per class)
+  if (can_parity && skipping && g.s_in == 2 && g.Ho % 2 == 0 && g.Wo % 2 == 0 && ((g.Ho / 2) * (g.Wo / 2)) % pl.tile.bm == 0) {
+    o.row_perm = 1;
+    o.skip_taps = 1;
+  }
+  return o;
+}
+
+// geometry, K split, tap skipping and row order of a launch
+static void set_gather_geometry(GatherConvParams& p, const GatherGeom& g, const FwdPlan& pl, const RowOrder& o) {
+  p.Hi = g.Hi;
+  p.Wi = g.Wi;
+  p.Cin = g.Cin;
+  p.Ho = g.Ho;
+  p.Wo = g.Wo;
+  p.HoWo = g.Ho * g.Wo;
+  p.M = (int)g.M;
+  p.N = g.N;
+  p.K = g.K;
+  p.kw = g.taps_w;
+  p.s_out = g.s_out;
+  p.s_in = g.s_in;
+  p.dstep = g.dstep;
+  p.off0 = g.off0;
+  p.kt_total = pl.kt_total;
+  p.kt_per_split = pl.kt_per_split;
+  p.ntaps = g.taps_h * g.taps_w;
+  p.skip_taps = o.skip_taps;
+  p.xcd_remap = o.xcd_remap;
+  p.prio = g.dstep < 0 ? cfg().dgrad_prio : 0;
+  p.row_perm = o.row_perm;
+  p.patch_w = o.patch_w;
+  p.patch_hw = o.patch_hw;
+  p.patches_per_row = o.patches_per_row;
+  if (o.row_perm == 3) {
+    // a 1 x M image: the kernel's per-row prologue is free of divisions (short-K layers -- K = 64 is two K-steps -- are
+    // prologue / epilogue bound)
+    p.Hi = 1;
+    p.Wi = (int)g.M;
+    p.Ho = 1;
+    p.Wo = (int)g.M;
+    p.HoWo = (int)g.M;
+  }
+  if (o.row_perm == 4) p.band = pl.band;
+}
+
 struct WgradPlan {
   TileCfg tile;
   int gridM, gridN, splits, pix_per_split;

@@ -2244,63 +2244,19 @@ static int run_gather_h(const void* x, long long x_bytes, int ldx, const void* w
   p.x_bytes = (uint32_t)x_bytes;
   p.w_bytes = (uint32_t)w_bytes;
   p.ldx = ldx;
-  p.Hi = Hi;
-  p.Wi = Wi;
-  p.Cin = Cin;
-  p.Ho = Ho;
-  p.Wo = Wo;
-  p.HoWo = Ho * Wo;
-  p.M = (int)M;
-  p.N = N;
-  p.K = K;
-  p.kw = taps_w;
-  p.s_out = s_out;
-  p.s_in = s_in;
-  p.dstep = dstep;
-  p.off0 = off0;
   p.accumulate = accumulate;
-  p.kt_total = pl.kt_total;
-  p.kt_per_split = pl.kt_per_split;
   p.slab_stride = 0;
   const int taps = K / Cin;
-  const int adil = dstep < 0 ? -dstep : dstep;
-  p.ntaps = taps;
+  [[maybe_unused]] const int adil = dstep < 0 ? -dstep : dstep;     // (lab kernels below)
   p.ktiles_per_tap = generic ? 1 : Cin / kb;
   // dilated convs: K-steps of taps that are zero padding for the whole M tile are skipped -- on the 4-wave tiles only.  On the
   // 128x128 / 8-wave tile (the ASPP data gradients: N = 2048) the tap-skipping instantiation is SLOWER than the dense one
   // even where it skips half the K-steps (rate 18: 269 us patch-ordered / 290 class-sorted against 168 dense; rate 6: 272
   // against 206): one fp16 MFMA pass per tile leaves the kernel bound by its operand stream, a padding tap's DMA is an
   // out-of-range no-op that costs nothing, and the skip bookkeeping does (tools/bench_conv_half.py with PSEG_CONV_NOSKIP=1).
-  p.skip_taps = (!generic && adil >= 4 && taps > 1 && taps <= 32 && cfg().conv_noskip == 0 &&
-                 !(pl.tile.bm == 128 && pl.tile.bn == 128)) ? 1 : 0;
-  p.xcd_remap = cfg().conv_noxcd == 0 ? 1 : 0;
-  p.prio = dstep < 0 ? cfg().dgrad_prio : 0;
-  p.row_perm = 0;
-  p.patch_w = p.patch_hw = p.patches_per_row = 1;
-  if (K == Cin && s_out == 1 && s_in == 1 && off0 == 0 && Hi == Ho && Wi == Wo) {
-    p.row_perm = 3;     // 1x1, unit stride: the tensor is one long row of M pixels (no index arithmetic per row)
-    p.Hi = 1;
-    p.Wi = (int)M;
-    p.Ho = 1;
-    p.Wo = (int)M;
-    p.HoWo = (int)M;
-  }
-  if (pl.patch_w > 0 && p.skip_taps) {
-    p.row_perm = 2;
-    p.patch_w = pl.patch_w;
-    p.patch_hw = pl.patch_h * pl.patch_w;
-    p.patches_per_row = Wo / pl.patch_w;
-  }
-  if (pl.banded && p.skip_taps) {
-    p.row_perm = 4;
-    p.band = pl.band;
-    p.xcd_remap = 2;
-  }
-  if (!generic && s_in == 2 && Ho % 2 == 0 && Wo % 2 == 0 && ((Ho / 2) * (Wo / 2)) % pl.tile.bm == 0 && taps <= 32 &&
-      cfg().conv_noskip == 0) {
-    p.row_perm = 1;     // stride-2 data gradient: parity-homogeneous tiles, 3/4 of the taps skipped
-    p.skip_taps = 1;
-  }
+  // The stride-2 data gradient runs parity-homogeneous tiles on every tile shape, 3/4 of the taps skipped.
+  const GatherGeom geo{M, N, K, Cin, Hi, Wi, Ho, Wo, taps / taps_w, taps_w, s_out, s_in, dstep, off0};
+  set_gather_geometry(p, geo, pl, gather_row_order(geo, pl, !generic && !(pl.tile.bm == 128 && pl.tile.bn == 128), !generic));
   p.trace = nullptr;
   p.bns_y = nullptr;
   p.bns_ldy = 0;

@@ -32,6 +32,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "../../include/pseg_amd.h"
 
 // Per-block phase timestamps in gather_f32_dma_kernel: compiled in only with -DPSEG_CONV_TRACE=1 (PSEG_BUILD_TRACE=1 python -m
@@ -2811,6 +2814,165 @@ struct LimbPlanes {
   long long xp_bytes, wp_bytes;
 };
 
+// BatchNorm-backward partial sums fused into a data gradient (GatherConvParams::bns_*)
+struct BnsArgs {
+  const float* y;
+  int ldy;
+  const float* mean;
+  const float* invstd;
+  const float* scale;
+  const float* shift;
+  int act;
+  float* db;
+  float* dg;
+  int rows;
+};
+
+// The tiles of the exact-fp32 LDS-DMA kernels, stated once: select_gather reads from this table what each family covers, the
+// launch helpers below map an entry to template arguments.  gather_f32_dma_kernel (plain and GENERIC) is instantiated for every
+// entry, gather_f32_pw_kernel / gather_f32_halo_kernel for those marked.  Threads per block = 64 * wm * wn.
+struct F32Tile {
+  int bm, bn, wm, wn;
+  bool pw;       // persistent pointwise kernel
+  int halo;      // halo-staged kernel: the lowest PSEG_CONV_HALO that takes the tile (0: not instantiated)
+  bool dma32;    // only with PSEG_CONV_DMA32 != 0
+};
+constexpr F32Tile kF32Tiles[] = {{128, 128, 2, 4, true, 0, false},
+                                 {128, 64, 2, 2, true, 2, false},
+                                 {64, 128, 2, 2, true, 0, false},
+                                 {128, 32, 4, 1, false, 1, true}};   // narrow outputs (HRNet's 32-channel branch, the 21-class classifier)
+constexpr int kNumF32Tiles = (int)(sizeof(kF32Tiles) / sizeof(kF32Tiles[0]));
+
+static int f32_tile_index(TileCfg t) {
+  for (int i = 0; i < kNumF32Tiles; ++i)
+    if (kF32Tiles[i].bm == t.bm && kF32Tiles[i].bn == t.bn && (!kF32Tiles[i].dma32 || cfg().conv_dma32 != 0)) return i;
+  return -1;
+}
+
+// f(std::integral_constant<int, i>) for table entry i: the entry's fields are then template arguments
+template <typename F, int... I>
+static void with_f32_tile(int i, F&& f, std::integer_sequence<int, I...>) {
+  (void)((i == I && (f(std::integral_constant<int, I>{}), true)) || ...);
+}
+template <typename F>
+static void with_f32_tile(int i, F&& f) {
+  with_f32_tile(i, f, std::make_integer_sequence<int, kNumF32Tiles>{});
+}
+
+static int waves_m(TileCfg t) { return t.bm == 256 ? 4 : (t.bn == 32 ? 4 : (t.bm == 32 ? 1 : 2)); }
+
+// A gather problem as run_gather sees it: the geometry plus what the caller asks of the kernel.
+struct GatherProblem : GatherGeom {
+  int precision;
+  bool stats, bias, planes, bns, accumulate;   // fused statistics / bias / pre-split limb planes / fused BatchNorm-backward sums
+};
+
+constexpr int kGatherRefused = 0;    // GatherChoice::kernel: no kernel carries the limb planes / fused sums asked for
+
+// Everything run_gather decides before it launches; the queries read their answers off the same choice.
+struct GatherChoice {
+  FwdPlan pl;
+  RowOrder order;   // (row_perm == 4: the classes are pl.band)
+  int kernel;       // PSEG_KERNEL_GATHER_* that runs -- after the pointwise kernel declined, if try_pw -- or kGatherRefused
+  int f32_tile;     // entry of kF32Tiles (ring, pointwise and halo kernels)
+  int stages;       // ring depth of gather_f32_dma_kernel
+  bool generic;     // ... and its GENERIC form
+  bool try_pw;      // offer the problem to the persistent pointwise kernel first; launch_pw declines by device occupancy
+  int stat_rows() const { return pl.gridM * waves_m(pl.tile); }
+};
+
+// The one place that picks the kernel of an exact-fp32 / limb gather conv.  Pure: launches nothing, touches no device.
+static GatherChoice select_gather(const GatherProblem& q) {
+  GatherChoice c;
+  DilGeom geom;
+  const bool has_geom = dil_geom(geom, q.Ho, q.Wo, q.Hi, q.Wi, q.taps_h, q.taps_w, q.Cin, q.s_out, q.s_in, q.dstep, q.off0);
+  // the 256x128 / 8-wave tile (one block per CU) of the limb kernels: measured 1 % SLOWER in the round-2 training step than
+  // two 128-row blocks per CU (mixed policy 35.85 vs 35.45 ms) -- opt-in (PSEG_CONV_BIG=1); the pre-split DMA kernel is
+  // built on it
+  const bool allow_big = !q.stats && (q.precision == 1 || q.precision == 3) &&
+                         (q.planes || cfg().conv_big != 0 || cfg().conv_forcebig != 0);
+  c.pl = plan_gather(q.M, q.N, q.K, allow_big, has_geom ? &geom : nullptr);
+  const FwdPlan& pl = c.pl;
+  const bool whole = q.Cin % BK == 0;    // whole K-steps inside a tap
+  c.order = gather_row_order(q, pl, whole, whole && pl.splits == 1);
+  c.kernel = q.bns ? kGatherRefused : PSEG_KERNEL_GATHER_REGISTER;
+  c.f32_tile = f32_tile_index(pl.tile);
+  c.stages = 0;
+  c.generic = c.try_pw = false;
+  if (q.planes) {
+    // the LDS-DMA limb kernel or nothing: whole K-steps inside a tap, the 256x128 tile, no split-K
+    const bool ok = q.precision == 1 && !q.stats && !q.bias && !q.bns && pl.tile.bm == kDmaBM && pl.tile.bn == kDmaBN &&
+                    pl.splits == 1 && whole && q.N >= kDmaBN && cfg().conv_nodma == 0;
+    c.kernel = ok ? PSEG_KERNEL_GATHER_LIMB_DMA : kGatherRefused;
+    return c;
+  }
+  if (!(q.precision == 0 && pl.splits == 1 && cfg().conv_f32dma != 0 && c.f32_tile >= 0)) return c;
+  const F32Tile& t = kF32Tiles[c.f32_tile];
+  const bool sk = c.order.skip_taps != 0;
+  const int taps = q.taps_h * q.taps_w;
+  static const int generic_on = env_int("PSEG_CONV_F32DMA_GENERIC", 1);
+  if (generic_on != 0 && !whole && q.Cin % 4 == 0 && !sk && (c.order.row_perm == 0 || c.order.row_perm == 3) && !q.bns) {
+    // channel counts off the K-step grid (stem, classifier data gradient, MobileNetV2 widths): the GENERIC form of the ring
+    // kernel with per-slot (tap, channel) derivation; two-stage ring
+    c.kernel = PSEG_KERNEL_GATHER_RING_GENERIC;
+    c.stages = 2;
+    c.generic = true;
+    return c;
+  }
+  // Exact-fp32 problems whose K-steps never straddle a tap run on the LDS-DMA kernel (same tile, same statistics
+  // layout).  PSEG_CONV_F32DMA: 3 (default) = two-stage ring for every such problem, 2 = only for those without tap
+  // skipping (51.0 -> 49.4 ms; the tap-skipping ASPP / stride-2 problems add 49.0 -> 48.4) -- 64 / 48 KB of LDS
+  // and ~100 VGPRs, so TWO blocks of 8 waves (128x128) or THREE of 4 (128x64) share a CU and one block's prologue /
+  // epilogue hides behind the others' MFMAs: medium and short-K layers +5-10 % (128x128 maps, 64 channels: 98 -> 109 TF),
+  // fp32 step 51.0 -> 49.4 ms; 1 = three-stage ring everywhere (one block per CU: equal to the register-staged kernel in
+  // the step); 0 = register-staged kernel only.  The large layers sit at the sustained fp32-MFMA rate either way.
+  if (!(whole && q.K % BK == 0 && taps <= 32 && !(cfg().conv_f32dma == 2 && sk))) return c;
+  if (q.bns && q.accumulate) return c;      // (the fused sums are those of the tile written, not of what it is added to)
+  // pointwise convs with short contractions and more tiles than the device holds blocks: the persistent kernel
+  // (PSEG_CONV_PW=0: off; PSEG_CONV_PW_KT: longest contraction, in K-steps, that takes it)
+  c.try_pw = t.pw && cfg().conv_pw != 0 && c.order.row_perm == 3 && !sk && pl.kt_total <= cfg().conv_pw_kt && cfg().conv_f32dma >= 2;
+  // narrow 3x3: the halo-staged kernel where the map is made of whole 8 x 16 patches (see gather_f32_halo_kernel)
+  const int halo = cfg().conv_halo;
+  if (halo != 0 && t.halo != 0 && (t.halo == 1 || halo >= t.halo) && !sk && taps == 9 && q.taps_w == 3 && q.s_out == 1 &&
+      q.s_in == 1 && (q.dstep == 1 || q.dstep == -1) && q.off0 == -q.dstep && q.Cin % 32 == 0 && q.Hi == q.Ho && q.Wi == q.Wo &&
+      q.Ho % kHaloPH == 0 && q.Wo % kHaloPW == 0 && c.order.row_perm == 0) {
+    c.kernel = PSEG_KERNEL_GATHER_HALO;
+    c.order.row_perm = 2;
+    c.order.patch_w = kHaloPW;
+    c.order.patch_hw = kHaloPH * kHaloPW;
+    c.order.patches_per_row = q.Wo / kHaloPW;
+    return c;
+  }
+  c.kernel = PSEG_KERNEL_GATHER_RING;
+  c.stages = cfg().conv_f32dma >= 2 ? 2 : 3;   // two-stage ring: 64 / 48 KB of LDS, 2 / 3 blocks per CU
+  return c;
+}
+
+template <int I, bool SKIP, int STAGES, bool GENERIC>
+static void launch_ring_as(dim3 grid, hipStream_t st, const GatherConvParams& p) {
+  constexpr F32Tile t = kF32Tiles[I];
+  hipLaunchKernelGGL((gather_f32_dma_kernel<t.bm, t.bn, t.wm, t.wn, SKIP, STAGES, GENERIC>), grid, dim3(64 * t.wm * t.wn), 0, st, p);
+}
+
+static void launch_ring(const GatherChoice& c, dim3 grid, hipStream_t st, const GatherConvParams& p) {
+  const bool sk = c.order.skip_taps != 0, two = c.stages == 2;
+  with_f32_tile(c.f32_tile, [&](auto tile) {
+    constexpr int I = decltype(tile)::value;
+    if (c.generic) launch_ring_as<I, false, 2, true>(grid, st, p);
+    else if (two && sk) launch_ring_as<I, true, 2, false>(grid, st, p);
+    else if (two) launch_ring_as<I, false, 2, false>(grid, st, p);
+    else if (sk) launch_ring_as<I, true, 3, false>(grid, st, p);
+    else launch_ring_as<I, false, 3, false>(grid, st, p);
+  });
+}
+
+static void launch_halo(const GatherChoice& c, dim3 grid, hipStream_t st, const GatherConvParams& p) {
+  with_f32_tile(c.f32_tile, [&](auto tile) {
+    constexpr F32Tile t = kF32Tiles[decltype(tile)::value];
+    if constexpr (t.halo != 0) hipLaunchKernelGGL((gather_f32_halo_kernel<t.wm, t.wn>), grid, dim3(64 * t.wm * t.wn), 0, st, p);
+  });
+}
+
 // one instantiation of the persistent pointwise kernel: grid = the blocks the device holds at once; 0 = launched, 1 = not worth it
 // (fewer tiles than resident blocks: every block would own one tile) or not launchable
 template <int BM, int BN, int WM, int WN>
@@ -2842,61 +3004,22 @@ static int launch_pw(int ntiles, hipStream_t st, const GatherConvParams& p) {
   return 0;
 }
 
-// ... and its GENERIC form: channels of the gathered tensor a multiple of 4 but not of the K-step (no tap skipping, natural or
-// pointwise row order, no split-K)
-static bool f32dma_generic(const FwdPlan& pl, int precision, int Cin, bool skip_taps, int row_perm) {
-  static const int on = env_int("PSEG_CONV_F32DMA_GENERIC", 1);
-  const bool tile_ok = (pl.tile.bm == 128 && (pl.tile.bn == 128 || pl.tile.bn == 64 || (pl.tile.bn == 32 && cfg().conv_dma32 != 0))) ||
-                       (pl.tile.bm == 64 && pl.tile.bn == 128);
-  return on != 0 && precision == 0 && Cin % BK != 0 && Cin % 4 == 0 && pl.splits == 1 && cfg().conv_f32dma != 0 && !skip_taps &&
-         (row_perm == 0 || row_perm == 3) && tile_ok;
+static int launch_pointwise(const GatherChoice& c, hipStream_t st, const GatherConvParams& p) {
+  int rc = 1;
+  with_f32_tile(c.f32_tile, [&](auto tile) {
+    constexpr F32Tile t = kF32Tiles[decltype(tile)::value];
+    if constexpr (t.pw) rc = launch_pw<t.bm, t.bn, t.wm, t.wn>(c.pl.gridM * c.pl.gridN, st, p);
+  });
+  return rc;
 }
 
-// BatchNorm-backward partial sums fused into a data gradient (GatherConvParams::bns_*)
-struct BnsArgs {
-  const float* y;
-  int ldy;
-  const float* mean;
-  const float* invstd;
-  const float* scale;
-  const float* shift;
-  int act;
-  float* db;
-  float* dg;
-  int rows;
-};
-
-// can the LDS-DMA limb kernel run this gather problem?  (whole K-steps inside a tap, the 256x128 tile, no split-K)
-static bool dma_plan_ok(const FwdPlan& pl, int Cin, int N) {
-  return pl.tile.bm == kDmaBM && pl.tile.bn == kDmaBN && pl.splits == 1 && Cin % BK == 0 && N >= kDmaBN &&
-         cfg().conv_nodma == 0;
-}
-
-static int waves_m(TileCfg t) { return t.bm == 256 ? 4 : (t.bn == 32 ? 4 : (t.bm == 32 ? 1 : 2)); }
-
-// does the exact-fp32 LDS-DMA kernel run this gather problem?  (whole K-steps inside a tap, one of its four tiles, no split-K)
-static bool f32dma_covers(const FwdPlan& pl, int precision, int Cin, int K, int taps, bool skip_taps) {
-  const bool tile_ok = (pl.tile.bm == 128 && (pl.tile.bn == 128 || pl.tile.bn == 64 || (pl.tile.bn == 32 && cfg().conv_dma32 != 0))) ||
-                       (pl.tile.bm == 64 && pl.tile.bn == 128);
-  return precision == 0 && Cin % BK == 0 && pl.splits == 1 && cfg().conv_f32dma != 0 && K % BK == 0 && taps <= 32 &&
-         !(cfg().conv_f32dma == 2 && skip_taps) && tile_ok;
-}
-
-// does the halo-staged kernel run this problem?  (see gather_f32_halo_kernel)
-static bool halo_f32_covers(const FwdPlan& pl, const GatherConvParams& p, int Cin, int taps, int taps_w, int s_out, int s_in, int dstep,
-                            int off0, int Hi, int Wi, int Ho, int Wo, bool skip) {
-  const bool tile_ok = pl.tile.bm == 128 && ((pl.tile.bn == 32 && cfg().conv_dma32 != 0) || (pl.tile.bn == 64 && cfg().conv_halo >= 2));
-  return cfg().conv_halo != 0 && tile_ok && pl.splits == 1 && !skip && taps == 9 && taps_w == 3 && s_out == 1 &&
-         s_in == 1 && (dstep == 1 || dstep == -1) && off0 == -dstep && Cin % 32 == 0 && Hi == Ho && Wi == Wo && Ho % kHaloPH == 0 &&
-         Wo % kHaloPW == 0 && p.row_perm == 0;
-}
-
-static int run_gather(const float* x, long long x_bytes, int ldx, const float* w, float* y, int ldy, const float* bias,
-                      float* stat, int B, int Hi, int Wi, int Cin, int Ho, int Wo, int N, int taps_w,
-                      int K, int s_out, int s_in, int dstep, int off0, int accumulate, int precision,
-                      const unsigned* amax_a, const unsigned* amax_b, void* workspace, int64_t workspace_bytes,
-                      hipStream_t st, const LimbPlanes* planes = nullptr, const BnsArgs* bns = nullptr) {
-  const long long M = (long long)B * Ho * Wo;
+// validate, select, fill the parameters from the choice and launch
+static int run_gather(const GatherGeom& g, const float* x, long long x_bytes, int ldx, const float* w, float* y, int ldy,
+                      const float* bias, float* stat, int accumulate, int precision, const unsigned* amax_a,
+                      const unsigned* amax_b, void* workspace, int64_t workspace_bytes, hipStream_t st,
+                      const LimbPlanes* planes = nullptr, const BnsArgs* bns = nullptr) {
+  const long long M = g.M;
+  const int N = g.N, K = g.K, Cin = g.Cin;
   PSEG_REQUIRE(M > 0 && M < (1LL << 31) && N > 0 && K > 0, "conv: empty or oversized problem M=%lld N=%d K=%d", M, N, K);
   PSEG_REQUIRE(Cin % 4 == 0 && ldx % 4 == 0, "conv: Cin (%d) and ldx (%d) must be multiples of 4", Cin, ldx);
   PSEG_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "conv: x / w must be 16-byte aligned");
@@ -2904,15 +3027,15 @@ static int run_gather(const float* x, long long x_bytes, int ldx, const float* w
   PSEG_REQUIRE(x_bytes < kMaxBytes && w_bytes < kMaxBytes, "conv: tensor exceeds 2 GiB (x %lld, w %lld bytes)", x_bytes,
                w_bytes);
   PSEG_REQUIRE(((M - 1) * ldy + N) * 4 < (1LL << 40), "conv: output too large");
-  DilGeom geom;
-  const bool has_geom = dil_geom(geom, Ho, Wo, Hi, Wi, (K / Cin) / taps_w, taps_w, Cin, s_out, s_in, dstep, off0);
-  // the 256x128 / 8-wave tile (one block per CU) of the limb kernels: measured 1 % SLOWER in the round-2 training step than
-  // two 128-row blocks per CU (mixed policy 35.85 vs 35.45 ms) -- opt-in (PSEG_CONV_BIG=1); the pre-split DMA kernel is
-  // built on it
-  const bool allow_big = stat == nullptr && (precision == 1 || precision == 3) &&
-                         (planes != nullptr || cfg().conv_big != 0 || cfg().conv_forcebig != 0);
-  FwdPlan pl = plan_gather(M, N, K, allow_big, has_geom ? &geom : nullptr);
-  if (planes != nullptr && !(precision == 1 && stat == nullptr && bias == nullptr && dma_plan_ok(pl, Cin, N))) {
+
+  const GatherChoice c = select_gather(GatherProblem{g, precision, stat != nullptr, bias != nullptr, planes != nullptr,
+                                                     bns != nullptr, accumulate != 0});
+  const FwdPlan& pl = c.pl;
+  if (stat != nullptr && pl.splits > 1) {
+    set_error("conv2d_fwd: fused statistics are unavailable when the plan splits K; use pseg_col_stats");
+    return PSEG_ERR_ARG;
+  }
+  if (planes != nullptr && c.kernel != PSEG_KERNEL_GATHER_LIMB_DMA) {
     set_error("conv: the pre-split (LDS-DMA) limb kernel does not cover this problem (M=%lld N=%d K=%d Cin=%d)", M, N, K, Cin);
     return PSEG_ERR_ARG;
   }
@@ -2922,62 +3045,12 @@ static int run_gather(const float* x, long long x_bytes, int ldx, const float* w
   p.w = w;
   p.bias = bias;
   p.stat = stat;
-  p.stat_rows = pl.gridM * waves_m(pl.tile);
+  p.stat_rows = c.stat_rows();
   p.x_bytes = (uint32_t)x_bytes;
   p.w_bytes = (uint32_t)w_bytes;
   p.ldx = ldx;
-  p.Hi = Hi;
-  p.Wi = Wi;
-  p.Cin = Cin;
-  p.Ho = Ho;
-  p.Wo = Wo;
-  p.HoWo = Ho * Wo;
-  p.M = (int)M;
-  p.N = N;
-  p.K = K;
-  p.kw = taps_w;
-  p.s_out = s_out;
-  p.s_in = s_in;
-  p.dstep = dstep;
-  p.off0 = off0;
-  p.kt_total = pl.kt_total;
-  p.kt_per_split = pl.kt_per_split;
-  const int taps = K / Cin;
-  const int adil = dstep < 0 ? -dstep : dstep;
-  p.ntaps = taps;
+  set_gather_geometry(p, g, pl, c.order);
   p.ktiles_per_tap = Cin / BK;
-  p.skip_taps = (adil >= 4 && taps > 1 && taps <= 32 && Cin % BK == 0 && cfg().conv_noskip == 0) ? 1 : 0;
-  // stride-2 data gradient (s_in == 2): parity-homogeneous tiles + tap skipping (needs whole tiles per class, no split-K)
-  p.xcd_remap = cfg().conv_noxcd == 0 ? 1 : 0;
-  p.prio = dstep < 0 ? cfg().dgrad_prio : 0;
-  p.row_perm = 0;
-  p.patch_w = p.patch_hw = p.patches_per_row = 1;
-  if (K == Cin && s_out == 1 && s_in == 1 && off0 == 0 && Hi == Ho && Wi == Wo) {
-    // 1x1, unit stride: GEMM row m is pixel m of the source.  Present the tensor as a 1 x M image so that the kernel's
-    // per-row prologue is free of divisions (short-K layers -- K = 64 is two K-steps -- are prologue / epilogue bound)
-    p.row_perm = 3;
-    p.Hi = 1;
-    p.Wi = (int)M;
-    p.Ho = 1;
-    p.Wo = (int)M;
-    p.HoWo = (int)M;
-  }
-  if (pl.patch_w > 0 && p.skip_taps) {
-    p.row_perm = 2;
-    p.patch_w = pl.patch_w;
-    p.patch_hw = pl.patch_h * pl.patch_w;
-    p.patches_per_row = Wo / pl.patch_w;
-  }
-  if (pl.banded && p.skip_taps) {
-    p.row_perm = 4;
-    p.band = pl.band;
-    p.xcd_remap = 2;     // the descending-cost order is the schedule (band_makespan)
-  }
-  if (s_in == 2 && Ho % 2 == 0 && Wo % 2 == 0 && ((Ho / 2) * (Wo / 2)) % pl.tile.bm == 0 && pl.splits == 1 &&
-      taps <= 32 && Cin % BK == 0 && cfg().conv_noskip == 0) {
-    p.row_perm = 1;
-    p.skip_taps = 1;
-  }
   const dim3 grid((unsigned)(pl.gridM * pl.gridN), 1, (unsigned)pl.splits);
   if (pl.splits == 1) {
     p.y = y;
@@ -3007,9 +3080,8 @@ static int run_gather(const float* x, long long x_bytes, int ldx, const float* w
   p.bns_act = 0;
   p.bns_db = p.bns_dg = nullptr;
   if (bns != nullptr) {
-    // only the exact-fp32 LDS-DMA kernel carries the fused sums: the caller asked pseg_conv2d_dgrad_bnstat_rows first
-    if (!(f32dma_covers(pl, precision, Cin, K, taps, p.skip_taps != 0) && planes == nullptr && accumulate == 0 &&
-          bns->rows == pl.gridM * waves_m(pl.tile))) {
+    // only the exact-fp32 LDS-DMA kernels carry the fused sums: the caller asked pseg_conv2d_dgrad_bnstat_rows first
+    if (c.kernel == kGatherRefused || bns->rows != c.stat_rows()) {
       set_error("conv: the fused BatchNorm-backward sums are not available for this data gradient (M=%lld N=%d K=%d, rows %d)", M,
                 N, K, bns->rows);
       return PSEG_ERR_ARG;
@@ -3024,6 +3096,14 @@ static int run_gather(const float* x, long long x_bytes, int ldx, const float* w
     p.bns_db = bns->db;
     p.bns_dg = bns->dg;
   }
+  const bool reg = c.kernel == PSEG_KERNEL_GATHER_REGISTER;     // the one kernel with every arithmetic; the others are fixed
+  p.precision = reg ? precision : (c.kernel == PSEG_KERNEL_GATHER_LIMB_DMA ? 1 : 0);
+  p.amax_a = reg ? amax_a : nullptr;
+  p.amax_b = reg ? amax_b : nullptr;
+  if (reg && precision == 3 && (amax_a == nullptr || amax_b == nullptr)) {
+    set_error("conv: PSEG_PREC_FP16X3 needs the amax of both operands");
+    return PSEG_ERR_ARG;
+  }
   if (planes != nullptr) {
     PSEG_REQUIRE(planes->xp_bytes < kMaxBytes && planes->wp_bytes < kMaxBytes && planes->ldxp % 8 == 0 &&
                      ((uintptr_t)planes->xh & 15) == 0 && ((uintptr_t)planes->xl & 15) == 0 &&
@@ -3036,130 +3116,51 @@ static int run_gather(const float* x, long long x_bytes, int ldx, const float* w
     p.xp_bytes = (uint32_t)planes->xp_bytes;
     p.wp_bytes = (uint32_t)planes->wp_bytes;
     p.ldxp = planes->ldxp;
-    p.precision = 1;
-    p.amax_a = p.amax_b = nullptr;
-    if (p.skip_taps) hipLaunchKernelGGL(gather_limb_dma_kernel<true>, grid, dim3(512), 0, st, p);
-    else hipLaunchKernelGGL(gather_limb_dma_kernel<false>, grid, dim3(512), 0, st, p);
-    g_last_conv_kernel = PSEG_KERNEL_GATHER_LIMB_DMA;
+  }
+  if (c.try_pw && launch_pointwise(c, st, p) == 0) {
+    g_last_conv_kernel = PSEG_KERNEL_GATHER_POINTWISE;
     PSEG_LAUNCH_CHECK();
     return PSEG_OK;
   }
-  if (f32dma_generic(pl, precision, Cin, p.skip_taps != 0, p.row_perm) && planes == nullptr && bns == nullptr) {
-    // channel counts off the K-step grid (stem, classifier data gradient, MobileNetV2 widths): the same kernel with per-slot
-    // (tap, channel) derivation; two-stage ring
-    p.precision = 0;
-    p.amax_a = p.amax_b = nullptr;
-    p.gen_spt = FastDiv((uint32_t)(Cin / 4));
-    p.gen_kw = FastDiv((uint32_t)taps_w);
-    if (pl.tile.bm == 128 && pl.tile.bn == 128)
-      hipLaunchKernelGGL((gather_f32_dma_kernel<128, 128, 2, 4, false, 2, true>), grid, dim3(512), 0, st, p);
-    else if (pl.tile.bm == 128 && pl.tile.bn == 64)
-      hipLaunchKernelGGL((gather_f32_dma_kernel<128, 64, 2, 2, false, 2, true>), grid, dim3(256), 0, st, p);
-    else if (pl.tile.bm == 64 && pl.tile.bn == 128)
-      hipLaunchKernelGGL((gather_f32_dma_kernel<64, 128, 2, 2, false, 2, true>), grid, dim3(256), 0, st, p);
-    else
-      hipLaunchKernelGGL((gather_f32_dma_kernel<128, 32, 4, 1, false, 2, true>), grid, dim3(256), 0, st, p);
-    g_last_conv_kernel = PSEG_KERNEL_GATHER_RING_GENERIC;
-    PSEG_LAUNCH_CHECK();
-    return PSEG_OK;
-  }
-  if (f32dma_covers(pl, precision, Cin, K, taps, p.skip_taps != 0)) {   // (3 = two-stage ring for the tap-skipping problems as well)
-    // Exact-fp32 problems whose K-steps never straddle a tap run on the LDS-DMA kernel (same tile, same statistics
-    // layout).  PSEG_CONV_F32DMA: 3 (default) = two-stage ring for every such problem, 2 = only for those without tap
-    // skipping (51.0 -> 49.4 ms; the tap-skipping ASPP / stride-2 problems add 49.0 -> 48.4) -- 64 / 48 KB of LDS
-    // and ~100 VGPRs, so TWO blocks of 8 waves (128x128) or THREE of 4 (128x64) share a CU and one block's prologue /
-    // epilogue hides behind the others' MFMAs: medium and short-K layers +5-10 % (128x128 maps, 64 channels: 98 -> 109 TF),
-    // fp32 step 51.0 -> 49.4 ms; 1 = three-stage ring everywhere (one block per CU: equal to the register-staged kernel in
-    // the step); 0 = register-staged kernel only.  The large layers sit at the sustained fp32-MFMA rate either way.
-    p.precision = 0;
-    p.amax_a = p.amax_b = nullptr;
-    const bool sk = p.skip_taps != 0;
-    // pointwise convs with short contractions and more tiles than the device holds blocks: the persistent kernel
-    // (PSEG_CONV_PW=0: off; PSEG_CONV_PW_KT: longest contraction, in K-steps, that takes it)
-    if (cfg().conv_pw != 0 && p.row_perm == 3 && !sk && pl.kt_total <= cfg().conv_pw_kt && cfg().conv_f32dma >= 2) {
-      const int ntiles = pl.gridM * pl.gridN;
-      int rc = 1;
-      if (pl.tile.bm == 128 && pl.tile.bn == 128) rc = launch_pw<128, 128, 2, 4>(ntiles, st, p);
-      else if (pl.tile.bm == 128 && pl.tile.bn == 64) rc = launch_pw<128, 64, 2, 2>(ntiles, st, p);
-      else if (pl.tile.bm == 64 && pl.tile.bn == 128) rc = launch_pw<64, 128, 2, 2>(ntiles, st, p);
-      if (rc == 0) {
-        g_last_conv_kernel = PSEG_KERNEL_GATHER_POINTWISE;
-        PSEG_LAUNCH_CHECK();
-        return PSEG_OK;
-      }
-    }
-    // narrow 3x3 (128x32 plan tile): the halo-staged kernel where the map is made of whole 8 x 16 patches
-    if (halo_f32_covers(pl, p, Cin, taps, taps_w, s_out, s_in, dstep, off0, Hi, Wi, Ho, Wo, sk)) {
-      p.row_perm = 2;
-      p.patch_w = kHaloPW;
-      p.patch_hw = kHaloPH * kHaloPW;
-      p.patches_per_row = Wo / kHaloPW;
-      if (pl.tile.bn == 32) hipLaunchKernelGGL((gather_f32_halo_kernel<4, 1>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((gather_f32_halo_kernel<2, 2>), grid, dim3(256), 0, st, p);
-      g_last_conv_kernel = PSEG_KERNEL_GATHER_HALO;
-      PSEG_LAUNCH_CHECK();
-      return PSEG_OK;
-    }
-    bool launched = true;
-    const bool two = cfg().conv_f32dma >= 2;   // two-stage ring: 64 / 48 KB of LDS, 2 / 3 blocks per CU
-#define PSEG_DMA_LAUNCH(BM_, BN_, WM_, WN_, NTHR)                                                                    \
-  do {                                                                                                               \
-    if (two && sk) hipLaunchKernelGGL((gather_f32_dma_kernel<BM_, BN_, WM_, WN_, true, 2>), grid, dim3(NTHR), 0, st, p);   \
-    else if (two) hipLaunchKernelGGL((gather_f32_dma_kernel<BM_, BN_, WM_, WN_, false, 2>), grid, dim3(NTHR), 0, st, p);   \
-    else if (sk) hipLaunchKernelGGL((gather_f32_dma_kernel<BM_, BN_, WM_, WN_, true, 3>), grid, dim3(NTHR), 0, st, p);     \
-    else hipLaunchKernelGGL((gather_f32_dma_kernel<BM_, BN_, WM_, WN_, false, 3>), grid, dim3(NTHR), 0, st, p);            \
-  } while (0)
-    if (pl.tile.bm == 128 && pl.tile.bn == 128) {
-      PSEG_DMA_LAUNCH(128, 128, 2, 4, 512);
-    } else if (pl.tile.bm == 128 && pl.tile.bn == 64) {
-      PSEG_DMA_LAUNCH(128, 64, 2, 2, 256);
-    } else if (pl.tile.bm == 64 && pl.tile.bn == 128) {
-      PSEG_DMA_LAUNCH(64, 128, 2, 2, 256);
-    } else if (pl.tile.bm == 128 && pl.tile.bn == 32 && cfg().conv_dma32 != 0) {
-      PSEG_DMA_LAUNCH(128, 32, 4, 1, 256);     // narrow outputs (HRNet's 32-channel branch, the 21-class classifier)
-#undef PSEG_DMA_LAUNCH
-    } else {
-      launched = false;
-    }
-    if (launched) {
-      g_last_conv_kernel = PSEG_KERNEL_GATHER_RING;
-      PSEG_LAUNCH_CHECK();
-      return PSEG_OK;
-    }
-  }
-  typedef void (*Kfn)(const GatherConvParams);
+  g_last_conv_kernel = c.kernel;
+  switch (c.kernel) {
+    case PSEG_KERNEL_GATHER_LIMB_DMA:
+      if (p.skip_taps) hipLaunchKernelGGL(gather_limb_dma_kernel<true>, grid, dim3(512), 0, st, p);
+      else hipLaunchKernelGGL(gather_limb_dma_kernel<false>, grid, dim3(512), 0, st, p);
+      break;
+    case PSEG_KERNEL_GATHER_RING_GENERIC:
+      p.gen_spt = FastDiv((uint32_t)(Cin / 4));
+      p.gen_kw = FastDiv((uint32_t)g.taps_w);
+      launch_ring(c, grid, st, p);
+      break;
+    case PSEG_KERNEL_GATHER_RING:
+      launch_ring(c, grid, st, p);
+      break;
+    case PSEG_KERNEL_GATHER_HALO:
+      launch_halo(c, grid, st, p);
+      break;
+    default: {
+      typedef void (*Kfn)(const GatherConvParams);
 #define PSEG_GATHER_ROW(SK, PR, BIG)                                                                   \
   {gather_conv_kernel<128, 128, 2, 2, SK, PR>, gather_conv_kernel<128, 64, 2, 2, SK, PR>,              \
    gather_conv_kernel<128, 32, 4, 1, SK, PR>, gather_conv_kernel<64, 128, 2, 2, SK, PR>,               \
    gather_conv_kernel<32, 128, 1, 4, SK, PR>, BIG}
-  // the 256x128 tile (8 waves, one block per CU) exists for the LDS-staging-bound two-limb variants
-  static const Kfn fns32[2][6] = {PSEG_GATHER_ROW(false, 0, nullptr), PSEG_GATHER_ROW(true, 0, nullptr)};
-  static const Kfn fnsb3[2][6] = {PSEG_GATHER_ROW(false, 1, (gather_conv_kernel<256, 128, 4, 2, false, 1>)),
-                                  PSEG_GATHER_ROW(true, 1, (gather_conv_kernel<256, 128, 4, 2, true, 1>))};
-  static const Kfn fnsb6[2][6] = {PSEG_GATHER_ROW(false, 2, nullptr), PSEG_GATHER_ROW(true, 2, nullptr)};
-  static const Kfn fnsh3[2][6] = {PSEG_GATHER_ROW(false, 3, (gather_conv_kernel<256, 128, 4, 2, false, 3>)),
-                                  PSEG_GATHER_ROW(true, 3, (gather_conv_kernel<256, 128, 4, 2, true, 3>))};
+      // the 256x128 tile (8 waves, one block per CU) exists for the LDS-staging-bound two-limb variants
+      static const Kfn fns32[2][6] = {PSEG_GATHER_ROW(false, 0, nullptr), PSEG_GATHER_ROW(true, 0, nullptr)};
+      static const Kfn fnsb3[2][6] = {PSEG_GATHER_ROW(false, 1, (gather_conv_kernel<256, 128, 4, 2, false, 1>)),
+                                      PSEG_GATHER_ROW(true, 1, (gather_conv_kernel<256, 128, 4, 2, true, 1>))};
+      static const Kfn fnsb6[2][6] = {PSEG_GATHER_ROW(false, 2, nullptr), PSEG_GATHER_ROW(true, 2, nullptr)};
+      static const Kfn fnsh3[2][6] = {PSEG_GATHER_ROW(false, 3, (gather_conv_kernel<256, 128, 4, 2, false, 3>)),
+                                      PSEG_GATHER_ROW(true, 3, (gather_conv_kernel<256, 128, 4, 2, true, 3>))};
 #undef PSEG_GATHER_ROW
-  p.precision = precision;
-  p.amax_a = amax_a;
-  p.amax_b = amax_b;
-  if (precision == 3 && (amax_a == nullptr || amax_b == nullptr)) {
-    set_error("conv: PSEG_PREC_FP16X3 needs the amax of both operands");
-    return PSEG_ERR_ARG;
+      const auto& fns = precision == 3 ? fnsh3 : precision == 2 ? fnsb6 : precision == 1 ? fnsb3 : fns32;
+      const int rc = launch_tiles<GatherConvParams, Kfn, 6>(fns, p.skip_taps != 0, pl.tile, grid, p, st);
+      if (rc != PSEG_OK) return rc;
+      if (pl.splits > 1) return launch_slab_reduce((const float*)workspace, M * N, pl.splits, y, ldy, M, N, bias, accumulate, st);
+      return PSEG_OK;
+    }
   }
-  g_last_conv_kernel = PSEG_KERNEL_GATHER_REGISTER;
-  int rc = precision == 3   ? launch_tiles<GatherConvParams, Kfn, 6>(fnsh3, p.skip_taps != 0, pl.tile, grid, p, st)
-           : precision == 2 ? launch_tiles<GatherConvParams, Kfn, 6>(fnsb6, p.skip_taps != 0, pl.tile, grid, p, st)
-           : precision == 1 ? launch_tiles<GatherConvParams, Kfn, 6>(fnsb3, p.skip_taps != 0, pl.tile, grid, p, st)
-                            : launch_tiles<GatherConvParams, Kfn, 6>(fns32, p.skip_taps != 0, pl.tile, grid, p, st);
-  if (rc != PSEG_OK) return rc;
-  if (pl.splits > 1) {
-    const long long total = M * N;
-    const int blocks = (int)(total / 256 + 1 < 4096 ? total / 256 + 1 : 4096);
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)workspace, M * N, pl.splits, y,
-                       ldy, M, N, bias, accumulate);
-    PSEG_LAUNCH_CHECK();
-  }
+  PSEG_LAUNCH_CHECK();
   return PSEG_OK;
 }
 
@@ -3186,27 +3187,35 @@ int pseg_config_reload(void) {
 }
 const char* pseg_last_error(void) { return pseg::last_error(); }
 
-// the forward plan of a conv as far as the statistics layout depends on it (tile shape; K does not enter)
-static FwdPlan plan_fwd_stats(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int stride, int pad, int dil) {
-  const long long M = (long long)B * Ho * Wo;
+// forward conv as a gather GEMM: rows = output pixels, gather source = x
+static GatherGeom fwd_geom(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil) {
+  return GatherGeom{(long long)B * Ho * Wo, Cout, kh * kw * Cin, Cin, H, W, Ho, Wo, kh, kw, stride, 1, dil, -pad};
+}
+
+// data gradient as a gather GEMM: rows = input pixels, N = Cin, contraction over (r,s,co); gather source = dy [B,Ho,Wo,Cout]
+static GatherGeom dgrad_geom(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil) {
+  return GatherGeom{(long long)B * H * W, Cin, kh * kw * Cout, Cout, Ho, Wo, H, W, kh, kw, 1, stride, -dil, pad};
+}
+
+// the choice of a forward conv with fused statistics (the queries know Ho / Wo only: the smallest input that gives them)
+static GatherChoice select_fwd_stats(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int stride, int pad, int dil) {
   const int H = (Ho - 1) * stride - 2 * pad + dil * (kh - 1) + 1, W = (Wo - 1) * stride - 2 * pad + dil * (kw - 1) + 1;
-  DilGeom geom;
-  const bool has_geom = dil_geom(geom, Ho, Wo, H, W, kh, kw, Cin, stride, 1, dil, -pad);
-  return plan_gather(M, Cout, kh * kw * Cin, false, has_geom ? &geom : nullptr);
+  return select_gather(GatherProblem{fwd_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil), PSEG_PREC_FP32, true, false,
+                                     false, false, false});
 }
 
 int pseg_conv2d_stat_rows(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int stride, int pad, int dil) {
-  FwdPlan pl = plan_fwd_stats(B, Ho, Wo, Cin, Cout, kh, kw, stride, pad, dil);
-  return pl.gridM * waves_m(pl.tile);
+  return select_fwd_stats(B, Ho, Wo, Cin, Cout, kh, kw, stride, pad, dil).stat_rows();
 }
 
 int pseg_conv2d_stat_group(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int stride, int pad, int dil) {
-  FwdPlan pl = plan_fwd_stats(B, Ho, Wo, Cin, Cout, kh, kw, stride, pad, dil);
-  return pl.tile.bm / waves_m(pl.tile);
+  const TileCfg t = select_fwd_stats(B, Ho, Wo, Cin, Cout, kh, kw, stride, pad, dil).pl.tile;
+  return t.bm / waves_m(t);
 }
 
 int64_t pseg_conv2d_fwd_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw) {
   const long long M = (long long)B * Ho * Wo;
+  // plans without geometry (the signature has no stride / dilation): geometry only swaps tiles among plans of >= 256 tiles, never splits
   FwdPlan pl = plan_gather(M, Cout, kh * kw * Cin);
   return pl.splits > 1 ? (int64_t)pl.splits * M * Cout * 4 : 0;
 }
@@ -3220,16 +3229,10 @@ int pseg_conv2d_fwd(const float* x, int ldx, const float* w, const float* bias, 
   PSEG_REQUIRE(Ho == (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1,
                "conv2d_fwd: Ho/Wo (%d,%d) inconsistent with H/W (%d,%d) k=%dx%d s=%d p=%d d=%d", Ho, Wo, H, W, kh, kw,
                stride, pad, dil);
-  const int K = kh * kw * Cin;
-  FwdPlan pl = plan_fwd_stats(B, Ho, Wo, Cin, Cout, kh, kw, stride, pad, dil);
-  if (stat != nullptr && pl.splits > 1) {
-    set_error("conv2d_fwd: fused statistics are unavailable when the plan splits K; use pseg_col_stats");
-    return PSEG_ERR_ARG;
-  }
   PSEG_REQUIRE(precision >= 0 && precision <= 3, "conv2d_fwd: precision must be one of PSEG_PREC_*");
-  return run_gather(x, nhwc_bytes(B, H, W, Cin, ldx), ldx, w, y, ldy, bias, stat, B, H, W, Cin, Ho, Wo,
-                    Cout, kw, K, stride, 1, dil, -pad, accumulate, precision, (const unsigned*)amax_x,
-                    (const unsigned*)amax_w, workspace, workspace_bytes, (hipStream_t)stream);
+  return run_gather(fwd_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil), x, nhwc_bytes(B, H, W, Cin, ldx), ldx, w, y, ldy,
+                    bias, stat, accumulate, precision, (const unsigned*)amax_x, (const unsigned*)amax_w, workspace,
+                    workspace_bytes, (hipStream_t)stream);
 }
 
 int pseg_conv2d_dgrad(const float* dy, int ldy, const float* wT, float* dx, int ldx, int B, int H, int W, int Cin, int Ho,
@@ -3239,35 +3242,19 @@ int pseg_conv2d_dgrad(const float* dy, int ldy, const float* wT, float* dx, int 
   PSEG_REQUIRE(dy && wT && dx, "conv2d_dgrad: null pointer");
   PSEG_REQUIRE(precision >= 0 && precision <= 3, "conv2d_dgrad: precision must be one of PSEG_PREC_*");
   PSEG_REQUIRE(stride >= 1 && dil >= 1 && pad >= 0, "conv2d_dgrad: bad geometry");
-  // GEMM rows = input pixels (B,H,W); contraction over (r,s,co); gather source = dy [B,Ho,Wo,Cout]
-  const int K = kh * kw * Cout;
-  return run_gather(dy, nhwc_bytes(B, Ho, Wo, Cout, ldy), ldy, wT, dx, ldx, nullptr, nullptr, B, Ho, Wo, Cout, H,
-                    W, Cin, kw, K, 1, stride, -dil, pad, accumulate, precision, (const unsigned*)amax_dy,
-                    (const unsigned*)amax_w, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-// geometry of the dgrad gather problem as run_gather sees it -> does the LDS-DMA kernel (the one with the fused sums) take it?
-static bool dgrad_bnstat_plan(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil,
-                              FwdPlan& pl) {
-  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 || kh * kw > 32 || Cin % 4 != 0) return false;
-  const long long M = (long long)B * H * W;
-  if (M >= (1LL << 31)) return false;
-  const int K = kh * kw * Cout;
-  DilGeom geom;
-  const bool has_geom = dil_geom(geom, H, W, Ho, Wo, kh, kw, Cout, 1, stride, -dil, pad);
-  pl = plan_gather(M, Cin, K, false, has_geom ? &geom : nullptr);
-  const int adil = dil;
-  const bool skip = (adil >= 4 && kh * kw > 1 && Cout % BK == 0 && cfg().conv_noskip == 0) ||
-                    (stride == 2 && H % 2 == 0 && W % 2 == 0 && ((H / 2) * (W / 2)) % pl.tile.bm == 0 && pl.splits == 1 &&
-                     Cout % BK == 0 && cfg().conv_noskip == 0);
-  return f32dma_covers(pl, 0, Cout, K, kh * kw, skip);
+  return run_gather(dgrad_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil), dy, nhwc_bytes(B, Ho, Wo, Cout, ldy), ldy, wT,
+                    dx, ldx, nullptr, nullptr, accumulate, precision, (const unsigned*)amax_dy, (const unsigned*)amax_w,
+                    workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int pseg_conv2d_dgrad_bnstat_rows(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
                                   int dil) {
-  FwdPlan pl;
-  if (!dgrad_bnstat_plan(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil, pl)) return 0;
-  return pl.gridM * waves_m(pl.tile);
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 || kh * kw > 32 || Cin % 4 != 0) return 0;
+  if ((long long)B * H * W >= (1LL << 31)) return 0;
+  // the problem pseg_conv2d_dgrad_bnstat hands to run_gather: 0 unless a kernel that carries the fused sums takes it
+  const GatherChoice c = select_gather(GatherProblem{dgrad_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil), PSEG_PREC_FP32,
+                                                     false, false, false, true, false});
+  return c.kernel == kGatherRefused ? 0 : c.stat_rows();
 }
 
 int pseg_conv2d_dgrad_bnstat(const float* dy, int ldy, const float* wT, float* dx, int ldx, int B, int H, int W, int Cin, int Ho,
@@ -3286,9 +3273,8 @@ int pseg_conv2d_dgrad_bnstat(const float* dy, int ldy, const float* wT, float* d
                "conv2d_dgrad_bnstat: part_rows (%d) is not pseg_conv2d_dgrad_bnstat_rows() of this problem (0 = not covered)",
                part_rows);
   const BnsArgs bns{y_prev, ldy_prev, mean, invstd, scale, shift, act, part_db, part_dg, part_rows};
-  const int K = kh * kw * Cout;
-  return run_gather(dy, nhwc_bytes(B, Ho, Wo, Cout, ldy), ldy, wT, dx, ldx, nullptr, nullptr, B, Ho, Wo, Cout, H, W, Cin, kw, K, 1,
-                    stride, -dil, pad, 0, PSEG_PREC_FP32, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, nullptr, &bns);
+  return run_gather(dgrad_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil), dy, nhwc_bytes(B, Ho, Wo, Cout, ldy), ldy, wT,
+                    dx, ldx, nullptr, nullptr, 0, PSEG_PREC_FP32, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, nullptr, &bns);
 }
 
 int pseg_split_planes(const float* x, int ldx, int64_t M, int C, uint16_t* hi, uint16_t* lo, int ldp, void* stream) {
@@ -3303,17 +3289,13 @@ int pseg_split_planes(const float* x, int ldx, int64_t M, int C, uint16_t* hi, u
   return PSEG_OK;
 }
 
-// plan of the data gradient as a gather GEMM: rows = input pixels, N = Cin, gather source = dy (Cout channels)
-static FwdPlan plan_dgrad(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil) {
-  DilGeom geom;
-  const bool has_geom = dil_geom(geom, H, W, Ho, Wo, kh, kw, Cout, 1, stride, -dil, pad);
-  return plan_gather((long long)B * H * W, Cin, kh * kw * Cout, true, has_geom ? &geom : nullptr);
-}
-
 int pseg_conv2d_dgrad_planes_ok(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
                                 int dil) {
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  return dma_plan_ok(plan_dgrad(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil), Cout, Cin) ? 1 : 0;
+  // the problem pseg_conv2d_dgrad_planes hands to run_gather
+  const GatherChoice c = select_gather(GatherProblem{dgrad_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil),
+                                                     PSEG_PREC_BF16X3, false, false, true, false, false});
+  return c.kernel == PSEG_KERNEL_GATHER_LIMB_DMA ? 1 : 0;
 }
 
 int pseg_conv2d_dgrad_planes(const uint16_t* dy_hi, const uint16_t* dy_lo, int ldp, const uint16_t* wT_hi,
@@ -3321,12 +3303,11 @@ int pseg_conv2d_dgrad_planes(const uint16_t* dy_hi, const uint16_t* dy_lo, int l
                              int Cout, int kh, int kw, int stride, int pad, int dil, int accumulate, void* stream) {
   PSEG_REQUIRE(dy_hi && dy_lo && wT_hi && wT_lo && dx, "conv2d_dgrad_planes: null pointer");
   PSEG_REQUIRE(stride >= 1 && dil >= 1 && pad >= 0 && ldp >= Cout, "conv2d_dgrad_planes: bad geometry");
-  const int K = kh * kw * Cout;
-  LimbPlanes pln{dy_hi, dy_lo, wT_hi, wT_lo, ldp, (((long long)B * Ho * Wo - 1) * ldp + Cout) * 2, (long long)Cin * K * 2};
+  const GatherGeom g = dgrad_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil);
+  LimbPlanes pln{dy_hi, dy_lo, wT_hi, wT_lo, ldp, (((long long)B * Ho * Wo - 1) * ldp + Cout) * 2, (long long)Cin * g.K * 2};
   // (x / w of run_gather are unused on this path; pass the planes for the alignment checks)
-  return run_gather(reinterpret_cast<const float*>(dy_hi), 16, 4, reinterpret_cast<const float*>(wT_hi), dx, ldx, nullptr,
-                    nullptr, B, Ho, Wo, Cout, H, W, Cin, kw, K, 1, stride, -dil, pad, accumulate, PSEG_PREC_BF16X3, nullptr,
-                    nullptr, nullptr, 0, (hipStream_t)stream, &pln);
+  return run_gather(g, reinterpret_cast<const float*>(dy_hi), 16, 4, reinterpret_cast<const float*>(wT_hi), dx, ldx, nullptr,
+                    nullptr, accumulate, PSEG_PREC_BF16X3, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, &pln);
 }
 
 // All filters of a model in ONE launch: jobs[j] = {w, wT, Cout, taps, Cin, first 32x32 tile of job j} (6 x int64, device

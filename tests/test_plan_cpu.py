@@ -1,0 +1,59 @@
+"""The planning decisions behind the integer-only conv queries are pinned: tests/golden/plan_table.json holds the answers of every
+query (tests/plan_queries.py) for a few hundred conv problems, under the default environment and under PSEG_CONV_NOSKIP=1, written
+by tools/plan_table.py with the library of the commit BEFORE the kernel selection was gathered into select_gather (conv_mfma.hip).
+A selection that moves changes the statistics layout, the fused-sum rows or a workspace size, and shows here without a GPU."""
+import json
+import os
+import re
+
+import pytest
+
+import plan_queries
+from pytorch_segmentation_amd import _lib
+from pytorch_segmentation_amd.csrc import build as csrc_build
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+TABLE = json.load(open(os.path.join(HERE, 'golden', 'plan_table.json')))
+
+
+@pytest.fixture(scope='module')
+def lib():
+    csrc_build.build(verbose=False)
+    return _lib.load()
+
+
+@pytest.mark.parametrize('setting', sorted(TABLE))
+def test_queries_answer_as_pinned(lib, setting, monkeypatch):
+    rows = TABLE[setting]
+    assert len(rows) >= 200
+    for kv in filter(None, setting.split(',')):
+        monkeypatch.setenv(*kv.split('='))
+    _lib.clear_query_cache()          # the library re-reads its PSEG_* switches
+    try:
+        bad = []
+        for prob, want in rows:
+            got = plan_queries.answers(lib, tuple(prob))
+            bad += ['%s %s: %d, pinned %d' % (prob, n, g, w) for n, g, w in zip(plan_queries.NAMES, got, want) if g != w]
+            assert len(got) == len(want) == len(plan_queries.NAMES)
+        assert not bad, '%d answers moved:\n%s' % (len(bad), '\n'.join(bad[:40]))
+    finally:
+        monkeypatch.undo()
+        _lib.clear_query_cache()
+
+
+def test_pinned_problems_cover_the_cases():
+    probs = [tuple(p) for p, _ in TABLE['']]
+    assert {p[5] for p in probs} >= {1, 3, 7} and {p[6] for p in probs} >= {1, 2} and {p[8] for p in probs} >= {1, 2, 6, 12, 18}
+    assert {p[0] for p in probs} >= {1, 2, 16} and {p[1] for p in probs} & {33, 65}
+    assert {p[3] for p in probs} & {3, 21} and {p[3] for p in probs} & {48, 144}
+
+
+def test_gather_selection_is_written_once():
+    """conv_mfma.hip decides tap skipping nowhere itself (gather_row_order, conv_common.h, does, for fp32 and fp16) and the rows
+    query has no plan of its own."""
+    src = open(os.path.join(os.path.dirname(HERE), 'pytorch_segmentation_amd', 'csrc', 'conv_mfma.hip')).read()
+    host = src[src.index('static GatherChoice select_gather('):]
+    assert 'dgrad_bnstat_plan' not in src and 'plan_fwd_stats' not in src and 'plan_dgrad' not in src
+    assert not re.search(r'skip_taps\s*=[^=]', host)
+    common = open(os.path.join(os.path.dirname(HERE), 'pytorch_segmentation_amd', 'csrc', 'conv_common.h')).read()
+    assert len(re.findall(r'\.skip_taps = \(', common)) == 1
