@@ -553,7 +553,6 @@ struct FwdPlan {
   int patch_h, patch_w;   // > 0: GEMM rows run in patch_h x patch_w pixel patches (dilated convs), one M tile per patch
   bool banded;            // GEMM rows sorted by liveness class (takes precedence over the patch order)
   BandMap band;
-  int hwaves = 0;         // fp16 kernels: waves per block of the chosen instantiation (0: the tile's default)
 };
 
 // Geometry of a gather problem, for the dilated-conv planning below (unit strides only).
@@ -842,6 +841,16 @@ struct GatherGeom {
   long long M;
   int N, K, Cin, Hi, Wi, Ho, Wo, taps_h, taps_w, s_out, s_in, dstep, off0;
 };
+
+// forward conv as a gather GEMM: rows = output pixels, gather source = x
+static GatherGeom fwd_geom(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil) {
+  return GatherGeom{(long long)B * Ho * Wo, Cout, kh * kw * Cin, Cin, H, W, Ho, Wo, kh, kw, stride, 1, dil, -pad};
+}
+
+// data gradient as a gather GEMM: rows = input pixels, N = Cin, contraction over (r,s,co); gather source = dy [B,Ho,Wo,Cout]
+static GatherGeom dgrad_geom(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil) {
+  return GatherGeom{(long long)B * H * W, Cin, kh * kw * Cout, Cout, Ho, Wo, H, W, kh, kw, 1, stride, -dil, pad};
+}
 
 // Order of the GEMM rows (GatherConvParams::row_perm and the fields that go with it) and whether dead taps are skipped.
 struct RowOrder {

@@ -20,6 +20,7 @@
 #include "half_io.h"
 
 #include <type_traits>
+#include <utility>
 
 namespace pseg {
 
@@ -2046,10 +2047,77 @@ __global__ __launch_bounds__(256) void convert2d_kernel(const TI* __restrict__ x
 // ------------------------------------------------------------------------------------------------ host side
 static long long nhwc_bytes_h(int B, int H, int W, int C, int ld) { return (((long long)B * H * W - 1) * ld + C) * 2; }
 
-// wave rows of a tile (= statistics groups per row tile)
-static int waves_m_h(TileCfg t) { return (t.bn == 32 || (t.bm == 256 && t.bn == 128)) ? 4 : 2; }
+// The tiles of the fp16 gather kernels, stated once: select_gather_h picks an entry, the launch helpers map it to template
+// arguments.  Which (entry, K-step, ring depth) is instantiated is said by the constexpr predicates below and nowhere else: the
+// selection calls them at run time, the launch helpers in `if constexpr`.  Threads per block = 64 * wm * wn; the wm wave rows are
+// the statistics groups of a row tile.
+struct HTile {
+  int bm, bn, wm, wn;
+  bool persistent;   // gather_hp_kernel is instantiated for it
+  int bns_kb;        // K-steps (32 | 64) with which it carries the fused BatchNorm-backward sums: the tiles the Bottleneck and
+                     // BasicBlock data gradients of the reference's models are planned onto
+  bool lab;          // lab build only: PSEG_HCONV_TILE = 1..4, in this order
+};
+constexpr HTile kHTiles[] = {{128, 128, 2, 4, true, 32 | 64, false}, {128, 64, 2, 2, true, 32 | 64, false},
+                             {64, 128, 2, 2, true, 0, false},        {128, 32, 4, 1, true, 32, false},
+                             {128, 128, 2, 2, true, 0, true},        {256, 128, 4, 2, true, 0, true},
+                             {256, 256, 2, 4, false, 0, true},       {256, 128, 4, 4, false, 0, true}};
+constexpr int kNumHTiles = (int)(sizeof(kHTiles) / sizeof(kHTiles[0])), kFirstLabHTile = 4;
 
-// tiles the fp16 gather kernel is instantiated for
+static int h_tile_index(TileCfg t) {
+  for (int i = 0; i < kFirstLabHTile; ++i)
+    if (kHTiles[i].bm == t.bm && kHTiles[i].bn == t.bn) return i;
+  return -1;
+}
+
+constexpr long long kLdsBytes = 160 * 1024;
+// LDS of one block: gather_h_kernel's epilogue patch overlays its ring, gather_hp_kernel keeps a (smaller) patch beside it
+constexpr long long h_ring_lds(const HTile& t, int kb, int st) {
+  const long long ring = (long long)st * (t.bm + t.bn) * kb * 2, patch = (long long)t.wm * t.wn * 32 * (t.bn / t.wn + 4) * 4;
+  return ring > patch ? ring : patch;
+}
+constexpr long long h_persistent_lds(const HTile& t, int kb, int st) {
+  return (long long)st * (t.bm + t.bn) * kb * 2 + (long long)t.wm * t.wn * 32 * 72;
+}
+// the 256x256 tile only with the short K-step: its accumulators take 128 registers
+constexpr bool h_kb_ok(const HTile& t, int kb) { return !(t.bm == 256 && t.bn == 256 && kb == 64); }
+// (K-step, ring depth) pairs with a BNS = true instantiation: what the heuristics of select_gather_h give those data gradients
+constexpr bool h_bns_steps(int kb, int st, bool persistent) {
+  return (kb == 32 && st == 3) || (kb == 64 && (st == 2 || (st == 3 && !persistent)));
+}
+constexpr bool h_ring_exists(const HTile& t, int kb, int st, bool bns) {
+  return (PSEG_LAB || !t.lab) && h_ring_lds(t, kb, st) <= kLdsBytes && h_kb_ok(t, kb) &&
+         (!bns || ((t.bns_kb & kb) != 0 && h_bns_steps(kb, st, false)));
+}
+constexpr bool h_persistent_exists(const HTile& t, int kb, int st, bool bns) {      // (its ring is two or three deep)
+  return (PSEG_LAB || !t.lab) && t.persistent && st <= 3 && h_persistent_lds(t, kb, st) <= kLdsBytes &&
+         (!bns || ((t.bns_kb & kb) != 0 && h_bns_steps(kb, st, true)));
+}
+
+// f(std::integral_constant<int, tile>, HSteps<kb, st>) for a table entry, a K-step (32 / 64) and a ring depth (2 .. 4): the
+// entry's fields and the steps are then template arguments
+template <int KB, int ST>
+struct HSteps { static constexpr int kb = KB, st = ST; };
+template <int I, typename F>
+static void with_h_steps(int kb, int st, F&& f) {
+  constexpr std::integral_constant<int, I> tile{};
+  if (kb == 32 && st == 2) f(tile, HSteps<32, 2>{});
+  else if (kb == 32 && st == 3) f(tile, HSteps<32, 3>{});
+  else if (kb == 32) f(tile, HSteps<32, 4>{});
+  else if (st == 2) f(tile, HSteps<64, 2>{});
+  else if (st == 3) f(tile, HSteps<64, 3>{});
+  else f(tile, HSteps<64, 4>{});
+}
+template <typename F, int... I>
+static void with_h_kernel(int tile, int kb, int st, F&& f, std::integer_sequence<int, I...>) {
+  (void)((tile == I && (with_h_steps<I>(kb, st, f), true)) || ...);
+}
+template <typename F>
+static void with_h_kernel(int tile, int kb, int st, F&& f) {
+  with_h_kernel(tile, kb, st, f, std::make_integer_sequence<int, kNumHTiles>{});
+}
+
+// the planner's tile -> one of the default entries of kHTiles
 static TileCfg half_tile(TileCfg t) {
   if (t.bm == 256) t.bm = 128;
   if (t.bm == 32) t.bm = 64;
@@ -2058,8 +2126,6 @@ static TileCfg half_tile(TileCfg t) {
   return t;
 }
 
-// the plan of a gather problem on the fp16 kernels: tile and row order from the shared planner (the schedules of the
-// dilated convs carry over), never split-K
 // K-step (halves per LDS row) of a gather problem.  PSEG_HCONV_KB = 32 / 64 forces one.
 static int hconv_kb(int Cin, int K) {
   static const int forced = env_int("PSEG_HCONV_KB", 0);
@@ -2071,91 +2137,159 @@ static int hconv_kb(int Cin, int K) {
   return K <= 576 ? 32 : 64;
 }
 
-static FwdPlan plan_gather_h(long long M, int N, int K, int Cin, const DilGeom* geom) {
-  const int kb = hconv_kb(Cin, K);
-  // dilated convs: the tap-skipping schedules (patch / class-sorted rows, 64-row candidate tiles) are only searched when the
-  // plain plan lands on a 4-wave tile; a 128x128 / 8-wave problem runs dense and row-major (see run_gather_h)
-  FwdPlan pl = plan_gather(M, N, K, false, nullptr);
-  if (geom != nullptr && Cin % kb == 0 && !(pl.tile.bm == 128 && pl.tile.bn == 128)) pl = plan_gather(M, N, K, false, geom);
+// A gather problem as run_gather_h sees it: the geometry plus what the caller asks of the kernel.
+struct HGatherProblem : GatherGeom {
+  bool y_f32, bias, stats, accumulate, bns;   // fp32 result / bias / fused statistics / y += / fused BatchNorm-backward sums
+};
+
+// Everything run_gather_h decides before it launches; the queries read their answers off the same choice.
+struct HGatherChoice {
+  FwdPlan pl;       // (never split-K)
+  RowOrder order;
+  int tile;         // entry of kHTiles; -1: a forced tile that nothing is instantiated for
+  int kb, stages;   // K-step and ring depth of gather_h_kernel
+  int variant;      // 0 plain, 1 tap-skipping, 2 GENERIC (channels off the K-step grid)
+  bool persistent;  // gather_hp_kernel is offered the problem first (and is instantiated for it, with the sums if asked) ...
+  int pstages;      // ... with a ring this deep
+  bool ring;        // the gather_h_kernel instantiation exists (with the sums if asked)
+  bool sums;        // the fused sums are asked for and a kernel that carries them takes the problem
+  int halo;         // lab build: 1 gather_hh_kernel, 2 gather_hr_kernel run instead
+  int wave_rows() const { return tile >= 0 ? kHTiles[tile].wm : 2; }
+  int stat_rows() const { return pl.gridM * wave_rows(); }
+};
+
+// The one place that picks the kernel of an fp16 gather conv.  Pure: launches nothing, touches no device.
+static HGatherChoice select_gather_h(const HGatherProblem& q) {
+  HGatherChoice c;
+  const long long M = q.M;
+  const int N = q.N, K = q.K;
+  [[maybe_unused]] const int taps = q.taps_h * q.taps_w;     // (lab kernels below)
+  const int kb = c.kb = hconv_kb(q.Cin, K);
+  const bool generic = q.Cin % kb != 0;
+  // the plan: tile and row order from the shared planner (the schedules of the dilated convs carry over), never split-K.
+  // Dilated convs: the tap-skipping schedules (patch / class-sorted rows, 64-row candidate tiles) are only searched when the
+  // plain plan lands on a 4-wave tile; a 128x128 / 8-wave problem runs dense and row-major (see below)
+  DilGeom geom;
+  const bool has_geom = !generic && dil_geom(geom, q.Ho, q.Wo, q.Hi, q.Wi, q.taps_h, q.taps_w, q.Cin, q.s_out, q.s_in, q.dstep, q.off0);
+  FwdPlan& pl = c.pl;
+  pl = plan_gather(M, N, K, false, nullptr);
+  if (has_geom && !(pl.tile.bm == 128 && pl.tile.bn == 128)) pl = plan_gather(M, N, K, false, &geom);
   // one 128x128 block per CU beats two 128x64 blocks on the fp16 kernels when the problem has no dead taps to skip (round 4:
   // M = 16384 x N = 256, K = 2304 -- layer 3's 3x3 convs -- 32 -> 28 us, 26 on the persistent kernel): the kernels are bound by
   // the bytes a CU pulls through its LDS-DMA path, and the wider tile pulls a third fewer of them per MAC
-  if (geom == nullptr && pl.tile.bm == 128 && pl.tile.bn == 64 && N >= 128 && K >= 1024 &&
-      (long long)cdiv(M, 128) * cdiv(N, 128) >= 256 && cfg().conv_bm == 0) {
+  if (!has_geom && pl.tile.bm == 128 && pl.tile.bn == 64 && N >= 128 && K >= 1024 &&
+      (long long)cdiv(M, 128) * cdiv(N, 128) >= 256 && cfg().conv_bm == 0)
     pl.tile.bn = 128;
-    pl.gridN = cdiv(N, 128);
+  TileCfg t = half_tile(pl.tile);
+  // (a substituted tile keeps the plain row order: patch / class schedules were costed for the planner's own tile)
+  if (t.bm != pl.tile.bm) {
+    pl.patch_h = pl.patch_w = 0;
+    pl.banded = false;
   }
-  const TileCfg t = half_tile(pl.tile);
-  if (t.bm != pl.tile.bm || t.bn != pl.tile.bn || pl.splits > 1) {
-    // (a substituted tile keeps the plain row order: patch / class schedules were costed for the planner's own tile)
-    if (t.bm != pl.tile.bm) {
-      pl.patch_h = pl.patch_w = 0;
-      pl.banded = false;
-    }
-    pl.tile = t;
-    pl.gridM = cdiv(M, t.bm);
-    pl.gridN = cdiv(N, t.bn);
-  }
-  pl.splits = 1;
+  c.tile = h_tile_index(t);
 #if PSEG_LAB
   // experiments (tools/bench_conv_half.py): PSEG_HCONV_TILE = 1: 128x128 on four waves (64x64 wave tiles), 2: 256x128 on eight
-  // waves (64x64 wave tiles), 3: 256x256 on eight waves (128x64 wave tiles)
+  // waves (64x64 wave tiles), 3: 256x256 on eight waves (128x64 wave tiles), 4: 256x128 on sixteen waves
   const int forced_tile = cfg().hconv_tile;
-  if (forced_tile >= 1 && forced_tile <= 4 && Cin % kb == 0 && !pl.banded && pl.patch_w == 0) {
-    pl.tile = forced_tile == 1 ? TileCfg{128, 128} : (forced_tile == 3 ? TileCfg{256, 256} : TileCfg{256, 128});
-    pl.hwaves = forced_tile == 1 ? 4 : (forced_tile == 4 ? 16 : 8);
-    pl.gridM = cdiv(M, pl.tile.bm);
-    pl.gridN = cdiv(N, pl.tile.bn);
+  if (forced_tile >= 1 && forced_tile <= 4 && !generic && !pl.banded && pl.patch_w == 0) {
+    c.tile = kFirstLabHTile + forced_tile - 1;
+    t = TileCfg{kHTiles[c.tile].bm, kHTiles[c.tile].bn};
   }
 #endif
-  pl.kt_total = cdiv(K, kb);
-  pl.kt_per_split = pl.kt_total;
-  return pl;
-}
-
-// Instantiations that also exist with the fused BatchNorm-backward sums (BNS = true): the tiles / K-steps / ring depths the
-// Bottleneck and BasicBlock data gradients of the reference's models are planned onto (every tap live, channels in whole
-// K-steps).  Everything else answers pseg_conv2d_dgrad_bnstat_rows_h with 0 and the layer keeps its reduction pass.
-template <int BM, int BN, int WM, int WN, int KB, int ST>
-constexpr bool kHasBnsH = ((BM == 128 && BN == 128 && WM == 2 && WN == 4) || (BM == 128 && BN == 64 && WM == 2 && WN == 2) ||
-                           (BM == 128 && BN == 32 && WM == 4 && WN == 1 && KB == 32)) &&
-                          ((KB == 32 && ST == 3) || (KB == 64 && (ST == 2 || ST == 3)));
-template <int BM, int BN, int WM, int WN, int KB, int ST>
-constexpr bool kHasBnsHP = ((BM == 128 && BN == 128 && WM == 2 && WN == 4) || (BM == 128 && BN == 64 && WM == 2 && WN == 2) ||
-                            (BM == 128 && BN == 32 && WM == 4 && WN == 1 && KB == 32)) &&
-                           ((KB == 32 && ST == 3) || (KB == 64 && ST == 2));
-
-// one instantiation of the gather kernel, if it exists (LDS budget; the 256x256 tile only with the short K-step: its
-// accumulators take 128 registers).  bns: 0 plain; 1 launch the BNS instantiation; 2 only say whether it exists.
-template <int BM, int BN, int WM, int WN, int KB, int ST>
-static bool launch_gather_h(int variant, dim3 grid, hipStream_t st, const HGatherParams& hp, int bns = 0) {
-  constexpr int NW = WM * WN;
-  constexpr long long ring = (long long)ST * (BM + BN) * KB * 2, patch = (long long)NW * 32 * (BN / WN + 4) * 4;
-  constexpr bool fits = (ring > patch ? ring : patch) <= 160 * 1024 && !(BM == 256 && BN == 256 && KB == 64);
-  if constexpr (fits) {
-    const dim3 block(64 * NW);
-    if (bns != 0) {
-      if constexpr (kHasBnsH<BM, BN, WM, WN, KB, ST>) {
-        if (variant != 0) return false;
-        if (bns == 1) hipLaunchKernelGGL((gather_h_kernel<BM, BN, WM, WN, false, false, KB, ST, true>), grid, block, 0, st, hp);
-        return true;
-      } else {
-        return false;
-      }
-    }
-    if (variant == 2) hipLaunchKernelGGL((gather_h_kernel<BM, BN, WM, WN, false, true, KB, ST>), grid, block, 0, st, hp);
-    else if (variant == 1) hipLaunchKernelGGL((gather_h_kernel<BM, BN, WM, WN, true, false, KB, ST>), grid, block, 0, st, hp);
-    else hipLaunchKernelGGL((gather_h_kernel<BM, BN, WM, WN, false, false, KB, ST>), grid, block, 0, st, hp);
-    return true;
+  pl.tile = t;
+  pl.gridM = cdiv(M, t.bm);
+  pl.gridN = cdiv(N, t.bn);
+  pl.splits = 1;
+  pl.kt_total = pl.kt_per_split = cdiv(K, kb);
+  // dilated convs: K-steps of taps that are zero padding for the whole M tile are skipped -- on the 4-wave tiles only.  On the
+  // 128x128 / 8-wave tile (the ASPP data gradients: N = 2048) the tap-skipping instantiation is SLOWER than the dense one
+  // even where it skips half the K-steps (rate 18: 269 us patch-ordered / 290 class-sorted against 168 dense; rate 6: 272
+  // against 206): one fp16 MFMA pass per tile leaves the kernel bound by its operand stream, a padding tap's DMA is an
+  // out-of-range no-op that costs nothing, and the skip bookkeeping does (tools/bench_conv_half.py with PSEG_CONV_NOSKIP=1).
+  // The stride-2 data gradient runs parity-homogeneous tiles on every tile shape, 3/4 of the taps skipped.
+  c.order = gather_row_order(q, pl, !generic && !(t.bm == 128 && t.bn == 128), !generic);
+  c.variant = generic ? 2 : (c.order.skip_taps != 0 ? 1 : 0);
+  c.halo = 0;
+#if PSEG_LAB
+  // halo-staged 3x3 (gather_hh_kernel): unit stride, dilation 1 / 2, channels in whole 64-chunks, maps of 8 x 16 patches, fp16
+  // result without bias / accumulation, and a plan whose statistics layout is the kernel's (128-row tiles, two wave rows).
+  // PSEG_HCONV_HALO=0: off.  With the filter as a ring of taps (gather_hr_kernel): 128x128 / 128x64 plan tiles, every tap live.
+  // PSEG_HCONV_HALO2=0: off.
+  static const int halo_on = env_int("PSEG_HCONV_HALO", 0), halo2_on = env_int("PSEG_HCONV_HALO2", 0);      // (opt-in)
+  const int adil = q.dstep < 0 ? -q.dstep : q.dstep;
+  const bool halo_shape = !q.bns && !generic && taps == 9 && q.taps_w == 3 && q.s_out == 1 && q.s_in == 1 && (adil == 1 || adil == 2) &&
+                          q.Cin % 64 == 0 && q.Hi == q.Ho && q.Wi == q.Wo && t.bm == 128 && (t.bn == 128 || t.bn == 64) &&
+                          c.order.row_perm == 0;
+  if (halo_on != 0 && halo_shape && (q.off0 == -adil || q.off0 == adil) && q.Ho % kHaloPH == 0 && q.Wo % kHaloPW == 0 && !q.y_f32 &&
+      !q.bias && !q.accumulate && N >= 64 && M % 128 == 0) {
+    c.halo = 1;
+    c.order.skip_taps = 0;
+    c.order.row_perm = 2;
+    c.order.patch_w = kHaloPW;
+    c.order.patch_hw = kHaloPH * kHaloPW;
+    c.order.patches_per_row = q.Wo / kHaloPW;
+  } else if (halo2_on != 0 && halo_shape && q.off0 == -q.dstep && q.Ho % kH2PH == 0 && q.Wo % kH2PW == 0 && c.order.skip_taps == 0) {
+    c.halo = 2;
+    c.order.row_perm = 2;
+    c.order.patch_w = kH2PW;
+    c.order.patch_hw = kH2PH * kH2PW;
+    c.order.patches_per_row = q.Wo / kH2PW;
   }
-  return false;
+#endif
+  // ring depth (PSEG_HCONV_STAGES forces 2 / 3 / 4); never deeper than the K loop is long
+  // Measured: the short K-step always wants three stages (its blocks are small: four to eight stay resident anyway); the long
+  // one only on narrow tiles with a deep contraction, where a deeper ring costs no resident block the grid needs -- the ASPP
+  // convs (128x64 tiles, K = 18432: 237 -> 197 / 208 -> 151 us with three stages) and the classifier (128x32, K = 3456: 238 ->
+  // 158 us with four); 128x128 tiles lose their second resident block to a third stage (layer-4 3x3: 89 -> 98 us).
+  static const int forced_stages = env_int("PSEG_HCONV_STAGES", 0);
+  int stages = 2;
+  if (kb == 32) stages = 3;
+  else if (t.bn == 32 && K >= 2048) stages = 4;
+  else if (t.bn == 64 && t.bm == 128 && K >= 2048) stages = 3;
+  if (forced_stages >= 2 && forced_stages <= 4) stages = forced_stages;
+  if (pl.kt_total < stages) stages = pl.kt_total < 2 ? 2 : pl.kt_total;
+  c.stages = stages;
+  c.pstages = stages >= 3 ? 3 : 2;
+  // the persistent kernel (gather_hp_kernel) takes the launches it covers; PSEG_HCONV_PERSIST=0 keeps everything on
+  // gather_h_kernel (A/B runs)
+  // ... where it pays: SHORT contractions (measured, tools/bench_conv_half.py with PSEG_HCONV_PERSIST=0/1: K <= 1280 -- 2 to 20
+  // K-steps per tile -- 5-20 % faster, e.g. 64 -> 256 channels on 128x128 maps 41 -> 35 us = 4.8 TB/s of operand + result
+  // traffic; the deep contractions lose 15-25 %: ring + patch leave one resident block per CU where gather_h_kernel holds two,
+  // and with 32+ K-steps per tile there is no chain left to hide).  PSEG_HCONV_PERSIST=2 forces it everywhere it is valid.
+  const int persist = cfg().hconv_persist;
+  const bool offered = persist != 0 && c.variant == 0 && !q.y_f32 && !q.bias && !q.accumulate &&
+                       (c.order.row_perm == 0 || c.order.row_perm == 3) && pl.kt_total >= 1 &&
+                       (pl.kt_total <= cfg().hconv_persist_kt || persist == 2 || (pl.gridM * pl.gridN <= 256 && pl.kt_total <= 48));
+  c.persistent = offered && c.halo == 0 && c.tile >= 0 && h_persistent_exists(kHTiles[c.tile], kb, c.pstages, q.bns);
+  // (the sums come with the plain variant only: every tap live, channels in whole K-steps)
+  c.ring = c.tile >= 0 && h_ring_exists(kHTiles[c.tile], kb, stages, q.bns) && !(q.bns && c.variant != 0);
+  c.sums = q.bns && !q.y_f32 && !q.bias && !q.stats && !q.accumulate && (c.persistent || c.ring);
+  return c;
 }
 
-// one instantiation of the persistent kernel, if it exists; grid = min(tiles, CUs x resident blocks per CU)
+// the gather_h_kernel instantiation of a choice (c.ring says that it exists)
+static void launch_ring_h(const HGatherChoice& c, bool bns, hipStream_t st, const HGatherParams& hp) {
+  const dim3 grid((unsigned)(c.pl.gridM * c.pl.gridN), 1, 1);
+  with_h_kernel(c.tile, c.kb, c.stages, [&](auto tile, auto steps) {
+    constexpr HTile t = kHTiles[decltype(tile)::value];
+    constexpr int KB = decltype(steps)::kb, ST = decltype(steps)::st;
+    if constexpr (h_ring_exists(t, KB, ST, false)) {
+      const dim3 block(64 * t.wm * t.wn);
+      if (bns) {
+        if constexpr (h_ring_exists(t, KB, ST, true))
+          hipLaunchKernelGGL((gather_h_kernel<t.bm, t.bn, t.wm, t.wn, false, false, KB, ST, true>), grid, block, 0, st, hp);
+      } else if (c.variant == 2) hipLaunchKernelGGL((gather_h_kernel<t.bm, t.bn, t.wm, t.wn, false, true, KB, ST>), grid, block, 0, st, hp);
+      else if (c.variant == 1) hipLaunchKernelGGL((gather_h_kernel<t.bm, t.bn, t.wm, t.wn, true, false, KB, ST>), grid, block, 0, st, hp);
+      else hipLaunchKernelGGL((gather_h_kernel<t.bm, t.bn, t.wm, t.wn, false, false, KB, ST>), grid, block, 0, st, hp);
+    }
+  });
+}
+
+// one instantiation of the persistent kernel; grid = min(tiles, CUs x resident blocks per CU).  false: the device does not say
+// how many blocks it holds
 template <int BM, int BN, int WM, int WN, int KB, int ST, bool BNS>
-static bool launch_gather_hp_one(int ntiles, hipStream_t st, const HGatherParams& hp, bool dry) {
+static bool launch_gather_hp_one(int ntiles, hipStream_t st, const HGatherParams& hp) {
   constexpr int NW = WM * WN;
-  constexpr long long lds_bytes = (long long)ST * (BM + BN) * KB * 2 + (long long)NW * 32 * 72;
   static int resident = 0;      // blocks of this instantiation the device holds at once
   if (resident == 0) {
     int per_cu = 0, dev = 0;
@@ -2164,30 +2298,32 @@ static bool launch_gather_hp_one(int ntiles, hipStream_t st, const HGatherParams
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gather_hp_kernel<BM, BN, WM, WN, KB, ST, BNS>, 64 * NW, 0) != hipSuccess ||
         per_cu < 1)
       return false;
-    const int by_lds = (int)((160 * 1024) / lds_bytes);
+    const int by_lds = (int)(kLdsBytes / h_persistent_lds(HTile{BM, BN, WM, WN, true, 0, false}, KB, ST));
     if (per_cu > by_lds) per_cu = by_lds;
     static const int forced_bpc = env_int("PSEG_HCONV_PBPC", 0);
     if (forced_bpc > 0 && forced_bpc < per_cu) per_cu = forced_bpc;
     resident = prop.multiProcessorCount * per_cu;
   }
-  if (dry) return true;
   const int blocks = ntiles < resident ? ntiles : resident;
   hipLaunchKernelGGL((gather_hp_kernel<BM, BN, WM, WN, KB, ST, BNS>), dim3((unsigned)blocks), dim3(64 * NW), 0, st, hp);
   return true;
 }
 
-template <int BM, int BN, int WM, int WN, int KB, int ST>
-static bool launch_gather_hp(int ntiles, hipStream_t st, const HGatherParams& hp, int bns = 0) {
-  constexpr int NW = WM * WN;
-  constexpr long long lds_bytes = (long long)ST * (BM + BN) * KB * 2 + (long long)NW * 32 * 72;
-  if constexpr (lds_bytes <= 160 * 1024 && !(BM == 256 && BN == 256)) {
-    if (bns != 0) {
-      if constexpr (kHasBnsHP<BM, BN, WM, WN, KB, ST>) return launch_gather_hp_one<BM, BN, WM, WN, KB, ST, true>(ntiles, st, hp, bns == 2);
-      else return false;
+// the gather_hp_kernel instantiation of a choice (c.persistent says that it exists)
+static bool launch_persistent_h(const HGatherChoice& c, bool bns, hipStream_t st, const HGatherParams& hp) {
+  bool ok = false;
+  with_h_kernel(c.tile, c.kb, c.pstages, [&](auto tile, auto steps) {
+    constexpr HTile t = kHTiles[decltype(tile)::value];
+    constexpr int KB = decltype(steps)::kb, ST = decltype(steps)::st;
+    if constexpr (h_persistent_exists(t, KB, ST, false)) {
+      if (bns) {
+        if constexpr (h_persistent_exists(t, KB, ST, true)) ok = launch_gather_hp_one<t.bm, t.bn, t.wm, t.wn, KB, ST, true>(hp.ntiles, st, hp);
+      } else {
+        ok = launch_gather_hp_one<t.bm, t.bn, t.wm, t.wn, KB, ST, false>(hp.ntiles, st, hp);
+      }
     }
-    return launch_gather_hp_one<BM, BN, WM, WN, KB, ST, false>(ntiles, st, hp, false);
-  }
-  return false;
+  });
+  return ok;
 }
 
 // fused BatchNorm-backward partial sums of a data gradient (pseg_conv2d_dgrad_bnstat_h): the producing layer's y (fp16), its
@@ -2195,44 +2331,39 @@ static bool launch_gather_hp(int ntiles, hipStream_t st, const HGatherParams& hp
 struct HBnsArgs {
   const void* y;
   int ldy;
-  const float* mean;
-  const float* invstd;
-  const float* scale;
-  const float* shift;
+  const float *mean, *invstd, *scale, *shift;
   int act;
-  float* db;
-  float* dg;
+  float *db, *dg;
   int rows;
 };
 
-// plan of a gather problem as run_gather_h makes it (shared with the queries)
-static FwdPlan plan_run_h(int Hi, int Wi, int Cin, int Ho, int Wo, long long M, int N, int taps_w, int K, int s_out, int s_in,
-                          int dstep, int off0) {
-  const int kb = hconv_kb(Cin, K);
-  const bool generic = Cin % kb != 0;
-  DilGeom geom;
-  const bool has_geom = !generic && dil_geom(geom, Ho, Wo, Hi, Wi, (K / Cin) / taps_w, taps_w, Cin, s_out, s_in, dstep, off0);
-  return plan_gather_h(M, N, K, Cin, has_geom ? &geom : nullptr);
+// What the kernels' 32-bit row indices and buffer addressing cap, for the launch and the fused-sums query alike: nullptr, or
+// what is wrong with the sizes of a problem whose source tensor spans x_bytes and whose result has the row stride ldy.
+static const char* gather_size_error_h(const GatherGeom& g, long long x_bytes, int ldy) {
+  if (!(g.M > 0 && g.M < (1LL << 31) && g.N > 0 && g.K > 0)) return "empty or oversized problem";
+  if (!(x_bytes < kMaxBytes && (long long)g.N * g.K * 2 < kMaxBytes)) return "x or w exceeds 2 GiB";
+  if (!(((g.M - 1) * ldy + g.N) * 4 < (1LL << 40))) return "output too large";
+  return nullptr;
 }
 
-static int run_gather_h(const void* x, long long x_bytes, int ldx, const void* w, void* y, int ldy, int y_f32,
-                        const float* bias, float* stat, int B, int Hi, int Wi, int Cin, int Ho, int Wo, int N, int taps_w,
-                        int K, int s_out, int s_in, int dstep, int off0, int accumulate, hipStream_t st,
-                        const HBnsArgs* bns = nullptr, bool bns_query = false) {
-  const long long M = (long long)B * Ho * Wo;
-  PSEG_REQUIRE(M > 0 && M < (1LL << 31) && N > 0 && K > 0, "conv_h: empty or oversized problem M=%lld N=%d K=%d", M, N, K);
-  PSEG_REQUIRE(Cin % 8 == 0 && ldx % 8 == 0 && N % 8 == 0, "conv_h: Cin (%d), ldx (%d) and the output channels (%d) must be multiples of 8",
-               Cin, ldx, N);
-  PSEG_REQUIRE(ldy % (y_f32 ? 4 : 8) == 0 && ldy >= N, "conv_h: ldy (%d) must cover N and be a multiple of %d", ldy, y_f32 ? 4 : 8);
+// validate, select, fill the parameters from the choice and launch
+static int run_gather_h(const GatherGeom& g, const void* x, long long x_bytes, int ldx, const void* w, void* y, int ldy, int y_f32,
+                        const float* bias, float* stat, int accumulate, hipStream_t st, const HBnsArgs* bns = nullptr) {
+  const char* size_error = gather_size_error_h(g, x_bytes, ldy);
+  PSEG_REQUIRE(size_error == nullptr, "conv_h: %s (M=%lld N=%d K=%d, x %lld bytes, ldy %d)", size_error, g.M, g.N, g.K, x_bytes, ldy);
+  PSEG_REQUIRE(g.Cin % 8 == 0 && ldx % 8 == 0 && g.N % 8 == 0, "conv_h: Cin (%d), ldx (%d) and the output channels (%d) must be multiples of 8",
+               g.Cin, ldx, g.N);
+  PSEG_REQUIRE(ldy % (y_f32 ? 4 : 8) == 0 && ldy >= g.N, "conv_h: ldy (%d) must cover N and be a multiple of %d", ldy, y_f32 ? 4 : 8);
   PSEG_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)y & 15) == 0, "conv_h: x / w / y must be 16-byte aligned");
-  const long long w_bytes = (long long)N * K * 2;
-  PSEG_REQUIRE(x_bytes < kMaxBytes && w_bytes < kMaxBytes, "conv_h: tensor exceeds 2 GiB (x %lld, w %lld bytes)", x_bytes, w_bytes);
-  PSEG_REQUIRE(((M - 1) * ldy + N) * 4 < (1LL << 40), "conv_h: output too large");
-  const int kb = hconv_kb(Cin, K);
-  const bool generic = Cin % kb != 0;
-  FwdPlan pl = plan_run_h(Hi, Wi, Cin, Ho, Wo, M, N, taps_w, K, s_out, s_in, dstep, off0);
+  PSEG_REQUIRE(bns == nullptr || (!y_f32 && bias == nullptr && !accumulate && stat == nullptr),
+               "conv_h: the fused BatchNorm-backward sums need an fp16 result without bias / accumulation / statistics");
 
-  HGatherParams hp;
+  const HGatherChoice c = select_gather_h(HGatherProblem{g, y_f32 != 0, bias != nullptr, stat != nullptr, accumulate != 0, bns != nullptr});
+  const FwdPlan& pl = c.pl;
+  PSEG_REQUIRE(bns == nullptr || bns->rows == c.stat_rows(), "conv_h: %d partial rows handed in, the plan has %d",
+               bns == nullptr ? 0 : bns->rows, c.stat_rows());
+
+  HGatherParams hp{};      // (everything a gather conv of this kind does not use stays null / zero)
   GatherConvParams& p = hp.g;
   p.x = reinterpret_cast<const float*>(x);
   p.w = reinterpret_cast<const float*>(w);
@@ -2240,33 +2371,14 @@ static int run_gather_h(const void* x, long long x_bytes, int ldx, const void* w
   p.ldy = ldy;
   p.bias = bias;
   p.stat = stat;
-  p.stat_rows = pl.gridM * waves_m_h(pl.tile);
+  p.stat_rows = c.stat_rows();
   p.x_bytes = (uint32_t)x_bytes;
-  p.w_bytes = (uint32_t)w_bytes;
+  p.w_bytes = (uint32_t)((long long)g.N * g.K * 2);
   p.ldx = ldx;
   p.accumulate = accumulate;
-  p.slab_stride = 0;
-  const int taps = K / Cin;
-  [[maybe_unused]] const int adil = dstep < 0 ? -dstep : dstep;     // (lab kernels below)
-  p.ktiles_per_tap = generic ? 1 : Cin / kb;
-  // dilated convs: K-steps of taps that are zero padding for the whole M tile are skipped -- on the 4-wave tiles only.  On the
-  // 128x128 / 8-wave tile (the ASPP data gradients: N = 2048) the tap-skipping instantiation is SLOWER than the dense one
-  // even where it skips half the K-steps (rate 18: 269 us patch-ordered / 290 class-sorted against 168 dense; rate 6: 272
-  // against 206): one fp16 MFMA pass per tile leaves the kernel bound by its operand stream, a padding tap's DMA is an
-  // out-of-range no-op that costs nothing, and the skip bookkeeping does (tools/bench_conv_half.py with PSEG_CONV_NOSKIP=1).
-  // The stride-2 data gradient runs parity-homogeneous tiles on every tile shape, 3/4 of the taps skipped.
-  const GatherGeom geo{M, N, K, Cin, Hi, Wi, Ho, Wo, taps / taps_w, taps_w, s_out, s_in, dstep, off0};
-  set_gather_geometry(p, geo, pl, gather_row_order(geo, pl, !generic && !(pl.tile.bm == 128 && pl.tile.bn == 128), !generic));
-  p.trace = nullptr;
-  p.bns_y = nullptr;
-  p.bns_ldy = 0;
-  p.bns_mean = p.bns_invstd = p.bns_scale = p.bns_shift = nullptr;
-  p.bns_act = 0;
-  p.bns_db = p.bns_dg = nullptr;
+  p.ktiles_per_tap = c.variant == 2 ? 1 : g.Cin / c.kb;
+  set_gather_geometry(p, g, pl, c.order);
   if (bns != nullptr) {
-    PSEG_REQUIRE(!y_f32 && bias == nullptr && !accumulate && stat == nullptr,
-                 "conv_h: the fused BatchNorm-backward sums need an fp16 result without bias / accumulation / statistics");
-    PSEG_REQUIRE(bns->rows == p.stat_rows, "conv_h: %d partial rows handed in, the plan has %d", bns->rows, p.stat_rows);
     p.bns_y = reinterpret_cast<const float*>(bns->y);
     p.bns_ldy = bns->ldy;
     p.bns_mean = bns->mean;
@@ -2277,37 +2389,19 @@ static int run_gather_h(const void* x, long long x_bytes, int ldx, const void* w
     p.bns_db = bns->db;
     p.bns_dg = bns->dg;
   }
-  p.precision = 0;
-  p.amax_a = p.amax_b = nullptr;
-  p.xh = p.xl = p.wh = p.wl = nullptr;
-  p.xp_bytes = p.wp_bytes = 0;
-  p.ldxp = 0;
   hp.y_f32 = y_f32;
 #if PSEG_LAB
   static const int ablate = env_int("PSEG_HCONV_ABLATE", 0);
   hp.ablate = ablate;
-#else
-  hp.ablate = 0;
 #endif
-  hp.cin_div = FastDiv((uint32_t)Cin);
-  hp.kw_div = FastDiv((uint32_t)taps_w);
-  hp.howo_div = FastDiv((uint32_t)p.HoWo);      // (after the pointwise rewrite above: HoWo = Wo = M there)
+  hp.cin_div = FastDiv((uint32_t)g.Cin);
+  hp.kw_div = FastDiv((uint32_t)g.taps_w);
+  hp.howo_div = FastDiv((uint32_t)p.HoWo);      // (after the pointwise rewrite of set_gather_geometry: HoWo = Wo = M there)
   hp.wo_div = FastDiv((uint32_t)p.Wo);
+  hp.ntiles = pl.gridM * pl.gridN;
 #if PSEG_LAB
-  // halo-staged 3x3 (gather_hh_kernel): unit stride, dilation 1 / 2, channels in whole 64-chunks, maps of 8 x 16 patches, fp16
-  // result without bias / accumulation, and a plan whose statistics layout is the kernel's (128-row tiles, two wave rows).
-  // PSEG_HCONV_HALO=0: off.
-  static const int halo_on = env_int("PSEG_HCONV_HALO", 0);      // (lab build, opt-in)
-  if (halo_on != 0 && bns == nullptr && !generic && taps == 9 && taps_w == 3 && s_out == 1 && s_in == 1 && (adil == 1 || adil == 2) &&
-      (off0 == -adil || off0 == adil) && Cin % 64 == 0 && Ho % kHaloPH == 0 && Wo % kHaloPW == 0 && Hi == Ho && Wi == Wo &&
-      !y_f32 && bias == nullptr && !accumulate && pl.tile.bm == 128 && (pl.tile.bn == 128 || pl.tile.bn == 64) && N >= 64 &&
-      p.row_perm == 0 && M % 128 == 0) {
-    p.row_perm = 2;
-    p.skip_taps = 0;
-    p.patch_w = kHaloPW;
-    p.patch_hw = kHaloPH * kHaloPW;
-    p.patches_per_row = Wo / kHaloPW;
-    const dim3 hgrid((unsigned)((M / 128) * cdiv(N, 128)), 1, 1);
+  if (c.halo == 1) {
+    const dim3 hgrid((unsigned)((g.M / 128) * cdiv(g.N, 128)), 1, 1);
     static const int hstages = env_int("PSEG_HCONV_HALO_STAGES", 6);
     if (hstages <= 3) hipLaunchKernelGGL(gather_hh_kernel<3>, hgrid, dim3(512), 0, st, hp);
     else if (hstages == 4) hipLaunchKernelGGL(gather_hh_kernel<4>, hgrid, dim3(512), 0, st, hp);
@@ -2316,111 +2410,24 @@ static int run_gather_h(const void* x, long long x_bytes, int ldx, const void* w
     PSEG_LAUNCH_CHECK();
     return PSEG_OK;
   }
-#endif
-#if PSEG_LAB
-  // halo-staged 3x3 with the filter as a ring of taps (gather_hr_kernel): unit stride, dilation 1 / 2, channels in whole 64-chunks,
-  // maps of 8 x 16 patches, 128x128 / 128x64 plan tiles, every tap live.  PSEG_HCONV_HALO2=0: off.
-  static const int halo2_on = env_int("PSEG_HCONV_HALO2", 0);
-  if (halo2_on != 0 && bns == nullptr && !generic && taps == 9 && taps_w == 3 && s_out == 1 && s_in == 1 && (adil == 1 || adil == 2) &&
-      off0 == -dstep && Cin % 64 == 0 && Ho % kH2PH == 0 && Wo % kH2PW == 0 && Hi == Ho && Wi == Wo && pl.tile.bm == 128 &&
-      (pl.tile.bn == 128 || pl.tile.bn == 64) && p.row_perm == 0 && p.skip_taps == 0) {
-    p.row_perm = 2;
-    p.patch_w = kH2PW;
-    p.patch_hw = kH2PH * kH2PW;
-    p.patches_per_row = Wo / kH2PW;
-    hp.howo_div = FastDiv((uint32_t)p.HoWo);
-    hp.wo_div = FastDiv((uint32_t)p.Wo);
-    const dim3 hgrid((unsigned)(pl.gridM * pl.gridN), 1, 1);
-    if (pl.tile.bn == 128) hipLaunchKernelGGL(gather_hr_kernel<4>, hgrid, dim3(512), 0, st, hp);
-    else hipLaunchKernelGGL(gather_hr_kernel<2>, hgrid, dim3(256), 0, st, hp);
+  if (c.halo == 2) {
+    if (pl.tile.bn == 128) hipLaunchKernelGGL(gather_hr_kernel<4>, dim3((unsigned)hp.ntiles), dim3(512), 0, st, hp);
+    else hipLaunchKernelGGL(gather_hr_kernel<2>, dim3((unsigned)hp.ntiles), dim3(256), 0, st, hp);
     PSEG_LAUNCH_CHECK();
     return PSEG_OK;
   }
 #endif
-  const dim3 grid((unsigned)(pl.gridM * pl.gridN), 1, 1);
-  const bool sk = p.skip_taps != 0;
-  // ring depth (PSEG_HCONV_STAGES forces 2 / 3 / 4); never deeper than the K loop is long
-  // Measured: the short K-step always wants three stages (its blocks are small: four to eight stay resident anyway); the long
-  // one only on narrow tiles with a deep contraction, where a deeper ring costs no resident block the grid needs -- the ASPP
-  // convs (128x64 tiles, K = 18432: 237 -> 197 / 208 -> 151 us with three stages) and the classifier (128x32, K = 3456: 238 ->
-  // 158 us with four); 128x128 tiles lose their second resident block to a third stage (layer-4 3x3: 89 -> 98 us).
-  static const int forced_stages = env_int("PSEG_HCONV_STAGES", 0);
-  int stages = 2;
-  if (kb == 32) stages = 3;
-  else if (pl.tile.bn == 32 && K >= 2048) stages = 4;
-  else if (pl.tile.bn == 64 && pl.tile.bm == 128 && K >= 2048) stages = 3;
-  if (forced_stages >= 2 && forced_stages <= 4) stages = forced_stages;
-  if (pl.kt_total < stages) stages = pl.kt_total < 2 ? 2 : pl.kt_total;
-  bool launched = true;
-  const int variant = generic ? 2 : (sk ? 1 : 0);
-  const int bmode = bns == nullptr ? 0 : (bns_query ? 2 : 1);
-  // the persistent kernel (gather_hp_kernel) takes the launches it covers; PSEG_HCONV_PERSIST=0 keeps everything on
-  // gather_h_kernel (A/B runs)
-  const int persist = cfg().hconv_persist;
-  hp.ntiles = pl.gridM * pl.gridN;
-  // ... where it pays: SHORT contractions (measured, tools/bench_conv_half.py with PSEG_HCONV_PERSIST=0/1: K <= 1280 -- 2 to 20
-  // K-steps per tile -- 5-20 % faster, e.g. 64 -> 256 channels on 128x128 maps 41 -> 35 us = 4.8 TB/s of operand + result
-  // traffic; the deep contractions lose 15-25 %: ring + patch leave one resident block per CU where gather_h_kernel holds two,
-  // and with 32+ K-steps per tile there is no chain left to hide).  PSEG_HCONV_PERSIST=2 forces it everywhere it is valid.
-  const int persist_max_kt = cfg().hconv_persist_kt;
-  if (persist != 0 && variant == 0 && !y_f32 && bias == nullptr && !accumulate && (p.row_perm == 0 || p.row_perm == 3) &&
-      pl.kt_total >= 1 && (pl.kt_total <= persist_max_kt || persist == 2 || (hp.ntiles <= 256 && pl.kt_total <= 48))) {
-    const int pst = stages >= 3 ? 3 : 2;
-    bool ok = false;
-#define PSEG_HP_LAUNCH(BM_, BN_, WM_, WN_)                                                                    \
-  do {                                                                                                         \
-    if (kb == 32 && pst == 2) ok = launch_gather_hp<BM_, BN_, WM_, WN_, 32, 2>(hp.ntiles, st, hp, bmode);      \
-    else if (kb == 32) ok = launch_gather_hp<BM_, BN_, WM_, WN_, 32, 3>(hp.ntiles, st, hp, bmode);             \
-    else if (pst == 2) ok = launch_gather_hp<BM_, BN_, WM_, WN_, 64, 2>(hp.ntiles, st, hp, bmode);             \
-    else ok = launch_gather_hp<BM_, BN_, WM_, WN_, 64, 3>(hp.ntiles, st, hp, bmode);                           \
-  } while (0)
-#if PSEG_LAB
-    if (pl.tile.bm == 128 && pl.tile.bn == 128 && pl.hwaves == 4) PSEG_HP_LAUNCH(128, 128, 2, 2);
-    else if (pl.tile.bm == 256 && pl.tile.bn == 128 && pl.hwaves == 16) ok = false;
-    else if (pl.tile.bm == 256 && pl.tile.bn == 128) PSEG_HP_LAUNCH(256, 128, 4, 2);
-    else
-#endif
-    if (pl.tile.bm == 128 && pl.tile.bn == 128) PSEG_HP_LAUNCH(128, 128, 2, 4);
-    else if (pl.tile.bm == 128 && pl.tile.bn == 64) PSEG_HP_LAUNCH(128, 64, 2, 2);
-    else if (pl.tile.bm == 64 && pl.tile.bn == 128) PSEG_HP_LAUNCH(64, 128, 2, 2);
-    else if (pl.tile.bm == 128 && pl.tile.bn == 32) PSEG_HP_LAUNCH(128, 32, 4, 1);
-#undef PSEG_HP_LAUNCH
-    if (ok) {
-      if (bns_query) return PSEG_OK;
-      g_last_conv_kernel = PSEG_KERNEL_GATHER_H_PERSISTENT;
-      PSEG_LAUNCH_CHECK();
-      return PSEG_OK;
-    }
+  if (c.persistent && launch_persistent_h(c, bns != nullptr, st, hp)) {
+    g_last_conv_kernel = PSEG_KERNEL_GATHER_H_PERSISTENT;
+    PSEG_LAUNCH_CHECK();
+    return PSEG_OK;
   }
-#define PSEG_H_LAUNCH(BM_, BN_, WM_, WN_)                                                                       \
-  do {                                                                                                          \
-    if (kb == 32 && stages == 2) launched = launch_gather_h<BM_, BN_, WM_, WN_, 32, 2>(variant, grid, st, hp, bmode);  \
-    else if (kb == 32 && stages == 3) launched = launch_gather_h<BM_, BN_, WM_, WN_, 32, 3>(variant, grid, st, hp, bmode); \
-    else if (kb == 32) launched = launch_gather_h<BM_, BN_, WM_, WN_, 32, 4>(variant, grid, st, hp, bmode);            \
-    else if (stages == 2) launched = launch_gather_h<BM_, BN_, WM_, WN_, 64, 2>(variant, grid, st, hp, bmode);         \
-    else if (stages == 3) launched = launch_gather_h<BM_, BN_, WM_, WN_, 64, 3>(variant, grid, st, hp, bmode);         \
-    else launched = launch_gather_h<BM_, BN_, WM_, WN_, 64, 4>(variant, grid, st, hp, bmode);                          \
-  } while (0)
-#if PSEG_LAB
-  if (pl.tile.bm == 128 && pl.tile.bn == 128 && pl.hwaves == 4) PSEG_H_LAUNCH(128, 128, 2, 2);
-  else if (pl.tile.bm == 256 && pl.tile.bn == 128 && pl.hwaves == 16) PSEG_H_LAUNCH(256, 128, 4, 4);
-  else if (pl.tile.bm == 256 && pl.tile.bn == 128) PSEG_H_LAUNCH(256, 128, 4, 2);
-  else if (pl.tile.bm == 256 && pl.tile.bn == 256) PSEG_H_LAUNCH(256, 256, 2, 4);
-  else
-#endif
-  if (pl.tile.bm == 128 && pl.tile.bn == 128) PSEG_H_LAUNCH(128, 128, 2, 4);
-  else if (pl.tile.bm == 128 && pl.tile.bn == 64) PSEG_H_LAUNCH(128, 64, 2, 2);
-  else if (pl.tile.bm == 64 && pl.tile.bn == 128) PSEG_H_LAUNCH(64, 128, 2, 2);
-  else if (pl.tile.bm == 128 && pl.tile.bn == 32) PSEG_H_LAUNCH(128, 32, 4, 1);
-  else launched = false;
-#undef PSEG_H_LAUNCH
-  if (!launched) {
-    if (bns_query) return PSEG_ERR_ARG;
-    set_error("conv_h: no kernel for tile %dx%d (K-step %d, %d stages)%s", pl.tile.bm, pl.tile.bn, kb, stages,
+  if (!c.ring) {
+    set_error("conv_h: no kernel for tile %dx%d (K-step %d, %d stages)%s", pl.tile.bm, pl.tile.bn, c.kb, c.stages,
               bns != nullptr ? " with the fused BatchNorm-backward sums" : "");
     return PSEG_ERR_ARG;
   }
-  if (bns_query) return PSEG_OK;
+  launch_ring_h(c, bns != nullptr, st, hp);
   g_last_conv_kernel = PSEG_KERNEL_GATHER_H;
   PSEG_LAUNCH_CHECK();
   return PSEG_OK;
@@ -2568,22 +2575,19 @@ using namespace pseg;
 
 extern "C" {
 
-static FwdPlan plan_fwd_stats_h(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int stride, int pad, int dil) {
-  const long long M = (long long)B * Ho * Wo;
+// the choice of a forward conv with fused statistics (the queries know Ho / Wo only: the smallest input that gives them)
+static HGatherChoice select_fwd_stats_h(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int stride, int pad, int dil) {
   const int H = (Ho - 1) * stride - 2 * pad + dil * (kh - 1) + 1, W = (Wo - 1) * stride - 2 * pad + dil * (kw - 1) + 1;
-  DilGeom geom;
-  const bool has_geom = Cin % hconv_kb(Cin, kh * kw * Cin) == 0 && dil_geom(geom, Ho, Wo, H, W, kh, kw, Cin, stride, 1, dil, -pad);
-  return plan_gather_h(M, Cout, kh * kw * Cin, Cin, has_geom ? &geom : nullptr);
+  return select_gather_h(HGatherProblem{fwd_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil), false, false, true, false, false});
 }
 
 int pseg_conv2d_stat_rows_h(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int stride, int pad, int dil) {
-  FwdPlan pl = plan_fwd_stats_h(B, Ho, Wo, Cin, Cout, kh, kw, stride, pad, dil);
-  return pl.gridM * waves_m_h(pl.tile);
+  return select_fwd_stats_h(B, Ho, Wo, Cin, Cout, kh, kw, stride, pad, dil).stat_rows();
 }
 
 int pseg_conv2d_stat_group_h(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int stride, int pad, int dil) {
-  FwdPlan pl = plan_fwd_stats_h(B, Ho, Wo, Cin, Cout, kh, kw, stride, pad, dil);
-  return pl.tile.bm / waves_m_h(pl.tile);
+  const HGatherChoice c = select_fwd_stats_h(B, Ho, Wo, Cin, Cout, kh, kw, stride, pad, dil);
+  return c.pl.tile.bm / c.wave_rows();
 }
 
 int pseg_conv2d_fwd_h(const pseg_half_t* x, int ldx, const pseg_half_t* w, const float* bias, void* y, int ldy, int y_is_f32,
@@ -2594,8 +2598,8 @@ int pseg_conv2d_fwd_h(const pseg_half_t* x, int ldx, const pseg_half_t* w, const
   PSEG_REQUIRE(Ho == (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1,
                "conv2d_fwd_h: Ho/Wo (%d,%d) inconsistent with H/W (%d,%d) k=%dx%d s=%d p=%d d=%d", Ho, Wo, H, W, kh, kw,
                stride, pad, dil);
-  return run_gather_h(x, nhwc_bytes_h(B, H, W, Cin, ldx), ldx, w, y, ldy, y_is_f32, bias, stat, B, H, W, Cin, Ho, Wo, Cout,
-                      kw, kh * kw * Cin, stride, 1, dil, -pad, accumulate, (hipStream_t)stream);
+  return run_gather_h(fwd_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil), x, nhwc_bytes_h(B, H, W, Cin, ldx), ldx, w, y,
+                      ldy, y_is_f32, bias, stat, accumulate, (hipStream_t)stream);
 }
 
 int pseg_conv2d_dgrad_h(const pseg_half_t* dy, int ldy, const pseg_half_t* wT, pseg_half_t* dx, int ldx, int B, int H, int W,
@@ -2603,9 +2607,8 @@ int pseg_conv2d_dgrad_h(const pseg_half_t* dy, int ldy, const pseg_half_t* wT, p
                         void* stream) {
   PSEG_REQUIRE(dy && wT && dx, "conv2d_dgrad_h: null pointer");
   PSEG_REQUIRE(stride >= 1 && dil >= 1 && pad >= 0, "conv2d_dgrad_h: bad geometry");
-  // GEMM rows = input pixels (B,H,W); contraction over (r,s,co); gather source = dy [B,Ho,Wo,Cout]
-  return run_gather_h(dy, nhwc_bytes_h(B, Ho, Wo, Cout, ldy), ldy, wT, dx, ldx, 0, nullptr, nullptr, B, Ho, Wo, Cout, H, W,
-                      Cin, kw, kh * kw * Cout, 1, stride, -dil, pad, accumulate, (hipStream_t)stream);
+  return run_gather_h(dgrad_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil), dy, nhwc_bytes_h(B, Ho, Wo, Cout, ldy), ldy,
+                      wT, dx, ldx, 0, nullptr, nullptr, accumulate, (hipStream_t)stream);
 }
 
 int pseg_conv2d_dgrad_bnstat_rows_h(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
@@ -2613,16 +2616,12 @@ int pseg_conv2d_dgrad_bnstat_rows_h(int B, int H, int W, int Cin, int Ho, int Wo
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 || Cin % 8 != 0 || Cout % 8 != 0 || stride < 1 ||
       dil < 1 || pad < 0)
     return 0;
-  const long long M = (long long)B * H * W;
-  if (M >= (1LL << 31) || nhwc_bytes_h(B, Ho, Wo, Cout, Cout) >= kMaxBytes || (long long)Cin * kh * kw * Cout * 2 >= kMaxBytes) return 0;
-  const FwdPlan pl = plan_run_h(Ho, Wo, Cout, H, W, M, Cin, kw, kh * kw * Cout, 1, stride, -dil, pad);
-  const int rows = pl.gridM * waves_m_h(pl.tile);
-  // walk the launch decisions of this problem without launching: is the kernel it lands on instantiated with the sums?
-  static float dummy[4] __attribute__((aligned(16)));
-  const HBnsArgs probe{dummy, Cin, dummy, dummy, dummy, dummy, 0, dummy, dummy, rows};
-  const int rc = run_gather_h(dummy, nhwc_bytes_h(B, Ho, Wo, Cout, Cout), Cout, dummy, dummy, Cin, 0, nullptr, nullptr, B, Ho, Wo, Cout,
-                              H, W, Cin, kw, kh * kw * Cout, 1, stride, -dil, pad, 0, nullptr, &probe, true);
-  return rc == PSEG_OK ? rows : 0;
+  // the problem pseg_conv2d_dgrad_bnstat_h hands to run_gather_h (densely packed): 0 where the launch refuses its sizes or no
+  // kernel that carries the fused sums takes it
+  const GatherGeom g = dgrad_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil);
+  if (gather_size_error_h(g, nhwc_bytes_h(B, Ho, Wo, Cout, Cout), Cin) != nullptr) return 0;
+  const HGatherChoice c = select_gather_h(HGatherProblem{g, false, false, false, false, true});
+  return c.sums ? c.stat_rows() : 0;
 }
 
 int pseg_conv2d_dgrad_bnstat_h(const pseg_half_t* dy, int ldy, const pseg_half_t* wT, pseg_half_t* dx, int ldx, int B, int H, int W,
@@ -2640,8 +2639,8 @@ int pseg_conv2d_dgrad_bnstat_h(const pseg_half_t* dy, int ldy, const pseg_half_t
   PSEG_REQUIRE(part_rows > 0 && part_rows == pseg_conv2d_dgrad_bnstat_rows_h(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil),
                "conv2d_dgrad_bnstat_h: part_rows (%d) is not pseg_conv2d_dgrad_bnstat_rows_h() of this problem", part_rows);
   const HBnsArgs bns{y_prev, ldy_prev, mean, invstd, scale, shift, act, part_db, part_dg, part_rows};
-  return run_gather_h(dy, nhwc_bytes_h(B, Ho, Wo, Cout, ldy), ldy, wT, dx, ldx, 0, nullptr, nullptr, B, Ho, Wo, Cout, H, W, Cin, kw,
-                      kh * kw * Cout, 1, stride, -dil, pad, 0, (hipStream_t)stream, &bns);
+  return run_gather_h(dgrad_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil), dy, nhwc_bytes_h(B, Ho, Wo, Cout, ldy), ldy,
+                      wT, dx, ldx, 0, nullptr, nullptr, 0, (hipStream_t)stream, &bns);
 }
 
 int64_t pseg_conv2d_wgrad_workspace_bytes_h(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw) {

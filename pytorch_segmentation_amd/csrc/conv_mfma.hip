@@ -3187,16 +3187,6 @@ int pseg_config_reload(void) {
 }
 const char* pseg_last_error(void) { return pseg::last_error(); }
 
-// forward conv as a gather GEMM: rows = output pixels, gather source = x
-static GatherGeom fwd_geom(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil) {
-  return GatherGeom{(long long)B * Ho * Wo, Cout, kh * kw * Cin, Cin, H, W, Ho, Wo, kh, kw, stride, 1, dil, -pad};
-}
-
-// data gradient as a gather GEMM: rows = input pixels, N = Cin, contraction over (r,s,co); gather source = dy [B,Ho,Wo,Cout]
-static GatherGeom dgrad_geom(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil) {
-  return GatherGeom{(long long)B * H * W, Cin, kh * kw * Cout, Cout, Ho, Wo, H, W, kh, kw, 1, stride, -dil, pad};
-}
-
 // the choice of a forward conv with fused statistics (the queries know Ho / Wo only: the smallest input that gives them)
 static GatherChoice select_fwd_stats(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int stride, int pad, int dil) {
   const int H = (Ho - 1) * stride - 2 * pad + dil * (kh - 1) + 1, W = (Wo - 1) * stride - 2 * pad + dil * (kw - 1) + 1;

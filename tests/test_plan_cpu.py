@@ -1,6 +1,7 @@
 """The planning decisions behind the integer-only conv queries are pinned: tests/golden/plan_table.json holds the answers of every
-query (tests/plan_queries.py) for a few hundred conv problems, under the default environment and under PSEG_CONV_NOSKIP=1, written
-by tools/plan_table.py with the library of the commit BEFORE the kernel selection was gathered into select_gather (conv_mfma.hip).
+query (tests/plan_queries.py) for a few hundred conv problems, under the default environment, PSEG_CONV_NOSKIP=1 and
+PSEG_HCONV_PERSIST=0 / 2, written by tools/plan_table.py with the library of the commit BEFORE the kernel selection was gathered
+into select_gather (conv_mfma.hip) and select_gather_h (conv_half.hip).
 A selection that moves changes the statistics layout, the fused-sum rows or a workspace size, and shows here without a GPU."""
 import json
 import os
@@ -57,3 +58,15 @@ def test_gather_selection_is_written_once():
     assert not re.search(r'skip_taps\s*=[^=]', host)
     common = open(os.path.join(os.path.dirname(HERE), 'pytorch_segmentation_amd', 'csrc', 'conv_common.h')).read()
     assert len(re.findall(r'\.skip_taps = \(', common)) == 1
+
+
+def test_half_gather_selection_is_written_once():
+    """conv_half.hip has one selection, select_gather_h: no dry run of the launch path behind the fused-sums query, no second or
+    third derivation of the statistics layout, no launch ladders -- and the selection asks the device nothing."""
+    src = open(os.path.join(os.path.dirname(HERE), 'pytorch_segmentation_amd', 'csrc', 'conv_half.hip')).read()
+    for gone in ('bns_query', 'plan_fwd_stats_h', 'plan_run_h', 'PSEG_H_LAUNCH', 'PSEG_HP_LAUNCH'):
+        assert gone not in src, gone
+    start = src.index('static HGatherChoice select_gather_h(')
+    body = src[start:src.index('\n}\n', start)]
+    assert 'return c;' in body and len(body.splitlines()) > 40
+    assert not re.search(r'\bhip[A-Z]\w*', body), re.findall(r'\bhip[A-Z]\w*', body)
