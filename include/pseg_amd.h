@@ -58,8 +58,8 @@ extern "C" {
 #define PSEG_ACT_RELU 1
 #define PSEG_ACT_RELU6 2
 
-/* bumped whenever an existing prototype changes incompatibly; pseg_abi_version() returns the value the library was built with */
-#define PSEG_ABI_VERSION 12
+/* bumped whenever an existing prototype changes incompatibly or entry points are added; pseg_abi_version() returns the value the library was built with */
+#define PSEG_ABI_VERSION 13
 int pseg_abi_version(void);
 const char* pseg_last_error(void);
 /* The PSEG_CONV_* / PSEG_WGRAD_* planning overrides are read from the environment once, at the first launch;
@@ -453,6 +453,32 @@ int pseg_image_preprocess(const uint8_t* src, int64_t src_bytes, const int64_t* 
                           float mean2, float std0, float std1, float std2, float* out, int oh, int ow, void* stream);
 int pseg_seg_decode(const float* logits, int B, int C, int h, int w, const int64_t* table, int64_t npix_total, uint8_t* mask,
                     uint8_t* rgb, const uint8_t* lut, void* stream);
+
+/* ------------------------------------------------------------------ training augmentation (csrc/augment.hip)
+ * The geometric and colour-affine part of the reference's online augmentation (utils/datasets.py:26-125, imgaug on the
+ * host) fused with CocoDataset.post_fetch_fn (utils/datasets.py:199-213) into one launch over the collated uint8 batch.
+ * img uint8 [B,3,H,W] planar RGB, seg uint8 [B,H,W]; out fp32 [B,3,oh,ow], target int64 [B,H,W] (targets keep the input
+ * size: the loss resizes the logits).  params: fp32 [B][PSEG_AUGMENT_ROW], one row per sample:
+ *   [0..5]   inverse affine a00 a01 a02 a10 a11 a12: output pixel index (x, y) of the H x W working grid reads source index
+ *            coordinates sx = a00*x + a01*y + a02, sy = a10*x + a11*y + a12 (pixel centres at integers, fp32 fma).  The
+ *            host folds flips, crop-and-pad, scale, rotate, shear, translate and every centre offset into it.
+ *   [6..17]  colour matrix M, 3 x 4 row-major, in 0..255 units: output channel c = M[c] . [r, g, b, 1].
+ *   [18]     cval, the image fill value (0..255 units)
+ *   [19]     image interpolation order: 0 nearest, otherwise bilinear
+ *   [20]     border mode: 0 constant (a tap outside the image contributes cval), otherwise edge (tap indices are clamped)
+ *   [21..23] reserved, ignored
+ * Image, per output pixel (oy, ox): working-grid index ix = min((int)floorf(ox * ((float)W / ow)), W - 1), iy likewise
+ * (ATen's nearest: the identity when (oh, ow) == (H, W)); (sx, sy) from the affine; nearest takes floorf(s + 0.5f),
+ * bilinear the taps floorf(s) and + 1; the sample is rounded to 8 bits half up and saturated, the colour matrix is applied
+ * in fp32 and rounded the same way, then (q - mean_c) / std_c with a correctly rounded division.  Labels, per pixel of
+ * [H, W]: the same affine, nearest sample, 0 outside the image, widened to int64 (colour, cval and border mode do not apply).
+ * Coordinates are clamped to [-1, size] before they become integers, which changes no result; a NaN / infinite coordinate
+ * counts as outside in either border mode (cval / label 0).  Nothing outside img and seg is read, whatever the table holds.
+ * Identity rows give exactly post_fetch_fn's tensors (including its multi-scale nearest resize). */
+#define PSEG_AUGMENT_ROW 24
+int pseg_augment_batch(const uint8_t* img, const uint8_t* seg, const float* params, int B, int H, int W, float mean0, float mean1,
+                       float mean2, float std0, float std1, float std2, float* out, int oh, int ow, int64_t* target,
+                       void* stream);
 
 /* ------------------------------------------------------------------ optimiser (flat parameter arena)
  * One launch over the whole arena; grad_scale folds the 1/world_size of the data-parallel mean

@@ -1226,6 +1226,30 @@ def seg_decode(logits, table, npix_total, lut=None, out=None):
     return mask, rgb
 
 
+AUGMENT_ROW = 24        # PSEG_AUGMENT_ROW: floats per sample of augment_batch's parameter table (layout: include/pseg_amd.h)
+
+
+def augment_batch(imgs, segs, params, oh, ow, mean, std, out=None, target=None):
+    """The collated uint8 batch -> (fp32 model input [B,3,oh,ow], int64 targets [B,H,W]) in one launch (pseg_augment_batch):
+    per-sample inverse affine warp + 3x4 colour matrix + normalisation + multi-scale nearest resize for the images, the
+    same warp with a nearest sample for the labels.  imgs: uint8 [B,3,H,W] planar RGB, segs: uint8 [B,H,W], params: fp32
+    device table [B, AUGMENT_ROW].  out / target (optional): contiguous device tensors of exactly those shapes to write into."""
+    assert imgs.is_cuda and imgs.dtype == torch.uint8 and imgs.is_contiguous() and imgs.dim() == 4 and imgs.shape[1] == 3
+    B, _, H, W = imgs.shape
+    assert segs.device == imgs.device and segs.dtype == torch.uint8 and segs.is_contiguous() and segs.shape == (B, H, W)
+    assert params.device == imgs.device and params.dtype == torch.float32 and params.is_contiguous()
+    assert params.shape == (B, AUGMENT_ROW) and len(mean) == 3 and len(std) == 3
+    if out is None:
+        out = torch.empty(B, 3, oh, ow, dtype=torch.float32, device=imgs.device)
+    if target is None:
+        target = torch.empty(B, H, W, dtype=torch.int64, device=imgs.device)
+    assert out.device == imgs.device and out.dtype == torch.float32 and out.is_contiguous() and out.shape == (B, 3, oh, ow)
+    assert target.device == imgs.device and target.dtype == torch.int64 and target.is_contiguous() and target.shape == (B, H, W)
+    _lib.call('pseg_augment_batch', imgs.data_ptr(), segs.data_ptr(), params.data_ptr(), B, H, W, *[float(m) for m in mean],
+              *[float(v) for v in std], out.data_ptr(), oh, ow, target.data_ptr(), _stream())
+    return out, target
+
+
 def confusion(pred, target, counters):
     """counters: int64 [3][C] (tp, fn, fp), accumulated in place."""
     assert pred.dtype == torch.int64 and target.dtype == torch.int64 and counters.dtype == torch.int64

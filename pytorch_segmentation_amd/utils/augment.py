@@ -1,0 +1,271 @@
+"""On-device training augmentation: the geometric and colour-affine part of the reference's online augmentation
+(``TRAIN_AUGS``, reference utils/datasets.py:26-125, imgaug on the host, one sample at a time) as ONE kernel over the
+collated uint8 batch (csrc/augment.hip), fused with ``CocoDataset.post_fetch_fn``'s normalisation, multi-scale resize and
+label widening.
+
+The host only draws numbers.  ``DeviceAugment.draw(B)`` draws one *recipe* per sample from a seedable
+``numpy.random.Generator``; ``DeviceAugment.rows(recipes, H, W)`` folds each recipe into one row of the kernel's parameter
+table (layout: include/pseg_amd.h, ``PSEG_AUGMENT_ROW`` floats): the INVERSE affine of the whole geometric chain, a 3x4
+colour matrix in 0..255 units, the fill value, the interpolation order and the border mode.
+
+Built (defaults of ``DeviceAugment.reference()`` = the reference's values):
+  * ``Fliplr(0.5)``, ``Flipud(0.2)``;
+  * ``Sometimes(0.5, CropAndPad(percent=(-0.05, 0.1)))``: each side drawn on its own, negative crops, positive pads, the
+    result is resized back to H x W (imgaug's ``keep_size``);
+  * ``Sometimes(0.5, Affine(...))`` about the image centre: scale 0.8..1.2 per axis, translate +-20 % per axis, rotate
+    +-90 degrees, shear +-16 degrees, order drawn from {0, 1}, cval 0..255, mode drawn from {constant, edge};
+  * of the ``SomeOf((0, 5), [...16 augmenters...], random_order=True)`` block the five that are affine in colour: ``Invert(0.05,
+    per_channel=True)``, ``Add((-10, 10), per_channel=0.5)``, ``Multiply((0.5, 1.5), per_channel=0.5)`` (one of the two
+    branches of its ``OneOf``), ``LinearContrast((0.5, 2.0), per_channel=0.5)`` and ``Grayscale(alpha=(0, 1))``.  As in the
+    reference, 0..5 of the block's 16 slots are picked per sample; a picked slot that holds one of these five is applied,
+    in a random order; the other slots do nothing here.
+Labels are warped with the same matrix, nearest sample, background 0, as imgaug warps segmentation maps.
+
+OUT OF SCOPE -- every neighbourhood or non-affine augmenter of ``TRAIN_AUGS``: the blurs (Gaussian, average, median),
+Sharpen, Emboss, the edge-detect blends (BlendAlphaSimplexNoise), Superpixels, AdditiveGaussianNoise, Dropout and
+CoarseDropout, AddToHueAndSaturation, the frequency-noise blend (BlendAlphaFrequencyNoise), ElasticTransformation,
+PiecewiseAffine and PerspectiveTransform; and imgaug's border modes other than constant and edge (``ia.ALL`` also draws
+reflect, symmetric and wrap).
+
+Simplifications, all on the host side: the geometric augmenters run in the fixed order flips, crop-and-pad, affine (the
+reference shuffles the top-level list), and the chain is ONE warp (imgaug resamples once per augmenter); one (order, cval,
+mode) triple serves a sample -- crop-and-pad alone is bilinear, the affine's own draw wins when it is active; the colour
+operations are composed into one matrix, so the 8-bit rounding and saturation that imgaug applies between two of them
+happens once, after the last.
+"""
+import numpy as np
+import torch
+
+from .datasets import MEAN, STD
+
+ROW = 24                         # PSEG_AUGMENT_ROW
+CONTRAST_CENTRE = 127.0          # imgaug LinearContrast on uint8: 127 + alpha * (v - 127)
+GRAY_WEIGHTS = (0.299, 0.587, 0.114)
+COLOUR_SLOTS = 16                # augmenters in the reference's SomeOf block
+_COLOUR_OPS = ('invert', 'add', 'multiply', 'contrast', 'grayscale')
+MODES = {'constant': 0, 'edge': 1}
+
+
+def _eye3():
+    return np.eye(3, dtype=np.float64)
+
+
+def flip_matrix(H, W, lr, ud):
+    m = _eye3()
+    if lr:
+        m[0, 0], m[0, 2] = -1.0, W - 1.0
+    if ud:
+        m[1, 1], m[1, 2] = -1.0, H - 1.0
+    return m
+
+
+def crop_pad_matrix(H, W, top, right, bottom, left):
+    """source index -> output index of CropAndPad(percent=(top, right, bottom, left), keep_size=True): the image grows by the
+    fractions on each side (negative: shrinks) and is resized back to H x W, pixel centres at index + 0.5 of the edge grid."""
+    kx, ky = 1.0 / (1.0 + left + right), 1.0 / (1.0 + top + bottom)
+    m = _eye3()
+    m[0, 0], m[0, 2] = kx, kx * (left * W + 0.5) - 0.5
+    m[1, 1], m[1, 2] = ky, ky * (top * H + 0.5) - 0.5
+    return m
+
+
+def affine_matrix(H, W, rotate=0.0, scale=(1.0, 1.0), shear=0.0, translate=(0.0, 0.0)):
+    """source index -> output index: scale, shear, rotate about the image centre ((W-1)/2, (H-1)/2), then translate by
+    fractions of the image size.  Angles in degrees."""
+    c = _eye3()
+    c[0, 2], c[1, 2] = (W - 1) / 2.0, (H - 1) / 2.0
+    r, s = np.deg2rad(rotate), np.deg2rad(shear)
+    R = np.array([[np.cos(r), -np.sin(r), 0.0], [np.sin(r), np.cos(r), 0.0], [0.0, 0.0, 1.0]])
+    Sh = np.array([[1.0, -np.tan(s), 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]])
+    S = np.diag([float(scale[0]), float(scale[1]), 1.0])
+    T = _eye3()
+    T[0, 2], T[1, 2] = translate[0] * W, translate[1] * H
+    return T @ c @ R @ Sh @ S @ np.linalg.inv(c)
+
+
+def colour_op_matrix(name, value):
+    """4x4 homogeneous matrix (0..255 units) of one named colour operation; per-channel values are length-3."""
+    m = np.eye(4, dtype=np.float64)
+    if name == 'add':
+        m[:3, 3] = value
+    elif name == 'multiply':
+        m[:3, :3] = np.diag(np.asarray(value, dtype=np.float64))
+    elif name == 'contrast':
+        a = np.asarray(value, dtype=np.float64)
+        m[:3, :3] = np.diag(a)
+        m[:3, 3] = CONTRAST_CENTRE * (1.0 - a)
+    elif name == 'invert':
+        for c in range(3):
+            if value[c]:
+                m[c, c], m[c, 3] = -1.0, 255.0
+    elif name == 'grayscale':
+        a = float(value)
+        m[:3, :3] = (1.0 - a) * np.eye(3) + a * np.tile(np.asarray(GRAY_WEIGHTS, dtype=np.float64), (3, 1))
+    else:
+        raise ValueError('unknown colour operation %r' % (name,))
+    return m
+
+
+def colour_matrix(colour_ops):
+    """3x4 matrix of a list of (name, value) operations applied first to last."""
+    m = np.eye(4, dtype=np.float64)
+    for name, value in colour_ops:
+        m = colour_op_matrix(name, value) @ m
+    return m[:3]
+
+
+def forward_matrix(recipe, H, W):
+    """source index -> output index of a recipe's whole geometric chain (3x3, fp64)."""
+    m = flip_matrix(H, W, recipe.get('fliplr', False), False)
+    m = flip_matrix(H, W, False, recipe.get('flipud', False)) @ m
+    if recipe.get('crop_pad') is not None:
+        m = crop_pad_matrix(H, W, *recipe['crop_pad']) @ m
+    if recipe.get('affine') is not None:
+        m = affine_matrix(H, W, **recipe['affine']) @ m
+    return m
+
+
+def make_row(inverse=None, colour=None, cval=0.0, order=0, mode=0):
+    """one parameter row from an inverse affine (2x3 or 3x3: output index -> source index), a 3x4 colour matrix, the fill
+    value, the interpolation order (0 nearest, 1 bilinear) and the border mode (0 / 'constant', 1 / 'edge')."""
+    row = np.zeros(ROW, dtype=np.float32)
+    row[0:6] = (np.eye(3)[:2] if inverse is None else np.asarray(inverse, dtype=np.float64)[:2]).reshape(6)
+    row[6:18] = (np.eye(4)[:3] if colour is None else np.asarray(colour, dtype=np.float64)).reshape(12)
+    row[18], row[19], row[20] = cval, order, MODES.get(mode, mode)
+    return row
+
+
+def _range(v):
+    return None if v is None else (float(v[0]), float(v[1]))
+
+
+class DeviceAugment:
+    """See the module docstring.  A probability of 0 or a range of None switches an augmenter off."""
+
+    def __init__(self, fliplr=0.5, flipud=0.2, crop_pad=(-0.05, 0.1), crop_pad_p=0.5, affine_p=0.5, scale=(0.8, 1.2),
+                 translate=(-0.2, 0.2), rotate=(-90.0, 90.0), shear=(-16.0, 16.0), orders=(0, 1), cval=(0, 255),
+                 modes=('constant', 'edge'), add=(-10, 10), multiply=(0.5, 1.5), contrast=(0.5, 2.0), invert=0.05,
+                 grayscale=(0.0, 1.0), per_channel=0.5, some_of=(0, 5), seed=None, rank=None, mean=MEAN, std=STD):
+        self.fliplr, self.flipud = float(fliplr), float(flipud)
+        self.crop_pad, self.crop_pad_p = _range(crop_pad), float(crop_pad_p if crop_pad is not None else 0.0)
+        if self.crop_pad is not None and self.crop_pad[0] <= -0.45:
+            raise ValueError('crop_pad: cropping %g of a side from both ends leaves no image' % -self.crop_pad[0])
+        self.affine_p = float(affine_p)
+        self.scale, self.translate, self.rotate, self.shear = _range(scale), _range(translate), _range(rotate), _range(shear)
+        self.orders, self.cval, self.modes = tuple(orders), _range(cval), tuple(MODES[m] for m in modes)
+        self.add, self.multiply, self.contrast = _range(add), _range(multiply), _range(contrast)
+        self.invert, self.grayscale = float(invert or 0.0), _range(grayscale)
+        self.per_channel, self.some_of = float(per_channel), (int(some_of[0]), int(some_of[1]))
+        self.seed, self.rank = seed, rank
+        self.mean, self.std = tuple(mean), tuple(std)
+        self._rng = None
+
+    @classmethod
+    def reference(cls, **kw):
+        """the reference's TRAIN_AUGS values (the constructor defaults)"""
+        return cls(**kw)
+
+    @classmethod
+    def identity(cls, order=0, **kw):
+        """samples only identity rows (order 0 or 1): the kernel then computes exactly CocoDataset.post_fetch_fn"""
+        return cls(fliplr=0.0, flipud=0.0, crop_pad=None, affine_p=0.0, orders=(order,), cval=(0, 0), modes=('constant',),
+                   add=None, multiply=None, contrast=None, invert=0.0, grayscale=None, some_of=(0, 0), **kw)
+
+    # ------------------------------------------------------------------ drawing
+    @property
+    def rng(self):
+        if self._rng is None:            # made at the first draw: the process group exists by then
+            if self.seed is None:
+                self._rng = np.random.default_rng()
+            else:
+                rank = self.rank
+                if rank is None:
+                    import torch.distributed as dist
+                    rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+                self._rng = np.random.default_rng(int(self.seed) + int(rank))
+        return self._rng
+
+    def _values(self, rng, lo_hi, integer=False):
+        """one value for the image, or one per channel (per_channel of the time) -> length-3 array"""
+        n = 3 if rng.random() < self.per_channel else 1
+        v = rng.integers(int(lo_hi[0]), int(lo_hi[1]) + 1, n).astype(np.float64) if integer else rng.uniform(lo_hi[0], lo_hi[1], n)
+        return np.broadcast_to(v, (3,)).copy()
+
+    def _draw_colour(self, rng):
+        lo, hi = self.some_of
+        n = int(rng.integers(lo, hi + 1)) if hi > 0 else 0
+        picked = rng.permutation(COLOUR_SLOTS)[:n]            # slots 0..4 hold this module's five, in _COLOUR_OPS order
+        ops = []
+        for slot in picked:
+            name = _COLOUR_OPS[slot] if slot < len(_COLOUR_OPS) else None
+            if name == 'invert' and self.invert > 0.0:
+                flags = rng.random(3) < self.invert
+                if flags.any():
+                    ops.append(('invert', flags))
+            elif name == 'add' and self.add is not None:
+                ops.append(('add', self._values(rng, self.add, integer=True)))
+            elif name == 'multiply' and self.multiply is not None:
+                if rng.random() < 0.5:                        # the other branch of the reference's OneOf is out of scope
+                    ops.append(('multiply', self._values(rng, self.multiply)))
+            elif name == 'contrast' and self.contrast is not None:
+                ops.append(('contrast', self._values(rng, self.contrast)))
+            elif name == 'grayscale' and self.grayscale is not None:
+                ops.append(('grayscale', float(rng.uniform(*self.grayscale))))
+        return ops
+
+    def draw(self, B):
+        """-> list of B recipes (dicts): fliplr, flipud, crop_pad (top, right, bottom, left) or None, affine (keyword
+        arguments of affine_matrix) or None, order, cval, mode, colour [(name, value), ...]"""
+        rng, out = self.rng, []
+        for _ in range(B):
+            r = {'fliplr': bool(rng.random() < self.fliplr), 'flipud': bool(rng.random() < self.flipud), 'crop_pad': None,
+                 'affine': None}
+            if self.crop_pad is not None and rng.random() < self.crop_pad_p:
+                r['crop_pad'] = tuple(float(v) for v in rng.uniform(self.crop_pad[0], self.crop_pad[1], 4))
+            order = 1 if r['crop_pad'] is not None else self.orders[0]
+            if rng.random() < self.affine_p:
+                one = (1.0, 1.0)
+                r['affine'] = {
+                    'scale': tuple(float(v) for v in rng.uniform(*(self.scale or one), 2)),
+                    'translate': tuple(float(v) for v in rng.uniform(*(self.translate or (0.0, 0.0)), 2)),
+                    'rotate': float(rng.uniform(*(self.rotate or (0.0, 0.0)))),
+                    'shear': float(rng.uniform(*(self.shear or (0.0, 0.0))))}
+                order = int(self.orders[int(rng.integers(len(self.orders)))])
+            r['order'] = int(order)
+            r['cval'] = float(rng.integers(int(self.cval[0]), int(self.cval[1]) + 1))
+            r['mode'] = int(self.modes[int(rng.integers(len(self.modes)))])
+            r['colour'] = self._draw_colour(rng)
+            out.append(r)
+        return out
+
+    @staticmethod
+    def rows(recipes, H, W):
+        """recipes -> the kernel's parameter table, numpy float32 [B, ROW] (matrices composed and inverted in fp64)"""
+        table = np.zeros((len(recipes), ROW), dtype=np.float32)
+        for i, r in enumerate(recipes):
+            inv = np.linalg.inv(forward_matrix(r, H, W))
+            table[i] = make_row(inv, colour_matrix(r.get('colour', ())), r.get('cval', 0.0), r.get('order', 0), r.get('mode', 0))
+        return table
+
+    def sample(self, B, H, W):
+        """-> numpy float32 [B, ROW]: one parameter row per sample of a B x 3 x H x W batch"""
+        return self.rows(self.draw(B), H, W)
+
+    # ------------------------------------------------------------------ device side
+    def apply(self, imgs, segs, params, out_hw=None):
+        """explicit rows (numpy or tensor [B, ROW]) -> (fp32 [B,3,oh,ow], int64 [B,H,W]); out_hw=None keeps (H, W)"""
+        from .. import ops
+        assert ROW == ops.AUGMENT_ROW
+        B, _, H, W = imgs.shape
+        if not torch.is_tensor(params):
+            params = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32))
+        if not params.is_cuda:
+            # one pinned, non-blocking copy per batch (the pinned block stays alive until the copy ran: the caching
+            # host allocator holds it back for the stream that used it)
+            params = params.pin_memory().to(imgs.device, non_blocking=True)
+        oh, ow = (H, W) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        return ops.augment_batch(imgs.contiguous(), segs.contiguous(), params.contiguous(), oh, ow, self.mean, self.std)
+
+    def __call__(self, imgs_u8, segs_u8, out_hw=None):
+        B, _, H, W = imgs_u8.shape
+        return self.apply(imgs_u8, segs_u8, self.sample(B, H, W), out_hw)

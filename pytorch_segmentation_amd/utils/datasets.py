@@ -7,7 +7,10 @@ polygon = ``category_id + 1`` (0 is background, utils/datasets.py:301); ``classe
 ``__getitem__`` -> (uint8 CHW RGB image resized to ``img_size=[w,h]``, uint8 HW mask); ``post_fetch_fn`` applies the
 reference's mean/std normalisation (utils/datasets.py:199-205) and turns masks into int64.
 
-Out of scope: the imgaug augmentation pipeline, the random instance crop of CocoInstance and
+``augments=DeviceAugment(...)`` (utils/augment.py) turns ``post_fetch_fn`` into one augmenting kernel over the uint8 batch:
+the geometric and colour-affine part of the reference's imgaug pipeline (partly built).
+
+Out of scope: the rest of the imgaug pipeline, the random instance crop of CocoInstance and
 the --rect letterboxing; images are decoded with PIL and resized directly.
 """
 import json
@@ -54,12 +57,20 @@ def _warn_ignored(flag, why):
                       RuntimeWarning, stacklevel=3)
 
 
+def _multi_scale_hw(h, w):
+    """the multi-scale draw of post_fetch_fn (reference utils/datasets.py:206-212): a multiple of 32, at least 32"""
+    scale = random.uniform(0.7, 1.5)
+    return max(32, int(h * scale / 32) * 32), max(32, int(w * scale / 32) * 32)
+
+
 class CocoDataset(torch.utils.data.Dataset):
     def __init__(self, path, img_size=224, augments=None, multi_scale=False, rect=False):
         if rect:
             _warn_ignored('--rect', 'the letterboxing of reference utils/datasets.py:161-194 is part of the cv2 loader, which is out '
                                     'of scope here (SURVEY.md section 2, #9); images are resized straight to -s W H')
-        if augments:
+        from .augment import DeviceAugment          # (augment.py imports this module's MEAN / STD)
+        self.augments = augments if isinstance(augments, DeviceAugment) else None
+        if augments and self.augments is None:
             _warn_ignored('augments', 'the imgaug pipeline of reference utils/datasets.py:26-125 is out of scope here (SURVEY.md '
                                       'section 2, #9); samples are decoded and resized only')
         if isinstance(img_size, int):
@@ -101,14 +112,15 @@ class CocoDataset(torch.utils.data.Dataset):
 
     def post_fetch_fn(self, batch):
         imgs, segs = batch
+        augments = getattr(self, 'augments', None)      # (callers also pass a bare namespace with multi_scale only)
+        if augments is not None:
+            # one kernel: warp, recolour, normalise, multi-scale, labels to int64 (csrc/augment.hip)
+            return augments(imgs, segs, _multi_scale_hw(imgs.size(2), imgs.size(3)) if self.multi_scale else None)
         imgs = imgs.float()
         imgs = (imgs - torch.tensor(MEAN, device=imgs.device).view(1, 3, 1, 1)) / \
             torch.tensor(STD, device=imgs.device).view(1, 3, 1, 1)
         if self.multi_scale:
-            h, w = imgs.size(2), imgs.size(3)
-            scale = random.uniform(0.7, 1.5)
-            h, w = max(32, int(h * scale / 32) * 32), max(32, int(w * scale / 32) * 32)
-            imgs = F.interpolate(imgs, (h, w))
+            imgs = F.interpolate(imgs, _multi_scale_hw(imgs.size(2), imgs.size(3)))
         return imgs.contiguous(), segs.long()
 
 

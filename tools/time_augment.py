@@ -1,0 +1,104 @@
+"""Timing of the augmentation kernel (csrc/augment.hip, utils/augment.py) with HIP events.
+
+    python tools/time_augment.py [--out FILE.json] [--iters N]
+
+At B = 16, 3 x 512 x 512 and at B = 8, 3 x 256 x 256, on the same uint8 tensors:
+  * `post_fetch_fn`: the five torch ops the kernel replaces (CocoDataset.post_fetch_fn without augments: float, subtract,
+    divide, labels to int64; at the multi-scale size additionally the nearest interpolate);
+  * `augment identity`: ops.augment_batch with identity rows already on the device (the kernel alone);
+  * `augment reference`: ops.augment_batch with DeviceAugment.reference() rows already on the device (rotated / bilinear
+    gathers, colour matrices);
+  * `DeviceAugment()`: the whole call as the loader makes it -- host sampling, the pinned copy of the table, the launch.
+Each figure is the median over --iters (>= 50) single calls, each between its own pair of events, after warm-up; the
+variants alternate inside one loop so that they see the same machine.  Algorithmic bytes = every input byte once + the fp32
+output + the int64 targets; fractions of the roof are over 6.3 TB/s HBM.
+"""
+import argparse
+import json
+import os
+import random
+import statistics
+import sys
+import tempfile
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pytorch_segmentation_amd import ops  # noqa: E402
+from pytorch_segmentation_amd.utils.augment import DeviceAugment  # noqa: E402
+from pytorch_segmentation_amd.utils.datasets import MEAN, STD, CocoDataset  # noqa: E402
+
+HBM = 6.3e12
+
+
+def timed_median(fns, iters, warmup=10):
+    """{name: fn} -> {name: median ms of `iters` single calls}; the functions alternate call by call"""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)] for k in fns}
+    for i in range(iters):
+        for k, fn in fns.items():
+            a, b = ev[k][i]
+            a.record()
+            fn()
+            b.record()
+    torch.cuda.synchronize()
+    return {k: statistics.median(a.elapsed_time(b) for a, b in ev[k]) for k in fns}
+
+
+def rows_for(B, H, W, out_hw, iters):
+    g = torch.Generator().manual_seed(B * H)
+    imgs = torch.randint(0, 256, (B, 3, H, W), dtype=torch.uint8, generator=g).cuda()
+    segs = torch.randint(0, 21, (B, H, W), dtype=torch.uint8, generator=g).cuda()
+    oh, ow = out_hw or (H, W)
+    with tempfile.TemporaryDirectory() as d:             # post_fetch_fn of a loader without augments: an empty dataset will do
+        with open(os.path.join(d, 'train.json'), 'w') as f:
+            json.dump({'categories': [{'name': 'a'}], 'images': [], 'annotations': []}, f)
+        loader = CocoDataset(os.path.join(d, 'train.json'))
+    ident = torch.from_numpy(DeviceAugment.identity(seed=0).sample(B, H, W)).cuda()
+    ref_aug = DeviceAugment.reference(seed=0)
+    ref = torch.from_numpy(ref_aug.sample(B, H, W)).cuda()
+
+    def torch_path():
+        x, t = loader.post_fetch_fn((imgs, segs))
+        if out_hw:
+            x = torch.nn.functional.interpolate(x, out_hw)
+        return x, t
+    fns = {
+        'post_fetch_fn (torch ops)': torch_path,
+        'augment identity rows': lambda: ops.augment_batch(imgs, segs, ident, oh, ow, MEAN, STD),
+        'augment reference rows': lambda: ops.augment_batch(imgs, segs, ref, oh, ow, MEAN, STD),
+        'DeviceAugment() sample + copy + launch': lambda: ref_aug(imgs, segs, out_hw),
+    }
+    a, b = torch_path(), ops.augment_batch(imgs, segs, ident, oh, ow, MEAN, STD)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), 'identity rows must reproduce post_fetch_fn'
+    ms = timed_median(fns, iters)
+    nbytes = imgs.numel() + segs.numel() + B * 3 * oh * ow * 4 + segs.numel() * 8
+    out = []
+    for k, v in ms.items():
+        r = {'name': k, 'B': B, 'in': [H, W], 'out': [oh, ow], 'median_ms': round(v, 4), 'iters': iters, 'alg_bytes': nbytes,
+             'roof_fraction': round(nbytes / HBM / (v * 1e-3), 3)}
+        print(json.dumps(r), flush=True)
+        out.append(r)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default='')
+    ap.add_argument('--iters', type=int, default=100)
+    opt = ap.parse_args()
+    assert torch.cuda.is_available(), 'time_augment.py measures on the GPU'
+    assert opt.iters >= 50, 'a median over fewer than 50 calls is not reported'
+    random.seed(0)
+    rows = rows_for(16, 512, 512, None, opt.iters) + rows_for(8, 256, 256, None, opt.iters)
+    rows += rows_for(16, 512, 512, (384, 384), opt.iters)          # one multi-scale size: the torch path adds its interpolate
+    if opt.out:
+        with open(opt.out, 'w') as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == '__main__':
+    main()

@@ -3,7 +3,7 @@
 on the MI355X HIP path.
 
     python3 train.py data/<custom> [--epochs N] [-s W H] [-bs N] [-a ACC] [--lr LR] [--adam] [--resume]
-                     [--weights F] [--notest] [--nosave] [--model unet|deeplabv3plus]
+                     [--weights F] [--notest] [--nosave] [--model unet|deeplabv3plus] [--augment]
     python3 -m torch.distributed.run --nproc-per-node <n> train.py data/<custom>        # RCCL data parallel
 
 Differences from the reference that are visible here: the model is picked with --model (the reference edits
@@ -25,6 +25,7 @@ from torch.utils.data import DataLoader, DistributedSampler
 
 from pytorch_segmentation_amd.models import DeepLabV3Plus, HRNet, UNet
 from pytorch_segmentation_amd.utils import Fetcher, Trainer, compute_loss
+from pytorch_segmentation_amd.utils.augment import DeviceAugment
 from pytorch_segmentation_amd.utils.datasets import CocoInstance
 from test import test
 
@@ -42,9 +43,13 @@ def _loader(dataset, batch_size, num_workers, train=True):
 
 def train(data_dir, epochs=100, img_size=(320, 320), batch_size=32, accumulate=2, lr=1e-3, adam=False, resume=False,
           weights='', num_workers=4, multi_scale=False, rect=False, mixed_precision=False, notest=False, nosave=False,
-          model_name='unet'):
+          model_name='unet', augment=False):
+    # --augment: the training batches (never the validation ones) go through the on-device augmentation kernel; True =
+    # the reference's values, or a DeviceAugment of the caller's own (seeded, other ranges)
+    if augment and not isinstance(augment, DeviceAugment):
+        augment = DeviceAugment.reference()
     train_data = CocoInstance(osp.join(data_dir, 'train.json'), img_size=list(img_size), multi_scale=multi_scale,
-                              rect=rect)
+                              rect=rect, augments=augment or None)
     train_fetcher = Fetcher(_loader(train_data, batch_size, num_workers), train_data.post_fetch_fn)
     val_fetcher = None
     if not notest:
@@ -69,7 +74,7 @@ def train(data_dir, epochs=100, img_size=(320, 320), batch_size=32, accumulate=2
     return trainer, last_loss
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('data', type=str, default='data/voc')
     ap.add_argument('--epochs', type=int, default=100)
@@ -89,7 +94,14 @@ def main():
     ap.add_argument('--backend', type=str, default='nccl')
     ap.add_argument('--local-rank', '--local_rank', type=int, default=int(os.environ.get('LOCAL_RANK', 0)))
     ap.add_argument('--model', choices=sorted(MODELS), default='unet')
-    opt = ap.parse_args()
+    ap.add_argument('--augment', action='store_true',
+                    help='on-device training augmentation (flips, crop-and-pad, affine, colour): the affine part of the '
+                         "reference's TRAIN_AUGS, utils/augment.py")
+    return ap
+
+
+def main():
+    opt = build_parser().parse_args()
 
     if os.environ.get('WORLD_SIZE'):
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
@@ -101,7 +113,7 @@ def main():
         sys.stdout = open(os.devnull, 'w')
     print(opt)
     train(opt.data, opt.epochs, opt.img_size, opt.batch_size, opt.accumulate, opt.lr, opt.adam, opt.resume, opt.weights,
-          opt.num_workers, opt.multi_scale, opt.rect, opt.mix_precision, opt.notest, opt.nosave, opt.model)
+          opt.num_workers, opt.multi_scale, opt.rect, opt.mix_precision, opt.notest, opt.nosave, opt.model, opt.augment)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()
 
