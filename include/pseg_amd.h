@@ -59,7 +59,7 @@ extern "C" {
 #define PSEG_ACT_RELU6 2
 
 /* bumped whenever an existing prototype changes incompatibly or entry points are added; pseg_abi_version() returns the value the library was built with */
-#define PSEG_ABI_VERSION 13
+#define PSEG_ABI_VERSION 14
 int pseg_abi_version(void);
 const char* pseg_last_error(void);
 /* The PSEG_CONV_* / PSEG_WGRAD_* planning overrides are read from the environment once, at the first launch;
@@ -479,6 +479,46 @@ int pseg_seg_decode(const float* logits, int B, int C, int h, int w, const int64
 int pseg_augment_batch(const uint8_t* img, const uint8_t* seg, const float* params, int B, int H, int W, float mean0, float mean1,
                        float mean2, float std0, float std1, float std2, float* out, int oh, int ow, int64_t* target,
                        void* stream);
+
+/* pseg_augment_batch_nbhd: pseg_augment_batch with a neighbourhood stage and two per-pixel random stages (the reference's
+ * GaussianBlur / AverageBlur / Sharpen / Emboss, AdditiveGaussianNoise, Dropout / CoarseDropout).  Arguments, labels, the
+ * multi-scale index and the read / write footprint are pseg_augment_batch's.  params: fp32 [B][PSEG_AUGMENT_NBHD_ROW]:
+ *   [0..23]    pseg_augment_batch's row, verbatim
+ *   [24]       K, the filter size: 0 or 1 = no filter, otherwise odd, at most PSEG_AUGMENT_NBHD_KMAX
+ *   [25]       noise scale in 0..255 units (<= 0: no noise)       [26] != 0: one normal per plane, otherwise one per pixel
+ *   [27]       dropout probability p as fp32 (<= 0: no dropout)   [28] != 0: one draw per plane, otherwise one per pixel
+ *   [29] [30]  mh, mw: the coarse dropout mask's size; 0 0 = one draw per working-grid pixel
+ *   [31] [32]  the sample's 64-bit seed, low and high 32 bits, BIT-CAST into the two floats (never converted)
+ *   [33..39]   reserved, ignored
+ *   [40..208]  K x K filter weights, row-major with row length K
+ *   [209..211] reserved, ignored
+ * shape_host: HOST int [B][3] = {K, mh, mw} of each row, the values the entry point validates and sizes LDS from (the
+ * table itself lives on the device); they must equal the rows'.  The kernel clamps what it reads from the row so that a
+ * table that disagrees still touches nothing but img, seg, its row and its own LDS tile.
+ * Image, per sample on the H x W working grid, each stage rounded to 8 bits half up and saturated:
+ *   1. the warp, exactly pseg_augment_batch's;
+ *   2. correlation (cv2 filter2D): f(y, x) = sum_j sum_i w[j][i] * warp(y + j - K/2, x + i - K/2), fp32; indices beyond the
+ *      grid reflect without repeating the edge pixel (-1 -> 1, H -> H - 2; the only pixel when the dimension is 1);
+ *   3. the 3 x 4 colour matrix;
+ *   4. noise: round(q + scale * n), n = sqrtf(-2 logf(u1)) * cosf(2 pi u2), u1 = ((r0 >> 8) + 1) * 2^-24, u2 = (r1 >> 8) * 2^-24;
+ *   5. dropout: the value is kept iff u >= p, u = (r0 >> 8) * 2^-24, and is 0 otherwise;
+ *   6. (q - mean_c) / std_c.
+ * r0..r3 = Philox4x32-10(key = the seed, counter = (n, stream, 0, 0)).  Noise: n = y * W + x of the working-grid pixel,
+ * stream 0, or stream c for plane c when per plane.  Dropout: n = y * W + x, or the mask cell (y * mh / H) * mw + x * mw / W
+ * (integer division) with a coarse mask; stream 4, or 4 + c when per plane.  An output pixel (multi-scale) takes the result
+ * of its working-grid pixel, noise and dropout included.  Rows with K <= 1, scale <= 0 and p <= 0 give pseg_augment_batch's
+ * output bit for bit.  Dynamic LDS: 4 bytes per working-grid pixel of the span of a 32 x 8 output tile plus a halo of
+ * K/2 for the launch's largest K; refused above 64 KiB (a multi-scale reduction by more than about 3). */
+#define PSEG_AUGMENT_NBHD_ROW 212
+#define PSEG_AUGMENT_NBHD_KMAX 13
+#define PSEG_AUGMENT_NBHD_K 24
+#define PSEG_AUGMENT_NBHD_NOISE 25
+#define PSEG_AUGMENT_NBHD_DROP 27
+#define PSEG_AUGMENT_NBHD_SEED 31
+#define PSEG_AUGMENT_NBHD_WEIGHTS 40
+int pseg_augment_batch_nbhd(const uint8_t* img, const uint8_t* seg, const float* params, const int* shape_host, int B, int H, int W,
+                            float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh, int ow,
+                            int64_t* target, void* stream);
 
 /* ------------------------------------------------------------------ optimiser (flat parameter arena)
  * One launch over the whole arena; grad_scale folds the 1/world_size of the data-parallel mean

@@ -121,6 +121,200 @@ __global__ __launch_bounds__(256) void augment_batch_kernel(const uint8_t* __res
   }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same preprocess with a neighbourhood stage and per-pixel random stages (pseg_augment_batch_nbhd): per sample, on
+// the working grid, warp -> K x K correlation filter -> colour matrix -> Gaussian noise -> dropout -> normalise, 8-bit
+// rounding after each of the first four (row layout and contract: include/pseg_amd.h).
+//  - image blocks: a 32x8 tile of the output.  With a filter (K >= 3, per sample and hence block-uniform) the block first
+//    evaluates the warp ONCE per working-grid pixel of the span its output pixels map to, plus a halo of K/2 (indices
+//    beyond the grid reflect without repeating the edge pixel; a reflected halo pixel is evaluated again), and keeps the
+//    three rounded bytes packed in one LDS dword per pixel: a tap is one ds_read_b32 for the three planes, a wave's lanes
+//    read consecutive dwords (its two rows lie in different 32-lane halves, which never conflict).  Filter weights are
+//    block-uniform loads from the sample's row.  Without a filter the thread evaluates its own pixel and LDS is not used.
+//  - label blocks: exactly augment_batch_kernel's.
+// Random numbers: Philox4x32-10, key = the row's 64-bit seed, counter = (working-grid pixel or mask cell, stream, 0, 0).
+constexpr int kNbTileW = 32, kNbTileH = 8;
+constexpr uint32_t kStreamNoise = 0, kStreamDrop = 4;      // + the channel where the draw is per channel
+
+// ATen's nearest source index of output index o (fp32, as augment_batch_kernel); also evaluated on the host to size LDS
+__host__ __device__ __forceinline__ int aug_ms_index(int o, int in, int on) {
+  const int i = (int)floorf((float)o * ((float)in / (float)on));
+  return i < in - 1 ? i : in - 1;
+}
+
+// cv2's BORDER_REFLECT_101: -1 -> 1, n -> n - 2; the only pixel when n == 1
+__device__ __forceinline__ int reflect101(int i, int n) {
+  if (n == 1) return 0;
+  while ((unsigned)i >= (unsigned)n) i = i < 0 ? -i : 2 * n - 2 - i;
+  return i;
+}
+
+struct Philox4 {
+  uint32_t v[4];
+};
+
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1) {
+  uint32_t c2 = 0u, c3 = 0u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return Philox4{{c0, c1, c2, c3}};
+}
+
+// the warp of augment_batch_kernel for working-grid pixel (ix, iy): three values before the 8-bit rounding
+__device__ __forceinline__ void aug_warp(const uint8_t* __restrict__ p, const float* __restrict__ row, int ix, int iy, int H, int W,
+                                         int64_t plane, float v[3]) {
+  const AugCoord c = aug_coord(row, ix, iy, H, W);
+  const float cval = row[18];
+  const bool bilinear = row[19] != 0.f, edge = row[20] != 0.f && c.finite;
+  if (!bilinear) {
+    const int x = (int)floorf(c.sx + 0.5f), y = (int)floorf(c.sy + 0.5f);
+    const bool use = edge || (c.finite && x >= 0 && x < W && y >= 0 && y < H);
+    const int64_t at = (int64_t)clampi(y, H - 1) * W + clampi(x, W - 1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float s = (float)p[k * plane + at];
+      v[k] = use ? s : cval;
+    }
+  } else {
+    const float fx0 = floorf(c.sx), fy0 = floorf(c.sy);
+    const int x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
+    const float lx1 = c.sx - fx0, lx0 = 1.f - lx1, ly1 = c.sy - fy0, ly0 = 1.f - ly1;
+    const bool in_x0 = x0 >= 0 && x0 < W, in_x1 = x1 >= 0 && x1 < W, in_y0 = y0 >= 0 && y0 < H, in_y1 = y1 >= 0 && y1 < H;
+    const bool u00 = edge || (c.finite && in_y0 && in_x0), u01 = edge || (c.finite && in_y0 && in_x1);
+    const bool u10 = edge || (c.finite && in_y1 && in_x0), u11 = edge || (c.finite && in_y1 && in_x1);
+    const int cx0 = clampi(x0, W - 1), cx1 = clampi(x1, W - 1);
+    const int64_t r0 = (int64_t)clampi(y0, H - 1) * W, r1 = (int64_t)clampi(y1, H - 1) * W;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const uint8_t* q = p + k * plane;
+      const float s00 = (float)q[r0 + cx0], s01 = (float)q[r0 + cx1], s10 = (float)q[r1 + cx0], s11 = (float)q[r1 + cx1];
+      const float p00 = u00 ? s00 : cval, p01 = u01 ? s01 : cval, p10 = u10 ? s10 : cval, p11 = u11 ? s11 : cval;
+      v[k] = ly0 * (lx0 * p00 + lx1 * p01) + ly1 * (lx0 * p10 + lx1 * p11);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void augment_batch_nbhd_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ seg,
+                                                                 const float* __restrict__ params, AugNorm nm, float* __restrict__ out,
+                                                                 int64_t* __restrict__ target, int H, int W, int oh, int ow,
+                                                                 uint32_t n_img, uint32_t img_tiles_x, uint32_t img_tiles,
+                                                                 uint32_t lab_tiles_x, uint32_t lab_tiles, int halo_max,
+                                                                 uint32_t lds_elems) {
+  extern __shared__ uint32_t aug_tile[];                   // [span_h][span_w] of r | g << 8 | b << 16
+  const bool is_img = blockIdx.x < n_img;
+  const uint32_t blk = is_img ? blockIdx.x : blockIdx.x - n_img;
+  const uint32_t per = is_img ? img_tiles : lab_tiles, per_x = is_img ? img_tiles_x : lab_tiles_x;
+  const uint32_t b = blk / per, t = blk - b * per;
+  const uint32_t tyi = t / per_x, txi = t - tyi * per_x;
+  const float* __restrict__ row = params + (int64_t)b * PSEG_AUGMENT_NBHD_ROW;
+  const int64_t plane = (int64_t)H * W;
+
+  if (!is_img) {                                           // ---- labels: [H, W], nearest, 0 outside
+    const int ox = (int)txi * kAugTileW + (threadIdx.x & (kAugTileW - 1)), oy = (int)tyi * kAugTileH + threadIdx.x / kAugTileW;
+    if (ox >= W || oy >= H) return;
+    const AugCoord c = aug_coord(row, ox, oy, H, W);
+    const int x = (int)floorf(c.sx + 0.5f), y = (int)floorf(c.sy + 0.5f);
+    const bool inside = c.finite && x >= 0 && x < W && y >= 0 && y < H;
+    const uint8_t v = seg[(int64_t)b * plane + (int64_t)clampi(y, H - 1) * W + clampi(x, W - 1)];
+    target[(int64_t)b * plane + (int64_t)oy * W + ox] = inside ? (int64_t)v : 0;
+    return;
+  }
+
+  const int ox0 = (int)txi * kNbTileW, oy0 = (int)tyi * kNbTileH;
+  const int ox = ox0 + (threadIdx.x & (kNbTileW - 1)), oy = oy0 + threadIdx.x / kNbTileW;
+  const bool live = ox < ow && oy < oh;
+  const uint8_t* __restrict__ p = img + (int64_t)b * 3 * plane;
+  // working-grid pixel of this thread (a dead thread takes the tile's first: it only helps to fill LDS)
+  const int ix = aug_ms_index(live ? ox : ox0, W, ow), iy = aug_ms_index(live ? oy : oy0, H, oh);
+
+  // K of the sample; whatever the table holds, the halo stays inside what the host sized LDS for and the weights inside the row
+  const float kf = row[PSEG_AUGMENT_NBHD_K];
+  int k2 = (kf >= 2.f && kf <= (float)PSEG_AUGMENT_NBHD_KMAX) ? (int)kf / 2 : 0;
+  k2 = min(k2, halo_max);
+  // the span of working-grid pixels the tile's outputs map to (the index is monotone in the output index)
+  const int gx0 = aug_ms_index(ox0, W, ow), gx1 = aug_ms_index(min(ox0 + kNbTileW, ow) - 1, W, ow);
+  const int gy0 = aug_ms_index(oy0, H, oh), gy1 = aug_ms_index(min(oy0 + kNbTileH, oh) - 1, H, oh);
+  const int sw = gx1 - gx0 + 1 + 2 * k2, sh = gy1 - gy0 + 1 + 2 * k2;
+  if ((uint64_t)sw * (uint64_t)sh > lds_elems) k2 = 0;              // cannot happen with the host's sizing; never write past LDS
+
+  float v[3];
+  if (k2 == 0) {
+    aug_warp(p, row, ix, iy, H, W, plane, v);
+    v[0] = round_u8(v[0]), v[1] = round_u8(v[1]), v[2] = round_u8(v[2]);
+  } else {
+    for (int i = threadIdx.x; i < sw * sh; i += 256) {
+      const int ly = i / sw, lx = i - ly * sw;
+      float w[3];
+      aug_warp(p, row, reflect101(gx0 - k2 + lx, W), reflect101(gy0 - k2 + ly, H), H, W, plane, w);
+      aug_tile[i] = (uint32_t)round_u8(w[0]) | ((uint32_t)round_u8(w[1]) << 8) | ((uint32_t)round_u8(w[2]) << 16);
+    }
+    __syncthreads();
+    if (!live) return;
+    const int K = 2 * k2 + 1;
+    const uint32_t* __restrict__ win = aug_tile + (iy - gy0) * sw + (ix - gx0);   // the window's top-left tap
+    const float* __restrict__ wt = row + PSEG_AUGMENT_NBHD_WEIGHTS;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    for (int j = 0; j < K; ++j) {
+      for (int i = 0; i < K; ++i) {
+        const float wji = wt[j * K + i];
+        const uint32_t px = win[j * sw + i];
+        a0 = fmaf(wji, (float)(px & 0xffu), a0);
+        a1 = fmaf(wji, (float)((px >> 8) & 0xffu), a1);
+        a2 = fmaf(wji, (float)((px >> 16) & 0xffu), a2);
+      }
+    }
+    v[0] = round_u8(a0), v[1] = round_u8(a1), v[2] = round_u8(a2);
+  }
+  if (!live) return;
+
+  // noise and dropout of the working-grid pixel
+  const uint32_t seed_lo = __float_as_uint(row[PSEG_AUGMENT_NBHD_SEED]), seed_hi = __float_as_uint(row[PSEG_AUGMENT_NBHD_SEED + 1]);
+  const uint32_t pix = (uint32_t)iy * (uint32_t)W + (uint32_t)ix;
+  const float nscale = row[PSEG_AUGMENT_NBHD_NOISE];
+  const bool noisy = nscale > 0.f && nscale <= 3.0e38f, noise_pc = row[PSEG_AUGMENT_NBHD_NOISE + 1] != 0.f;
+  const float drop_p = row[PSEG_AUGMENT_NBHD_DROP];
+  const bool dropping = drop_p > 0.f, drop_pc = row[PSEG_AUGMENT_NBHD_DROP + 1] != 0.f;
+  const uint32_t mh = (uint32_t)fminf(fmaxf(row[PSEG_AUGMENT_NBHD_DROP + 2], 0.f), 65535.f);
+  const uint32_t mw = (uint32_t)fminf(fmaxf(row[PSEG_AUGMENT_NBHD_DROP + 3], 0.f), 65535.f);
+  const uint32_t cell = (mh && mw) ? ((uint32_t)iy * mh / (uint32_t)H) * mw + (uint32_t)ix * mw / (uint32_t)W : pix;
+
+  const int64_t oplane = (int64_t)oh * ow;
+  float* o = out + (int64_t)b * 3 * oplane + (int64_t)oy * ow + ox;
+  float n_shared = 0.f;
+  bool keep_shared = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float* m = row + 6 + 4 * k;
+    float q = round_u8(fmaf(m[0], v[0], fmaf(m[1], v[1], fmaf(m[2], v[2], m[3]))));
+    if (noisy) {
+      if (k == 0 || noise_pc) {
+        const Philox4 r = philox4x32_10(pix, kStreamNoise + (uint32_t)k, seed_lo, seed_hi);
+        const float u1 = (float)((r.v[0] >> 8) + 1u) * 0x1p-24f, u2 = (float)(r.v[1] >> 8) * 0x1p-24f;
+        n_shared = sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
+      }
+      q = round_u8(fmaf(nscale, n_shared, q));
+    }
+    if (dropping) {
+      if (k == 0 || drop_pc) {
+        const Philox4 r = philox4x32_10(cell, kStreamDrop + (uint32_t)k, seed_lo, seed_hi);
+        keep_shared = (float)(r.v[0] >> 8) * 0x1p-24f >= drop_p;
+      }
+      q = keep_shared ? q : 0.f;
+    }
+    o[k * oplane] = (q - nm.mean[k]) / nm.std[k];
+  }
+}
+
 }  // namespace pseg
 
 using namespace pseg;
@@ -145,6 +339,55 @@ int pseg_augment_batch(const uint8_t* img, const uint8_t* seg, const float* para
   hipLaunchKernelGGL(augment_batch_kernel, dim3((uint32_t)(n_img + n_lab)), dim3(256), 0, (hipStream_t)stream, img, seg, params, nm,
                      out, target, H, W, oh, ow, (uint32_t)n_img, (uint32_t)img_tiles_x, (uint32_t)img_tiles,
                      (uint32_t)lab_tiles_x, (uint32_t)lab_tiles);
+  PSEG_LAUNCH_CHECK();
+  return PSEG_OK;
+}
+
+int pseg_augment_batch_nbhd(const uint8_t* img, const uint8_t* seg, const float* params, const int* shape_host, int B, int H, int W,
+                            float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh, int ow,
+                            int64_t* target, void* stream) {
+  PSEG_REQUIRE(img && seg && params && shape_host && out && target, "augment_batch_nbhd: null pointer");
+  PSEG_REQUIRE(B >= 1 && B <= 65535, "augment_batch_nbhd: batch %d outside [1, 65535]", B);
+  PSEG_REQUIRE(H >= 1 && H <= 65535 && W >= 1 && W <= 65535, "augment_batch_nbhd: input size %dx%d outside [1, 65535]", H, W);
+  PSEG_REQUIRE(oh >= 1 && oh <= 65535 && ow >= 1 && ow <= 65535, "augment_batch_nbhd: output size %dx%d outside [1, 65535]", oh, ow);
+  PSEG_REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "augment_batch_nbhd: std must be non-zero");
+  int kmax = 0;
+  for (int b = 0; b < B; ++b) {
+    const int K = shape_host[3 * b], mh = shape_host[3 * b + 1], mw = shape_host[3 * b + 2];
+    PSEG_REQUIRE(K >= 0 && K <= PSEG_AUGMENT_NBHD_KMAX && (K <= 1 || (K & 1)),
+                 "augment_batch_nbhd: sample %d: filter size %d is not 0, 1 or an odd number up to %d", b, K, PSEG_AUGMENT_NBHD_KMAX);
+    PSEG_REQUIRE(mh >= 0 && mw >= 0 && mh <= 65535 && mw <= 65535 && (mh == 0) == (mw == 0),
+                 "augment_batch_nbhd: sample %d: dropout mask %dx%d (0x0 = per pixel, otherwise 1..65535 each way)", b, mh, mw);
+    kmax = K > kmax ? K : kmax;
+  }
+  const int halo = kmax / 2;
+  const int64_t img_tiles_x = cdiv(ow, kNbTileW), img_tiles_y = cdiv(oh, kNbTileH), img_tiles = img_tiles_x * img_tiles_y;
+  const int64_t lab_tiles_x = cdiv(W, kAugTileW), lab_tiles = lab_tiles_x * cdiv(H, kAugTileH);
+  const int64_t n_img = (int64_t)B * img_tiles, n_lab = (int64_t)B * lab_tiles;
+  PSEG_REQUIRE(n_img + n_lab <= 0xffffffLL, "augment_batch_nbhd: %lld tiles exceed one launch (batch %d of %dx%d -> %dx%d)",
+               (long long)(n_img + n_lab), B, H, W, oh, ow);
+  // LDS: the widest and the tallest working-grid span of an output tile (the kernel's own index function), plus the halo
+  int64_t lds_elems = 0;
+  if (halo > 0) {
+    int span_w = 1, span_h = 1;
+    for (int64_t t = 0; t < img_tiles_x; ++t) {
+      const int o0 = (int)t * kNbTileW, o1 = (o0 + kNbTileW < ow ? o0 + kNbTileW : ow) - 1;
+      const int s = aug_ms_index(o1, W, ow) - aug_ms_index(o0, W, ow) + 1;
+      span_w = s > span_w ? s : span_w;
+    }
+    for (int64_t t = 0; t < img_tiles_y; ++t) {
+      const int o0 = (int)t * kNbTileH, o1 = (o0 + kNbTileH < oh ? o0 + kNbTileH : oh) - 1;
+      const int s = aug_ms_index(o1, H, oh) - aug_ms_index(o0, H, oh) + 1;
+      span_h = s > span_h ? s : span_h;
+    }
+    lds_elems = (int64_t)(span_w + 2 * halo) * (span_h + 2 * halo);
+    PSEG_REQUIRE(lds_elems * 4 <= 65536, "augment_batch_nbhd: a %dx%d output tile of %dx%d -> %dx%d with K = %d needs %lld bytes of LDS (limit 65536)",
+                 kNbTileW, kNbTileH, H, W, oh, ow, kmax, (long long)(lds_elems * 4));
+  }
+  AugNorm nm{{mean0, mean1, mean2}, {std0, std1, std2}};
+  hipLaunchKernelGGL(augment_batch_nbhd_kernel, dim3((uint32_t)(n_img + n_lab)), dim3(256), (size_t)lds_elems * 4, (hipStream_t)stream,
+                     img, seg, params, nm, out, target, H, W, oh, ow, (uint32_t)n_img, (uint32_t)img_tiles_x, (uint32_t)img_tiles,
+                     (uint32_t)lab_tiles_x, (uint32_t)lab_tiles, halo, (uint32_t)lds_elems);
   PSEG_LAUNCH_CHECK();
   return PSEG_OK;
 }

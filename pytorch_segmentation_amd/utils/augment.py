@@ -1,12 +1,15 @@
-"""On-device training augmentation: the geometric and colour-affine part of the reference's online augmentation
-(``TRAIN_AUGS``, reference utils/datasets.py:26-125, imgaug on the host, one sample at a time) as ONE kernel over the
-collated uint8 batch (csrc/augment.hip), fused with ``CocoDataset.post_fetch_fn``'s normalisation, multi-scale resize and
-label widening.
+"""On-device training augmentation: the geometric, colour-affine, small-filter, noise and dropout part of the reference's
+online augmentation (``TRAIN_AUGS``, reference utils/datasets.py:26-125, imgaug on the host, one sample at a time) as ONE
+kernel over the collated uint8 batch (csrc/augment.hip), fused with ``CocoDataset.post_fetch_fn``'s normalisation,
+multi-scale resize and label widening.
 
 The host only draws numbers.  ``DeviceAugment.draw(B)`` draws one *recipe* per sample from a seedable
 ``numpy.random.Generator``; ``DeviceAugment.rows(recipes, H, W)`` folds each recipe into one row of the kernel's parameter
 table (layout: include/pseg_amd.h, ``PSEG_AUGMENT_ROW`` floats): the INVERSE affine of the whole geometric chain, a 3x4
-colour matrix in 0..255 units, the fill value, the interpolation order and the border mode.
+colour matrix in 0..255 units, the fill value, the interpolation order and the border mode.  A batch in which some sample
+drew a filter, noise or dropout gets the wider rows of ``pseg_augment_batch_nbhd`` (``PSEG_AUGMENT_NBHD_ROW`` floats: the
+same 24, then K, the noise and dropout parameters, the sample's 64-bit seed bit-cast into two floats, and the K x K
+weights) and goes through that kernel; every other batch goes through ``pseg_augment_batch`` as before.
 
 Built (defaults of ``DeviceAugment.reference()`` = the reference's values):
   * ``Fliplr(0.5)``, ``Flipud(0.2)``;
@@ -19,19 +22,41 @@ Built (defaults of ``DeviceAugment.reference()`` = the reference's values):
     branches of its ``OneOf``), ``LinearContrast((0.5, 2.0), per_channel=0.5)`` and ``Grayscale(alpha=(0, 1))``.  As in the
     reference, 0..5 of the block's 16 slots are picked per sample; a picked slot that holds one of these five is applied,
     in a random order; the other slots do nothing here.
+  * only with ``DeviceAugment.full()`` (all off by default, so ``DeviceAugment()`` / ``.reference()`` draw the tables they
+    always drew): five more slots of that block, the neighbourhood and per-pixel-random augmenters -- see "Filters, noise
+    and dropout" below.  With them 10 of the 16 slots are live.
 Labels are warped with the same matrix, nearest sample, background 0, as imgaug warps segmentation maps.
 
-OUT OF SCOPE -- every neighbourhood or non-affine augmenter of ``TRAIN_AUGS``: the blurs (Gaussian, average, median),
-Sharpen, Emboss, the edge-detect blends (BlendAlphaSimplexNoise), Superpixels, AdditiveGaussianNoise, Dropout and
-CoarseDropout, AddToHueAndSaturation, the frequency-noise blend (BlendAlphaFrequencyNoise), ElasticTransformation,
-PiecewiseAffine and PerspectiveTransform; and imgaug's border modes other than constant and edge (``ia.ALL`` also draws
-reflect, symmetric and wrap).
+Filters, noise and dropout (``full()``).  These formulas are THIS MODULE'S CONTRACT.  They were written down from imgaug's
+documentation as remembered; imgaug and cv2 are not installed where this was written, so they were NOT checked against
+either.  Each takes one slot of the ``SomeOf`` block (slots 5..9):
+  * blur ``OneOf``: one third of the time ``GaussianBlur``: sigma ~ U(0, 3), no blur if sigma < 0.001,
+    ``k = int(max(3.3 sigma, 5))`` (sigma < 3) made odd by + 1, weights ``exp(-d^2 / 2 sigma^2)`` normalised, the separable
+    outer product; one third ``AverageBlur``: integer k ~ U{2..7}, window ``[x - k//2, x - k//2 + k - 1]``, weights 1/k^2,
+    embedded in the next odd K; one third ``MedianBlur``, which is out of scope: nothing happens;
+  * ``Sharpen``: alpha ~ U(0, 1), lightness l ~ U(0.75, 1.5): ``(1 - alpha) delta + alpha [[-1,-1,-1],[-1,8+l,-1],[-1,-1,-1]]``;
+  * ``Emboss``: alpha ~ U(0, 1), strength s ~ U(0, 2): ``(1 - alpha) delta + alpha [[-1-s,-s,0],[-s,1,s],[0,s,1+s]]``;
+  * ``AdditiveGaussianNoise``: scale ~ U(0, 12.75), per channel with probability 0.5;
+  * dropout ``OneOf``: ``Dropout``: p ~ U(0.01, 0.1), per channel 0.5; or ``CoarseDropout``: p ~ U(0.03, 0.15), size fraction
+    f ~ U(0.02, 0.05), mask ``mh = max(4, int(H f))``, ``mw = max(4, int(W f))``, per channel 0.2; pixel (y, x) takes the
+    draw of mask cell ``(y mh // H, x mw // W)``.
+Filters are correlations (cv2 ``filter2D``, which imgaug's ``Convolve`` calls) with cv2's default border (reflect without
+repeating the edge pixel).  Noise and dropout are drawn on the device: Philox4x32-10 keyed by a 64-bit seed that the host
+draws per sample, counted by the working-grid pixel (include/pseg_amd.h).
+
+OUT OF SCOPE -- the remaining six slots of the block: the edge-detect blend (BlendAlphaSimplexNoise), Superpixels,
+AddToHueAndSaturation, the frequency-noise blend (BlendAlphaFrequencyNoise), ElasticTransformation and PiecewiseAffine /
+PerspectiveTransform, and the median blur and the frequency-noise branch inside two ``OneOf``s; and imgaug's border modes
+other than constant and edge (``ia.ALL`` also draws reflect, symmetric and wrap).
 
 Simplifications, all on the host side: the geometric augmenters run in the fixed order flips, crop-and-pad, affine (the
 reference shuffles the top-level list), and the chain is ONE warp (imgaug resamples once per augmenter); one (order, cval,
 mode) triple serves a sample -- crop-and-pad alone is bilinear, the affine's own draw wins when it is active; the colour
 operations are composed into one matrix, so the 8-bit rounding and saturation that imgaug applies between two of them
-happens once, after the last.
+happens once, after the last; the picked filters of a sample (blur, sharpen, emboss) are composed, in fp64, into ONE K x K
+filter by full 2-D convolution (K <= 13: 9 + 2 + 2), which likewise gives up the 8-bit rounding between them (and the
+border handling of each on its own); and the stages of a sample run in the fixed order warp, filter, colour matrix,
+noise, dropout, whatever order the ``SomeOf`` block drew (the reference applies the picked augmenters in a random order).
 """
 import numpy as np
 import torch
@@ -44,6 +69,10 @@ GRAY_WEIGHTS = (0.299, 0.587, 0.114)
 COLOUR_SLOTS = 16                # augmenters in the reference's SomeOf block
 _COLOUR_OPS = ('invert', 'add', 'multiply', 'contrast', 'grayscale')
 MODES = {'constant': 0, 'edge': 1}
+NBHD_ROW = 212                   # PSEG_AUGMENT_NBHD_ROW; the offsets below are PSEG_AUGMENT_NBHD_* of include/pseg_amd.h
+NBHD_KMAX = 13
+NBHD_K, NBHD_NOISE, NBHD_DROP, NBHD_SEED, NBHD_WEIGHTS = 24, 25, 27, 31, 40
+_NBHD_OPS = ('blur', 'sharpen', 'emboss', 'noise', 'dropout')        # slots 5..9 of the SomeOf block
 
 
 def _eye3():
@@ -135,6 +164,86 @@ def make_row(inverse=None, colour=None, cval=0.0, order=0, mode=0):
     return row
 
 
+def gaussian_kernel(sigma):
+    """GaussianBlur(sigma) as a K x K correlation filter (fp64), None below sigma = 0.001"""
+    if sigma < 0.001:
+        return None
+    k = int(max(3.3 * sigma, 5))
+    k += 1 - k % 2
+    d = np.arange(k, dtype=np.float64) - k // 2
+    g = np.exp(-d * d / (2.0 * sigma * sigma))
+    g /= g.sum()
+    return np.outer(g, g)
+
+
+def average_kernel(k):
+    """AverageBlur(k): the mean over the window [x - k//2, x - k//2 + k - 1], embedded in the next odd K"""
+    k = int(k)
+    K = k + 1 - k % 2
+    m = np.zeros((K, K), dtype=np.float64)
+    m[:k, :k] = 1.0 / (k * k)
+    return m
+
+
+def _blend_with_identity(alpha, m):
+    out = alpha * np.asarray(m, dtype=np.float64)
+    out[1, 1] += 1.0 - alpha
+    return out
+
+
+def sharpen_kernel(alpha, lightness):
+    return _blend_with_identity(alpha, [[-1, -1, -1], [-1, 8 + lightness, -1], [-1, -1, -1]])
+
+
+def emboss_kernel(alpha, strength):
+    s = strength
+    return _blend_with_identity(alpha, [[-1 - s, -s, 0], [-s, 1, s], [0, s, 1 + s]])
+
+
+def filter_kernel(name, *args):
+    return {'gaussian': gaussian_kernel, 'average': average_kernel, 'sharpen': sharpen_kernel, 'emboss': emboss_kernel}[name](*args)
+
+
+def compose_filters(kernels):
+    """one filter that stands for the correlation filters applied one after the other: their full 2-D convolution (fp64)"""
+    out = np.ones((1, 1), dtype=np.float64)
+    for k in kernels:
+        k = np.asarray(k, dtype=np.float64)
+        acc = np.zeros((out.shape[0] + k.shape[0] - 1, out.shape[1] + k.shape[1] - 1), dtype=np.float64)
+        for j in range(k.shape[0]):
+            for i in range(k.shape[1]):
+                acc[j:j + out.shape[0], i:i + out.shape[1]] += k[j, i] * out
+        out = acc
+    return out
+
+
+def make_nbhd_row(base=None, kernel=None, noise=None, dropout=None, seed=0):
+    """one row of pseg_augment_batch_nbhd's table from a make_row() row, a K x K filter (K odd, at most NBHD_KMAX), noise =
+    (scale, per_channel), dropout = (p, per_channel[, mh, mw]) and the sample's 64-bit seed (bit-cast, not converted)"""
+    row = np.zeros(NBHD_ROW, dtype=np.float32)
+    row[:ROW] = make_row() if base is None else base
+    if kernel is not None:
+        kernel = np.asarray(kernel, dtype=np.float64)
+        K = kernel.shape[0]
+        if kernel.shape != (K, K) or K % 2 == 0 or K > NBHD_KMAX:
+            raise ValueError('a filter is K x K with K odd and at most %d, not %s' % (NBHD_KMAX, kernel.shape))
+        row[NBHD_K] = K
+        row[NBHD_WEIGHTS:NBHD_WEIGHTS + K * K] = kernel.reshape(-1)
+    if noise is not None:
+        row[NBHD_NOISE], row[NBHD_NOISE + 1] = noise[0], bool(noise[1])
+    if dropout is not None:
+        row[NBHD_DROP], row[NBHD_DROP + 1] = dropout[0], bool(dropout[1])
+        if len(dropout) > 2:
+            row[NBHD_DROP + 2], row[NBHD_DROP + 3] = dropout[2], dropout[3]
+    row.view(np.uint32)[NBHD_SEED:NBHD_SEED + 2] = (int(seed) & 0xffffffff, (int(seed) >> 32) & 0xffffffff)
+    return row
+
+
+def row_shapes(table):
+    """int32 [B, 3] = {K, mh, mw} of each row: what pseg_augment_batch_nbhd validates on the host"""
+    return np.ascontiguousarray(np.asarray(table)[:, [NBHD_K, NBHD_DROP + 2, NBHD_DROP + 3]].astype(np.int32))
+
+
 def _range(v):
     return None if v is None else (float(v[0]), float(v[1]))
 
@@ -145,7 +254,10 @@ class DeviceAugment:
     def __init__(self, fliplr=0.5, flipud=0.2, crop_pad=(-0.05, 0.1), crop_pad_p=0.5, affine_p=0.5, scale=(0.8, 1.2),
                  translate=(-0.2, 0.2), rotate=(-90.0, 90.0), shear=(-16.0, 16.0), orders=(0, 1), cval=(0, 255),
                  modes=('constant', 'edge'), add=(-10, 10), multiply=(0.5, 1.5), contrast=(0.5, 2.0), invert=0.05,
-                 grayscale=(0.0, 1.0), per_channel=0.5, some_of=(0, 5), seed=None, rank=None, mean=MEAN, std=STD):
+                 grayscale=(0.0, 1.0), per_channel=0.5, some_of=(0, 5), seed=None, rank=None, mean=MEAN, std=STD,
+                 gaussian_blur=None, average_blur=None, sharpen_alpha=None, sharpen_lightness=(0.75, 1.5), emboss_alpha=None,
+                 emboss_strength=(0.0, 2.0), noise_scale=None, noise_per_channel=0.5, dropout_p=None, dropout_per_channel=0.5,
+                 coarse_p=None, coarse_size=(0.02, 0.05), coarse_per_channel=0.2):
         self.fliplr, self.flipud = float(fliplr), float(flipud)
         self.crop_pad, self.crop_pad_p = _range(crop_pad), float(crop_pad_p if crop_pad is not None else 0.0)
         if self.crop_pad is not None and self.crop_pad[0] <= -0.45:
@@ -158,12 +270,28 @@ class DeviceAugment:
         self.per_channel, self.some_of = float(per_channel), (int(some_of[0]), int(some_of[1]))
         self.seed, self.rank = seed, rank
         self.mean, self.std = tuple(mean), tuple(std)
+        # the neighbourhood and per-pixel-random augmenters: a range of None (the default) switches one off
+        self.gaussian_blur, self.average_blur = _range(gaussian_blur), _range(average_blur)
+        self.sharpen_alpha, self.sharpen_lightness = _range(sharpen_alpha), _range(sharpen_lightness)
+        self.emboss_alpha, self.emboss_strength = _range(emboss_alpha), _range(emboss_strength)
+        self.noise_scale, self.noise_per_channel = _range(noise_scale), float(noise_per_channel)
+        self.dropout_p, self.dropout_per_channel = _range(dropout_p), float(dropout_per_channel)
+        self.coarse_p, self.coarse_size, self.coarse_per_channel = _range(coarse_p), _range(coarse_size), float(coarse_per_channel)
         self._rng = None
 
     @classmethod
     def reference(cls, **kw):
         """the reference's TRAIN_AUGS values (the constructor defaults)"""
         return cls(**kw)
+
+    @classmethod
+    def full(cls, **kw):
+        """reference() plus GaussianBlur / AverageBlur, Sharpen, Emboss, AdditiveGaussianNoise and Dropout / CoarseDropout at
+        the reference's ranges: 10 of the 16 slots of the SomeOf block"""
+        on = dict(gaussian_blur=(0.0, 3.0), average_blur=(2, 7), sharpen_alpha=(0.0, 1.0), emboss_alpha=(0.0, 1.0),
+                  noise_scale=(0.0, 0.05 * 255), dropout_p=(0.01, 0.1), coarse_p=(0.03, 0.15))
+        on.update(kw)
+        return cls(**on)
 
     @classmethod
     def identity(cls, order=0, **kw):
@@ -191,7 +319,37 @@ class DeviceAugment:
         v = rng.integers(int(lo_hi[0]), int(lo_hi[1]) + 1, n).astype(np.float64) if integer else rng.uniform(lo_hi[0], lo_hi[1], n)
         return np.broadcast_to(v, (3,)).copy()
 
-    def _draw_colour(self, rng):
+    def _draw_nbhd(self, rng, name, nbhd):
+        """one picked slot of the five neighbourhood / per-pixel-random augmenters -> nbhd (an augmenter that is off draws
+        nothing, so the default tables are those of the colour-only sampler)"""
+        if name == 'blur' and (self.gaussian_blur is not None or self.average_blur is not None):
+            which = int(rng.integers(3))                      # Gaussian, average, median (out of scope)
+            if which == 0 and self.gaussian_blur is not None:
+                sigma = float(rng.uniform(*self.gaussian_blur))
+                if sigma >= 0.001:
+                    nbhd.setdefault('filters', []).append(('gaussian', sigma))
+            elif which == 1 and self.average_blur is not None:
+                k = int(rng.integers(int(self.average_blur[0]), int(self.average_blur[1]) + 1))
+                if k > 1:
+                    nbhd.setdefault('filters', []).append(('average', k))
+        elif name == 'sharpen' and self.sharpen_alpha is not None:
+            nbhd.setdefault('filters', []).append(('sharpen', float(rng.uniform(*self.sharpen_alpha)),
+                                                   float(rng.uniform(*self.sharpen_lightness))))
+        elif name == 'emboss' and self.emboss_alpha is not None:
+            nbhd.setdefault('filters', []).append(('emboss', float(rng.uniform(*self.emboss_alpha)),
+                                                   float(rng.uniform(*self.emboss_strength))))
+        elif name == 'noise' and self.noise_scale is not None:
+            nbhd['noise'] = (float(rng.uniform(*self.noise_scale)), bool(rng.random() < self.noise_per_channel))
+        elif name == 'dropout' and (self.dropout_p is not None or self.coarse_p is not None):
+            which = int(rng.integers(2))                      # Dropout, CoarseDropout
+            if which == 0 and self.dropout_p is not None:
+                nbhd['dropout'] = {'p': float(rng.uniform(*self.dropout_p)), 'per_channel': bool(rng.random() < self.dropout_per_channel),
+                                   'size': None}
+            elif which == 1 and self.coarse_p is not None:
+                nbhd['dropout'] = {'p': float(rng.uniform(*self.coarse_p)), 'per_channel': bool(rng.random() < self.coarse_per_channel),
+                                   'size': float(rng.uniform(*self.coarse_size))}
+
+    def _draw_colour(self, rng, nbhd=None):
         lo, hi = self.some_of
         n = int(rng.integers(lo, hi + 1)) if hi > 0 else 0
         picked = rng.permutation(COLOUR_SLOTS)[:n]            # slots 0..4 hold this module's five, in _COLOUR_OPS order
@@ -211,11 +369,17 @@ class DeviceAugment:
                 ops.append(('contrast', self._values(rng, self.contrast)))
             elif name == 'grayscale' and self.grayscale is not None:
                 ops.append(('grayscale', float(rng.uniform(*self.grayscale))))
+            elif nbhd is not None and len(_COLOUR_OPS) <= slot < len(_COLOUR_OPS) + len(_NBHD_OPS):
+                self._draw_nbhd(rng, _NBHD_OPS[slot - len(_COLOUR_OPS)], nbhd)
+        if nbhd and ('noise' in nbhd or 'dropout' in nbhd):
+            nbhd['seed'] = int(rng.integers(0, 2 ** 64, dtype=np.uint64))
         return ops
 
     def draw(self, B):
         """-> list of B recipes (dicts): fliplr, flipud, crop_pad (top, right, bottom, left) or None, affine (keyword
-        arguments of affine_matrix) or None, order, cval, mode, colour [(name, value), ...]"""
+        arguments of affine_matrix) or None, order, cval, mode, colour [(name, value), ...]; and only where drawn: filters
+        [(name, parameters of filter_kernel...), ...], noise (scale, per_channel), dropout {p, per_channel, size: the mask's
+        fraction of the image or None}, seed"""
         rng, out = self.rng, []
         for _ in range(B):
             r = {'fliplr': bool(rng.random() < self.fliplr), 'flipud': bool(rng.random() < self.flipud), 'crop_pad': None,
@@ -234,36 +398,59 @@ class DeviceAugment:
             r['order'] = int(order)
             r['cval'] = float(rng.integers(int(self.cval[0]), int(self.cval[1]) + 1))
             r['mode'] = int(self.modes[int(rng.integers(len(self.modes)))])
-            r['colour'] = self._draw_colour(rng)
+            nbhd = {}
+            r['colour'] = self._draw_colour(rng, nbhd)
+            r.update(nbhd)
             out.append(r)
         return out
 
     @staticmethod
     def rows(recipes, H, W):
-        """recipes -> the kernel's parameter table, numpy float32 [B, ROW] (matrices composed and inverted in fp64)"""
-        table = np.zeros((len(recipes), ROW), dtype=np.float32)
+        """recipes -> the kernel's parameter table, numpy float32 (matrices and filters composed in fp64): [B, ROW], or
+        [B, NBHD_ROW] when some recipe holds a filter, noise or dropout"""
+        wide = any(r.get('filters') or r.get('noise') or r.get('dropout') for r in recipes)
+        table = np.zeros((len(recipes), NBHD_ROW if wide else ROW), dtype=np.float32)
         for i, r in enumerate(recipes):
             inv = np.linalg.inv(forward_matrix(r, H, W))
-            table[i] = make_row(inv, colour_matrix(r.get('colour', ())), r.get('cval', 0.0), r.get('order', 0), r.get('mode', 0))
+            row = make_row(inv, colour_matrix(r.get('colour', ())), r.get('cval', 0.0), r.get('order', 0), r.get('mode', 0))
+            if wide:
+                kernel = compose_filters([filter_kernel(*f) for f in r['filters']]) if r.get('filters') else None
+                d = r.get('dropout')
+                if d is not None:
+                    mask = (0, 0) if d['size'] is None else (max(4, int(H * d['size'])), max(4, int(W * d['size'])))
+                    d = (d['p'], d['per_channel']) + mask
+                row = make_nbhd_row(row, kernel, r.get('noise'), d, r.get('seed', 0))
+            table[i] = row
         return table
 
     def sample(self, B, H, W):
-        """-> numpy float32 [B, ROW]: one parameter row per sample of a B x 3 x H x W batch"""
+        """-> numpy float32 [B, ROW] or [B, NBHD_ROW]: one parameter row per sample of a B x 3 x H x W batch"""
         return self.rows(self.draw(B), H, W)
 
     # ------------------------------------------------------------------ device side
-    def apply(self, imgs, segs, params, out_hw=None):
-        """explicit rows (numpy or tensor [B, ROW]) -> (fp32 [B,3,oh,ow], int64 [B,H,W]); out_hw=None keeps (H, W)"""
+    def apply(self, imgs, segs, params, out_hw=None, shapes=None):
+        """explicit rows (numpy or tensor [B, ROW] or [B, NBHD_ROW]) -> (fp32 [B,3,oh,ow], int64 [B,H,W]); out_hw=None keeps
+        (H, W).  Rows of NBHD_ROW floats go through pseg_augment_batch_nbhd; when they already live on the device, shapes
+        (row_shapes() of the table) has to come with them."""
         from .. import ops
-        assert ROW == ops.AUGMENT_ROW
+        assert ROW == ops.AUGMENT_ROW and NBHD_ROW == ops.AUGMENT_NBHD_ROW
         B, _, H, W = imgs.shape
         if not torch.is_tensor(params):
             params = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32))
+        wide = params.shape[1] == NBHD_ROW
+        if wide and shapes is None:
+            if params.is_cuda:
+                raise ValueError('a device table of NBHD_ROW floats needs shapes=row_shapes(table) from the host')
+            shapes = row_shapes(params.numpy())
         if not params.is_cuda:
             # one pinned, non-blocking copy per batch (the pinned block stays alive until the copy ran: the caching
             # host allocator holds it back for the stream that used it)
             params = params.pin_memory().to(imgs.device, non_blocking=True)
         oh, ow = (H, W) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        if wide:
+            shapes = torch.as_tensor(shapes, dtype=torch.int32).contiguous()
+            return ops.augment_batch_nbhd(imgs.contiguous(), segs.contiguous(), params.contiguous(), shapes, oh, ow, self.mean,
+                                          self.std)
         return ops.augment_batch(imgs.contiguous(), segs.contiguous(), params.contiguous(), oh, ow, self.mean, self.std)
 
     def __call__(self, imgs_u8, segs_u8, out_hw=None):

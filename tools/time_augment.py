@@ -9,6 +9,10 @@ At B = 16, 3 x 512 x 512 and at B = 8, 3 x 256 x 256, on the same uint8 tensors:
   * `augment reference`: ops.augment_batch with DeviceAugment.reference() rows already on the device (rotated / bilinear
     gathers, colour matrices);
   * `DeviceAugment()`: the whole call as the loader makes it -- host sampling, the pinned copy of the table, the launch.
+At B = 16, 3 x 512 x 512 also the neighbourhood kernel (ops.augment_batch_nbhd: filter, noise, dropout), tables on the device:
+  * `nbhd identity rows`: identity rows without a filter, noise or dropout (next to `augment identity rows` of the same loop);
+  * `nbhd full(seed=0) rows`: the first batch that DeviceAugment.full(seed=0) draws;
+  * `nbhd K=13 every sample`: identity rows with a dense 13 x 13 filter on every sample, the upper end.
 Each figure is the median over --iters (>= 50) single calls, each between its own pair of events, after warm-up; the
 variants alternate inside one loop so that they see the same machine.  Algorithmic bytes = every input byte once + the fp32
 output + the int64 targets; fractions of the roof are over 6.3 TB/s HBM.
@@ -85,6 +89,41 @@ def rows_for(B, H, W, out_hw, iters):
     return out
 
 
+def nbhd_rows_for(B, H, W, iters):
+    import numpy as np
+    from pytorch_segmentation_amd.utils import augment as aug
+    g = torch.Generator().manual_seed(B * H)
+    imgs = torch.randint(0, 256, (B, 3, H, W), dtype=torch.uint8, generator=g).cuda()
+    segs = torch.randint(0, 21, (B, H, W), dtype=torch.uint8, generator=g).cuda()
+    narrow = DeviceAugment.identity(seed=0).sample(B, H, W)
+    full = DeviceAugment.full(seed=0).sample(B, H, W)
+    assert full.shape[1] == aug.NBHD_ROW, 'the first batch of full(seed=0) draws a filter'
+    tables = {
+        'nbhd identity rows': np.stack([aug.make_nbhd_row(r) for r in narrow]),
+        'nbhd full(seed=0) rows': full,
+        'nbhd K=13 every sample': np.stack([aug.make_nbhd_row(r, np.full((13, 13), 1.0 / 169)) for r in narrow]),
+    }
+    ident = torch.from_numpy(narrow).cuda()
+    fns = {'augment identity rows': lambda: ops.augment_batch(imgs, segs, ident, H, W, MEAN, STD)}
+    for name, t in tables.items():
+        dev, shapes = torch.from_numpy(t).cuda(), torch.from_numpy(aug.row_shapes(t))
+        fns[name] = lambda dev=dev, shapes=shapes: ops.augment_batch_nbhd(imgs, segs, dev, shapes, H, W, MEAN, STD)
+    a, b = fns['augment identity rows'](), fns['nbhd identity rows']()
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), 'rows without neighbourhood fields must reproduce augment_batch'
+    ms = timed_median(fns, iters)
+    shapes = aug.row_shapes(full)
+    out = []
+    for k, v in ms.items():
+        r = {'name': k, 'B': B, 'in': [H, W], 'out': [H, W], 'median_ms': round(v, 4), 'iters': iters, 'section': 'nbhd'}
+        if k.startswith('nbhd full'):
+            r['K'] = shapes[:, 0].tolist()
+            r['noise'] = int((full[:, aug.NBHD_NOISE] > 0).sum())
+            r['dropout'] = int((full[:, aug.NBHD_DROP] > 0).sum())
+        print(json.dumps(r), flush=True)
+        out.append(r)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='')
@@ -95,6 +134,7 @@ def main():
     random.seed(0)
     rows = rows_for(16, 512, 512, None, opt.iters) + rows_for(8, 256, 256, None, opt.iters)
     rows += rows_for(16, 512, 512, (384, 384), opt.iters)          # one multi-scale size: the torch path adds its interpolate
+    rows += nbhd_rows_for(16, 512, 512, opt.iters)
     if opt.out:
         with open(opt.out, 'w') as f:
             json.dump(rows, f, indent=1)
