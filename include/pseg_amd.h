@@ -520,6 +520,44 @@ int pseg_augment_batch_nbhd(const uint8_t* img, const uint8_t* seg, const float*
                             float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh, int ow,
                             int64_t* target, void* stream);
 
+/* pseg_augment_batch_warp: pseg_augment_batch_nbhd with a coordinate map that is not one affine (the reference's
+ * ElasticTransformation, PiecewiseAffine and PerspectiveTransform).  Arguments, shape_host [B][3] = {K, mh, mw}, its
+ * validation and the LDS sizing are pseg_augment_batch_nbhd's.  params: fp32 [B][PSEG_AUGMENT_WARP_ROW]:
+ *   [0..211]   pseg_augment_batch_nbhd's row, verbatim; [0..5] are now the first two rows h00 h01 h02 / h10 h11 h12 of a 3 x 3
+ *              inverse homography
+ *   [212..214] h20 h21 h22, its third row
+ *   [215]      elastic alpha in pixels; anything not > 0 and <= 3e38 means no jitter
+ *   [216]      != 0: the 4 x 4 displacement grid is applied
+ *   [217..219] reserved, ignored
+ *   [220..251] the grid: node (j, i), row j and column i in 0..3, at 220 + 2 * (4 j + i), holds dx, dy in pixels and sits at
+ *              index coordinate (i (W-1)/3, j (H-1)/3)
+ * Source coordinate of working-grid pixel (x, y), fp32, in this order:
+ *   1. px = x, py = y;
+ *   2. elastic jitter: r = Philox4x32-10(key = the row's seed [31] [32], counter = (y * W + x, 8, 0, 0)), u(r) = (r >> 8) * 2^-24;
+ *      px = fma(alpha, 2 u(r0) - 1, px), py = fma(alpha, 2 u(r1) - 1, py) (2 u - 1 is exact).  Stream 8; streams 0..6 stay
+ *      noise and dropout;
+ *   3. grid: gu = clamp(px * (3 / (W - 1)), 0, 3), or 0 when W == 1, gv likewise with H; cell i0 = min((int)gu, 2), j0
+ *      likewise; with fu = gu - i0, fv = gv - j0 and the cell's nodes n00 n01 / n10 n11, per component
+ *      t = fma(fu, n01 - n00, n00), b = fma(fu, n11 - n10, n10), d = fma(fv, b - t, t); px += dx, py += dy.  A coordinate beyond
+ *      the image takes the border's displacement.  The clamp comes before the float -> int conversion: no index leaves the row;
+ *   4. homography: den = fma(h20, px, fma(h21, py, h22)); sx = fma(h00, px, fma(h01, py, h02)) / den, sy likewise, correctly
+ *      rounded divisions.  The pixel is outside in either border mode (image: cval, label: 0) when den is not > 0 or sx or sy
+ *      is NaN / infinite; then pseg_augment_batch's clamp to [-1, size] and its nearest / bilinear taps.
+ * Everything after the coordinate is pseg_augment_batch_nbhd's: taps, 8-bit rounding, the filter over the LDS tile, colour
+ * matrix, noise, dropout, normalisation, the multi-scale index, and the footprint (nothing but img, seg, the row and the
+ * block's own LDS tile is touched, whatever the row holds).  The map is a pure function of the working-grid pixel: the
+ * filter's halo evaluates it at the REFLECTED pixel's index, jitter included, and the label blocks evaluate the same function
+ * on [H, W], so image and labels move together.  A row with h2 = (0, 0, 1), alpha <= 0 and the grid off gives
+ * pseg_augment_batch_nbhd's output bit for bit. */
+#define PSEG_AUGMENT_WARP_ROW 252
+#define PSEG_AUGMENT_WARP_H2 212
+#define PSEG_AUGMENT_WARP_ALPHA 215
+#define PSEG_AUGMENT_WARP_GRID_ON 216
+#define PSEG_AUGMENT_WARP_GRID 220
+int pseg_augment_batch_warp(const uint8_t* img, const uint8_t* seg, const float* params, const int* shape_host, int B, int H, int W,
+                            float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh, int ow,
+                            int64_t* target, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (flat parameter arena)
  * One launch over the whole arena; grad_scale folds the 1/world_size of the data-parallel mean
  * (README.md:42-44, train.py:112-117) and the 1/accumulate of gradient accumulation (train.py:65).

@@ -29,21 +29,71 @@ struct AugCoord {
   bool finite;
 };
 
+// Philox4x32-10 with counter (c0, c1, 0, 0) and key (k0, k1): the random numbers of the nbhd / warp kernels (below)
+struct Philox4 {
+  uint32_t v[4];
+};
+
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1) {
+  uint32_t c2 = 0u, c3 = 0u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return Philox4{{c0, c1, c2, c3}};
+}
+
+__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+constexpr uint32_t kStreamElastic = 8;                    // streams 0..6: noise and dropout (below)
+
 // source index coordinate of working-grid pixel (x, y): pixel centres at integers.  Clamped to [-1, size] BEFORE any
 // float -> int conversion: a coordinate beyond that range behaves exactly like the bound itself (every tap outside the
 // image in constant mode, the edge pixel in edge mode).  A NaN / infinite coordinate is reported and counts as outside.
+// kWarp (pseg_augment_batch_warp's row): elastic jitter -> 4 x 4 displacement grid -> homography in front of that, a pure
+// function of (x, y) and the row; with the three fields off, the same sx, sy bit for bit (the division is by 1.0f).
+template <bool kWarp>
 __device__ __forceinline__ AugCoord aug_coord(const float* __restrict__ row, int x, int y, int H, int W) {
-  const float fx = (float)x, fy = (float)y;
-  const float sx = fmaf(row[0], fx, fmaf(row[1], fy, row[2]));
-  const float sy = fmaf(row[3], fx, fmaf(row[4], fy, row[5]));
+  float px = (float)x, py = (float)y, den = 1.f;
+  if constexpr (kWarp) {
+    const float alpha = row[PSEG_AUGMENT_WARP_ALPHA];
+    if (alpha > 0.f && alpha <= 3.0e38f) {                  // sample-uniform
+      const Philox4 r = philox4x32_10((uint32_t)y * (uint32_t)W + (uint32_t)x, kStreamElastic,
+                                      __float_as_uint(row[PSEG_AUGMENT_NBHD_SEED]), __float_as_uint(row[PSEG_AUGMENT_NBHD_SEED + 1]));
+      px = fmaf(alpha, fmaf(2.f, (float)(r.v[0] >> 8) * 0x1p-24f, -1.f), px);
+      py = fmaf(alpha, fmaf(2.f, (float)(r.v[1] >> 8) * 0x1p-24f, -1.f), py);
+    }
+    if (row[PSEG_AUGMENT_WARP_GRID_ON] != 0.f) {
+      // clamped before the conversion: the cell lies in 0..2 and the eight loads inside the row, whatever px, py are
+      const float gu = W > 1 ? fminf(fmaxf(px * (3.f / (float)(W - 1)), 0.f), 3.f) : 0.f;
+      const float gv = H > 1 ? fminf(fmaxf(py * (3.f / (float)(H - 1)), 0.f), 3.f) : 0.f;
+      const int i0 = clampi((int)gu, 2), j0 = clampi((int)gv, 2);
+      const float fu = gu - (float)i0, fv = gv - (float)j0;
+      const float* __restrict__ n = row + PSEG_AUGMENT_WARP_GRID + 2 * (4 * j0 + i0);   // nodes (j0, i0), (j0, i0 + 1); + 8: row j0 + 1
+      const float tx = fmaf(fu, n[2] - n[0], n[0]), ty = fmaf(fu, n[3] - n[1], n[1]);
+      const float bx = fmaf(fu, n[10] - n[8], n[8]), by = fmaf(fu, n[11] - n[9], n[9]);
+      px += fmaf(fv, bx - tx, tx);
+      py += fmaf(fv, by - ty, ty);
+    }
+    den = fmaf(row[PSEG_AUGMENT_WARP_H2], px, fmaf(row[PSEG_AUGMENT_WARP_H2 + 1], py, row[PSEG_AUGMENT_WARP_H2 + 2]));
+  }
+  float sx = fmaf(row[0], px, fmaf(row[1], py, row[2]));
+  float sy = fmaf(row[3], px, fmaf(row[4], py, row[5]));
+  if constexpr (kWarp) sx = sx / den, sy = sy / den;        // correctly rounded
   AugCoord c;
   c.finite = fabsf(sx) <= 3.0e38f && fabsf(sy) <= 3.0e38f;   // false for NaN and +-inf
+  if constexpr (kWarp) c.finite = c.finite && den > 0.f;    // behind the camera, or a NaN denominator: outside
   c.sx = c.finite ? fminf(fmaxf(sx, -1.f), (float)W) : -1.f;
   c.sy = c.finite ? fminf(fmaxf(sy, -1.f), (float)H) : -1.f;
   return c;
 }
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 __device__ __forceinline__ float round_u8(float v) {      // 8-bit result, half up, saturated
   float q = floorf(v + 0.5f);
@@ -67,7 +117,7 @@ __global__ __launch_bounds__(256) void augment_batch_kernel(const uint8_t* __res
 
   if (!is_img) {                                           // ---- labels: [H, W], nearest, 0 outside
     if (ox >= W || oy >= H) return;
-    const AugCoord c = aug_coord(row, ox, oy, H, W);
+    const AugCoord c = aug_coord<false>(row, ox, oy, H, W);
     const int x = (int)floorf(c.sx + 0.5f), y = (int)floorf(c.sy + 0.5f);
     const bool inside = c.finite && x >= 0 && x < W && y >= 0 && y < H;
     const uint8_t v = seg[(int64_t)b * plane + (int64_t)clampi(y, H - 1) * W + clampi(x, W - 1)];
@@ -79,7 +129,7 @@ __global__ __launch_bounds__(256) void augment_batch_kernel(const uint8_t* __res
   // multi-scale: ATen's nearest source index (identity when (oh, ow) == (H, W))
   const int ix = min((int)floorf((float)ox * ((float)W / (float)ow)), W - 1);
   const int iy = min((int)floorf((float)oy * ((float)H / (float)oh)), H - 1);
-  const AugCoord c = aug_coord(row, ix, iy, H, W);
+  const AugCoord c = aug_coord<false>(row, ix, iy, H, W);
   const float cval = row[18];
   const bool bilinear = row[19] != 0.f, edge = row[20] != 0.f && c.finite;
   const uint8_t* __restrict__ p = img + (int64_t)b * 3 * plane;
@@ -150,30 +200,11 @@ __device__ __forceinline__ int reflect101(int i, int n) {
   return i;
 }
 
-struct Philox4 {
-  uint32_t v[4];
-};
-
-__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1) {
-  uint32_t c2 = 0u, c3 = 0u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return Philox4{{c0, c1, c2, c3}};
-}
-
 // the warp of augment_batch_kernel for working-grid pixel (ix, iy): three values before the 8-bit rounding
+template <bool kWarp>
 __device__ __forceinline__ void aug_warp(const uint8_t* __restrict__ p, const float* __restrict__ row, int ix, int iy, int H, int W,
                                          int64_t plane, float v[3]) {
-  const AugCoord c = aug_coord(row, ix, iy, H, W);
+  const AugCoord c = aug_coord<kWarp>(row, ix, iy, H, W);
   const float cval = row[18];
   const bool bilinear = row[19] != 0.f, edge = row[20] != 0.f && c.finite;
   if (!bilinear) {
@@ -204,6 +235,9 @@ __device__ __forceinline__ void aug_warp(const uint8_t* __restrict__ p, const fl
   }
 }
 
+// one kernel for pseg_augment_batch_nbhd (kWarp = false) and pseg_augment_batch_warp (true): they differ in the row length and
+// in aug_coord, which the halo fill evaluates at the REFLECTED pixel's index and the label blocks on [H, W]
+template <bool kWarp>
 __global__ __launch_bounds__(256) void augment_batch_nbhd_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ seg,
                                                                  const float* __restrict__ params, AugNorm nm, float* __restrict__ out,
                                                                  int64_t* __restrict__ target, int H, int W, int oh, int ow,
@@ -216,13 +250,13 @@ __global__ __launch_bounds__(256) void augment_batch_nbhd_kernel(const uint8_t* 
   const uint32_t per = is_img ? img_tiles : lab_tiles, per_x = is_img ? img_tiles_x : lab_tiles_x;
   const uint32_t b = blk / per, t = blk - b * per;
   const uint32_t tyi = t / per_x, txi = t - tyi * per_x;
-  const float* __restrict__ row = params + (int64_t)b * PSEG_AUGMENT_NBHD_ROW;
+  const float* __restrict__ row = params + (int64_t)b * (kWarp ? PSEG_AUGMENT_WARP_ROW : PSEG_AUGMENT_NBHD_ROW);
   const int64_t plane = (int64_t)H * W;
 
   if (!is_img) {                                           // ---- labels: [H, W], nearest, 0 outside
     const int ox = (int)txi * kAugTileW + (threadIdx.x & (kAugTileW - 1)), oy = (int)tyi * kAugTileH + threadIdx.x / kAugTileW;
     if (ox >= W || oy >= H) return;
-    const AugCoord c = aug_coord(row, ox, oy, H, W);
+    const AugCoord c = aug_coord<kWarp>(row, ox, oy, H, W);
     const int x = (int)floorf(c.sx + 0.5f), y = (int)floorf(c.sy + 0.5f);
     const bool inside = c.finite && x >= 0 && x < W && y >= 0 && y < H;
     const uint8_t v = seg[(int64_t)b * plane + (int64_t)clampi(y, H - 1) * W + clampi(x, W - 1)];
@@ -249,13 +283,13 @@ __global__ __launch_bounds__(256) void augment_batch_nbhd_kernel(const uint8_t* 
 
   float v[3];
   if (k2 == 0) {
-    aug_warp(p, row, ix, iy, H, W, plane, v);
+    aug_warp<kWarp>(p, row, ix, iy, H, W, plane, v);
     v[0] = round_u8(v[0]), v[1] = round_u8(v[1]), v[2] = round_u8(v[2]);
   } else {
     for (int i = threadIdx.x; i < sw * sh; i += 256) {
       const int ly = i / sw, lx = i - ly * sw;
       float w[3];
-      aug_warp(p, row, reflect101(gx0 - k2 + lx, W), reflect101(gy0 - k2 + ly, H), H, W, plane, w);
+      aug_warp<kWarp>(p, row, reflect101(gx0 - k2 + lx, W), reflect101(gy0 - k2 + ly, H), H, W, plane, w);
       aug_tile[i] = (uint32_t)round_u8(w[0]) | ((uint32_t)round_u8(w[1]) << 8) | ((uint32_t)round_u8(w[2]) << 16);
     }
     __syncthreads();
@@ -319,6 +353,56 @@ __global__ __launch_bounds__(256) void augment_batch_nbhd_kernel(const uint8_t* 
 
 using namespace pseg;
 
+// pseg_augment_batch_nbhd and pseg_augment_batch_warp: the same arguments, checks, launch geometry and LDS sizing
+static int augment_nbhd_launch(const char* what, bool warp, const uint8_t* img, const uint8_t* seg, const float* params,
+                               const int* shape_host, int B, int H, int W, const AugNorm& nm, float* out, int oh, int ow,
+                               int64_t* target, void* stream) {
+  PSEG_REQUIRE(img && seg && params && shape_host && out && target, "%s: null pointer", what);
+  PSEG_REQUIRE(B >= 1 && B <= 65535, "%s: batch %d outside [1, 65535]", what, B);
+  PSEG_REQUIRE(H >= 1 && H <= 65535 && W >= 1 && W <= 65535, "%s: input size %dx%d outside [1, 65535]", what, H, W);
+  PSEG_REQUIRE(oh >= 1 && oh <= 65535 && ow >= 1 && ow <= 65535, "%s: output size %dx%d outside [1, 65535]", what, oh, ow);
+  PSEG_REQUIRE(nm.std[0] != 0.f && nm.std[1] != 0.f && nm.std[2] != 0.f, "%s: std must be non-zero", what);
+  int kmax = 0;
+  for (int b = 0; b < B; ++b) {
+    const int K = shape_host[3 * b], mh = shape_host[3 * b + 1], mw = shape_host[3 * b + 2];
+    PSEG_REQUIRE(K >= 0 && K <= PSEG_AUGMENT_NBHD_KMAX && (K <= 1 || (K & 1)),
+                 "%s: sample %d: filter size %d is not 0, 1 or an odd number up to %d", what, b, K, PSEG_AUGMENT_NBHD_KMAX);
+    PSEG_REQUIRE(mh >= 0 && mw >= 0 && mh <= 65535 && mw <= 65535 && (mh == 0) == (mw == 0),
+                 "%s: sample %d: dropout mask %dx%d (0x0 = per pixel, otherwise 1..65535 each way)", what, b, mh, mw);
+    kmax = K > kmax ? K : kmax;
+  }
+  const int halo = kmax / 2;
+  const int64_t img_tiles_x = cdiv(ow, kNbTileW), img_tiles_y = cdiv(oh, kNbTileH), img_tiles = img_tiles_x * img_tiles_y;
+  const int64_t lab_tiles_x = cdiv(W, kAugTileW), lab_tiles = lab_tiles_x * cdiv(H, kAugTileH);
+  const int64_t n_img = (int64_t)B * img_tiles, n_lab = (int64_t)B * lab_tiles;
+  PSEG_REQUIRE(n_img + n_lab <= 0xffffffLL, "%s: %lld tiles exceed one launch (batch %d of %dx%d -> %dx%d)", what,
+               (long long)(n_img + n_lab), B, H, W, oh, ow);
+  // LDS: the widest and the tallest working-grid span of an output tile (the kernel's own index function), plus the halo
+  int64_t lds_elems = 0;
+  if (halo > 0) {
+    int span_w = 1, span_h = 1;
+    for (int64_t t = 0; t < img_tiles_x; ++t) {
+      const int o0 = (int)t * kNbTileW, o1 = (o0 + kNbTileW < ow ? o0 + kNbTileW : ow) - 1;
+      const int s = aug_ms_index(o1, W, ow) - aug_ms_index(o0, W, ow) + 1;
+      span_w = s > span_w ? s : span_w;
+    }
+    for (int64_t t = 0; t < img_tiles_y; ++t) {
+      const int o0 = (int)t * kNbTileH, o1 = (o0 + kNbTileH < oh ? o0 + kNbTileH : oh) - 1;
+      const int s = aug_ms_index(o1, H, oh) - aug_ms_index(o0, H, oh) + 1;
+      span_h = s > span_h ? s : span_h;
+    }
+    lds_elems = (int64_t)(span_w + 2 * halo) * (span_h + 2 * halo);
+    PSEG_REQUIRE(lds_elems * 4 <= 65536, "%s: a %dx%d output tile of %dx%d -> %dx%d with K = %d needs %lld bytes of LDS (limit 65536)", what,
+                 kNbTileW, kNbTileH, H, W, oh, ow, kmax, (long long)(lds_elems * 4));
+  }
+  const auto kernel = warp ? augment_batch_nbhd_kernel<true> : augment_batch_nbhd_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((uint32_t)(n_img + n_lab)), dim3(256), (size_t)lds_elems * 4, (hipStream_t)stream, img, seg, params, nm,
+                     out, target, H, W, oh, ow, (uint32_t)n_img, (uint32_t)img_tiles_x, (uint32_t)img_tiles,
+                     (uint32_t)lab_tiles_x, (uint32_t)lab_tiles, halo, (uint32_t)lds_elems);
+  PSEG_LAUNCH_CHECK();
+  return PSEG_OK;
+}
+
 extern "C" {
 
 int pseg_augment_batch(const uint8_t* img, const uint8_t* seg, const float* params, int B, int H, int W, float mean0, float mean1,
@@ -346,50 +430,15 @@ int pseg_augment_batch(const uint8_t* img, const uint8_t* seg, const float* para
 int pseg_augment_batch_nbhd(const uint8_t* img, const uint8_t* seg, const float* params, const int* shape_host, int B, int H, int W,
                             float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh, int ow,
                             int64_t* target, void* stream) {
-  PSEG_REQUIRE(img && seg && params && shape_host && out && target, "augment_batch_nbhd: null pointer");
-  PSEG_REQUIRE(B >= 1 && B <= 65535, "augment_batch_nbhd: batch %d outside [1, 65535]", B);
-  PSEG_REQUIRE(H >= 1 && H <= 65535 && W >= 1 && W <= 65535, "augment_batch_nbhd: input size %dx%d outside [1, 65535]", H, W);
-  PSEG_REQUIRE(oh >= 1 && oh <= 65535 && ow >= 1 && ow <= 65535, "augment_batch_nbhd: output size %dx%d outside [1, 65535]", oh, ow);
-  PSEG_REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "augment_batch_nbhd: std must be non-zero");
-  int kmax = 0;
-  for (int b = 0; b < B; ++b) {
-    const int K = shape_host[3 * b], mh = shape_host[3 * b + 1], mw = shape_host[3 * b + 2];
-    PSEG_REQUIRE(K >= 0 && K <= PSEG_AUGMENT_NBHD_KMAX && (K <= 1 || (K & 1)),
-                 "augment_batch_nbhd: sample %d: filter size %d is not 0, 1 or an odd number up to %d", b, K, PSEG_AUGMENT_NBHD_KMAX);
-    PSEG_REQUIRE(mh >= 0 && mw >= 0 && mh <= 65535 && mw <= 65535 && (mh == 0) == (mw == 0),
-                 "augment_batch_nbhd: sample %d: dropout mask %dx%d (0x0 = per pixel, otherwise 1..65535 each way)", b, mh, mw);
-    kmax = K > kmax ? K : kmax;
-  }
-  const int halo = kmax / 2;
-  const int64_t img_tiles_x = cdiv(ow, kNbTileW), img_tiles_y = cdiv(oh, kNbTileH), img_tiles = img_tiles_x * img_tiles_y;
-  const int64_t lab_tiles_x = cdiv(W, kAugTileW), lab_tiles = lab_tiles_x * cdiv(H, kAugTileH);
-  const int64_t n_img = (int64_t)B * img_tiles, n_lab = (int64_t)B * lab_tiles;
-  PSEG_REQUIRE(n_img + n_lab <= 0xffffffLL, "augment_batch_nbhd: %lld tiles exceed one launch (batch %d of %dx%d -> %dx%d)",
-               (long long)(n_img + n_lab), B, H, W, oh, ow);
-  // LDS: the widest and the tallest working-grid span of an output tile (the kernel's own index function), plus the halo
-  int64_t lds_elems = 0;
-  if (halo > 0) {
-    int span_w = 1, span_h = 1;
-    for (int64_t t = 0; t < img_tiles_x; ++t) {
-      const int o0 = (int)t * kNbTileW, o1 = (o0 + kNbTileW < ow ? o0 + kNbTileW : ow) - 1;
-      const int s = aug_ms_index(o1, W, ow) - aug_ms_index(o0, W, ow) + 1;
-      span_w = s > span_w ? s : span_w;
-    }
-    for (int64_t t = 0; t < img_tiles_y; ++t) {
-      const int o0 = (int)t * kNbTileH, o1 = (o0 + kNbTileH < oh ? o0 + kNbTileH : oh) - 1;
-      const int s = aug_ms_index(o1, H, oh) - aug_ms_index(o0, H, oh) + 1;
-      span_h = s > span_h ? s : span_h;
-    }
-    lds_elems = (int64_t)(span_w + 2 * halo) * (span_h + 2 * halo);
-    PSEG_REQUIRE(lds_elems * 4 <= 65536, "augment_batch_nbhd: a %dx%d output tile of %dx%d -> %dx%d with K = %d needs %lld bytes of LDS (limit 65536)",
-                 kNbTileW, kNbTileH, H, W, oh, ow, kmax, (long long)(lds_elems * 4));
-  }
-  AugNorm nm{{mean0, mean1, mean2}, {std0, std1, std2}};
-  hipLaunchKernelGGL(augment_batch_nbhd_kernel, dim3((uint32_t)(n_img + n_lab)), dim3(256), (size_t)lds_elems * 4, (hipStream_t)stream,
-                     img, seg, params, nm, out, target, H, W, oh, ow, (uint32_t)n_img, (uint32_t)img_tiles_x, (uint32_t)img_tiles,
-                     (uint32_t)lab_tiles_x, (uint32_t)lab_tiles, halo, (uint32_t)lds_elems);
-  PSEG_LAUNCH_CHECK();
-  return PSEG_OK;
+  return augment_nbhd_launch("augment_batch_nbhd", false, img, seg, params, shape_host, B, H, W, AugNorm{{mean0, mean1, mean2}, {std0, std1, std2}},
+                             out, oh, ow, target, stream);
+}
+
+int pseg_augment_batch_warp(const uint8_t* img, const uint8_t* seg, const float* params, const int* shape_host, int B, int H, int W,
+                            float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh, int ow,
+                            int64_t* target, void* stream) {
+  return augment_nbhd_launch("augment_batch_warp", true, img, seg, params, shape_host, B, H, W, AugNorm{{mean0, mean1, mean2}, {std0, std1, std2}},
+                             out, oh, ow, target, stream);
 }
 
 }  // extern "C"

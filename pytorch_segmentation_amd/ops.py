@@ -1254,15 +1254,12 @@ AUGMENT_NBHD_ROW = 212  # PSEG_AUGMENT_NBHD_ROW: floats per sample of augment_ba
 AUGMENT_NBHD_KMAX = 13  # PSEG_AUGMENT_NBHD_KMAX
 
 
-def augment_batch_nbhd(imgs, segs, params, shapes, oh, ow, mean, std, out=None, target=None):
-    """augment_batch with a K x K filter, Gaussian noise and (coarse) dropout per sample, in one launch
-    (pseg_augment_batch_nbhd).  params: fp32 device table [B, AUGMENT_NBHD_ROW]; shapes: HOST int32 tensor [B, 3] of each
-    row's {K, mh, mw}, which the library validates and sizes its LDS tile from.  Everything else as augment_batch."""
+def _augment_batch_wide(entry, row, imgs, segs, params, shapes, oh, ow, mean, std, out, target):
     assert imgs.is_cuda and imgs.dtype == torch.uint8 and imgs.is_contiguous() and imgs.dim() == 4 and imgs.shape[1] == 3
     B, _, H, W = imgs.shape
     assert segs.device == imgs.device and segs.dtype == torch.uint8 and segs.is_contiguous() and segs.shape == (B, H, W)
     assert params.device == imgs.device and params.dtype == torch.float32 and params.is_contiguous()
-    assert params.shape == (B, AUGMENT_NBHD_ROW) and len(mean) == 3 and len(std) == 3
+    assert params.shape == (B, row) and len(mean) == 3 and len(std) == 3
     assert not shapes.is_cuda and shapes.dtype == torch.int32 and shapes.is_contiguous() and shapes.shape == (B, 3)
     if out is None:
         out = torch.empty(B, 3, oh, ow, dtype=torch.float32, device=imgs.device)
@@ -1270,9 +1267,26 @@ def augment_batch_nbhd(imgs, segs, params, shapes, oh, ow, mean, std, out=None, 
         target = torch.empty(B, H, W, dtype=torch.int64, device=imgs.device)
     assert out.device == imgs.device and out.dtype == torch.float32 and out.is_contiguous() and out.shape == (B, 3, oh, ow)
     assert target.device == imgs.device and target.dtype == torch.int64 and target.is_contiguous() and target.shape == (B, H, W)
-    _lib.call('pseg_augment_batch_nbhd', imgs.data_ptr(), segs.data_ptr(), params.data_ptr(), shapes.data_ptr(), B, H, W,
+    _lib.call(entry, imgs.data_ptr(), segs.data_ptr(), params.data_ptr(), shapes.data_ptr(), B, H, W,
               *[float(m) for m in mean], *[float(v) for v in std], out.data_ptr(), oh, ow, target.data_ptr(), _stream())
     return out, target
+
+
+def augment_batch_nbhd(imgs, segs, params, shapes, oh, ow, mean, std, out=None, target=None):
+    """augment_batch with a K x K filter, Gaussian noise and (coarse) dropout per sample, in one launch
+    (pseg_augment_batch_nbhd).  params: fp32 device table [B, AUGMENT_NBHD_ROW]; shapes: HOST int32 tensor [B, 3] of each
+    row's {K, mh, mw}, which the library validates and sizes its LDS tile from.  Everything else as augment_batch."""
+    return _augment_batch_wide('pseg_augment_batch_nbhd', AUGMENT_NBHD_ROW, imgs, segs, params, shapes, oh, ow, mean, std, out, target)
+
+
+AUGMENT_WARP_ROW = 252  # PSEG_AUGMENT_WARP_ROW: floats per sample of augment_batch_warp's table (layout: include/pseg_amd.h)
+
+
+def augment_batch_warp(imgs, segs, params, shapes, oh, ow, mean, std, out=None, target=None):
+    """augment_batch_nbhd with a per-sample elastic jitter, 4 x 4 displacement grid and inverse homography in the coordinate
+    map of images and labels, in one launch (pseg_augment_batch_warp).  params: fp32 device table [B, AUGMENT_WARP_ROW];
+    everything else as augment_batch_nbhd."""
+    return _augment_batch_wide('pseg_augment_batch_warp', AUGMENT_WARP_ROW, imgs, segs, params, shapes, oh, ow, mean, std, out, target)
 
 
 def confusion(pred, target, counters):

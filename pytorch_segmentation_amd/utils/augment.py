@@ -1,5 +1,5 @@
-"""On-device training augmentation: the geometric, colour-affine, small-filter, noise and dropout part of the reference's
-online augmentation (``TRAIN_AUGS``, reference utils/datasets.py:26-125, imgaug on the host, one sample at a time) as ONE
+"""On-device training augmentation: the geometric (affine and local), colour-affine, small-filter, noise and dropout part of
+the reference's online augmentation (``TRAIN_AUGS``, reference utils/datasets.py:26-125, imgaug on the host, one sample at a time) as ONE
 kernel over the collated uint8 batch (csrc/augment.hip), fused with ``CocoDataset.post_fetch_fn``'s normalisation,
 multi-scale resize and label widening.
 
@@ -9,7 +9,10 @@ table (layout: include/pseg_amd.h, ``PSEG_AUGMENT_ROW`` floats): the INVERSE aff
 colour matrix in 0..255 units, the fill value, the interpolation order and the border mode.  A batch in which some sample
 drew a filter, noise or dropout gets the wider rows of ``pseg_augment_batch_nbhd`` (``PSEG_AUGMENT_NBHD_ROW`` floats: the
 same 24, then K, the noise and dropout parameters, the sample's 64-bit seed bit-cast into two floats, and the K x K
-weights) and goes through that kernel; every other batch goes through ``pseg_augment_batch`` as before.
+weights) and goes through that kernel; a batch in which some sample drew an elastic, piecewise-affine or perspective warp
+gets the still wider rows of ``pseg_augment_batch_warp`` (``PSEG_AUGMENT_WARP_ROW`` floats: the same 212, then the third row
+of an inverse homography, the elastic alpha and a 4 x 4 displacement grid); every other batch goes through
+``pseg_augment_batch`` as before.
 
 Built (defaults of ``DeviceAugment.reference()`` = the reference's values):
   * ``Fliplr(0.5)``, ``Flipud(0.2)``;
@@ -25,7 +28,10 @@ Built (defaults of ``DeviceAugment.reference()`` = the reference's values):
   * only with ``DeviceAugment.full()`` (all off by default, so ``DeviceAugment()`` / ``.reference()`` draw the tables they
     always drew): five more slots of that block, the neighbourhood and per-pixel-random augmenters -- see "Filters, noise
     and dropout" below.  With them 10 of the 16 slots are live.
-Labels are warped with the same matrix, nearest sample, background 0, as imgaug warps segmentation maps.
+  * only with ``DeviceAugment.warps()`` (= ``full()`` plus these, all off by default): the three slots that move pixels by
+    something other than one matrix, ``ElasticTransformation``, ``PiecewiseAffine`` and ``PerspectiveTransform`` -- see
+    "Local warps" below.  With them 13 of the 16 slots are live.
+Labels are warped with the same coordinate map, nearest sample, background 0, as imgaug warps segmentation maps.
 
 Filters, noise and dropout (``full()``).  These formulas are THIS MODULE'S CONTRACT.  They were written down from imgaug's
 documentation as remembered; imgaug and cv2 are not installed where this was written, so they were NOT checked against
@@ -44,13 +50,32 @@ Filters are correlations (cv2 ``filter2D``, which imgaug's ``Convolve`` calls) w
 repeating the edge pixel).  Noise and dropout are drawn on the device: Philox4x32-10 keyed by a 64-bit seed that the host
 draws per sample, counted by the working-grid pixel (include/pseg_amd.h).
 
-OUT OF SCOPE -- the remaining six slots of the block: the edge-detect blend (BlendAlphaSimplexNoise), Superpixels,
-AddToHueAndSaturation, the frequency-noise blend (BlendAlphaFrequencyNoise), ElasticTransformation and PiecewiseAffine /
-PerspectiveTransform, and the median blur and the frequency-noise branch inside two ``OneOf``s; and imgaug's border modes
-other than constant and edge (``ia.ALL`` also draws reflect, symmetric and wrap).
+Local warps (``warps()``).  Like the filters', these draws are THIS MODULE'S CONTRACT, written down from imgaug's
+documentation and NOT checked against imgaug.  Each takes one slot of the ``SomeOf`` block (slots 10..12) and, when picked,
+applies with its ``Sometimes`` probability (0.5 each).  The kernel's inverse coordinate map is, from the output pixel towards
+the source: elastic jitter -> displacement grid -> inverse homography (include/pseg_amd.h has the arithmetic):
+  * ``ElasticTransformation``: alpha ~ U(0.5, 3.5); every pixel is displaced by alpha * U(-1, 1) per axis, drawn on the device
+    (Philox stream 8 of the sample's seed, counted by the pixel).  The reference smooths the displacement field with a
+    Gaussian of sigma 0.25; that is NOT applied: a 3-tap Gaussian of that sigma weighs its neighbours 3e-4;
+  * ``PiecewiseAffine``: s ~ U(0.01, 0.05), each of the 4 x 4 control points is moved by N(0, s) per coordinate, as a fraction
+    of (W, H).  The row holds MINUS the jitter times (W, H) per node, the first-order inverse of moving the control points,
+    and the kernel blends it bilinearly inside each of the 3 x 3 cells, where the reference triangulates the cells and maps
+    each triangle by its own affine;
+  * ``PerspectiveTransform``: s ~ U(0.01, 0.1), |N(0, s)| per corner coordinate, clipped to 0.4; each corner moves INWARD by that
+    fraction of (W - 1, H - 1) and the homography that maps the moved quad onto the image corners is multiplied in after the
+    affine (imgaug's ``keep_size``: a zoom onto the quad).  The clip keeps each corner in its own quadrant; that alone does
+    not keep the quad convex when several corners reach it (4 sigma and more), so a draw whose quad is not strictly
+    convex is dropped (the slot then does nothing, which puts the slot's rate a hair below 2.5 / 16 * 0.5: of 20000
+    draws at s = 0.1, the upper end, none was dropped).  For a convex quad the inverse's denominator is positive on the whole
+    grid, which ``rows()`` checks: it raises ``ValueError`` for a hand-made recipe that fails it.
 
-Simplifications, all on the host side: the geometric augmenters run in the fixed order flips, crop-and-pad, affine (the
-reference shuffles the top-level list), and the chain is ONE warp (imgaug resamples once per augmenter); one (order, cval,
+OUT OF SCOPE -- the remaining three slots of the block: the edge-detect blend (BlendAlphaSimplexNoise), Superpixels and
+AddToHueAndSaturation; and the frequency-noise blend (BlendAlphaFrequencyNoise), the median blur and the frequency-noise
+branch inside two ``OneOf``s; and imgaug's border modes other than constant and edge (``ia.ALL`` also draws reflect,
+symmetric and wrap).
+
+Simplifications, all on the host side: the geometric augmenters run in the fixed order flips, crop-and-pad, affine,
+perspective, piecewise-affine, elastic (the reference shuffles the top-level list and the block), and the chain is ONE warp (imgaug resamples once per augmenter); one (order, cval,
 mode) triple serves a sample -- crop-and-pad alone is bilinear, the affine's own draw wins when it is active; the colour
 operations are composed into one matrix, so the 8-bit rounding and saturation that imgaug applies between two of them
 happens once, after the last; the picked filters of a sample (blur, sharpen, emboss) are composed, in fp64, into ONE K x K
@@ -73,6 +98,12 @@ NBHD_ROW = 212                   # PSEG_AUGMENT_NBHD_ROW; the offsets below are 
 NBHD_KMAX = 13
 NBHD_K, NBHD_NOISE, NBHD_DROP, NBHD_SEED, NBHD_WEIGHTS = 24, 25, 27, 31, 40
 _NBHD_OPS = ('blur', 'sharpen', 'emboss', 'noise', 'dropout')        # slots 5..9 of the SomeOf block
+WARP_ROW = 252                   # PSEG_AUGMENT_WARP_ROW; the offsets below are PSEG_AUGMENT_WARP_* of include/pseg_amd.h
+WARP_H2, WARP_ALPHA, WARP_GRID_ON, WARP_GRID = 212, 215, 216, 220
+WARP_NODES = 4                   # the displacement grid is 4 x 4 nodes of (dx, dy)
+_WARP_OPS = ('elastic', 'piecewise', 'perspective')                  # slots 10..12
+PERSPECTIVE_CLIP = 0.4           # a corner moves inward by less than half a side and stays in its own quadrant (that alone
+                                 # does not keep the quad convex: quad_is_convex)
 
 
 def _eye3():
@@ -110,6 +141,36 @@ def affine_matrix(H, W, rotate=0.0, scale=(1.0, 1.0), shear=0.0, translate=(0.0,
     T = _eye3()
     T[0, 2], T[1, 2] = translate[0] * W, translate[1] * H
     return T @ c @ R @ Sh @ S @ np.linalg.inv(c)
+
+
+def _moved_quad(corners, w=1.0, h=1.0):
+    f = np.asarray(corners, dtype=np.float64).reshape(4, 2)
+    return np.array([[f[0, 0] * w, f[0, 1] * h], [w - f[1, 0] * w, f[1, 1] * h], [w - f[2, 0] * w, h - f[2, 1] * h],
+                     [f[3, 0] * w, h - f[3, 1] * h]])
+
+
+def quad_is_convex(corners):
+    """the quad that the inward corner moves leave is strictly convex (whatever the image size: scaling keeps convexity).
+    Only then is its homography onto the image corners one with a positive denominator on the whole grid."""
+    q = _moved_quad(corners)
+    e = np.roll(q, -1, axis=0) - q
+    return bool((e[:, 0] * np.roll(e, -1, axis=0)[:, 1] - e[:, 1] * np.roll(e, -1, axis=0)[:, 0] > 0).all())
+
+
+def perspective_matrix(H, W, corners):
+    """source index -> output index (3x3, fp64) of PerspectiveTransform(keep_size=True): corners [4, 2] = (fx, fy) of the top
+    left, top right, bottom right and bottom left corner, each moved INWARD by that fraction of (W - 1, H - 1); the
+    homography sends the moved quad to the image corners.  The identity where the image is a line (H or W of 1)."""
+    if min(H, W) < 2:
+        return _eye3()
+    w, h = W - 1.0, H - 1.0
+    src = _moved_quad(corners, w, h)
+    dst = np.array([[0.0, 0.0], [w, 0.0], [w, h], [0.0, h]])
+    A, b = np.zeros((8, 8)), np.zeros(8)
+    for k, ((x, y), (u, v)) in enumerate(zip(src, dst)):      # u = (m00 x + m01 y + m02) / (m20 x + m21 y + 1), v likewise
+        A[2 * k], b[2 * k] = [x, y, 1, 0, 0, 0, -u * x, -u * y], u
+        A[2 * k + 1], b[2 * k + 1] = [0, 0, 0, x, y, 1, -v * x, -v * y], v
+    return np.append(np.linalg.solve(A, b), 1.0).reshape(3, 3)
 
 
 def colour_op_matrix(name, value):
@@ -151,6 +212,8 @@ def forward_matrix(recipe, H, W):
         m = crop_pad_matrix(H, W, *recipe['crop_pad']) @ m
     if recipe.get('affine') is not None:
         m = affine_matrix(H, W, **recipe['affine']) @ m
+    if recipe.get('perspective') is not None:
+        m = perspective_matrix(H, W, recipe['perspective']) @ m
     return m
 
 
@@ -239,8 +302,27 @@ def make_nbhd_row(base=None, kernel=None, noise=None, dropout=None, seed=0):
     return row
 
 
+def make_warp_row(base=None, h2=None, alpha=None, grid=None):
+    """one row of pseg_augment_batch_warp's table from a make_nbhd_row() row (its [0..5] are the first two rows of the inverse
+    homography), the third row h2 (None: 0 0 1), the elastic alpha in pixels (None: no jitter) and the [4, 4, 2]
+    displacement grid of (dx, dy) in pixels, node (j, i) at [j, i] (None: off)"""
+    row = np.zeros(WARP_ROW, dtype=np.float32)
+    base = np.ascontiguousarray(make_nbhd_row() if base is None else base, dtype=np.float32)
+    row.view(np.uint32)[:NBHD_ROW] = base.view(np.uint32)                # (the seed's bits, not its value as a float)
+    row[WARP_H2:WARP_H2 + 3] = (0.0, 0.0, 1.0) if h2 is None else h2
+    if alpha is not None:
+        row[WARP_ALPHA] = alpha
+    if grid is not None:
+        grid = np.asarray(grid, dtype=np.float64)
+        if grid.shape != (WARP_NODES, WARP_NODES, 2):
+            raise ValueError('a displacement grid is %d x %d x 2, not %s' % (WARP_NODES, WARP_NODES, grid.shape))
+        row[WARP_GRID_ON] = 1.0
+        row[WARP_GRID:WARP_GRID + 2 * WARP_NODES ** 2] = grid.reshape(-1)
+    return row
+
+
 def row_shapes(table):
-    """int32 [B, 3] = {K, mh, mw} of each row: what pseg_augment_batch_nbhd validates on the host"""
+    """int32 [B, 3] = {K, mh, mw} of each row: what pseg_augment_batch_nbhd / _warp validate on the host"""
     return np.ascontiguousarray(np.asarray(table)[:, [NBHD_K, NBHD_DROP + 2, NBHD_DROP + 3]].astype(np.int32))
 
 
@@ -257,7 +339,8 @@ class DeviceAugment:
                  grayscale=(0.0, 1.0), per_channel=0.5, some_of=(0, 5), seed=None, rank=None, mean=MEAN, std=STD,
                  gaussian_blur=None, average_blur=None, sharpen_alpha=None, sharpen_lightness=(0.75, 1.5), emboss_alpha=None,
                  emboss_strength=(0.0, 2.0), noise_scale=None, noise_per_channel=0.5, dropout_p=None, dropout_per_channel=0.5,
-                 coarse_p=None, coarse_size=(0.02, 0.05), coarse_per_channel=0.2):
+                 coarse_p=None, coarse_size=(0.02, 0.05), coarse_per_channel=0.2, elastic_alpha=None, elastic_p=None,
+                 piecewise_scale=None, piecewise_p=None, perspective_scale=None, perspective_p=None):
         self.fliplr, self.flipud = float(fliplr), float(flipud)
         self.crop_pad, self.crop_pad_p = _range(crop_pad), float(crop_pad_p if crop_pad is not None else 0.0)
         if self.crop_pad is not None and self.crop_pad[0] <= -0.45:
@@ -277,6 +360,10 @@ class DeviceAugment:
         self.noise_scale, self.noise_per_channel = _range(noise_scale), float(noise_per_channel)
         self.dropout_p, self.dropout_per_channel = _range(dropout_p), float(dropout_per_channel)
         self.coarse_p, self.coarse_size, self.coarse_per_channel = _range(coarse_p), _range(coarse_size), float(coarse_per_channel)
+        # the local warps: a range or a probability of None (the default) switches one off
+        self.elastic_alpha, self.elastic_p = _range(elastic_alpha), None if elastic_p is None else float(elastic_p)
+        self.piecewise_scale, self.piecewise_p = _range(piecewise_scale), None if piecewise_p is None else float(piecewise_p)
+        self.perspective_scale, self.perspective_p = _range(perspective_scale), None if perspective_p is None else float(perspective_p)
         self._rng = None
 
     @classmethod
@@ -292,6 +379,15 @@ class DeviceAugment:
                   noise_scale=(0.0, 0.05 * 255), dropout_p=(0.01, 0.1), coarse_p=(0.03, 0.15))
         on.update(kw)
         return cls(**on)
+
+    @classmethod
+    def warps(cls, **kw):
+        """full() plus ElasticTransformation, PiecewiseAffine and PerspectiveTransform at the reference's ranges, each
+        Sometimes(0.5): 13 of the 16 slots of the SomeOf block"""
+        on = dict(elastic_alpha=(0.5, 3.5), elastic_p=0.5, piecewise_scale=(0.01, 0.05), piecewise_p=0.5,
+                  perspective_scale=(0.01, 0.1), perspective_p=0.5)
+        on.update(kw)
+        return cls.full(**on)
 
     @classmethod
     def identity(cls, order=0, **kw):
@@ -349,6 +445,22 @@ class DeviceAugment:
                 nbhd['dropout'] = {'p': float(rng.uniform(*self.coarse_p)), 'per_channel': bool(rng.random() < self.coarse_per_channel),
                                    'size': float(rng.uniform(*self.coarse_size))}
 
+    def _draw_warp(self, rng, name, nbhd):
+        """one picked slot of the three local warps -> nbhd (one that is off draws nothing)"""
+        scale, p = {'elastic': (self.elastic_alpha, self.elastic_p), 'piecewise': (self.piecewise_scale, self.piecewise_p),
+                    'perspective': (self.perspective_scale, self.perspective_p)}[name]
+        if scale is None or p is None or not rng.random() < p:
+            return
+        s = float(rng.uniform(*scale))
+        if name == 'elastic':
+            nbhd['elastic'] = s
+        elif name == 'piecewise':
+            nbhd['piecewise'] = rng.normal(0.0, s, (WARP_NODES, WARP_NODES, 2))
+        else:
+            f = np.minimum(np.abs(rng.normal(0.0, s, (4, 2))), PERSPECTIVE_CLIP)
+            if quad_is_convex(f):                             # (several corners near the clip can fold the quad: nothing happens then)
+                nbhd['perspective'] = f
+
     def _draw_colour(self, rng, nbhd=None):
         lo, hi = self.some_of
         n = int(rng.integers(lo, hi + 1)) if hi > 0 else 0
@@ -371,7 +483,9 @@ class DeviceAugment:
                 ops.append(('grayscale', float(rng.uniform(*self.grayscale))))
             elif nbhd is not None and len(_COLOUR_OPS) <= slot < len(_COLOUR_OPS) + len(_NBHD_OPS):
                 self._draw_nbhd(rng, _NBHD_OPS[slot - len(_COLOUR_OPS)], nbhd)
-        if nbhd and ('noise' in nbhd or 'dropout' in nbhd):
+            elif nbhd is not None and 0 <= slot - len(_COLOUR_OPS) - len(_NBHD_OPS) < len(_WARP_OPS):
+                self._draw_warp(rng, _WARP_OPS[slot - len(_COLOUR_OPS) - len(_NBHD_OPS)], nbhd)
+        if nbhd and ('noise' in nbhd or 'dropout' in nbhd or 'elastic' in nbhd):
             nbhd['seed'] = int(rng.integers(0, 2 ** 64, dtype=np.uint64))
         return ops
 
@@ -379,7 +493,8 @@ class DeviceAugment:
         """-> list of B recipes (dicts): fliplr, flipud, crop_pad (top, right, bottom, left) or None, affine (keyword
         arguments of affine_matrix) or None, order, cval, mode, colour [(name, value), ...]; and only where drawn: filters
         [(name, parameters of filter_kernel...), ...], noise (scale, per_channel), dropout {p, per_channel, size: the mask's
-        fraction of the image or None}, seed"""
+        fraction of the image or None}, elastic (alpha), piecewise ([4,4,2] node jitter as fractions of (W, H)), perspective
+        ([4,2] inward corner moves as fractions), seed (with noise, dropout or elastic)"""
         rng, out = self.rng, []
         for _ in range(B):
             r = {'fliplr': bool(rng.random() < self.fliplr), 'flipud': bool(rng.random() < self.flipud), 'crop_pad': None,
@@ -407,11 +522,20 @@ class DeviceAugment:
     @staticmethod
     def rows(recipes, H, W):
         """recipes -> the kernel's parameter table, numpy float32 (matrices and filters composed in fp64): [B, ROW], or
-        [B, NBHD_ROW] when some recipe holds a filter, noise or dropout"""
-        wide = any(r.get('filters') or r.get('noise') or r.get('dropout') for r in recipes)
-        table = np.zeros((len(recipes), NBHD_ROW if wide else ROW), dtype=np.float32)
+        [B, NBHD_ROW] when some recipe holds a filter, noise or dropout, or [B, WARP_ROW] when some recipe holds an elastic,
+        piecewise or perspective warp.  ValueError for a perspective whose inverse has no positive denominator on the grid."""
+        warp = any(r.get(k) is not None for r in recipes for k in _WARP_OPS)
+        wide = warp or any(r.get('filters') or r.get('noise') or r.get('dropout') for r in recipes)
+        table = np.zeros((len(recipes), WARP_ROW if warp else NBHD_ROW if wide else ROW), dtype=np.float32)
         for i, r in enumerate(recipes):
             inv = np.linalg.inv(forward_matrix(r, H, W))
+            if r.get('perspective') is not None:
+                # den = h20 x + h21 y + h22 is linear: one sign at the four corners of the grid is one sign on all of it
+                den = inv[2] @ np.array([[0.0, W - 1.0, 0.0, W - 1.0], [0.0, 0.0, H - 1.0, H - 1.0], [1.0, 1.0, 1.0, 1.0]])
+                if not np.isfinite(inv).all() or not ((den > 0).all() or (den < 0).all()):
+                    raise ValueError('perspective %s: the inverse homography has no positive denominator on the %d x %d grid'
+                                     % (np.asarray(r['perspective']).tolist(), H, W))
+                inv = inv / inv[2, 2]
             row = make_row(inv, colour_matrix(r.get('colour', ())), r.get('cval', 0.0), r.get('order', 0), r.get('mode', 0))
             if wide:
                 kernel = compose_filters([filter_kernel(*f) for f in r['filters']]) if r.get('filters') else None
@@ -420,27 +544,31 @@ class DeviceAugment:
                     mask = (0, 0) if d['size'] is None else (max(4, int(H * d['size'])), max(4, int(W * d['size'])))
                     d = (d['p'], d['per_channel']) + mask
                 row = make_nbhd_row(row, kernel, r.get('noise'), d, r.get('seed', 0))
+            if warp:
+                grid = None if r.get('piecewise') is None else -np.asarray(r['piecewise'], dtype=np.float64) * (W, H)
+                row = make_warp_row(row, inv[2] if r.get('perspective') is not None else None, r.get('elastic'), grid)
             table[i] = row
         return table
 
     def sample(self, B, H, W):
-        """-> numpy float32 [B, ROW] or [B, NBHD_ROW]: one parameter row per sample of a B x 3 x H x W batch"""
+        """-> numpy float32 [B, ROW], [B, NBHD_ROW] or [B, WARP_ROW]: one parameter row per sample of a B x 3 x H x W batch"""
         return self.rows(self.draw(B), H, W)
 
     # ------------------------------------------------------------------ device side
     def apply(self, imgs, segs, params, out_hw=None, shapes=None):
-        """explicit rows (numpy or tensor [B, ROW] or [B, NBHD_ROW]) -> (fp32 [B,3,oh,ow], int64 [B,H,W]); out_hw=None keeps
-        (H, W).  Rows of NBHD_ROW floats go through pseg_augment_batch_nbhd; when they already live on the device, shapes
-        (row_shapes() of the table) has to come with them."""
+        """explicit rows (numpy or tensor [B, ROW], [B, NBHD_ROW] or [B, WARP_ROW]) -> (fp32 [B,3,oh,ow], int64 [B,H,W]);
+        out_hw=None keeps (H, W).  Rows of NBHD_ROW floats go through pseg_augment_batch_nbhd, rows of WARP_ROW floats through
+        pseg_augment_batch_warp; when they already live on the device, shapes (row_shapes() of the table) has to come with
+        them."""
         from .. import ops
-        assert ROW == ops.AUGMENT_ROW and NBHD_ROW == ops.AUGMENT_NBHD_ROW
+        assert ROW == ops.AUGMENT_ROW and NBHD_ROW == ops.AUGMENT_NBHD_ROW and WARP_ROW == ops.AUGMENT_WARP_ROW
         B, _, H, W = imgs.shape
         if not torch.is_tensor(params):
             params = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32))
-        wide = params.shape[1] == NBHD_ROW
+        wide = params.shape[1] in (NBHD_ROW, WARP_ROW)
         if wide and shapes is None:
             if params.is_cuda:
-                raise ValueError('a device table of NBHD_ROW floats needs shapes=row_shapes(table) from the host')
+                raise ValueError('a device table of NBHD_ROW or WARP_ROW floats needs shapes=row_shapes(table) from the host')
             shapes = row_shapes(params.numpy())
         if not params.is_cuda:
             # one pinned, non-blocking copy per batch (the pinned block stays alive until the copy ran: the caching
@@ -449,8 +577,8 @@ class DeviceAugment:
         oh, ow = (H, W) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
         if wide:
             shapes = torch.as_tensor(shapes, dtype=torch.int32).contiguous()
-            return ops.augment_batch_nbhd(imgs.contiguous(), segs.contiguous(), params.contiguous(), shapes, oh, ow, self.mean,
-                                          self.std)
+            kernel = ops.augment_batch_warp if params.shape[1] == WARP_ROW else ops.augment_batch_nbhd
+            return kernel(imgs.contiguous(), segs.contiguous(), params.contiguous(), shapes, oh, ow, self.mean, self.std)
         return ops.augment_batch(imgs.contiguous(), segs.contiguous(), params.contiguous(), oh, ow, self.mean, self.std)
 
     def __call__(self, imgs_u8, segs_u8, out_hw=None):

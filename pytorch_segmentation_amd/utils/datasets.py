@@ -8,7 +8,9 @@ polygon = ``category_id + 1`` (0 is background, utils/datasets.py:301); ``classe
 reference's mean/std normalisation (utils/datasets.py:199-205) and turns masks into int64.
 
 ``augments=DeviceAugment(...)`` (utils/augment.py) turns ``post_fetch_fn`` into one augmenting kernel over the uint8 batch:
-the geometric and colour-affine part of the reference's imgaug pipeline (partly built).
+the geometric (affine, and with ``DeviceAugment.warps()`` elastic, piecewise-affine and perspective), colour-affine, filter,
+noise and dropout part of the reference's imgaug pipeline: 13 of the 16 slots of its ``SomeOf`` block (SURVEY.md section 2,
+#9: partly built).
 
 Out of scope: the rest of the imgaug pipeline, the random instance crop of CocoInstance and
 the --rect letterboxing; images are decoded with PIL and resized directly.

@@ -12,7 +12,11 @@ At B = 16, 3 x 512 x 512 and at B = 8, 3 x 256 x 256, on the same uint8 tensors:
 At B = 16, 3 x 512 x 512 also the neighbourhood kernel (ops.augment_batch_nbhd: filter, noise, dropout), tables on the device:
   * `nbhd identity rows`: identity rows without a filter, noise or dropout (next to `augment identity rows` of the same loop);
   * `nbhd full(seed=0) rows`: the first batch that DeviceAugment.full(seed=0) draws;
-  * `nbhd K=13 every sample`: identity rows with a dense 13 x 13 filter on every sample, the upper end.
+  * `nbhd K=13 every sample`: identity rows with a dense 13 x 13 filter on every sample, the upper end;
+and the warp kernel (ops.augment_batch_warp: elastic jitter, displacement grid, homography) on the last two tables:
+  * `warp ..., fields off`: the same rows with h2 = (0, 0, 1), no jitter, no grid (the output is the nbhd kernel's);
+  * `warp ..., all three on`: the same rows with a mild perspective, a grid of N(0, 0.05) of the size and alpha = 3.5 on
+    every sample.
 Each figure is the median over --iters (>= 50) single calls, each between its own pair of events, after warm-up; the
 variants alternate inside one loop so that they see the same machine.  Algorithmic bytes = every input byte once + the fp32
 output + the int64 targets; fractions of the roof are over 6.3 TB/s HBM.
@@ -103,13 +107,21 @@ def nbhd_rows_for(B, H, W, iters):
         'nbhd full(seed=0) rows': full,
         'nbhd K=13 every sample': np.stack([aug.make_nbhd_row(r, np.full((13, 13), 1.0 / 169)) for r in narrow]),
     }
+    grid = np.random.default_rng(0).normal(0.0, 0.05, (4, 4, 2)) * (W, H)
+    for name in ('full(seed=0) rows', 'K=13 every sample'):
+        t = tables['nbhd ' + name]
+        tables['warp %s, fields off' % name] = np.stack([aug.make_warp_row(r) for r in t])
+        tables['warp %s, all three on' % name] = np.stack([aug.make_warp_row(r, (1e-4, -5e-5, 1.0), 3.5, grid) for r in t])
     ident = torch.from_numpy(narrow).cuda()
     fns = {'augment identity rows': lambda: ops.augment_batch(imgs, segs, ident, H, W, MEAN, STD)}
     for name, t in tables.items():
         dev, shapes = torch.from_numpy(t).cuda(), torch.from_numpy(aug.row_shapes(t))
-        fns[name] = lambda dev=dev, shapes=shapes: ops.augment_batch_nbhd(imgs, segs, dev, shapes, H, W, MEAN, STD)
+        kernel = ops.augment_batch_warp if name.startswith('warp') else ops.augment_batch_nbhd
+        fns[name] = lambda kernel=kernel, dev=dev, shapes=shapes: kernel(imgs, segs, dev, shapes, H, W, MEAN, STD)
     a, b = fns['augment identity rows'](), fns['nbhd identity rows']()
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), 'rows without neighbourhood fields must reproduce augment_batch'
+    a, b = fns['nbhd full(seed=0) rows'](), fns['warp full(seed=0) rows, fields off']()
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), 'rows without warp fields must reproduce augment_batch_nbhd'
     ms = timed_median(fns, iters)
     shapes = aug.row_shapes(full)
     out = []

@@ -3,7 +3,7 @@
 on the MI355X HIP path.
 
     python3 train.py data/<custom> [--epochs N] [-s W H] [-bs N] [-a ACC] [--lr LR] [--adam] [--resume]
-                     [--weights F] [--notest] [--nosave] [--model unet|deeplabv3plus] [--augment | --augment-full]
+                     [--weights F] [--notest] [--nosave] [--model unet|deeplabv3plus] [--augment | --augment-full | --augment-warps]
     python3 -m torch.distributed.run --nproc-per-node <n> train.py data/<custom>        # RCCL data parallel
 
 Differences from the reference that are visible here: the model is picked with --model (the reference edits
@@ -45,7 +45,8 @@ def train(data_dir, epochs=100, img_size=(320, 320), batch_size=32, accumulate=2
           weights='', num_workers=4, multi_scale=False, rect=False, mixed_precision=False, notest=False, nosave=False,
           model_name='unet', augment=False):
     # --augment: the training batches (never the validation ones) go through the on-device augmentation kernel; True =
-    # the reference's values, or a DeviceAugment of the caller's own (seeded, other ranges; --augment-full: DeviceAugment.full())
+    # the reference's values, or a DeviceAugment of the caller's own (seeded, other ranges; --augment-full: DeviceAugment.full(),
+    # --augment-warps: DeviceAugment.warps())
     if augment and not isinstance(augment, DeviceAugment):
         augment = DeviceAugment.reference()
     train_data = CocoInstance(osp.join(data_dir, 'train.json'), img_size=list(img_size), multi_scale=multi_scale,
@@ -99,6 +100,9 @@ def build_parser():
                          "reference's TRAIN_AUGS, utils/augment.py")
     ap.add_argument('--augment-full', action='store_true',
                     help='--augment plus blur, sharpen, emboss, Gaussian noise and (coarse) dropout: DeviceAugment.full()')
+    ap.add_argument('--augment-warps', action='store_true',
+                    help='--augment-full plus elastic, piecewise-affine and perspective warps of images and labels: '
+                         'DeviceAugment.warps()')
     return ap
 
 
@@ -116,7 +120,7 @@ def main():
     print(opt)
     train(opt.data, opt.epochs, opt.img_size, opt.batch_size, opt.accumulate, opt.lr, opt.adam, opt.resume, opt.weights,
           opt.num_workers, opt.multi_scale, opt.rect, opt.mix_precision, opt.notest, opt.nosave, opt.model,
-          DeviceAugment.full() if opt.augment_full else opt.augment)
+          DeviceAugment.warps() if opt.augment_warps else DeviceAugment.full() if opt.augment_full else opt.augment)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()
 
