@@ -426,6 +426,26 @@ int64_t pseg_ce_upsampled_workspace_bytes(int B, int h, int w);
 int pseg_ce_upsampled_fwd_bwd(const float* logits_lr, int ld, int B, int h, int w, int C, const int64_t* target, int H,
                               int W, int align_corners, int64_t ignore_index, float* dlogits_lr, int ldd,
                               float* loss_out, void* workspace, int64_t workspace_bytes, void* stream);
+/* pseg_lovasz_softmax_fwd_bwd (csrc/lovasz.hip): the multi-class Lovasz-softmax loss of Berman et al. (the reference names
+ *   it in utils/criterions.py: lovasz_softmax(probas, labels, classes='present', per_image=False, ignore=...)) and its
+ *   gradient with respect to the logits.  logits fp32 NCHW [B][C][HW], target int64 [B][HW].  A pixel is valid iff
+ *   target != ignore_index and 0 <= target < C (the predicate of pseg_ce_fwd_bwd); other targets that are not ignore_index
+ *   are counted in out[2].  p = softmax(logits) in fp32 with the max subtracted.  For every class c with n_c > 0 valid
+ *   pixels of label c ("present"): e_i = |[t_i == c] - p_ic| over all valid pixels, sorted descending, equal errors by
+ *   ascending flat pixel index b * HW + y * W + x; with I_k / U_k the intersection / union counts after the first k + 1
+ *   elements and J_k = 1 - I_k / U_k, loss_c = sum_k e_(k) * (J_k - J_(k-1)), J_(-1) = 0.  The differences are formed in
+ *   closed form from the integer counts (foreground element: 1 / U_k; background: I_k / (U_(k-1) * U_k)), never by
+ *   subtracting two values near 1.  out[4]: [0] = mean of loss_c over the present classes (0 when no pixel is valid),
+ *   [1] = n_valid, [2] = n_out_of_range, [3] = n_present (as floats).  dlogits ([B][C][HW], nullable, must not alias
+ *   logits) receives d out[0] / d logits (zero at invalid pixels); it is also the scratch of the call.  Deterministic: two
+ *   calls on the same input give the same bits.  No host synchronisation; absent classes are skipped on the device.
+ *   C <= 1024.  logits and target must each be below 2 GiB (B * C * HW * 4 and B * HW * 8 bytes): larger operands are
+ *   refused (PSEG_ERR_ARG), not chunked.  workspace: pseg_lovasz_workspace_bytes(B, C, HW) bytes, 16-byte aligned; it
+ *   holds the sort buffers of one group of classes (16 bytes per class and pixel, groups sized to stay near 512 MiB), so
+ *   it does not grow with C beyond that.  PSEG_LOVASZ_GROUP=n caps the classes per group (same workspace, same result). */
+int64_t pseg_lovasz_workspace_bytes(int B, int C, int64_t HW);
+int pseg_lovasz_softmax_fwd_bwd(const float* logits, const int64_t* target, int B, int C, int64_t HW, int64_t ignore_index,
+                                float* dlogits, float* out, void* workspace, int64_t workspace_bytes, void* stream);
 int pseg_scale_inplace(float* x, int64_t n, const float* gscale, void* stream);
 int pseg_argmax(const float* logits, int B, int C, int64_t HW, int64_t* mask, void* stream);
 int pseg_confusion(const int64_t* pred, const int64_t* target, int64_t n, int C, int64_t* counters, void* stream);

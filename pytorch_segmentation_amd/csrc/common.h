@@ -105,6 +105,11 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, uint32_t by
   return __builtin_bit_cast(f32x4, v);
 }
 
+// Which pixels a loss counts (loss.hip, lovasz.hip): the label is not ignore_index and names a class.
+__device__ __forceinline__ bool ce_valid(long long t, long long ignore_index, int C) {
+  return (t != ignore_index) && (t >= 0) && (t < C);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

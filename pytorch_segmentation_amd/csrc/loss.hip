@@ -20,10 +20,7 @@ struct CeHeader {
 };
 
 // The divisor of the mean must be the number of pixels whose loss term ce_fused_kernel / ce_generic_kernel add up:
-// the SAME predicate (target != ignore_index && 0 <= target < C) is used here and there.
-__device__ __forceinline__ bool ce_valid(long long t, long long ignore_index, int C) {
-  return (t != ignore_index) && (t >= 0) && (t < C);
-}
+// the SAME predicate (ce_valid, common.h: target != ignore_index && 0 <= target < C) is used here and there.
 
 __global__ __launch_bounds__(256) void ce_count_kernel(const int64_t* __restrict__ target, long long n,
                                                        long long ignore_index, int C, CeHeader* __restrict__ hdr) {

@@ -1151,6 +1151,27 @@ def ce_fwd_bwd(logits, target, want_grad=True, ignore_index=-100):
     return out, dl
 
 
+# the Lovasz loss's sort buffers (hundreds of MiB at training sizes) get a cache of their own: allocated once per stream,
+# and the small scratch every conv shares stays small
+lovasz_workspace = _Workspace()
+
+
+def lovasz_softmax_fwd_bwd(logits, target, want_grad=True, ignore_index=-100):
+    """Lovasz-softmax loss over the present classes of the whole batch (pseg_lovasz_softmax_fwd_bwd).
+    logits: contiguous NCHW fp32 cuda, target: NHW int64.
+    -> (out[4] = [loss, n_valid, n_out_of_range_targets, n_present], dlogits|None)."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.shape == (logits.shape[0],) + logits.shape[2:]
+    B, C, H, W = logits.shape
+    dl = torch.empty_like(logits) if want_grad else None
+    out = torch.empty(4, dtype=torch.float32, device=logits.device)
+    nbytes = _lib.query('pseg_lovasz_workspace_bytes', B, C, H * W)
+    ws = lovasz_workspace.get(nbytes, logits.device)
+    _lib.call('pseg_lovasz_softmax_fwd_bwd', logits.data_ptr(), target.data_ptr(), B, C, H * W, ignore_index, _ptr(dl),
+              out.data_ptr(), ws.data_ptr(), nbytes, _stream())
+    return out, dl
+
+
 def ce_upsampled_ok_shape(h, w, C, H, W, align_corners):
     return bool(_lib.query('pseg_ce_upsampled_ok', h, w, C, H, W, int(align_corners)))
 

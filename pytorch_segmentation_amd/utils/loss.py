@@ -70,6 +70,75 @@ def compute_loss(outputs, targets, model=None):
     return _CrossEntropyFn.apply(outputs.contiguous(), targets)
 
 
+class _LovaszSoftmaxFn(torch.autograd.Function):
+    """Lovasz-softmax over the classes present in the batch (Berman et al.; the loss the reference names in
+    utils/criterions.py).  Built like _CrossEntropyFn: forward runs pseg_lovasz_softmax_fwd_bwd, which leaves the gradient
+    with respect to the logits as well; backward only rescales it by the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, ignore_index):
+        need = logits.requires_grad
+        out, dl = ops.lovasz_softmax_fwd_bwd(logits, targets, want_grad=need, ignore_index=ignore_index)
+        if CHECK_LABELS and out[2].item() != 0:     # (host sync: debugging aid, off by default)
+            raise IndexError('%d target values are outside [0, %d) and are not ignore_index'
+                             % (int(out[2].item()), logits.shape[1]))
+        ctx.dl = dl
+        ctx.mark_non_differentiable()
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        dl = ctx.dl
+        ctx.dl = None
+        if dl is None:
+            return None, None, None
+        g = g.reshape(1) if g.dtype == torch.float32 else g.float().reshape(1)
+        ops.scale_inplace(dl, g.contiguous())
+        return dl, None, None
+
+
+def _logits_at_target_size(outputs, targets):
+    """What compute_loss does before the loss proper: int64 targets on the logits' device, logits resized to them."""
+    if not outputs.is_cuda:
+        raise RuntimeError('the loss runs on the HIP path only (got %s)' % outputs.device)
+    targets = targets.to(device=outputs.device, dtype=torch.int64).contiguous()
+    th, tw = targets.size(1), targets.size(2)
+    if outputs.dtype != torch.float32:      # -mp hands fp16 logits to a custom loss: the kernels read fp32 NCHW
+        outputs = outputs.float()
+    if (outputs.size(2), outputs.size(3)) != (th, tw):
+        outputs = _ResizeFn.apply(outputs, th, tw)
+    return outputs.contiguous(), targets
+
+
+def lovasz_softmax_loss(outputs, targets, ignore_index=-100):
+    """Multi-class Lovasz-softmax loss of NCHW logits (classes='present', the whole batch as one image, as the reference's
+    lovasz_softmax(probas, labels, ignore=...) describes it); the softmax is part of the kernel.  A direct surrogate of the
+    mean IoU the trainer selects checkpoints by."""
+    outputs, targets = _logits_at_target_size(outputs, targets)
+    return _LovaszSoftmaxFn.apply(outputs, targets, ignore_index)
+
+
+def _lovasz_loss_fn(outputs, targets, model=None):
+    return lovasz_softmax_loss(outputs, targets)
+
+
+def _ce_lovasz_loss_fn(outputs, targets, model=None):
+    outputs, targets = _logits_at_target_size(outputs, targets)
+    return _CrossEntropyFn.apply(outputs, targets) + _LovaszSoftmaxFn.apply(outputs, targets, -100)
+
+
+LOSSES = {'ce': compute_loss, 'lovasz': _lovasz_loss_fn, 'ce+lovasz': _ce_lovasz_loss_fn}
+
+
+def make_loss(name):
+    """'ce' | 'lovasz' | 'ce+lovasz' -> loss_fn(outputs, targets, model) for Trainer(loss_fn=...).  'ce' is compute_loss
+    itself (the Trainer's fused fast path keys on that object); the others go through the Trainer's autograd route."""
+    try:
+        return LOSSES[name]
+    except KeyError:
+        raise ValueError('unknown loss %r (choose from %s)' % (name, ', '.join(sorted(LOSSES))))
+
+
 def predict_mask(outputs):
     """``outputs.max(1)[1]`` (reference test.py:31): int64 [B,H,W], first index on ties."""
     return ops.argmax(outputs.contiguous())

@@ -4,6 +4,7 @@ on the MI355X HIP path.
 
     python3 train.py data/<custom> [--epochs N] [-s W H] [-bs N] [-a ACC] [--lr LR] [--adam] [--resume]
                      [--weights F] [--notest] [--nosave] [--model unet|deeplabv3plus] [--augment | --augment-full | --augment-warps]
+                     [--loss ce|lovasz|ce+lovasz]
     python3 -m torch.distributed.run --nproc-per-node <n> train.py data/<custom>        # RCCL data parallel
 
 Differences from the reference that are visible here: the model is picked with --model (the reference edits
@@ -24,12 +25,15 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader, DistributedSampler
 
 from pytorch_segmentation_amd.models import DeepLabV3Plus, HRNet, UNet
-from pytorch_segmentation_amd.utils import Fetcher, Trainer, compute_loss
+from pytorch_segmentation_amd.utils import Fetcher, Trainer, compute_loss, make_loss
 from pytorch_segmentation_amd.utils.augment import DeviceAugment
 from pytorch_segmentation_amd.utils.datasets import CocoInstance
 from test import test
 
 MODELS = {'deeplabv3plus': DeepLabV3Plus, 'unet': UNet, 'hrnet': HRNet}
+# what train() minimises: main() sets it from --loss (train()'s keyword surface is the reference's and stays as it is);
+# the validation loss test.py reports is cross-entropy whatever is chosen here
+LOSS_FN = compute_loss
 
 
 def _loader(dataset, batch_size, num_workers, train=True):
@@ -57,7 +61,7 @@ def train(data_dir, epochs=100, img_size=(320, 320), batch_size=32, accumulate=2
         val_data = CocoInstance(osp.join(data_dir, 'val.json'), img_size=list(img_size), augments=None, rect=rect)
         val_fetcher = Fetcher(_loader(val_data, batch_size, num_workers, train=False), post_fetch_fn=val_data.post_fetch_fn)
     model = MODELS[model_name](len(train_data.classes))
-    trainer = Trainer(model, train_fetcher, loss_fn=compute_loss, workdir='weights', accumulate=accumulate, adam=adam,
+    trainer = Trainer(model, train_fetcher, loss_fn=LOSS_FN, workdir='weights', accumulate=accumulate, adam=adam,
                       lr=lr, weights=weights, resume=resume, mixed_precision=mixed_precision)
     last_loss = None
     while trainer.epoch < epochs:
@@ -103,11 +107,16 @@ def build_parser():
     ap.add_argument('--augment-warps', action='store_true',
                     help='--augment-full plus elastic, piecewise-affine and perspective warps of images and labels: '
                          'DeviceAugment.warps()')
+    ap.add_argument('--loss', choices=['ce', 'lovasz', 'ce+lovasz'], default='ce',
+                    help='training objective: per-pixel cross-entropy, the Lovasz-softmax surrogate of the mean IoU '
+                         '(classes present in the batch), or their sum')
     return ap
 
 
 def main():
+    global LOSS_FN
     opt = build_parser().parse_args()
+    LOSS_FN = make_loss(opt.loss)
 
     if os.environ.get('WORLD_SIZE'):
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
