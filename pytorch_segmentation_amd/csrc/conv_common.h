@@ -363,6 +363,24 @@ __device__ __forceinline__ void set_wave_prio(int prio) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// WgradParams::skip_rows: how a weight-gradient kernel walks the pixels of its contraction (K-steps of 32 pixels), and which of
+// them it leaves out because they are zero padding for the block's tap.
+constexpr int kWgDense = 0;        // every K-step runs; pixels row-major, or in patch order (patch_mode)
+constexpr int kWgSkipRows = 1;     // dilated convs, row-major pixels: a K-step is dead when all its image ROWS are out of range
+constexpr int kWgSkipPatches = 2;  // dilated convs, patch order -- K-step q is the patch_h x patch_w (= 32 pixels, patch_w >= 8)
+                                   // patch q of the map, dead when its rows OR its columns are out of range for the tap (unit
+                                   // stride, P % 32 == 0)
+// exact-fp32 LDS-DMA kernel, unit stride, a column tile inside one tap: PACKED contraction.  The pixels a block multiplies are
+// exactly the live rectangle of its tap -- output rows [r0, r1) x columns [c0, c1) for which the tap's source pixel lies inside
+// the image -- of every image, numbered densely; K-step s of the block holds packed pixels [32 s, 32 s + 32), each lane derives
+// its pixel by two divisions per DMA piece.  No K-step multiplies padding (a 32-pixel patch that straddles the rectangle's edge
+// did: rate 6 on a 32x32 map ran 0.92 of the dense work for 0.77 live).  The pixel split divides each block's OWN step count
+// (pix_per_split is unused).
+constexpr int kWgPacked = 3;
+// exact-fp32 LDS-DMA kernel on a map that does not tile into 32-pixel patches: plain row-major pixels, every lane derives its
+// pixel (rm_howo, rm_wo); no dead-step skipping
+constexpr int kWgRowMajorDma = 4;
+
 struct WgradParams {
   const float* x;
   const float* dy;
@@ -377,25 +395,17 @@ struct WgradParams {
   int pix_per_split;
   int accumulate;
   long long slab_stride;
-  int skip_rows;  // dilated convs: skip pixel K-steps that are zero padding for this block's tap.
-                  // 1: pixels in row-major order, a K-step (32 pixels) is dead when all its image ROWS are out of range;
-                  // 2: pixels in patch order -- K-step q is the patch_h x patch_w (= 32 pixels, patch_w >= 8) patch q of
-                  //    the map, dead when its rows OR its columns are out of range for the tap (unit stride, P % 32 == 0)
+  int skip_rows;      // kWgDense .. kWgRowMajorDma
   int patch_mode;     // pixels of the contraction run in patch order (set whenever the map tiles into such patches, also
                       // without skipping: K-step addresses are then a block-uniform origin + a thread-constant offset)
   int patch_h, patch_w;
   FastDiv ppr, ppi;   // patches per patch-row (Wo / patch_w) and per image
-  // skip_rows == 3 (exact-fp32 LDS-DMA kernel, unit stride, a column tile inside one tap): PACKED contraction.  The pixels a
-  // block multiplies are exactly the live rectangle of its tap -- output rows [r0, r1) x columns [c0, c1) for which the tap's
-  // source pixel lies inside the image -- of every image, numbered densely; K-step s of the block holds packed pixels
-  // [32 s, 32 s + 32), each lane derives its pixel by two divisions per DMA piece.  No K-step multiplies padding (a 32-pixel
-  // patch that straddles the rectangle's edge did: rate 6 on a 32x32 map ran 0.92 of the dense work for 0.77 live).  The pixel
-  // split divides each block's OWN step count (pix_per_split is unused).
-  // lpt_per > 0: column tiles in LONGEST-FIRST order inside every group of taps x lpt_per tiles (one group = the range one XCD's
-  // blocks walk in order): tile position -> (group, rank, c) -> tap tap_order[rank], column tile group * lpt_per + c of that tap.
+  // kWgPacked, lpt_per > 0: column tiles in LONGEST-FIRST order inside every group of taps x lpt_per tiles (one group = the range
+  // one XCD's blocks walk in order): tile position -> (group, rank, c) -> tap tap_order[rank], column tile group * lpt_per + c of
+  // that tap.
   int lpt_per;
   int tap_order[9];
-  FastDiv rm_howo, rm_wo;   // skip_rows == 4 (row-major pixels on the LDS-DMA kernel): pixel -> (image, row, column)
+  FastDiv rm_howo, rm_wo;   // kWgRowMajorDma: pixel -> (image, row, column)
 };
 
 // patch mode: image index and top-left pixel of K-step `pt` (a multiple of 32)
@@ -411,7 +421,7 @@ __device__ __forceinline__ void wg_patch_origin(const WgradParams& p, int pt, in
 
 // is K-step `pt` pure padding for the tap at offset (t_dh, t_dw)?  (block-uniform)
 __device__ __forceinline__ bool wg_step_dead(const WgradParams& p, int pt, int p_end, int t_dh, int t_dw) {
-  if (p.skip_rows == 2) {
+  if (p.skip_rows == kWgSkipPatches) {
     int b, h0, w0;
     wg_patch_origin(p, pt, b, h0, w0);
     return ((h0 + p.patch_h - 1) * p.stride + t_dh < 0) || (h0 * p.stride + t_dh >= p.Hi) ||
@@ -461,8 +471,8 @@ static TileCfg pick_tile(long long rows, long long cols) {
 // that change PSEG_* at run time call it through _lib.clear_query_cache()).
 struct EnvCfg {
   int conv_nobig, conv_forcebig, conv_bm, conv_bn, conv_splitk, conv_noskip, conv_noband, plan_debug, wgrad_bpc, conv_dma32, conv_narrow, conv_noxcd, conv_nodma, conv_f32dma, wgrad_f32dma, conv_big, dgrad_prio;
-  int wgrad_big, wgrad_bm, wgrad_bn, wgrad_splits;
-  int hconv_persist, hconv_persist_kt, hconv_tile;
+  int wgrad_big, wgrad_bm, wgrad_bn, wgrad_splits, wgrad_narrow256;
+  int hconv_persist, hconv_persist_kt, hconv_tile, hwgrad_stages, hwgrad_bkp;
   int conv_pw, conv_pw_kt, conv_pw_resident, conv_halo, wgrad_halo;
 };
 inline EnvCfg g_cfg;
@@ -494,9 +504,12 @@ inline void cfg_load() {
   c.wgrad_bm = env_int("PSEG_WGRAD_BM", 0);
   c.wgrad_bn = env_int("PSEG_WGRAD_BN", 0);
   c.wgrad_splits = env_int("PSEG_WGRAD_SPLITS", 0);
+  c.wgrad_narrow256 = env_int("PSEG_WGRAD_NARROW256", 1);   // 32 x 256 tile of the exact-fp32 weight gradient (0: off; plan_wgrad)
   c.hconv_persist = env_int("PSEG_HCONV_PERSIST", 1);
   c.hconv_persist_kt = env_int("PSEG_HCONV_PERSIST_KT", 24);
   c.hconv_tile = env_int("PSEG_HCONV_TILE", 0);
+  c.hwgrad_stages = env_int("PSEG_HWGRAD_STAGES", 0);       // fp16 weight gradient: ring depth 2 .. 4 / pixels per K-step 32 | 64
+  c.hwgrad_bkp = env_int("PSEG_HWGRAD_BKP", 0);             // (0: select_wgrad_h's own choice)
   c.conv_pw = env_int("PSEG_CONV_PW", 1);                   // persistent pointwise kernel of the exact-fp32 path (0: off)
   c.conv_pw_kt = env_int("PSEG_CONV_PW_KT", 32);            // ... for contractions of at most this many K-steps
   c.conv_halo = env_int("PSEG_CONV_HALO", 2);               // halo-staged narrow 3x3 of the exact-fp32 path (0: off, 1: 128x32 plan tiles, 2: 128x64 too)
@@ -948,10 +961,9 @@ static WgradPlan plan_wgrad(long long P, int Cout, int K, bool allow_big = false
   // accumulator fed by register-staged loads (41 TF on HRNet's 32-channel branch, 68 on the 21-class classifier): eight waves
   // on 256 columns with the operands by LDS-DMA (wgrad_f32_dma_kernel<32, 256>), or four waves with two accumulators each where
   // the map does not tile into 32-pixel patches.  PSEG_WGRAD_NARROW256=0 goes back.
-  static const int narrow256 = env_int("PSEG_WGRAD_NARROW256", 1);
   // (only where 256-column tiles pad K by at most 5 % more than 128-column ones: 3 x 3 on 32 channels is K = 288 -- two
   // 256-column tiles waste 44 % and measured 62 against 55 us; the classifier's K = 3456 wastes 3.7 %: 649 -> 581 us)
-  if (!limb && narrow256 != 0 && pl.tile.bm == 32 && pl.tile.bn == 128 && K >= 256 &&
+  if (!limb && cfg().wgrad_narrow256 != 0 && pl.tile.bm == 32 && pl.tile.bn == 128 && K >= 256 &&
       (long long)cdiv(K, 256) * 256 * 100 <= (long long)cdiv(K, 128) * 128 * 105)
     pl.tile.bn = 256;
   // ... and K == 288 -- 3x3 on 32 channels, every conv of HRNet's fine branch -- as ONE 32 x 288 tile on nine waves
@@ -1005,6 +1017,105 @@ static WgradPlan plan_wgrad(long long P, int Cout, int K, bool allow_big = false
   pl.pix_per_split = (int)(tiles_per * BK);
   pl.splits = cdiv(P, pl.pix_per_split);
   return pl;
+}
+
+// A weight gradient: dW[Cout][kh * kw * Cin] = dY[P][Cout]^T * (gathered x)[P][K], contraction over the P = B * Ho * Wo pixels.
+struct WgradGeom {
+  int B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil;
+  long long P() const { return (long long)B * Ho * Wo; }
+  int K() const { return kh * kw * Cin; }
+};
+
+// Pixel order of the contraction (WgradParams::skip_rows and the fields that go with it).
+struct WgradPixelOrder {
+  bool can_skip;      // dilated, and a column tile sits inside one tap: the skip test is block-uniform
+  int mode;           // kWgDense .. kWgRowMajorDma
+  int patch_mode, patch_h, patch_w;
+  int lpt_per, tap_order[9];
+};
+
+// What every weight-gradient kernel can run: kWgDense, kWgSkipRows or kWgSkipPatches (the exact-fp32 LDS-DMA kernel's own orders
+// are select_wgrad's, conv_mfma.hip).  tile_bn: columns of the plan's tile.
+static WgradPixelOrder wgrad_pixel_order(const WgradGeom& g, int tile_bn) {
+  WgradPixelOrder o{};
+  o.can_skip = g.dil >= 4 && g.kh * g.kw > 1 && g.Cin % tile_bn == 0 && cfg().conv_noskip == 0;
+  o.mode = o.can_skip ? kWgSkipRows : kWgDense;
+  o.patch_h = 1;
+  o.patch_w = BK;
+  for (int t = 0; t < 9; ++t) o.tap_order[t] = t;
+  if (g.P() % BK == 0 && ((long long)g.Ho * g.Wo) % BK == 0 && cfg().conv_noskip == 0) {
+    // 32-pixel K-steps as PH x PW patches of the output map (PW % 8 == 0).  Addresses of a K-step are then a block-uniform
+    // origin plus thread constants, and a dilated tap is dead for the whole step when its rows OR its columns are out of range:
+    // take the shape that leaves the fewest live (K-step, tap) pairs (32x32 map: rate 12 -> 4x8 = 0.63 against 0.75 row-major,
+    // rate 18 -> 2x16 = 0.42 against 0.63).
+    const DilGeom dg{g.Ho, g.Wo, g.H, g.W, g.kh, g.kw, g.dil, -g.pad};
+    double best = 2.0;
+    for (int pw = BK; pw >= 8; pw /= 2) {
+      const int ph = BK / pw;
+      if (pw > g.Wo || g.Wo % pw != 0 || g.Ho % ph != 0) continue;
+      const double f = (o.can_skip && g.stride == 1) ? live_fraction(dg, ph, pw) : 1.0;
+      if (f < best - 1e-9) {
+        best = f;
+        o.patch_mode = 1;
+        o.patch_h = ph;
+        o.patch_w = pw;
+      }
+    }
+    if (o.patch_mode && o.can_skip) o.mode = kWgSkipPatches;
+  }
+  return o;
+}
+
+// geometry, pixel split and pixel order of a launch (the operand pointers, their sizes and strides, and where the result goes
+// are the caller's)
+static void set_wgrad_geometry(WgradParams& p, const WgradGeom& g, const WgradPlan& pl, const WgradPixelOrder& o) {
+  p.Hi = g.H;
+  p.Wi = g.W;
+  p.Cin = g.Cin;
+  p.Ho = g.Ho;
+  p.Wo = g.Wo;
+  p.HoWo = g.Ho * g.Wo;
+  p.Cout = g.Cout;
+  p.K = g.K();
+  p.P = (int)g.P();
+  p.kw = g.kw;
+  p.stride = g.stride;
+  p.pad = g.pad;
+  p.dil = g.dil;
+  p.pix_per_split = pl.pix_per_split;
+  p.skip_rows = o.mode;
+  p.patch_mode = o.patch_mode;
+  p.patch_h = o.patch_h;
+  p.patch_w = o.patch_w;
+  if (o.patch_mode) {
+    p.ppr = FastDiv((uint32_t)(g.Wo / o.patch_w));
+    p.ppi = FastDiv((uint32_t)((g.Ho / o.patch_h) * (g.Wo / o.patch_w)));
+  }
+  p.lpt_per = o.lpt_per;
+  for (int t = 0; t < 9; ++t) p.tap_order[t] = o.tap_order[t];
+  p.rm_howo = FastDiv((uint32_t)(g.Ho * g.Wo));
+  p.rm_wo = FastDiv((uint32_t)g.Wo);
+}
+
+// where a launch writes: dw itself, or -- a plan that splits the pixels -- one [Cout][K] slab per split in the workspace
+static int set_wgrad_output(WgradParams& p, const WgradPlan& pl, float* dw, int accumulate, void* workspace,
+                            int64_t workspace_bytes, const char* who) {
+  const long long wsz = (long long)p.Cout * p.K;
+  if (pl.splits == 1) {
+    p.dw = dw;
+    p.accumulate = accumulate;
+    p.slab_stride = 0;
+    return PSEG_OK;
+  }
+  const long long need = (long long)pl.splits * wsz * 4;
+  if (workspace == nullptr || workspace_bytes < need) {
+    set_error("%s: needs %lld workspace bytes, got %lld", who, need, (long long)workspace_bytes);
+    return PSEG_ERR_WORKSPACE;
+  }
+  p.dw = (float*)workspace;
+  p.accumulate = 0;
+  p.slab_stride = wsz;
+  return PSEG_OK;
 }
 
 // fixed-order slab reductions (kernels in conv_mfma.hip)

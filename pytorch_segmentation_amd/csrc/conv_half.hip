@@ -2433,35 +2433,77 @@ static int run_gather_h(const GatherGeom& g, const void* x, long long x_bytes, i
   return PSEG_OK;
 }
 
-// tiles the fp16 weight-gradient kernel is instantiated for (rows = Cout, columns = K)
-static TileCfg half_wtile(TileCfg t) {
-  if (t.bm == 256) t.bm = 128;
-  return t;
-}
+// ------------------------------------------------------------------------------------------------ weight gradient
+// The tiles wgrad_h_kernel is instantiated for (rows = Cout, columns = K; four waves), stated once: select_wgrad_h picks an
+// entry, launch_wgrad_h maps it to template arguments.
+struct HWgradTile {
+  int bm, bn, wm, wn;
+};
+constexpr HWgradTile kHWgradTiles[] = {{128, 128, 2, 2}, {128, 64, 2, 2}, {128, 32, 4, 1}, {64, 128, 2, 2}, {32, 128, 1, 4}};
+constexpr int kNumHWgradTiles = (int)(sizeof(kHWgradTiles) / sizeof(kHWgradTiles[0]));
 
-static WgradPlan plan_wgrad_h(long long P, int Cout, int K) {
+// Everything run_wgrad_h decides before it launches; the queries read their answers off the same choice.
+struct HWgradChoice {
+  WgradPlan pl;
+  WgradPixelOrder order;
+  int tile;        // entry of kHWgradTiles; -1: a forced tile that nothing is instantiated for
+  bool skip;       // the kernel's SKIP template flag
+  int stages;      // ring depth (2 .. 4; the 64-pixel K-step has no four-deep ring)
+  int bkp;         // pixels per K-step, 32 / 64
+};
+
+// The one place that picks the kernel of an fp16 weight gradient.  Pure: launches nothing, touches no device.
+static HWgradChoice select_wgrad_h(const WgradGeom& q) {
+  HWgradChoice c;
   // pixel splits for ONE resident block per CU (round 4): every split writes and re-reads a [Cout][K] fp32 slab, and under the
   // half policy that traffic was 40 % of the weight-gradient bytes (2.1 GB written + 2.1 GB read per DeepLabV3+ step for 157 MB
   // of gradients).  Half as many splits halve it; the step got 1.2 % faster with it (15.15 -> 14.97 ms: the blocks share the CUs
   // with the data gradients of the other stream anyway).  PSEG_WGRAD_BPC overrides.
-  WgradPlan pl = plan_wgrad(P, Cout, K, false, true, 1);
-  pl.tile = half_wtile(pl.tile);
-  return pl;
+  c.pl = plan_wgrad(q.P(), q.Cout, q.K(), false, true, 1);
+  if (c.pl.tile.bm == 256) c.pl.tile.bm = 128;      // (no 256-row tile here; the grid keeps the plan's rows)
+  c.order = wgrad_pixel_order(q, c.pl.tile.bn);
+  c.skip = c.order.mode != kWgDense;
+  c.tile = -1;
+  for (int i = 0; i < kNumHWgradTiles; ++i)
+    if (kHWgradTiles[i].bm == c.pl.tile.bm && kHWgradTiles[i].bn == c.pl.tile.bn) c.tile = i;
+  // ring depth: as deep as keeps the blocks the grid wants resident (measured: tools/bench_conv_half.py, PSEG_HWGRAD_STAGES)
+  const int forced_st = cfg().hwgrad_stages;
+  c.stages = (forced_st >= 2 && forced_st <= 4) ? forced_st : 2;
+  // pixels per K-step: 32 halves the ring (four blocks per CU instead of two) and pays on the deep 3x3 layers -- ASPP 361 -> 298
+  // / 294 -> 238 / 250 -> 216 us, layer-4 3x3 140 -> 111 -- while the short launches (bounded by their slab traffic and
+  // their prologue / epilogue) do not care and the narrow classifier loses 10 % (tools/bench_conv_half.py, PSEG_HWGRAD_BKP)
+  const int forced_bkp = cfg().hwgrad_bkp;
+  c.bkp = (forced_bkp == 32 || forced_bkp == 64) ? forced_bkp : ((q.kh * q.kw > 1 && q.Cout >= 128 && q.K() >= 4096) ? 32 : 64);
+  if (c.bkp == 64 && c.stages > 3) c.stages = 3;
+  return c;
 }
 
-static int run_wgrad_h(const void* x, int ldx, const void* dy, int ldy, float* dw, int B, int H, int W, int Cin, int Ho,
-                       int Wo, int Cout, int kh, int kw, int stride, int pad, int dil, int accumulate, void* workspace,
-                       int64_t workspace_bytes, void* stream, int defer) {
+template <int... I>
+static void launch_wgrad_h(const HWgradChoice& c, dim3 grid, hipStream_t st, const HWgradParams& hp, std::integer_sequence<int, I...>) {
+  auto launch = [&](auto tile, auto steps) {
+    constexpr HWgradTile t = kHWgradTiles[decltype(tile)::value];
+    using S = decltype(steps);
+    if constexpr (!(S::kb == 64 && S::st == 4)) {
+      if (c.skip) hipLaunchKernelGGL((wgrad_h_kernel<t.bm, t.bn, t.wm, t.wn, true, S::st, S::kb>), grid, dim3(256), 0, st, hp);
+      else hipLaunchKernelGGL((wgrad_h_kernel<t.bm, t.bn, t.wm, t.wn, false, S::st, S::kb>), grid, dim3(256), 0, st, hp);
+    }
+  };
+  (void)((c.tile == I && (with_h_steps<I>(c.bkp, c.stages, launch), true)) || ...);
+}
+
+// validate, select, check the workspace, fill the parameters from the choice and launch, reduce the slabs.
+// defer: a split plan leaves its slabs in the workspace (the caller reduces them later, pseg_slab_reduce_batch)
+static int run_wgrad_h(const WgradGeom& q, const void* x, int ldx, const void* dy, int ldy, float* dw, int accumulate,
+                       void* workspace, int64_t workspace_bytes, hipStream_t st, bool defer) {
   PSEG_REQUIRE(x && dy && dw, "conv2d_wgrad_h: null pointer");
-  PSEG_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "conv2d_wgrad_h: Cin, Cout, ldx, ldy must be multiples of 8");
+  PSEG_REQUIRE(q.Cin % 8 == 0 && q.Cout % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "conv2d_wgrad_h: Cin, Cout, ldx, ldy must be multiples of 8");
   PSEG_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)dw & 15) == 0,
                "conv2d_wgrad_h: x / dy / dw must be 16-byte aligned");
-  const long long P = (long long)B * Ho * Wo;
-  const int K = kh * kw * Cin;
-  PSEG_REQUIRE(P > 0 && P < (1LL << 31), "conv2d_wgrad_h: bad pixel count");
-  const long long xb = nhwc_bytes_h(B, H, W, Cin, ldx), db = nhwc_bytes_h(B, Ho, Wo, Cout, ldy);
+  PSEG_REQUIRE(q.P() > 0 && q.P() < (1LL << 31), "conv2d_wgrad_h: bad pixel count");
+  const long long xb = nhwc_bytes_h(q.B, q.H, q.W, q.Cin, ldx), db = nhwc_bytes_h(q.B, q.Ho, q.Wo, q.Cout, ldy);
   PSEG_REQUIRE(xb < kMaxBytes && db < kMaxBytes, "conv2d_wgrad_h: tensor exceeds 2 GiB");
-  WgradPlan pl = plan_wgrad_h(P, Cout, K);
+  const HWgradChoice c = select_wgrad_h(q);
+  const WgradPlan& pl = c.pl;
   HWgradParams hp;
   WgradParams& p = hp.g;
   p.x = reinterpret_cast<const float*>(x);
@@ -2470,102 +2512,16 @@ static int run_wgrad_h(const void* x, int ldx, const void* dy, int ldy, float* d
   p.dy_bytes = (uint32_t)db;
   p.ldx = ldx;
   p.ldy = ldy;
-  p.Hi = H;
-  p.Wi = W;
-  p.Cin = Cin;
-  p.Ho = Ho;
-  p.Wo = Wo;
-  p.HoWo = Ho * Wo;
-  p.Cout = Cout;
-  p.K = K;
-  p.P = (int)P;
-  p.kw = kw;
-  p.stride = stride;
-  p.pad = pad;
-  p.dil = dil;
-  p.pix_per_split = pl.pix_per_split;
-  const bool can_skip = (dil >= 4 && kh * kw > 1 && Cin % pl.tile.bn == 0 && cfg().conv_noskip == 0);
-  p.skip_rows = can_skip ? 1 : 0;
-  p.patch_mode = 0;
-  p.patch_h = 1;
-  p.patch_w = 32;
-  if (P % 32 == 0 && ((long long)Ho * Wo) % 32 == 0 && cfg().conv_noskip == 0) {
-    DilGeom g{Ho, Wo, H, W, kh, kw, dil, -pad};
-    double best = 2.0;
-    for (int pw = 32; pw >= 8; pw /= 2) {
-      const int ph = 32 / pw;
-      if (pw > Wo || Wo % pw != 0 || Ho % ph != 0) continue;
-      const double f = (can_skip && stride == 1) ? live_fraction(g, ph, pw) : 1.0;
-      if (f < best - 1e-9) {
-        best = f;
-        p.patch_mode = 1;
-        p.patch_h = ph;
-        p.patch_w = pw;
-      }
-    }
-    if (p.patch_mode) {
-      p.ppr = FastDiv((uint32_t)(Wo / p.patch_w));
-      p.ppi = FastDiv((uint32_t)((Ho / p.patch_h) * (Wo / p.patch_w)));
-      if (can_skip) p.skip_rows = 2;
-    }
-  }
-  hp.howo_div = FastDiv((uint32_t)(Ho * Wo));
-  hp.wo_div = FastDiv((uint32_t)Wo);
-  const long long wsz = (long long)Cout * K;
-  if (pl.splits == 1) {
-    p.dw = dw;
-    p.accumulate = accumulate;
-    p.slab_stride = 0;
-  } else {
-    const long long need = (long long)pl.splits * wsz * 4;
-    if (workspace == nullptr || workspace_bytes < need) {
-      set_error("conv2d_wgrad_h: needs %lld workspace bytes, got %lld", need, (long long)workspace_bytes);
-      return PSEG_ERR_WORKSPACE;
-    }
-    p.dw = (float*)workspace;
-    p.accumulate = 0;
-    p.slab_stride = wsz;
-  }
-  const dim3 grid((unsigned)(pl.gridM * pl.gridN), 1, (unsigned)pl.splits);
-  const bool sk = p.skip_rows != 0;
-  hipStream_t st = (hipStream_t)stream;
-  // ring depth: as deep as keeps the blocks the grid wants resident (measured: tools/bench_conv_half.py, PSEG_HWGRAD_STAGES)
-  static const int forced_wst = env_int("PSEG_HWGRAD_STAGES", 0);
-  int wst = 2;
-  if (forced_wst >= 2 && forced_wst <= 4) wst = forced_wst;
-  // pixels per K-step: 32 halves the ring (four blocks per CU instead of two) and pays on the deep 3x3 layers -- ASPP 361 -> 298
-  // / 294 -> 238 / 250 -> 216 us, layer-4 3x3 140 -> 111 -- while the short launches (bounded by their slab traffic and
-  // their prologue / epilogue) do not care and the narrow classifier loses 10 % (tools/bench_conv_half.py, PSEG_HWGRAD_BKP)
-  static const int forced_wkp = env_int("PSEG_HWGRAD_BKP", 0);
-  int wkp = (kh * kw > 1 && Cout >= 128 && K >= 4096) ? 32 : 64;
-  if (forced_wkp == 32 || forced_wkp == 64) wkp = forced_wkp;
-#define PSEG_HW_LAUNCH_S(BM_, BN_, WM_, WN_, ST_, KP_)                                                            \
-  do {                                                                                                            \
-    if (sk) hipLaunchKernelGGL((wgrad_h_kernel<BM_, BN_, WM_, WN_, true, ST_, KP_>), grid, dim3(256), 0, st, hp); \
-    else hipLaunchKernelGGL((wgrad_h_kernel<BM_, BN_, WM_, WN_, false, ST_, KP_>), grid, dim3(256), 0, st, hp);   \
-  } while (0)
-#define PSEG_HW_LAUNCH(BM_, BN_, WM_, WN_)                                       \
-  do {                                                                           \
-    if (wkp == 64 && wst == 2) PSEG_HW_LAUNCH_S(BM_, BN_, WM_, WN_, 2, 64);       \
-    else if (wkp == 64) PSEG_HW_LAUNCH_S(BM_, BN_, WM_, WN_, 3, 64);              \
-    else if (wst == 2) PSEG_HW_LAUNCH_S(BM_, BN_, WM_, WN_, 2, 32);               \
-    else if (wst == 3) PSEG_HW_LAUNCH_S(BM_, BN_, WM_, WN_, 3, 32);               \
-    else PSEG_HW_LAUNCH_S(BM_, BN_, WM_, WN_, 4, 32);                             \
-  } while (0)
-  if (pl.tile.bm == 128 && pl.tile.bn == 128) PSEG_HW_LAUNCH(128, 128, 2, 2);
-  else if (pl.tile.bm == 128 && pl.tile.bn == 64) PSEG_HW_LAUNCH(128, 64, 2, 2);
-  else if (pl.tile.bm == 128 && pl.tile.bn == 32) PSEG_HW_LAUNCH(128, 32, 4, 1);
-  else if (pl.tile.bm == 64 && pl.tile.bn == 128) PSEG_HW_LAUNCH(64, 128, 2, 2);
-  else if (pl.tile.bm == 32 && pl.tile.bn == 128) PSEG_HW_LAUNCH(32, 128, 1, 4);
-  else {
-    set_error("conv2d_wgrad_h: no kernel for tile %dx%d", pl.tile.bm, pl.tile.bn);
-    return PSEG_ERR_ARG;
-  }
-#undef PSEG_HW_LAUNCH
-#undef PSEG_HW_LAUNCH_S
+  set_wgrad_geometry(p, q, pl, c.order);
+  hp.howo_div = FastDiv((uint32_t)(q.Ho * q.Wo));
+  hp.wo_div = FastDiv((uint32_t)q.Wo);
+  const int rc = set_wgrad_output(p, pl, dw, accumulate, workspace, workspace_bytes, "conv2d_wgrad_h");
+  if (rc != PSEG_OK) return rc;
+  PSEG_REQUIRE(c.tile >= 0, "conv2d_wgrad_h: no kernel for tile %dx%d", pl.tile.bm, pl.tile.bn);
+  launch_wgrad_h(c, dim3((unsigned)(pl.gridM * pl.gridN), 1, (unsigned)pl.splits), st, hp, std::make_integer_sequence<int, kNumHWgradTiles>{});
   PSEG_LAUNCH_CHECK();
   if (pl.splits > 1 && !defer)
-    return launch_slab_reduce((const float*)workspace, wsz, pl.splits, dw, K, (long long)Cout, K, nullptr, accumulate, st);
+    return launch_slab_reduce((const float*)workspace, p.slab_stride, pl.splits, dw, p.K, (long long)q.Cout, p.K, nullptr, accumulate, st);
   return PSEG_OK;
 }
 
@@ -2643,21 +2599,27 @@ int pseg_conv2d_dgrad_bnstat_h(const pseg_half_t* dy, int ldy, const pseg_half_t
                       wT, dx, ldx, 0, nullptr, nullptr, 0, (hipStream_t)stream, &bns);
 }
 
+// the problem of a query, which knows Ho / Wo only: the smallest unit-stride input that gives them (the pixel split does not
+// depend on it)
+static WgradGeom wgrad_query_problem_h(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw) {
+  return WgradGeom{B, Ho + kh - 1, Wo + kw - 1, Cin, Ho, Wo, Cout, kh, kw, 1, 0, 1};
+}
+
+int pseg_conv2d_wgrad_splits_h(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw) {
+  if (B <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0) return 0;
+  return select_wgrad_h(wgrad_query_problem_h(B, Ho, Wo, Cin, Cout, kh, kw)).pl.splits;
+}
+
 int64_t pseg_conv2d_wgrad_workspace_bytes_h(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw) {
-  const WgradPlan a = plan_wgrad_h((long long)B * Ho * Wo, Cout, kh * kw * Cin);
-  return a.splits > 1 ? (int64_t)a.splits * Cout * kh * kw * Cin * 4 : 0;
+  const int splits = select_wgrad_h(wgrad_query_problem_h(B, Ho, Wo, Cin, Cout, kh, kw)).pl.splits;
+  return splits > 1 ? (int64_t)splits * Cout * kh * kw * Cin * 4 : 0;
 }
 
 int pseg_conv2d_wgrad_h(const pseg_half_t* x, int ldx, const pseg_half_t* dy, int ldy, float* dw, int B, int H, int W,
                         int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil, int accumulate,
                         void* workspace, int64_t workspace_bytes, void* stream) {
-  return run_wgrad_h(x, ldx, dy, ldy, dw, B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil, accumulate, workspace,
-                     workspace_bytes, stream, 0);
-}
-
-int pseg_conv2d_wgrad_splits_h(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw) {
-  if (B <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  return plan_wgrad_h((long long)B * Ho * Wo, Cout, kh * kw * Cin).splits;
+  return run_wgrad_h(WgradGeom{B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil}, x, ldx, dy, ldy, dw, accumulate, workspace,
+                     workspace_bytes, (hipStream_t)stream, false);
 }
 
 int pseg_conv2d_wgrad_slabs_h(const pseg_half_t* x, int ldx, const pseg_half_t* dy, int ldy, float* slabs, int B, int H,
@@ -2665,8 +2627,8 @@ int pseg_conv2d_wgrad_slabs_h(const pseg_half_t* x, int ldx, const pseg_half_t* 
                               int64_t slab_bytes, void* stream) {
   PSEG_REQUIRE(pseg_conv2d_wgrad_splits_h(B, Ho, Wo, Cin, Cout, kh, kw) > 1,
                "conv2d_wgrad_slabs_h: this plan does not split -- call pseg_conv2d_wgrad_h");
-  return run_wgrad_h(x, ldx, dy, ldy, slabs, B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil, 0, slabs, slab_bytes,
-                     stream, 1);
+  return run_wgrad_h(WgradGeom{B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil}, x, ldx, dy, ldy, slabs, 0, slabs, slab_bytes,
+                     (hipStream_t)stream, true);
 }
 
 int pseg_filter_prepare_h(const int64_t* jobs, int n, int64_t total_tiles, void* stream) {

@@ -1957,7 +1957,7 @@ __global__ __launch_bounds__(64 * WARPS_M * WARPS_N) void wgrad_f32_dma_kernel(c
   int p_end = p_begin + p.pix_per_split;
   if (p_end > p.P) p_end = p.P;
   // packed contraction (skip_rows == 3): the live rectangle of this block's tap, block-uniform
-  const bool packed = SKIP && p.skip_rows == 3;
+  const bool packed = SKIP && p.skip_rows == kWgPacked;
   int pk_r0 = 0, pk_c0 = 0, pk_total = 0, pk_dh = 0, pk_dw = 0;
   FastDiv pk_area_div, pk_lw_div;
   if (packed) {
@@ -1992,7 +1992,7 @@ __global__ __launch_bounds__(64 * WARPS_M * WARPS_N) void wgrad_f32_dma_kernel(c
     a_rel[g] = col < p.Cout ? ((row / p.patch_w) * p.Wo + row % p.patch_w) * p.ldy + col : -1;
     if (packed) a_rel[g] = col < p.Cout ? col : -1;               // (packed: the column; the pixel comes per K-step)
   }
-  const bool rowmajor = p.skip_rows == 4;      // plain pixel order, per-lane pixel derivation (no patches)
+  const bool rowmajor = p.skip_rows == kWgRowMajorDma;      // plain pixel order, per-lane pixel derivation (no patches)
   int b_prow[IB];                              // pixel row (0..31) of the K-step this lane's chunk of piece g belongs to
 #pragma unroll
   for (int g = 0; g < IB; ++g) {
@@ -2849,14 +2849,14 @@ static int f32_tile_index(TileCfg t) {
   return -1;
 }
 
-// f(std::integral_constant<int, i>) for table entry i: the entry's fields are then template arguments
+// f(std::integral_constant<int, i>) for entry i of a table of N: the entry's fields are then template arguments
 template <typename F, int... I>
-static void with_f32_tile(int i, F&& f, std::integer_sequence<int, I...>) {
+static void with_index(int i, F&& f, std::integer_sequence<int, I...>) {
   (void)((i == I && (f(std::integral_constant<int, I>{}), true)) || ...);
 }
 template <typename F>
 static void with_f32_tile(int i, F&& f) {
-  with_f32_tile(i, f, std::make_integer_sequence<int, kNumF32Tiles>{});
+  with_index(i, f, std::make_integer_sequence<int, kNumF32Tiles>{});
 }
 
 static int waves_m(TileCfg t) { return t.bm == 256 ? 4 : (t.bn == 32 ? 4 : (t.bm == 32 ? 1 : 2)); }
@@ -3165,6 +3165,195 @@ static int run_gather(const GatherGeom& g, const float* x, long long x_bytes, in
 }
 
 
+// ------------------------------------------------------------------------------------------------ weight gradient
+// The tiles of wgrad_f32_dma_kernel (rows = Cout, columns = K), stated once: select_wgrad reads from this table what the kernel
+// covers, launch_wgrad_dma maps an entry to template arguments.  Threads per block = 64 * wm * wn.
+struct WgradDmaTile {
+  int bm, bn, wm, wn;
+  bool skip;     // a SKIP = true instantiation exists
+};
+constexpr WgradDmaTile kWgradDmaTiles[] = {{128, 128, 2, 4, true},
+                                           {128, 64, 4, 2, true},
+                                           {64, 128, 2, 4, true},
+                                           {32, 256, 1, 8, true},     // narrow outputs (the 21-class classifier, HRNet's 32-channel branch): the x operand by DMA
+                                           {32, 288, 1, 9, false}};   // 3x3 on 32 channels: the whole filter as one column tile, nine waves
+constexpr int kNumWgradDmaTiles = (int)(sizeof(kWgradDmaTiles) / sizeof(kWgradDmaTiles[0]));
+
+static int wgrad_dma_tile_index(TileCfg t) {
+  for (int i = 0; i < kNumWgradDmaTiles; ++i)
+    if (kWgradDmaTiles[i].bm == t.bm && kWgradDmaTiles[i].bn == t.bn) return i;
+  return -1;
+}
+
+// A weight gradient as run_wgrad sees it: the geometry plus what the caller asks of the plan.
+struct WgradProblem : WgradGeom {
+  int precision;
+  bool concurrent;   // the launch shares the chip with another stream's kernels (see plan_wgrad)
+};
+
+constexpr int kWgradRefused = 0;     // WgradChoice::kernel: no kernel is instantiated for the (forced) tile
+
+// Everything run_wgrad decides before it launches; the queries read their answers off the same choice.
+struct WgradChoice {
+  WgradPlan pl;            // (the halo kernel's 32 x 288 tile and grid included)
+  WgradPixelOrder order;   // ... with the packed tap order and lpt_per
+  int kernel;              // PSEG_KERNEL_WGRAD_* that runs, or kWgradRefused
+  int dma_tile;            // entry of kWgradDmaTiles, -1: none
+  bool skip;               // the kernel's SKIP template flag
+};
+
+// The one place that picks the kernel of an exact-fp32 / limb weight gradient.  Pure: launches nothing, touches no device.
+static WgradChoice select_wgrad(const WgradProblem& q) {
+  WgradChoice c;
+  const long long P = q.P();
+  const int taps = q.kh * q.kw;
+  c.pl = plan_wgrad(P, q.Cout, q.K(), q.precision == 1, q.precision != 0, 0, q.concurrent);
+  c.order = wgrad_pixel_order(q, c.pl.tile.bn);
+  WgradPixelOrder& o = c.order;
+  const bool dma = q.precision == 0 && cfg().wgrad_f32dma != 0;
+  // narrow 3x3 filters on few channels: the halo-staged kernel (wgrad_f32_halo_kernel) on the plan's pixel splits -- a block is
+  // (row tile of 32 filters, one 32-channel chunk of the input, one split); K-steps are 2 x 16 strips of the output map.
+  // Measured (profiles/EXPERIMENTS.md 5.13): 32 -> 32 on 128x128 53 -> 45 us, HRNet fp32 14.19 -> 14.07 ms; the classifier (384
+  // channels: 583 -> 540 us alone) is SLOWER inside the two-stream DeepLabV3+ step (42.93 -> 43.03 ms) and 64-filter layers lose
+  // outright (64 -> 64: 40 -> 72 us) -- hence at most 64 input channels and 32 filters; PSEG_WGRAD_HALO=2 lifts the channel cap.
+  const bool halo = dma && cfg().wgrad_halo != 0 && q.kh == 3 && q.kw == 3 && q.stride == 1 && q.dil == 1 && q.pad == 1 &&
+                    q.Cin % 32 == 0 && (q.Cin <= 64 || cfg().wgrad_halo >= 2) && q.Cout <= 32 && q.H == q.Ho && q.W == q.Wo &&
+                    q.Ho % 2 == 0 && q.Wo % 16 == 0 && P % BK == 0;
+  if (halo) {
+    o.mode = kWgDense;
+    o.patch_mode = 1;
+    o.patch_h = 2;
+    o.patch_w = 16;
+    c.pl.tile = TileCfg{32, 288};
+    c.pl.gridM = cdiv(q.Cout, 32);
+    c.pl.gridN = q.Cin / 32;
+  }
+  const WgradPlan& pl = c.pl;
+  c.dma_tile = wgrad_dma_tile_index(pl.tile);
+  if (!dma || c.dma_tile < 0) {
+    // register-staged / limb kernels, in the shared pixel order
+    const bool tile288 = q.precision == 0 && pl.tile.bm == 32 && pl.tile.bn == 288;   // (PSEG_WGRAD_BM / _BN with PSEG_WGRAD_F32DMA=0)
+    c.kernel = tile288 ? kWgradRefused : (q.precision == 0 ? PSEG_KERNEL_WGRAD_REGISTER : PSEG_KERNEL_WGRAD_LIMB);
+    c.skip = o.mode != kWgDense;
+    return c;
+  }
+  // exact-fp32 weight gradient on the LDS-DMA kernel (8 waves, two blocks per CU); same tile, same split plan
+  c.kernel = halo ? PSEG_KERNEL_WGRAD_HALO : PSEG_KERNEL_WGRAD_DMA;
+  static const int packed_on = env_int("PSEG_WGRAD_PACKED", 1);
+  if (!o.patch_mode) {
+    // a map that does not tile into 32-pixel patches: plain row-major pixel order instead of the register-staged kernel
+    o.mode = kWgRowMajorDma;
+  } else if (o.can_skip && q.stride == 1 && taps <= 9 && packed_on != 0) {
+    // dilated conv: packed live rectangles instead of 32-pixel patches
+    o.mode = kWgPacked;
+    // longest-first order of the taps (live area, descending; ties keep the tap order: deterministic)
+    int area[9];
+    for (int t = 0; t < taps; ++t) {
+      const int dh = (t / q.kw) * q.dil - q.pad, dwv = (t % q.kw) * q.dil - q.pad;
+      const int r0 = dh < 0 ? -dh : 0, c0 = dwv < 0 ? -dwv : 0;
+      const int r1 = q.H - dh < q.Ho ? q.H - dh : q.Ho, c1 = q.W - dwv < q.Wo ? q.W - dwv : q.Wo;
+      area[t] = (r1 > r0 ? r1 - r0 : 0) * (c1 > c0 ? c1 - c0 : 0);
+    }
+    for (int i = 1; i < taps; ++i)
+      for (int j = i; j > 0 && area[o.tap_order[j]] > area[o.tap_order[j - 1]]; --j) {
+        const int t = o.tap_order[j];
+        o.tap_order[j] = o.tap_order[j - 1];
+        o.tap_order[j - 1] = t;
+      }
+    // one group = what one XCD walks in order (wgrad_block: eight contiguous ranges of the (split, tile) pairs)
+    const int tpt = q.Cin / pl.tile.bn;
+    const long long total = (long long)pl.gridM * pl.gridN * pl.splits;
+    int groups = 1;
+    if (total % 8 == 0 && pl.gridN % (total / 8) == 0) groups = (int)(pl.gridN / (total / 8));
+    if (groups < 1 || tpt % groups != 0) groups = 1;
+    o.lpt_per = tpt / groups;
+  }
+  c.skip = kWgradDmaTiles[c.dma_tile].skip && (o.mode == kWgSkipPatches || o.mode == kWgPacked);
+  return c;
+}
+
+static void launch_wgrad_dma(const WgradChoice& c, dim3 grid, hipStream_t st, const WgradParams& p) {
+  with_index(c.dma_tile, [&](auto tile) {
+    constexpr WgradDmaTile t = kWgradDmaTiles[decltype(tile)::value];
+    const dim3 block(64 * t.wm * t.wn);
+    if constexpr (t.skip) {
+      if (c.skip) {
+        hipLaunchKernelGGL((wgrad_f32_dma_kernel<t.bm, t.bn, t.wm, t.wn, true>), grid, block, 0, st, p);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((wgrad_f32_dma_kernel<t.bm, t.bn, t.wm, t.wn, false>), grid, block, 0, st, p);
+  }, std::make_integer_sequence<int, kNumWgradDmaTiles>{});
+}
+
+// the register-staged exact-fp32 kernel and the limb kernels
+static int launch_wgrad_staged(const WgradChoice& c, int precision, dim3 grid, hipStream_t st, const WgradParams& p) {
+  if (precision == 0 && c.pl.tile.bm == 32 && c.pl.tile.bn == 256) {
+    // (the 32 x 256 tile off the DMA kernel -- PSEG_WGRAD_F32DMA=0: two accumulators per wave)
+    if (c.skip) hipLaunchKernelGGL((wgrad_kernel<32, 256, 1, 4, true>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((wgrad_kernel<32, 256, 1, 4, false>), grid, dim3(256), 0, st, p);
+    PSEG_LAUNCH_CHECK();
+    return PSEG_OK;
+  }
+  typedef void (*Kfn)(const WgradParams);
+#define PSEG_WGRAD_ROW(KERNEL, BIG, ...)                                                                                \
+  {KERNEL<128, 128, 2, 2, __VA_ARGS__>, KERNEL<128, 64, 2, 2, __VA_ARGS__>, KERNEL<128, 32, 4, 1, __VA_ARGS__>,         \
+   KERNEL<64, 128, 2, 2, __VA_ARGS__>, KERNEL<32, 128, 1, 4, __VA_ARGS__>, BIG}
+  // the 256x128 tile (8 waves, one block per CU) exists for the two-limb variant
+  static const Kfn fns32[2][6] = {PSEG_WGRAD_ROW(wgrad_kernel, nullptr, false), PSEG_WGRAD_ROW(wgrad_kernel, nullptr, true)};
+  static const Kfn fnsb3[2][6] = {PSEG_WGRAD_ROW(wgrad_limb_kernel, (wgrad_limb_kernel<256, 128, 4, 2, false, 2>), false, 2),
+                                  PSEG_WGRAD_ROW(wgrad_limb_kernel, (wgrad_limb_kernel<256, 128, 4, 2, true, 2>), true, 2)};
+  static const Kfn fnsb6[2][6] = {PSEG_WGRAD_ROW(wgrad_limb_kernel, nullptr, false, 3),
+                                  PSEG_WGRAD_ROW(wgrad_limb_kernel, nullptr, true, 3)};
+#undef PSEG_WGRAD_ROW
+  const auto& fns = precision == 2 ? fnsb6 : precision == 1 ? fnsb3 : fns32;
+  return launch_tiles<WgradParams, Kfn, 6>(fns, c.skip, c.pl.tile, grid, p, st);
+}
+
+// validate, select, check the workspace, fill the parameters from the choice and launch, reduce the slabs.
+// defer: a split plan leaves its slabs in the workspace (the caller reduces them later, pseg_slab_reduce_batch)
+static int run_wgrad(const WgradProblem& q, const float* x, int ldx, const float* dy, int ldy, float* dw, int accumulate,
+                     void* workspace, int64_t workspace_bytes, hipStream_t st, bool defer) {
+  PSEG_REQUIRE(x && dy && dw, "conv2d_wgrad: null pointer");
+  PSEG_REQUIRE(q.precision >= 0 && q.precision <= 2, "conv2d_wgrad: precision must be PSEG_PREC_FP32 / _BF16X3 / _BF16X6");
+  PSEG_REQUIRE(q.Cin % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, "conv2d_wgrad: Cin, ldx, ldy must be multiples of 4");
+  PSEG_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0, "conv2d_wgrad: x / dy must be 16-byte aligned");
+  const long long P = q.P();
+  PSEG_REQUIRE(P > 0 && P < (1LL << 31), "conv2d_wgrad: bad pixel count");
+  const long long xb = nhwc_bytes(q.B, q.H, q.W, q.Cin, ldx), db = nhwc_bytes(q.B, q.Ho, q.Wo, q.Cout, ldy);
+  // dy chunks are read 4 channels at a time: the last chunk of a row may run up to 3 floats past Cout (inside ldy)
+  PSEG_REQUIRE(xb < kMaxBytes && db < kMaxBytes, "conv2d_wgrad: tensor exceeds 2 GiB");
+  PSEG_REQUIRE((q.Cout + 3) / 4 * 4 <= ldy, "conv2d_wgrad: ldy must cover Cout rounded up to 4");
+  const WgradChoice c = select_wgrad(q);
+  const WgradPlan& pl = c.pl;
+  WgradParams p;
+  p.x = x;
+  p.dy = dy;
+  p.x_bytes = (uint32_t)xb;
+  p.dy_bytes = (uint32_t)(((P - 1) * ldy + (q.Cout + 3) / 4 * 4) * 4);
+  p.ldx = ldx;
+  p.ldy = ldy;
+  set_wgrad_geometry(p, q, pl, c.order);
+  const int rc = set_wgrad_output(p, pl, dw, accumulate, workspace, workspace_bytes, "conv2d_wgrad");
+  if (rc != PSEG_OK) return rc;
+  PSEG_REQUIRE(c.kernel != kWgradRefused,
+               "conv2d_wgrad: the 32 x 288 tile runs on the LDS-DMA kernel only (PSEG_WGRAD_F32DMA=0 with PSEG_WGRAD_NARROW288=1?)");
+  const dim3 grid((unsigned)(pl.gridM * pl.gridN), 1, (unsigned)pl.splits);
+  g_last_conv_kernel = c.kernel;
+  if (c.kernel == PSEG_KERNEL_WGRAD_HALO) {
+    hipLaunchKernelGGL(wgrad_f32_halo_kernel<32>, grid, dim3(576), 0, st, p);
+  } else if (c.kernel == PSEG_KERNEL_WGRAD_DMA) {
+    launch_wgrad_dma(c, grid, st, p);
+  } else {
+    const int rl = launch_wgrad_staged(c, q.precision, grid, st, p);
+    if (rl != PSEG_OK) return rl;
+  }
+  PSEG_LAUNCH_CHECK();
+  if (pl.splits > 1 && !defer)
+    return launch_slab_reduce((const float*)workspace, p.slab_stride, pl.splits, dw, p.K, (long long)q.Cout, p.K, nullptr, accumulate, st);
+  return PSEG_OK;
+}
+
 }  // namespace pseg
 
 using namespace pseg;
@@ -3351,254 +3540,33 @@ int pseg_filter_transpose(const float* w, float* wT, int Cout, int taps, int Cin
   return PSEG_OK;
 }
 
-int64_t pseg_conv2d_wgrad_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw) {
-  // the plan depends on the arithmetic (the limb kernels may take the 256-row tile): size for the larger of the two
-  const WgradPlan a = plan_wgrad((long long)B * Ho * Wo, Cout, kh * kw * Cin, false, false);
-  const WgradPlan a2 = plan_wgrad((long long)B * Ho * Wo, Cout, kh * kw * Cin, false, false, 0, false);
-  const WgradPlan b = plan_wgrad((long long)B * Ho * Wo, Cout, kh * kw * Cin, true, true);
-  const WgradPlan c = plan_wgrad((long long)B * Ho * Wo, Cout, kh * kw * Cin, false, true);
-  int splits = a.splits > b.splits ? a.splits : b.splits;
-  if (c.splits > splits) splits = c.splits;
-  if (a2.splits > splits) splits = a2.splits;
-  return splits > 1 ? (int64_t)splits * Cout * kh * kw * Cin * 4 : 0;
-}
-
-// defer != 0: a split plan leaves its slabs in the workspace (the caller reduces them later, pseg_slab_reduce_batch)
-static int run_wgrad(const float* x, int ldx, const float* dy, int ldy, float* dw, int B, int H, int W, int Cin, int Ho,
-                     int Wo, int Cout, int kh, int kw, int stride, int pad, int dil, int accumulate, int precision,
-                     void* workspace, int64_t workspace_bytes, void* stream, int defer, int concurrent) {
-  PSEG_REQUIRE(x && dy && dw, "conv2d_wgrad: null pointer");
-  PSEG_REQUIRE(precision >= 0 && precision <= 2, "conv2d_wgrad: precision must be PSEG_PREC_FP32 / _BF16X3 / _BF16X6");
-  PSEG_REQUIRE(Cin % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, "conv2d_wgrad: Cin, ldx, ldy must be multiples of 4");
-  PSEG_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0, "conv2d_wgrad: x / dy must be 16-byte aligned");
-  const long long P = (long long)B * Ho * Wo;
-  const int K = kh * kw * Cin;
-  PSEG_REQUIRE(P > 0 && P < (1LL << 31), "conv2d_wgrad: bad pixel count");
-  const long long xb = nhwc_bytes(B, H, W, Cin, ldx), db = nhwc_bytes(B, Ho, Wo, Cout, ldy);
-  // dy chunks are read 4 channels at a time: the last chunk of a row may run up to 3 floats past Cout (inside ldy)
-  PSEG_REQUIRE(xb < kMaxBytes && db < kMaxBytes, "conv2d_wgrad: tensor exceeds 2 GiB");
-  PSEG_REQUIRE((Cout + 3) / 4 * 4 <= ldy, "conv2d_wgrad: ldy must cover Cout rounded up to 4");
-  WgradPlan pl = plan_wgrad(P, Cout, K, precision == 1, precision != 0, 0, concurrent != 0);
-  WgradParams p;
-  p.x = x;
-  p.dy = dy;
-  p.x_bytes = (uint32_t)xb;
-  p.dy_bytes = (uint32_t)(((P - 1) * ldy + (Cout + 3) / 4 * 4) * 4);
-  p.ldx = ldx;
-  p.ldy = ldy;
-  p.Hi = H;
-  p.Wi = W;
-  p.Cin = Cin;
-  p.Ho = Ho;
-  p.Wo = Wo;
-  p.HoWo = Ho * Wo;
-  p.Cout = Cout;
-  p.K = K;
-  p.P = (int)P;
-  p.kw = kw;
-  p.stride = stride;
-  p.pad = pad;
-  p.dil = dil;
-  p.pix_per_split = pl.pix_per_split;
-  // a column tile must sit inside one tap for the skip test to be block-uniform
-  const bool can_skip = (dil >= 4 && kh * kw > 1 && Cin % pl.tile.bn == 0 && cfg().conv_noskip == 0);
-  p.skip_rows = can_skip ? 1 : 0;
-  p.patch_mode = 0;
-  p.patch_h = 1;
-  p.patch_w = BK;
-  if (P % BK == 0 && ((long long)Ho * Wo) % BK == 0 && cfg().conv_noskip == 0) {
-    // pixel order of the contraction: 32-pixel K-steps as PH x PW patches of the output map (PW % 8 == 0).  Addresses of
-    // a K-step are then a block-uniform origin plus thread constants, and a dilated tap is dead for the whole step when
-    // its rows OR its columns are out of range: take the shape that leaves the fewest live (K-step, tap) pairs
-    // (32x32 map: rate 12 -> 4x8 = 0.63 against 0.75 row-major, rate 18 -> 2x16 = 0.42 against 0.63).
-    DilGeom g{Ho, Wo, H, W, kh, kw, dil, -pad};
-    double best = 2.0;
-    for (int pw = BK; pw >= 8; pw /= 2) {
-      const int ph = BK / pw;
-      if (pw > Wo || Wo % pw != 0 || Ho % ph != 0) continue;
-      const double f = (can_skip && stride == 1) ? live_fraction(g, ph, pw) : 1.0;
-      if (f < best - 1e-9) {
-        best = f;
-        p.patch_mode = 1;
-        p.patch_h = ph;
-        p.patch_w = pw;
-      }
-    }
-    if (p.patch_mode) {
-      p.ppr = FastDiv((uint32_t)(Wo / p.patch_w));
-      p.ppi = FastDiv((uint32_t)((Ho / p.patch_h) * (Wo / p.patch_w)));
-      if (can_skip) p.skip_rows = 2;
-    }
-  }
-  p.lpt_per = 0;
-  for (int t = 0; t < 9; ++t) p.tap_order[t] = t;
-  // narrow 3x3 filters on few channels: the halo-staged kernel (wgrad_f32_halo_kernel) on the plan's pixel splits -- a block is
-  // (row tile of 32 filters, one 32-channel chunk of the input, one split); K-steps are 2 x 16 strips of the output map.
-  // Measured (profiles/EXPERIMENTS.md 5.13): 32 -> 32 on 128x128 53 -> 45 us, HRNet fp32 14.19 -> 14.07 ms; the classifier (384
-  // channels: 583 -> 540 us alone) is SLOWER inside the two-stream DeepLabV3+ step (42.93 -> 43.03 ms) and 64-filter layers lose
-  // outright (64 -> 64: 40 -> 72 us) -- hence at most 64 input channels and 32 filters; PSEG_WGRAD_HALO=2 lifts the channel cap.
-  const bool halo = precision == 0 && cfg().wgrad_halo != 0 && cfg().wgrad_f32dma != 0 && kh == 3 && kw == 3 && stride == 1 &&
-                    dil == 1 && pad == 1 && Cin % 32 == 0 && (Cin <= 64 || cfg().wgrad_halo >= 2) && Cout <= 32 && H == Ho && W == Wo && Ho % 2 == 0 && Wo % 16 == 0 &&
-                    P % BK == 0 && pl.pix_per_split % BK == 0 && (Cout + 3) / 4 * 4 <= ldy;
-  if (halo) {
-    p.skip_rows = 0;
-    p.patch_mode = 1;
-    p.patch_h = 2;
-    p.patch_w = 16;
-    p.ppr = FastDiv((uint32_t)(Wo / 16));
-    p.ppi = FastDiv((uint32_t)((Ho / 2) * (Wo / 16)));
-    pl.tile.bm = 32;
-    pl.tile.bn = 288;
-    pl.gridM = cdiv(Cout, 32);
-    pl.gridN = Cin / 32;
-  }
-  const bool dma_tile = (pl.tile.bm == 128 && (pl.tile.bn == 128 || pl.tile.bn == 64)) || (pl.tile.bm == 64 && pl.tile.bn == 128) ||
-                        (pl.tile.bm == 32 && (pl.tile.bn == 256 || pl.tile.bn == 288));
-  p.rm_howo = FastDiv((uint32_t)(Ho * Wo));
-  p.rm_wo = FastDiv((uint32_t)Wo);
-  if (precision == 0 && !p.patch_mode && cfg().wgrad_f32dma != 0 && dma_tile && P < (1LL << 31)) {
-    // a map that does not tile into 32-pixel patches: the LDS-DMA kernel in plain row-major pixel order (per-lane pixel
-    // derivation; no dead-step skipping), instead of the register-staged kernel
-    p.skip_rows = 4;
-  }
-  static const int packed_on = env_int("PSEG_WGRAD_PACKED", 1);
-  if (precision == 0 && can_skip && stride == 1 && p.patch_mode && cfg().wgrad_f32dma != 0 && dma_tile && kh * kw <= 9 &&
-      (Cout + 3) / 4 * 4 <= ldy && packed_on != 0) {
-    // dilated conv on the LDS-DMA kernel: packed live rectangles instead of 32-pixel patches (WgradParams::lpt_per)
-    p.skip_rows = 3;
-    // longest-first order of the taps (live area, descending; ties keep the tap order: deterministic)
-    int area[9];
-    const int ntap = kh * kw;
-    for (int t = 0; t < ntap; ++t) {
-      const int dh = (t / kw) * dil - pad, dwv = (t % kw) * dil - pad;
-      int r0 = dh < 0 ? -dh : 0, c0 = dwv < 0 ? -dwv : 0;
-      int r1 = H - dh < Ho ? H - dh : Ho, c1 = W - dwv < Wo ? W - dwv : Wo;
-      area[t] = (r1 > r0 ? r1 - r0 : 0) * (c1 > c0 ? c1 - c0 : 0);
-    }
-    for (int i = 1; i < ntap; ++i)
-      for (int j = i; j > 0 && area[p.tap_order[j]] > area[p.tap_order[j - 1]]; --j) {
-        const int t = p.tap_order[j];
-        p.tap_order[j] = p.tap_order[j - 1];
-        p.tap_order[j - 1] = t;
-      }
-    // one group = what one XCD walks in order (wgrad_block: eight contiguous ranges of the (split, tile) pairs)
-    const int tpt = Cin / pl.tile.bn;
-    const long long total = (long long)pl.gridM * pl.gridN * pl.splits;
-    int groups = 1;
-    if (total % 8 == 0 && pl.gridN % (total / 8) == 0) groups = (int)(pl.gridN / (total / 8));
-    if (groups < 1 || tpt % groups != 0) groups = 1;
-    p.lpt_per = tpt / groups;
-  }
-  const long long wsz = (long long)Cout * K;
-  if (pl.splits == 1) {
-    p.dw = dw;
-    p.accumulate = accumulate;
-    p.slab_stride = 0;
-  } else {
-    const long long need = (long long)pl.splits * wsz * 4;
-    if (workspace == nullptr || workspace_bytes < need) {
-      set_error("conv2d_wgrad: needs %lld workspace bytes, got %lld", need, (long long)workspace_bytes);
-      return PSEG_ERR_WORKSPACE;
-    }
-    p.dw = (float*)workspace;
-    p.accumulate = 0;
-    p.slab_stride = wsz;
-  }
-  const dim3 grid((unsigned)(pl.gridM * pl.gridN), 1, (unsigned)pl.splits);
-  if (precision == 0 && (p.patch_mode || p.skip_rows == 4) && cfg().wgrad_f32dma != 0 && (Cout + 3) / 4 * 4 <= ldy) {
-    // exact-fp32 weight gradient on the LDS-DMA kernel (8 waves, two blocks per CU); same tile, same split plan
-    const bool sk = p.skip_rows != 0 && p.skip_rows != 4;
-    bool launched = true;
-    hipStream_t st = (hipStream_t)stream;
-    g_last_conv_kernel = halo ? PSEG_KERNEL_WGRAD_HALO : PSEG_KERNEL_WGRAD_DMA;
-    if (halo) {
-      hipLaunchKernelGGL(wgrad_f32_halo_kernel<32>, grid, dim3(576), 0, st, p);
-    } else if (pl.tile.bm == 128 && pl.tile.bn == 128) {
-      if (sk) hipLaunchKernelGGL((wgrad_f32_dma_kernel<128, 128, 2, 4, true>), grid, dim3(512), 0, st, p);
-      else hipLaunchKernelGGL((wgrad_f32_dma_kernel<128, 128, 2, 4, false>), grid, dim3(512), 0, st, p);
-    } else if (pl.tile.bm == 128 && pl.tile.bn == 64) {
-      if (sk) hipLaunchKernelGGL((wgrad_f32_dma_kernel<128, 64, 4, 2, true>), grid, dim3(512), 0, st, p);
-      else hipLaunchKernelGGL((wgrad_f32_dma_kernel<128, 64, 4, 2, false>), grid, dim3(512), 0, st, p);
-    } else if (pl.tile.bm == 64 && pl.tile.bn == 128) {
-      if (sk) hipLaunchKernelGGL((wgrad_f32_dma_kernel<64, 128, 2, 4, true>), grid, dim3(512), 0, st, p);
-      else hipLaunchKernelGGL((wgrad_f32_dma_kernel<64, 128, 2, 4, false>), grid, dim3(512), 0, st, p);
-    } else if (pl.tile.bm == 32 && pl.tile.bn == 256) {
-      // narrow outputs (the 21-class classifier, HRNet's 32-channel branch): 32 x 256 tile, the x operand by DMA
-      if (sk) hipLaunchKernelGGL((wgrad_f32_dma_kernel<32, 256, 1, 8, true>), grid, dim3(512), 0, st, p);
-      else hipLaunchKernelGGL((wgrad_f32_dma_kernel<32, 256, 1, 8, false>), grid, dim3(512), 0, st, p);
-    } else if (pl.tile.bm == 32 && pl.tile.bn == 288) {
-      // 3x3 on 32 channels: the whole filter as one column tile, nine waves
-      hipLaunchKernelGGL((wgrad_f32_dma_kernel<32, 288, 1, 9, false>), grid, dim3(576), 0, st, p);
-    } else {
-      launched = false;
-    }
-    if (launched) {
-      PSEG_LAUNCH_CHECK();
-      if (pl.splits > 1 && !defer) {
-        const int blocks = (int)(wsz / 256 + 1 < 4096 ? wsz / 256 + 1 : 4096);
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)workspace, wsz, pl.splits, dw,
-                           K, (long long)Cout, K, (const float*)nullptr, accumulate);
-        PSEG_LAUNCH_CHECK();
-      }
-      return PSEG_OK;
-    }
-  }
-  g_last_conv_kernel = precision == 0 ? PSEG_KERNEL_WGRAD_REGISTER : PSEG_KERNEL_WGRAD_LIMB;
-  if (precision == 0 && pl.tile.bm == 32 && pl.tile.bn == 288) {
-    set_error("conv2d_wgrad: the 32 x 288 tile runs on the LDS-DMA kernel only (PSEG_WGRAD_F32DMA=0 with PSEG_WGRAD_NARROW288=1?)");
-    return PSEG_ERR_ARG;
-  }
-  if (precision == 0 && pl.tile.bm == 32 && pl.tile.bn == 256) {
-    // (the 32 x 256 tile off the DMA kernel -- map sizes that do not tile into 32-pixel patches: register-staged, two
-    // accumulators per wave)
-    if (p.skip_rows != 0) hipLaunchKernelGGL((wgrad_kernel<32, 256, 1, 4, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((wgrad_kernel<32, 256, 1, 4, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    PSEG_LAUNCH_CHECK();
-    if (pl.splits > 1 && !defer) {
-      const int blocks = (int)(wsz / 256 + 1 < 4096 ? wsz / 256 + 1 : 4096);
-      hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, wsz,
-                         pl.splits, dw, K, (long long)Cout, K, (const float*)nullptr, accumulate);
-      PSEG_LAUNCH_CHECK();
-    }
-    return PSEG_OK;
-  }
-  typedef void (*Kfn)(const WgradParams);
-  static const Kfn fns[2][5] = {
-      {wgrad_kernel<128, 128, 2, 2, false>, wgrad_kernel<128, 64, 2, 2, false>, wgrad_kernel<128, 32, 4, 1, false>,
-       wgrad_kernel<64, 128, 2, 2, false>, wgrad_kernel<32, 128, 1, 4, false>},
-      {wgrad_kernel<128, 128, 2, 2, true>, wgrad_kernel<128, 64, 2, 2, true>, wgrad_kernel<128, 32, 4, 1, true>,
-       wgrad_kernel<64, 128, 2, 2, true>, wgrad_kernel<32, 128, 1, 4, true>}};
-#define PSEG_WLIMB_ROW(SK, NLIMB)                                                                                 \
-  wgrad_limb_kernel<128, 128, 2, 2, SK, NLIMB>, wgrad_limb_kernel<128, 64, 2, 2, SK, NLIMB>,                      \
-      wgrad_limb_kernel<128, 32, 4, 1, SK, NLIMB>, wgrad_limb_kernel<64, 128, 2, 2, SK, NLIMB>,                   \
-      wgrad_limb_kernel<32, 128, 1, 4, SK, NLIMB>
-  static const Kfn fnsb3[2][6] = {{PSEG_WLIMB_ROW(false, 2), wgrad_limb_kernel<256, 128, 4, 2, false, 2>},
-                                  {PSEG_WLIMB_ROW(true, 2), wgrad_limb_kernel<256, 128, 4, 2, true, 2>}};
-  static const Kfn fnsb6[2][5] = {{PSEG_WLIMB_ROW(false, 3)}, {PSEG_WLIMB_ROW(true, 3)}};
-#undef PSEG_WLIMB_ROW
-  int rc = precision == 2   ? launch_tiles<WgradParams, Kfn, 5>(fnsb6, p.skip_rows != 0, pl.tile, grid, p, (hipStream_t)stream)
-           : precision == 1 ? launch_tiles<WgradParams, Kfn, 6>(fnsb3, p.skip_rows != 0, pl.tile, grid, p, (hipStream_t)stream)
-                            : launch_tiles<WgradParams, Kfn, 5>(fns, p.skip_rows != 0, pl.tile, grid, p, (hipStream_t)stream);
-  if (rc != PSEG_OK) return rc;
-  if (pl.splits > 1 && !defer) {
-    const int blocks = (int)(wsz / 256 + 1 < 4096 ? wsz / 256 + 1 : 4096);
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, wsz,
-                       pl.splits, dw, K, (long long)Cout, K, (const float*)nullptr, accumulate);
-    PSEG_LAUNCH_CHECK();
-  }
-  return PSEG_OK;
-}
-
 int pseg_conv2d_wgrad(const float* x, int ldx, const float* dy, int ldy, float* dw, int B, int H, int W, int Cin, int Ho,
                       int Wo, int Cout, int kh, int kw, int stride, int pad, int dil, int accumulate, int precision,
                       int concurrent, void* workspace, int64_t workspace_bytes, void* stream) {
-  return run_wgrad(x, ldx, dy, ldy, dw, B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil, accumulate, precision,
-                   workspace, workspace_bytes, stream, 0, concurrent);
+  return run_wgrad(WgradProblem{{B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil}, precision, concurrent != 0}, x, ldx, dy, ldy,
+                   dw, accumulate, workspace, workspace_bytes, (hipStream_t)stream, false);
+}
+
+// the problem of a query, which knows Ho / Wo only: the smallest unit-stride input that gives them (the pixel split does not
+// depend on it)
+static WgradProblem wgrad_query_problem(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int precision, int concurrent) {
+  return WgradProblem{{B, Ho + kh - 1, Wo + kw - 1, Cin, Ho, Wo, Cout, kh, kw, 1, 0, 1}, precision, concurrent != 0};
 }
 
 int pseg_conv2d_wgrad_splits(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int precision, int concurrent) {
   if (B <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || precision < 0 || precision > 2) return 0;
-  return plan_wgrad((long long)B * Ho * Wo, Cout, kh * kw * Cin, precision == 1, precision != 0, 0, concurrent != 0).splits;
+  return select_wgrad(wgrad_query_problem(B, Ho, Wo, Cin, Cout, kh, kw, precision, concurrent)).pl.splits;
+}
+
+int64_t pseg_conv2d_wgrad_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw) {
+  // the plan depends on the arithmetic and on what the launch runs beside: size for the most slabs any of them asks for
+  int splits = 0;
+  for (int precision = 0; precision <= 2; ++precision)
+    for (int concurrent = 0; concurrent <= 1; ++concurrent) {
+      const int s = select_wgrad(wgrad_query_problem(B, Ho, Wo, Cin, Cout, kh, kw, precision, concurrent)).pl.splits;
+      splits = s > splits ? s : splits;
+    }
+  return splits > 1 ? (int64_t)splits * Cout * kh * kw * Cin * 4 : 0;
 }
 
 int pseg_conv2d_wgrad_slabs(const float* x, int ldx, const float* dy, int ldy, float* slabs, int B, int H, int W, int Cin,
@@ -3607,8 +3575,8 @@ int pseg_conv2d_wgrad_slabs(const float* x, int ldx, const float* dy, int ldy, f
   PSEG_REQUIRE(pseg_conv2d_wgrad_splits(B, Ho, Wo, Cin, Cout, kh, kw, precision, concurrent) > 1,
                "conv2d_wgrad_slabs: this plan does not split -- call pseg_conv2d_wgrad");
   // (dw is unused by a split plan; the slabs pointer stands in for the null check)
-  return run_wgrad(x, ldx, dy, ldy, slabs, B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil, 0, precision, slabs,
-                   slab_bytes, stream, 1, concurrent);
+  return run_wgrad(WgradProblem{{B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil}, precision, concurrent != 0}, x, ldx, dy, ldy,
+                   slabs, 0, slabs, slab_bytes, (hipStream_t)stream, true);
 }
 
 int pseg_slab_reduce_batch(const int64_t* jobs, int n, int64_t total_blocks, int accumulate, void* stream) {

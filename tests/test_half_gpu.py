@@ -180,6 +180,30 @@ def test_conv2d_dgrad_wgrad_half(ops, case):
     assert torch.equal(dw2, dw3)        # bit-reproducible (fixed-order slabs)
 
 
+@pytest.mark.parametrize('bkp', [32, 64])
+@pytest.mark.parametrize('H,W,dil', [(8, 8, 1), (7, 9, 1), (16, 16, 6)], ids=['patch_order', 'row_major', 'dilated'])
+def test_conv2d_wgrad_half_k_step_pixels(ops, H, W, dil, bkp, monkeypatch):
+    """wgrad_h_kernel with 32 and with 64 pixels per K-step (PSEG_HWGRAD_BKP; select_wgrad_h) on one image of 32 -> 64 channels,
+    3x3: a map of whole 32-pixel patches, one of 63 pixels (row-major order, ragged last K-step) and a dilated one."""
+    from pytorch_segmentation_amd import _lib
+    monkeypatch.setenv('PSEG_HWGRAD_BKP', str(bkp))
+    _lib.clear_query_cache()
+    try:
+        key = 'hwgrad_bkp/%dx%d' % (H, W)
+        x, gy = h(fill.uniform(key + '/x', (1, 32, H, W))), h(fill.uniform(key + '/gy', (1, 64, H, W)))
+        wr = torch.zeros(64, 32, 3, 3, dtype=torch.float64, requires_grad=True)
+        F.conv2d(x.double(), wr, None, 1, dil, dil).backward(gy.double())
+        xa, gya = to_act_h(ops, x, 32), to_act_h(ops, gy, 64)
+        dw = torch.empty(64, 3, 3, 32, device='cuda')
+        ops.conv2d_wgrad(xa, gya, dw, 3, 3, 1, dil, dil)
+        assert rel(dw.permute(0, 3, 1, 2), wr.grad) < TOL32
+        ops.conv2d_wgrad(xa, gya, dw, 3, 3, 1, dil, dil, accumulate=True)
+        assert rel(dw.permute(0, 3, 1, 2), 2 * wr.grad) < TOL32
+    finally:
+        monkeypatch.undo()
+        _lib.clear_query_cache()
+
+
 # BASELINE.json configs[2] shapes (DeepLabV3+ R50, 512x512, batch 16) under the half policy: the launches `bench.py
 # --precision half` / `train.py -mp` actually time, through the DEFAULT plan (no PSEG_* overrides) -- the 8-wave tiles with
 # the XCD remap on 2048-block grids, the tap-skipping 128x64 forward tiles, the 32-pixel K-step weight gradient with its

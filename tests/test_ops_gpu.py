@@ -462,6 +462,73 @@ def test_conv2d_wgrad_halo_staged(ops, case, monkeypatch, fresh_plans):
 
 
 
+WGRAD_FAMILY_CASES = [
+    # id, (B, Cin, H, W, Cout, pad = dil), precision, switches, kernel (pseg_debug_last_conv_kernel), deferred slabs too
+    ('patch_order_dma', (1, 32, 8, 8, 64, 1), 'fp32', {}, 13, False),
+    ('row_major_dma', (1, 32, 7, 9, 64, 1), 'fp32', {}, 13, False),               # 63 pixels: no 32-pixel patches
+    ('packed_dilated', (1, 128, 16, 16, 64, 6), 'fp32', {}, 13, False),
+    ('packed_dilated_noskip', (1, 128, 16, 16, 64, 6), 'fp32', {'PSEG_CONV_NOSKIP': '1'}, 13, False),
+    ('tile_32x288', (1, 32, 8, 8, 32, 1), 'fp32', {}, 13, False),
+    ('halo', (1, 32, 16, 16, 32, 1), 'fp32', {}, 14, False),
+    # 21 filters padded to 24 off the LDS-DMA kernel: K = 288 stays on the 32 x 128 register tile, K = 504 pads no further
+    # with 256 columns than with 128 and takes wgrad_kernel<32, 256>
+    ('register_32_to_21', (1, 32, 8, 8, 21, 1), 'fp32', {'PSEG_WGRAD_F32DMA': '0'}, 11, False),
+    ('register_32x256', (1, 56, 8, 8, 21, 1), 'fp32', {'PSEG_WGRAD_F32DMA': '0'}, 11, False),
+    ('limb_bf16x3', (1, 32, 8, 8, 64, 1), 'bf16x3', {}, 12, False),
+    ('limb_bf16x6', (1, 32, 8, 8, 64, 1), 'bf16x6', {}, 12, False),
+    # 128 pixels = four K-steps: a forced three-way split gives two per slab, TWO slabs; 192 pixels give three
+    ('forced_split_2x8x8', (2, 32, 8, 8, 64, 1), 'fp32', {'PSEG_WGRAD_SPLITS': '3'}, 13, True),
+    ('forced_split_3x8x8', (3, 32, 8, 8, 64, 1), 'fp32', {'PSEG_WGRAD_SPLITS': '3'}, 13, True),
+]
+
+
+@pytest.mark.parametrize('case', WGRAD_FAMILY_CASES, ids=[c[0] for c in WGRAD_FAMILY_CASES])
+def test_conv2d_wgrad_launch_families(ops, case, monkeypatch, fresh_plans):
+    """One small 3x3 problem per kernel family and pixel order the weight gradient's selection (select_wgrad) can pick: the
+    kernel that ran is the one meant, and dw, dw accumulated into a filled tensor and -- split plans -- the slabs parked in a
+    SlabPool and folded later all meet the fp64 CPU gradient within test_conv2d_dgrad_wgrad's bound for the arithmetic."""
+    from pytorch_segmentation_amd import _lib
+    name, (B, Cin, H, W, Cout, dil), prec, env, kernel, deferred = case
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    _lib.clear_query_cache()
+    tol, P = PREC_TOL[prec], ops._PREC_NAMES[prec]
+    cin_p, cout_p = (Cin + 3) // 4 * 4, (Cout + 3) // 4 * 4
+    x = fill.uniform('wfam/%s/x' % name, (B, Cin, H, W))
+    gy = fill.uniform('wfam/%s/gy' % name, (B, Cout, H, W))
+    wr = torch.zeros(Cout, Cin, 3, 3, dtype=torch.float64, requires_grad=True)
+    F.conv2d(x.double(), wr, None, 1, dil, dil).backward(gy.double())
+    ref64 = wr.grad
+    base = fill.uniform('wfam/%s/dw' % name, (cout_p, 3, 3, cin_p)).cuda()
+    base64 = base[:Cout, :, :, :Cin].permute(0, 3, 1, 2).double().cpu()
+    xa, gya = to_act(ops, x, cin_p), to_act(ops, gy, cout_p)
+    nchw = lambda dw: dw[:Cout, :, :, :Cin].permute(0, 3, 1, 2).cpu()
+    ran = lambda: _lib.load().pseg_debug_last_conv_kernel()
+    try:
+        dw = torch.empty(cout_p, 3, 3, cin_p, device='cuda')
+        ops.conv2d_wgrad(xa, gya, dw, 3, 3, 1, dil, dil, precision=P)
+        assert ran() == kernel
+        assert rel(nchw(dw), ref64) < tol
+        if cout_p > Cout:
+            assert dw[Cout:].abs().max().item() == 0.0
+        acc = base.clone()
+        ops.conv2d_wgrad(xa, gya, acc, 3, 3, 1, dil, dil, accumulate=True, precision=P)
+        assert ran() == kernel
+        assert rel(nchw(acc), base64 + ref64) < tol
+        if deferred:
+            assert _lib.query('pseg_conv2d_wgrad_splits', B, H, W, cin_p, cout_p, 3, 3, P, 0) == min(B, 3)
+            pool = ops.SlabPool(base.device)
+            parked = base.clone()
+            ops.conv2d_wgrad(xa, gya, parked, 3, 3, 1, dil, dil, precision=P, pool=pool)
+            assert ran() == kernel
+            assert torch.equal(parked, base)                  # the slabs wait in the pool
+            pool.reduce(accumulate=True)
+            assert rel(nchw(parked), base64 + ref64) < tol
+    finally:
+        monkeypatch.undo()
+        _lib.clear_query_cache()
+
+
 @pytest.mark.parametrize('half', [False, True])
 @pytest.mark.parametrize('act', [1, 2, 0])
 def test_bn_act_maxpool_fused(ops, half, act):

@@ -1,8 +1,10 @@
 """The planning decisions behind the integer-only conv queries are pinned: tests/golden/plan_table.json holds the answers of every
-query (tests/plan_queries.py) for a few hundred conv problems, under the default environment, PSEG_CONV_NOSKIP=1 and
-PSEG_HCONV_PERSIST=0 / 2, written by tools/plan_table.py with the library of the commit BEFORE the kernel selection was gathered
-into select_gather (conv_mfma.hip) and select_gather_h (conv_half.hip).
-A selection that moves changes the statistics layout, the fused-sum rows or a workspace size, and shows here without a GPU."""
+query (tests/plan_queries.py) for a few hundred conv problems, under the default environment, PSEG_CONV_NOSKIP=1,
+PSEG_HCONV_PERSIST=0 / 2 and PSEG_WGRAD_F32DMA=0 / PSEG_WGRAD_NARROW256=0 / PSEG_WGRAD_BPC=2, written by tools/plan_table.py with
+the library of the commit BEFORE the kernel selection was gathered into select_gather / select_wgrad (conv_mfma.hip) and
+select_gather_h / select_wgrad_h (conv_half.hip): the PSEG_WGRAD_* tables with the commit before the weight gradient's was.
+A selection that moves changes the statistics layout, the fused-sum rows, a split count or a workspace size, and shows here
+without a GPU."""
 import json
 import os
 import re
@@ -70,3 +72,40 @@ def test_half_gather_selection_is_written_once():
     body = src[start:src.index('\n}\n', start)]
     assert 'return c;' in body and len(body.splitlines()) > 40
     assert not re.search(r'\bhip[A-Z]\w*', body), re.findall(r'\bhip[A-Z]\w*', body)
+
+
+def _csrc(name):
+    return open(os.path.join(os.path.dirname(HERE), 'pytorch_segmentation_amd', 'csrc', name)).read()
+
+
+def _body(src, head):
+    start = src.index(head)
+    return src[start:src.index('\n}\n', start)]
+
+
+@pytest.mark.parametrize('name,head', [('conv_mfma.hip', 'static WgradChoice select_wgrad('),
+                                       ('conv_half.hip', 'static HWgradChoice select_wgrad_h(')])
+def test_wgrad_selection_is_pure(name, head):
+    """The weight gradient's kernel is picked in one function per number format, which launches nothing and asks the device
+    nothing; the launch path and the queries (_splits, _slabs, _workspace_bytes) all go through it."""
+    src = _csrc(name)
+    body = _body(src, head)
+    assert 'return c;' in body and len(body.splitlines()) > 20
+    assert not re.search(r'\bhip[A-Z]\w*', body), re.findall(r'\bhip[A-Z]\w*', body)
+    fn = head[head.index('select_wgrad'):-1]
+    assert len(re.findall(r'\b%s\(' % fn, src)) >= 4                   # its definition, the launch path, both queries
+    assert not re.search(r'\bplan_wgrad(_h)?\(', src.replace(body, ''))  # no plan of anyone's own beside it
+
+
+def test_wgrad_launches_are_written_once():
+    """No launch macros in conv_half.hip; the slab reduction is launched from launch_slab_reduce alone (the batch kernel is
+    another kernel); WgradParams::skip_rows is assigned by set_wgrad_geometry (conv_common.h) and nowhere else."""
+    mfma, half, common = _csrc('conv_mfma.hip'), _csrc('conv_half.hip'), _csrc('conv_common.h')
+    assert 'PSEG_HW_LAUNCH' not in half
+    launches = [m.start() for m in re.finditer(r'hipLaunchKernelGGL\(\s*\(?slab_reduce_kernel\b', mfma + half)]
+    assert len(launches) == 1
+    reduce_fn = _body(mfma, 'int launch_slab_reduce(')
+    assert 'hipLaunchKernelGGL(slab_reduce_kernel,' in reduce_fn
+    assign = r'skip_rows\s*=[^=]'
+    assert not re.search(assign, mfma) and not re.search(assign, half)
+    assert len(re.findall(assign, common)) == 1 and re.search(assign, _body(common, 'static void set_wgrad_geometry('))
