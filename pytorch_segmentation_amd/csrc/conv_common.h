@@ -466,14 +466,15 @@ static TileCfg pick_tile(long long rows, long long cols) {
   return c;
 }
 
-// Planning overrides (testing / tuning knobs).  Read from the environment ONCE (first launch) -- getenv is a linear scan
-// of the process environment and used to run 6-10 times per conv launch; pseg_config_reload() re-reads them (the tests
-// that change PSEG_* at run time call it through _lib.clear_query_cache()).
+// Planning overrides (testing / tuning knobs): every switch a plan, a selection or a launch helper reads is a field here and
+// cfg_load() is the only reader of the environment.  Read ONCE (first launch) -- getenv is a linear scan of the process
+// environment and used to run 6-10 times per conv launch; pseg_config_reload() re-reads them all (the tests that change
+// PSEG_* at run time call it through _lib.clear_query_cache()).
 struct EnvCfg {
-  int conv_nobig, conv_forcebig, conv_bm, conv_bn, conv_splitk, conv_noskip, conv_noband, plan_debug, wgrad_bpc, conv_dma32, conv_narrow, conv_noxcd, conv_nodma, conv_f32dma, wgrad_f32dma, conv_big, dgrad_prio;
-  int wgrad_big, wgrad_bm, wgrad_bn, wgrad_splits, wgrad_narrow256;
-  int hconv_persist, hconv_persist_kt, hconv_tile, hwgrad_stages, hwgrad_bkp;
-  int conv_pw, conv_pw_kt, conv_pw_resident, conv_halo, wgrad_halo;
+  int conv_nobig, conv_forcebig, conv_bm, conv_bn, conv_splitk, conv_noskip, conv_noband, plan_debug, conv_f32dma;
+  int wgrad_bpc, wgrad_f32dma, wgrad_splits, wgrad_narrow256, wgrad_halo;
+  int hconv_persist, hconv_kb, hconv_stages, hwgrad_bkp;
+  int conv_pw, conv_pw_resident, conv_halo;
 };
 inline EnvCfg g_cfg;
 inline volatile int g_cfg_ready = 0;
@@ -490,28 +491,17 @@ inline void cfg_load() {
   c.conv_splitk = env_int("PSEG_CONV_SPLITK", 0);
   c.conv_noskip = env_int("PSEG_CONV_NOSKIP", 0);
   c.conv_noband = env_int("PSEG_CONV_NOBAND", 0);
-  c.conv_narrow = env_int("PSEG_CONV_NARROW", 1);
-  c.dgrad_prio = env_int("PSEG_DGRAD_PRIO", 1);
-  c.conv_dma32 = env_int("PSEG_CONV_DMA32", 1);
   c.wgrad_bpc = env_int("PSEG_WGRAD_BPC", 0);
   c.plan_debug = env_int("PSEG_PLAN_DEBUG", 0);
-  c.conv_noxcd = env_int("PSEG_CONV_NOXCD", 0);
-  c.conv_nodma = env_int("PSEG_CONV_NODMA", 0);
   c.conv_f32dma = env_int("PSEG_CONV_F32DMA", 3);
   c.wgrad_f32dma = env_int("PSEG_WGRAD_F32DMA", 1);
-  c.conv_big = env_int("PSEG_CONV_BIG", 0);
-  c.wgrad_big = env_int("PSEG_WGRAD_BIG", 0);
-  c.wgrad_bm = env_int("PSEG_WGRAD_BM", 0);
-  c.wgrad_bn = env_int("PSEG_WGRAD_BN", 0);
   c.wgrad_splits = env_int("PSEG_WGRAD_SPLITS", 0);
   c.wgrad_narrow256 = env_int("PSEG_WGRAD_NARROW256", 1);   // 32 x 256 tile of the exact-fp32 weight gradient (0: off; plan_wgrad)
   c.hconv_persist = env_int("PSEG_HCONV_PERSIST", 1);
-  c.hconv_persist_kt = env_int("PSEG_HCONV_PERSIST_KT", 24);
-  c.hconv_tile = env_int("PSEG_HCONV_TILE", 0);
-  c.hwgrad_stages = env_int("PSEG_HWGRAD_STAGES", 0);       // fp16 weight gradient: ring depth 2 .. 4 / pixels per K-step 32 | 64
-  c.hwgrad_bkp = env_int("PSEG_HWGRAD_BKP", 0);             // (0: select_wgrad_h's own choice)
+  c.hconv_kb = env_int("PSEG_HCONV_KB", 0);                 // fp16 gather convs: K-step 32 | 64 and ring depth 2 .. 4
+  c.hconv_stages = env_int("PSEG_HCONV_STAGES", 0);         // (0: select_gather_h's own choice)
+  c.hwgrad_bkp = env_int("PSEG_HWGRAD_BKP", 0);             // fp16 weight gradient: pixels per K-step 32 | 64 (0: select_wgrad_h's own choice)
   c.conv_pw = env_int("PSEG_CONV_PW", 1);                   // persistent pointwise kernel of the exact-fp32 path (0: off)
-  c.conv_pw_kt = env_int("PSEG_CONV_PW_KT", 32);            // ... for contractions of at most this many K-steps
   c.conv_halo = env_int("PSEG_CONV_HALO", 2);               // halo-staged narrow 3x3 of the exact-fp32 path (0: off, 1: 128x32 plan tiles, 2: 128x64 too)
   c.wgrad_halo = env_int("PSEG_WGRAD_HALO", 1);             // halo-staged weight gradient of narrow 3x3 filters (0: off)
   c.conv_pw_resident = env_int("PSEG_CONV_PW_RESIDENT", 0); // ... grid size override (tests: several tiles per block on small problems)
@@ -723,8 +713,7 @@ static double patch_makespan(const DilGeom& g, int B, int PH, int PW, int grid_n
 // relative cost per executed MAC of a tile shape in the tap-skipping launches (operand bytes staged per MAC; measured on the
 // ASPP shapes)
 static double band_shape_cost(TileCfg t) {
-  static const int c32 = env_int("PSEG_CONV_BAND32_COST", 104);
-  if (t.bn == 32) return c32 / 100.0;
+  if (t.bn == 32) return 1.04;
   return (t.bm == 64 || t.bn == 64) ? 1.0 : (t.bm == 256 ? 0.90 : 0.92);
 }
 
@@ -749,7 +738,7 @@ static FwdPlan plan_gather(long long M, int N, int K, bool allow_big = false, co
   if (!big && pl.tile.bm == 128 && pl.tile.bn == 128 && (long long)cdiv(M, 128) * cdiv(N, 128) < 512) pl.tile.bn = 64;
   // still under two blocks per CU (HRNet's 64-channel branch: 256 tiles of 128x64, one 4-wave block per CU, 22 % of the
   // matrix pipe): 32-column tiles -- the gathered rows are fetched once more per column tile, from L2
-  if (!big && cfg().conv_narrow != 0 && pl.tile.bm == 128 && pl.tile.bn == 64 && N >= 64 && N % 32 == 0 &&
+  if (!big && pl.tile.bm == 128 && pl.tile.bn == 64 && N >= 64 && N % 32 == 0 &&
       (long long)cdiv(M, 128) * cdiv(N, 64) < 512 && (long long)cdiv(M, 128) * cdiv(N, 64) >= 128)
     pl.tile.bn = 32;
   const int force_bm = cfg().conv_bm, force_bn = cfg().conv_bn;
@@ -769,8 +758,7 @@ static FwdPlan plan_gather(long long M, int N, int K, bool allow_big = false, co
     // 9, 6 and 4 live taps, two of the 512 128x64 tiles per CU, worst pair 9 + 4 against a mean of 10.1 (0.72 of the dense time
     // for 0.56 live) -- and twice as many tiles of half the cost deal out more evenly (0.64).  The gathered rows are then
     // fetched once per 32 output columns (from L2): shape_cost below.
-    static const int band32 = env_int("PSEG_CONV_BAND32", 1);
-    if (ncand == 2 && band32 != 0 && N % 32 == 0 && cfg().conv_dma32 != 0) ncand = 3;
+    if (ncand == 2 && N % 32 == 0) ncand = 3;
     for (int c = 0; c < ncand; ++c) {
       const int bm = cands[c].bm;
       // relative cost per executed MAC of the tile shape (operand bytes staged per MAC; measured on the ASPP shapes)
@@ -780,8 +768,8 @@ static FwdPlan plan_gather(long long M, int N, int K, bool allow_big = false, co
         if (bm % pw != 0 || geom->Wo % pw != 0) continue;
         const int ph = bm / pw;
         if (ph > geom->Ho || geom->Ho % ph != 0) continue;
-        double score = patch_makespan(*geom, (int)(M / ((long long)geom->Ho * geom->Wo)), ph, pw, cdiv(N, cands[c].bn),
-                                      cfg().conv_noxcd == 0 ? 1 : 0) * shape_cost;
+        double score = patch_makespan(*geom, (int)(M / ((long long)geom->Ho * geom->Wo)), ph, pw, cdiv(N, cands[c].bn), 1) *
+                       shape_cost;
         if (pw == geom->Wo) score -= 1e-6;   // ties: keep the row-major order
         if (cfg().plan_debug != 0)
           fprintf(stderr, "[pseg plan]   %dx%d patch %dx%d: %.3f\n", cands[c].bm, cands[c].bn, ph, pw, score);
@@ -873,7 +861,7 @@ struct RowOrder {
 // can_skip / can_parity: what the number format adds to the conditions for skipping the padding taps of a dilated conv / for
 // the parity order of a stride-2 data gradient (whole K-steps per tap; fp32: no split-K; fp16: not on the 128x128 tile).
 static RowOrder gather_row_order(const GatherGeom& g, const FwdPlan& pl, bool can_skip, bool can_parity) {
-  RowOrder o{0, 0, 1, 1, 1, cfg().conv_noxcd == 0 ? 1 : 0};
+  RowOrder o{0, 0, 1, 1, 1, 1};
   const int taps = g.taps_h * g.taps_w;
   const int adil = g.dstep < 0 ? -g.dstep : g.dstep;
   const bool skipping = taps <= 32 && cfg().conv_noskip == 0;
@@ -919,7 +907,7 @@ static void set_gather_geometry(GatherConvParams& p, const GatherGeom& g, const 
   p.ntaps = g.taps_h * g.taps_w;
   p.skip_taps = o.skip_taps;
   p.xcd_remap = o.xcd_remap;
-  p.prio = g.dstep < 0 ? cfg().dgrad_prio : 0;
+  p.prio = g.dstep < 0 ? 1 : 0;      // the data gradients run at wave priority 1
   p.row_perm = o.row_perm;
   p.patch_w = o.patch_w;
   p.patch_hw = o.patch_hw;
@@ -950,13 +938,10 @@ static WgradPlan plan_wgrad(long long P, int Cout, int K, bool allow_big = false
   // limb kernels are bound by the split + LDS-write work per staged element: a 256(Cout) x 128 tile (8 waves, one
   // block per CU) does 25 % less of it per MAC.
   // Measured slower than two 128x128 blocks per CU (aspp d6 0.57 -> 0.67 ms): the gather side of the loader sits in
-  // two of the eight waves and becomes the critical path.  Kept selectable (PSEG_WGRAD_BIG=1, and the forced parity
-  // test) until the loader roles are spread over all waves.
+  // two of the eight waves and becomes the critical path.  Only PSEG_CONV_FORCEBIG takes it (the forced parity test).
   // (round 4, measured no: putting the 32-output-channel weight gradients of HRNet's fine branch on the LDS-DMA kernel through a
   // 64-row tile whose upper half is out of range -- instead of the register-staged wgrad_kernel<32,128> -- made the replayed
-  // HRNet fp32 step slower, 16.53 -> 17.02 ms; PSEG_WGRAD_NARROW64=1 re-enables it)
-  static const int narrow64 = env_int("PSEG_WGRAD_NARROW64", 0);
-  if (!limb && narrow64 != 0 && pl.tile.bm == 32 && pl.tile.bn == 128 && Cout > 16) pl.tile.bm = 64;
+  // HRNet fp32 step slower, 16.53 -> 17.02 ms)
   // Exact-fp32, at most 32 output channels (round 5): a 32 x 256 tile.  The 32 x 128 tile of wgrad_kernel gave every wave ONE
   // accumulator fed by register-staged loads (41 TF on HRNet's 32-channel branch, 68 on the 21-class classifier): eight waves
   // on 256 columns with the operands by LDS-DMA (wgrad_f32_dma_kernel<32, 256>), or four waves with two accumulators each where
@@ -968,14 +953,8 @@ static WgradPlan plan_wgrad(long long P, int Cout, int K, bool allow_big = false
     pl.tile.bn = 256;
   // ... and K == 288 -- 3x3 on 32 channels, every conv of HRNet's fine branch -- as ONE 32 x 288 tile on nine waves
   // (wgrad_f32_dma_kernel<32, 288, 1, 9>): dy is fetched once per K-step, not once per 128 columns, and no column is padding
-  static const int narrow288 = env_int("PSEG_WGRAD_NARROW288", 1);
-  if (!limb && narrow288 != 0 && cfg().wgrad_f32dma != 0 && pl.tile.bm == 32 && K == 288) pl.tile.bn = 288;
-  const bool big = allow_big && cfg().conv_nobig == 0 &&
-                   ((cfg().wgrad_big != 0 && Cout >= 256 && Cout % 256 == 0 && K >= 128) ||
-                    cfg().conv_forcebig != 0);
-  if (big) pl.tile = TileCfg{256, 128};
-  const int force_bm = cfg().wgrad_bm, force_bn = cfg().wgrad_bn;
-  if (force_bm && force_bn) pl.tile = TileCfg{force_bm, force_bn};
+  if (!limb && cfg().wgrad_f32dma != 0 && pl.tile.bm == 32 && K == 288) pl.tile.bn = 288;
+  if (allow_big && cfg().conv_nobig == 0 && cfg().conv_forcebig != 0) pl.tile = TileCfg{256, 128};
   pl.gridM = cdiv(Cout, pl.tile.bm);
   pl.gridN = cdiv(K, pl.tile.bn);
   const long long ptiles = cdiv(P, BK);
@@ -1004,9 +983,8 @@ static WgradPlan plan_wgrad(long long P, int Cout, int K, bool allow_big = false
   }
   // 32-row tiles of the exact-fp32 kernel (HRNet's 32-channel branch): every wave owns ONE 32x32 accumulator, its MFMAs form
   // one dependent chain and the wave cannot issue its gather / staging VALU work under them -- a second resident block per
-  // CU does (stand-alone 68 -> 59 us at 8x128x128x32 -> 32 3x3).  PSEG_WGRAD_BPC_NARROW=1 goes back to one.
-  static const int narrow_bpc = env_int("PSEG_WGRAD_BPC_NARROW", 2);
-  if (!limb && pl.tile.bm == 32 && narrow_bpc > 0) bpc = narrow_bpc;
+  // CU does (stand-alone 68 -> 59 us at 8x128x128x32 -> 32 3x3).
+  if (!limb && pl.tile.bm == 32) bpc = 2;
   if (want_bpc > 0) bpc = want_bpc;
   if (cfg().wgrad_bpc > 0) bpc = cfg().wgrad_bpc;
   int splits = pick_splits((long long)pl.gridM * pl.gridN, ptiles, 8, 1024, bpc,

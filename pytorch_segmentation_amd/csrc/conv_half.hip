@@ -74,36 +74,14 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-// keeps a value live without code (ablation builds: the compiler must not delete the work that produced it)
-__device__ __forceinline__ void keep_alive(const f32x16& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" ::"v"(v));
-#else
-  (void)v;
-#endif
-}
-
-// Lab build (-DPSEG_LAB=1: `python -m pytorch_segmentation_amd.csrc.build --lab` -> libpseg_amd_lab.so, PSEG_LIB_PATH selects it):
-// variants that were measured and NOT picked stay reachable there and nowhere else -- PSEG_HCONV_TILE = 1..4 (128x128 on four
-// waves, 256x128 on eight / sixteen, 256x256), PSEG_HCONV_ABLATE (stores / statistics / DMAs / fragment reads / MFMAs switched
-// off: results are then wrong).  The product library holds neither the instantiations nor the branches.
-#ifndef PSEG_LAB
-#define PSEG_LAB 0
-#endif
-#if PSEG_LAB
-#define PSEG_ABLATE(hp_) ((hp_).ablate)
-#else
-#define PSEG_ABLATE(hp_) 0
-#endif
-
 struct HGatherParams {
   GatherConvParams g;    // x / w / y are fp16 here (y fp32 when y_f32); element strides as in the fp32 kernels
   int y_f32;
   FastDiv cin_div, kw_div;   // GENERIC: k -> (tap, channel), tap -> (row, column)
   FastDiv howo_div, wo_div;  // gather_hp_kernel: GEMM row -> (image, row, column)
   int ntiles;                // gather_hp_kernel: tiles of the launch (a persistent block walks blockIdx, blockIdx + grid, ...)
-  int ablate;                // diagnostics (PSEG_HCONV_ABLATE, profiles/scripts/exp_ablate.sh; results are then WRONG): 1 no stores, 2 no
-                             // statistics, 4 no operand DMAs after the prologue, 8 no MFMAs, 16 no fragment reads
+  int tail_pad;              // unused: keeps the launch's implicit arguments (block counts), which follow this block, off ntiles'
+                             // neighbouring dword -- next to it hipcc fuses the two loads and re-allocates the persistent kernels
 };
 
 // One 32-row tile row of a wave's accumulators -> global memory through a wave-private [32][WTN + 4] fp32 patch, 8 columns
@@ -549,13 +527,12 @@ __global__ __launch_bounds__(64 * WARPS_M * WARPS_N) void gather_h_kernel(const 
       constexpr int ST = decltype(stc)::value;
       if (chunks_left == 0) open_tap();
       unsigned* sb = ldsw + ST * kStageDw;
-      const uint32_t kill = (PSEG_ABLATE(hp) & 4) ? kOOB : 0u;      // (an out-of-range DMA moves no byte but is issued and counted)
 #pragma unroll
       for (int g = 0; g < GA; ++g)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_ptr)(sb + kA + RPG * (wave + NW * g) * RDW), 16, (int)(a_cur[g] | kill), 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_ptr)(sb + kA + RPG * (wave + NW * g) * RDW), 16, (int)a_cur[g], 0, 0, 0);
 #pragma unroll
       for (int g = 0; g < GB; ++g)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_ptr)(sb + kB + RPG * b_grp[g] * RDW), 16, (int)(b_cur[g] | kill), 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_ptr)(sb + kB + RPG * b_grp[g] * RDW), 16, (int)b_cur[g], 0, 0, 0);
 #pragma unroll
       for (int g = 0; g < GA; ++g) a_cur[g] += (uint32_t)(KB * 2);
 #pragma unroll
@@ -595,17 +572,17 @@ __global__ __launch_bounds__(64 * WARPS_M * WARPS_N) void gather_h_kernel(const 
   {                                                                                                              \
     typedef std::integral_constant<int, (S)> cs;                                                                 \
     typedef std::integral_constant<int, ((S) + 1) % STAGES> cs1;                                                 \
-    if (!(PSEG_ABLATE(hp) & 16)) read_c(cs{}, c1{}, c1{});                                                             \
+    read_c(cs{}, c1{}, c1{});                                                                                    \
     __builtin_amdgcn_sched_barrier(0);                                                                           \
-    if (!(PSEG_ABLATE(hp) & 8)) mfmas(0);                                                                              \
+    mfmas(0);                                                                                                    \
     __builtin_amdgcn_sched_barrier(0);                                                                           \
     wait_vmcnt<(STAGES - 2) * NG>();                   /* the next tile has landed; STAGES - 2 more in flight */  \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* this wave is done reading stage S */                   \
     __builtin_amdgcn_s_barrier();                                                                                \
-    if (!(PSEG_ABLATE(hp) & 16)) read_c(cs1{}, c0{}, c0{});  /* (zeros on the last step: never multiplied) */          \
+    read_c(cs1{}, c0{}, c0{});                         /* (zeros on the last step: never multiplied) */          \
     __builtin_amdgcn_sched_barrier(0);                                                                           \
     issue_c(cs{});                                     /* stage S is free now */                                 \
-    if (!(PSEG_ABLATE(hp) & 8)) mfmas(1);                                                                              \
+    mfmas(1);                                                                                                    \
     __builtin_amdgcn_sched_barrier(0);                                                                           \
   }
     for (int it = 0;;) {
@@ -631,67 +608,60 @@ __global__ __launch_bounds__(64 * WARPS_M * WARPS_N) void gather_h_kernel(const 
   // ---- epilogue: bias / accumulate / row map, fused BatchNorm statistics
   const int col_l = lane & 31;
   const int row_h = (lane >> 5) * 4;
-  if (PSEG_ABLATE(hp) & 1) {
+  float* patch = lds + wave * (32 * (WTN + 4));
+  const int col0 = n0 + wn * WTN;
+  int cv = p.N - col0;
+  cv = cv < 0 ? 0 : (cv > WTN ? WTN : cv);
+  auto rowmap = [&](int m) {
+    if (!p.row_perm) return m;
+    int b, ho, wo;
+    row_to_pixel(p, m, b, ho, wo);
+    return (b * p.Ho + ho) * p.Wo + wo;
+  };
+  if constexpr (BNS) {
+    // (the host only launches this instantiation for an fp16 result without bias / accumulation)
+    constexpr int C8 = WTN / 8;
+    const int c8 = lane % C8, rr = lane / C8;
+    const bool cok = c8 * 8 < cv;
+    HBnsCoef bc;
+    HBnsSums bs;
+    bns_load_coef(p, col0 + c8 * 8, cok, bc);
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+    for (int h = 0; h < 2; ++h) bs.s1[h] = bs.s2[h] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int j = 0; j < TN; ++j) keep_alive(acc[i][j]);
-  } else {
-    float* patch = lds + wave * (32 * (WTN + 4));
-    const int col0 = n0 + wn * WTN;
-    int cv = p.N - col0;
-    cv = cv < 0 ? 0 : (cv > WTN ? WTN : cv);
-    auto rowmap = [&](int m) {
-      if (!p.row_perm) return m;
-      int b, ho, wo;
-      row_to_pixel(p, m, b, ho, wo);
-      return (b * p.Ho + ho) * p.Wo + wo;
-    };
-    if constexpr (BNS) {
-      // (the host only launches this instantiation for an fp16 result without bias / accumulation)
-      constexpr int C8 = WTN / 8;
-      const int c8 = lane % C8, rr = lane / C8;
-      const bool cok = c8 * 8 < cv;
-      HBnsCoef bc;
-      HBnsSums bs;
-      bns_load_coef(p, col0 + c8 * 8, cok, bc);
+    for (int i = 0; i < TM; ++i) {
+      const int row0 = m0 + wm * WTM + i * 32;
+      int rv = p.M - row0;
+      rv = rv < 0 ? 0 : (rv > 32 ? 32 : rv);
+      store_row32<TN, true>(acc[i], patch, p.y, false, p.ldy, row0, col0, rv, cv, nullptr, false, lane, rowmap, p, bc, bs);
+    }
 #pragma unroll
-      for (int h = 0; h < 2; ++h) bs.s1[h] = bs.s2[h] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int o = C8; o < 64; o <<= 1)
 #pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int row0 = m0 + wm * WTM + i * 32;
-        int rv = p.M - row0;
-        rv = rv < 0 ? 0 : (rv > 32 ? 32 : rv);
-        store_row32<TN, true>(acc[i], patch, p.y, false, p.ldy, row0, col0, rv, cv, nullptr, false, lane, rowmap, p, bc, bs);
-      }
+      for (int h = 0; h < 2; ++h)
 #pragma unroll
-      for (int o = C8; o < 64; o <<= 1)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            bs.s1[h][e] += __shfl_xor(bs.s1[h][e], o, 64);
-            bs.s2[h][e] += __shfl_xor(bs.s2[h][e], o, 64);
-          }
-      if (rr == 0 && cok) {
-        const long long o = (long long)(tile_m * WARPS_M + wm) * p.N + col0 + c8 * 8;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          *reinterpret_cast<f32x4*>(p.bns_db + o + 4 * h) = bs.s1[h];
-          *reinterpret_cast<f32x4*>(p.bns_dg + o + 4 * h) = bs.s2[h];
+        for (int e = 0; e < 4; ++e) {
+          bs.s1[h][e] += __shfl_xor(bs.s1[h][e], o, 64);
+          bs.s2[h][e] += __shfl_xor(bs.s2[h][e], o, 64);
         }
-      }
-    } else {
+    if (rr == 0 && cok) {
+      const long long o = (long long)(tile_m * WARPS_M + wm) * p.N + col0 + c8 * 8;
 #pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int row0 = m0 + wm * WTM + i * 32;
-        int rv = p.M - row0;
-        rv = rv < 0 ? 0 : (rv > 32 ? 32 : rv);
-        store_row32<TN>(acc[i], patch, p.y, hp.y_f32 != 0, p.ldy, row0, col0, rv, cv, p.bias, p.accumulate != 0, lane, rowmap);
+      for (int h = 0; h < 2; ++h) {
+        *reinterpret_cast<f32x4*>(p.bns_db + o + 4 * h) = bs.s1[h];
+        *reinterpret_cast<f32x4*>(p.bns_dg + o + 4 * h) = bs.s2[h];
       }
     }
+  } else {
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const int row0 = m0 + wm * WTM + i * 32;
+      int rv = p.M - row0;
+      rv = rv < 0 ? 0 : (rv > 32 ? 32 : rv);
+      store_row32<TN>(acc[i], patch, p.y, hp.y_f32 != 0, p.ldy, row0, col0, rv, cv, p.bias, p.accumulate != 0, lane, rowmap);
+    }
   }
-  if (p.stat != nullptr && !(PSEG_ABLATE(hp) & 2)) {
+  if (p.stat != nullptr) {
     // BatchNorm statistics of the tensor AS STORED: an fp16 result is rounded before it is summed, so that the layer
     // normalises exactly the values its backward pass and the next layer read (what a BatchNorm fed by an fp16 conv sees)
     const bool f32out = hp.y_f32 != 0;
@@ -1117,516 +1087,6 @@ __global__ __launch_bounds__(64 * WARPS_M * WARPS_N) void gather_hp_kernel(const
 #undef PSEG_GHP_STEP
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // no DMA may land after the block has given its LDS back
 }
-
-#if PSEG_LAB
-// ------------------------------------------------------------------------------------------------
-// HALO-STAGED 3x3 (round 5; VERDICT r4 item 3 i) -- LAB BUILD ONLY: measured slower than gather_h_kernel (layer-4 3x3 d = 2 forward
-// 101-108 us against 83, layer 3 30 against 27; profiles/EXPERIMENTS.md 5.2 has the numbers and the reason: the halo buffers take the
-// LDS of the second resident block, and eight waves per CU do not cover their own barrier / LDS latency).  gather_h_kernel fetches the A operand of a 3x3 conv once per TAP: nine
-// [128 pixels][64 channels] tiles per channel chunk, eight of them the same pixels shifted by one or two positions -- and
-// the operand stream into LDS (the L2 -> LDS DMA path, ~27 B/clk/CU) is exactly what bounds these kernels (round 4: MFMA busy
-// 0.41-0.43 on layer 4; a 128x128 tile moves 32 KB per 512 matrix cycles).  Here an M tile is an 8 x 16 PATCH of output pixels
-// and the A operand of a channel chunk is DMA'd ONCE, as the (8 + 2d) x (16 + 2d) halo patch of input pixels (d = dilation 1 or 2:
-// 180 / 240 pixels x 128 B); the nine taps read their fragments from that image at shifted pixel positions.  Per chunk and tile:
-// 23 / 31 KB of A instead of 144 KB, 9 x 16 KB of B as before -- 19.5 KB per K-step instead of 32.
-//   LDS: two halo buffers (chunk c is multiplied while chunk c + 1 lands) + a three-stage ring of B tiles = 108 KB, one 8-wave
-//   block per CU; K runs CHUNK-major (chunk, then tap) -- another summation order than gather_h_kernel, same products.
-//   The halo image keeps the ring's layout per pixel (128-byte rows, 16-byte k-slot XOR (pixel >> 1) & 7 -- applied on the source
-//   side of the DMA, keyed on the HALO pixel index), so a fragment read is the same ds_read_b128, at a per-tap row.
-// Covers: 3x3, unit stride, dilation 1 or 2, channels % 64 == 0, maps that tile into 8 x 16 patches, fp16 result without bias /
-// accumulation, forward (+ fused BatchNorm statistics) and data gradient (the same gather with the taps reversed).
-constexpr int kHaloPH = 8, kHaloPW = 16, kHaloMaxPix = 256;      // (8 + 2d) x (16 + 2d) <= 240 pixels, buffers of 32 whole DMA pieces
-
-template <int STAGES>
-__global__ __launch_bounds__(512) void gather_hh_kernel(const HGatherParams hp) {
-  const GatherConvParams& p = hp.g;
-  set_wave_prio(p.prio);
-  constexpr int BM = 128, BN = 128, WARPS_M = 2, WARPS_N = 4, NW = 8, KB = 64;
-  static_assert(STAGES >= 3 && STAGES <= 6, "B ring depth");
-  constexpr int WTM = BM / WARPS_M, WTN = BN / WARPS_N, TM = WTM / 32, TN = WTN / 32;     // 64 x 32 per wave: TM = 2, TN = 1
-  constexpr int RDW = 32;                                  // dwords per pixel / filter row of a chunk
-  constexpr int kHaloDw = kHaloMaxPix * RDW;               // one halo buffer
-  constexpr int kBStageDw = BN * RDW;
-  constexpr int kBBase = 2 * kHaloDw;
-  constexpr int kLds = 2 * kHaloDw + STAGES * kBStageDw;   // 112 KB with three B stages, 160 KB with six (the epilogue patches reuse it)
-  static_assert(kLds * 4 <= 160 * 1024, "LDS");
-  static_assert(NW * 32 * (WTN + 4) <= kLds, "epilogue patch");
-  __shared__ __attribute__((aligned(16))) float lds[kLds];
-  unsigned* ldsw = reinterpret_cast<unsigned*>(lds);
-  constexpr int GB = BN / 8 / NW;                          // B DMAs per wave and K-step (2)
-  constexpr int GAH = kHaloMaxPix / 8 / NW;                // halo DMAs per wave and chunk: always 4 (pieces past the halo fetch
-                                                           // nothing and land in the buffer's unused tail) -- a fixed count for vmcnt
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WARPS_N, wn = wave % WARPS_N;
-  const int gridN = (p.N + BN - 1) / BN;
-  int bid = blockIdx.x;
-  bid = remap_tile(p.xcd_remap, bid, (int)gridDim.x);
-  const int tile_n = bid % gridN;
-  const int tile_m = bid / gridN;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-  // the tile's patch: image b, top-left output pixel (y0, x0)   (row_perm == 2 order: patches_per_row, patch_hw set by the host)
-  const int ppi = p.HoWo / BM;                             // patches per image
-  const int b_img = tile_m / ppi, pidx = tile_m - b_img * ppi;
-  const int y0 = (pidx / p.patches_per_row) * kHaloPH, x0 = (pidx % p.patches_per_row) * kHaloPW;
-  const int d = p.dstep < 0 ? -p.dstep : p.dstep;
-  const int HW = kHaloPW + 2 * d, HPIX = (kHaloPH + 2 * d) * HW;
-
-  const __amdgpu_buffer_rsrc_t xr = make_rsrc(p.x, p.x_bytes);
-  const __amdgpu_buffer_rsrc_t wr = make_rsrc(p.w, p.w_bytes);
-  const int lrow = lane >> 3, lslot = lane & 7;
-
-  // ---- halo DMA pieces of this lane: halo pixel 8 * piece + lrow, physical slot lslot <- logical slot lslot ^ f(pixel)
-  uint32_t h_off[GAH];
-#pragma unroll
-  for (int g = 0; g < GAH; ++g) {
-    const int piece = wave + NW * g;
-    const int hpix = 8 * piece + lrow;
-    const int iy = y0 - d + hpix / HW, ix = x0 - d + hpix % HW;
-    const bool ok = hpix < HPIX && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-    // swizzle keyed on the halo COLUMN (not the linear pixel index): a fragment read's 16-lane service group holds columns
-    // x .. x + 3, x + 12 .. x + 15 of one patch row and x + 4 .. x + 11 of the next -- sixteen different columns mod 16 at every
-    // tap, so the group covers all 64 banks once (keyed on the linear index, rows 18 / 20 pixels apart collided 2- / 4-way)
-    h_off[g] = ok ? (uint32_t)(((b_img * p.Hi + iy) * p.Wi + ix) * p.ldx) * 2u + (uint32_t)((lslot ^ (((hpix % HW) >> 1) & 7)) * 16) : kOOB;
-  }
-  // ---- B rows of this lane
-  uint32_t b_row[GB];
-#pragma unroll
-  for (int g = 0; g < GB; ++g) {
-    const int row = 8 * (wave + NW * g) + lrow;
-    b_row[g] = (n0 + row) < p.N ? (uint32_t)(n0 + row) * (uint32_t)p.K * 2u + (uint32_t)((lslot ^ ((row >> 1) & 7)) * 16) : kOOB;
-  }
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  const int nchunks = p.Cin / KB;
-  const int n_steps = nchunks * 9;
-  const uint32_t tap_bytes = (uint32_t)p.Cin * 2u;
-
-  int h_chunk = 0;                       // next chunk whose halo is to be issued
-  auto issue_halo = [&]() {
-    if (h_chunk >= nchunks) return;
-    unsigned* hb = ldsw + (h_chunk & 1) * kHaloDw;
-#pragma unroll
-    for (int g = 0; g < GAH; ++g) {
-      const int piece = wave + NW * g;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_ptr)(hb + piece * 8 * RDW), 16, (int)h_off[g], 0, 0, 0);
-      h_off[g] += (uint32_t)(KB * 2);    // (kOOB + anything a launch adds stays out of range)
-    }
-    ++h_chunk;
-  };
-  int h_age = 3;                         // K-steps since the last halo issue inside the loop (>= 3: its DMAs no longer count)
-  int i_tap = 0, i_chunk = 0;            // the K-step the next B DMA belongs to
-  uint32_t b_cur[GB];
-#pragma unroll
-  for (int g = 0; g < GB; ++g) b_cur[g] = b_row[g];
-  auto issue_b = [&](auto stc) {
-    constexpr int ST = decltype(stc)::value;
-    unsigned* sb = ldsw + kBBase + ST * kBStageDw;
-    const bool live = i_chunk < nchunks;
-#pragma unroll
-    for (int g = 0; g < GB; ++g)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_ptr)(sb + 8 * (wave + NW * g) * RDW), 16, (int)(live ? b_cur[g] : kOOB), 0, 0, 0);
-    if (!live) return;
-    if (++i_tap == 9) {                  // next chunk: back to tap 0, 64 channels on
-      i_tap = 0;
-      ++i_chunk;
-#pragma unroll
-      for (int g = 0; g < GB; ++g) b_cur[g] = b_cur[g] - 8u * tap_bytes + (uint32_t)(KB * 2);
-    } else {
-#pragma unroll
-      for (int g = 0; g < GB; ++g) b_cur[g] += tap_bytes;
-    }
-  };
-
-  // ---- compute side
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  const int frag_row = lane & 31, frag_h = lane >> 5;
-  // halo pixel of this lane's fragment row of tile row i at the CENTRE tap
-  int hp0[TM], hx0[TM];
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int R = wm * WTM + i * 32 + frag_row;
-    hx0[i] = (R & 15) + d;
-    hp0[i] = ((R >> 4) + d) * HW + hx0[i];
-  }
-  int fb_off[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int row = wn * WTN + frag_row;
-    fb_off[q] = row * RDW + (((2 * q + frag_h) ^ ((row >> 1) & 7)) << 2);
-  }
-  f32x4 fa[2][2 * TM], fb[2][2 * TN];
-  int c_tap = 0, c_chunk = 0;            // the K-step being multiplied
-  int fa_base[TM], fa_x[TM];             // halo pixel row (dwords) and its swizzle term, of the current tap
-  auto open_tap = [&](int tap) {
-    const int kr = tap / 3, ks = tap - 3 * kr;
-    const int ox = p.off0 + ks * p.dstep;
-    const int sh = (p.off0 + kr * p.dstep) * HW + ox;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      fa_base[i] = (hp0[i] + sh) * RDW;
-      fa_x[i] = ((hx0[i] + ox) >> 1) & 7;
-    }
-  };
-  auto read_a = [&](int set, int half, const float* hb) {
-#pragma unroll
-    for (int gg = 0; gg < 2; ++gg) {
-      const int slot = 2 * (half * 2 + gg) + frag_h;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) fa[set][gg * TM + i] = *reinterpret_cast<const f32x4*>(&hb[fa_base[i] + ((slot ^ fa_x[i]) << 2)]);
-    }
-  };
-  auto read_b = [&](auto stc, int set, int half) {
-    constexpr int ST = decltype(stc)::value;
-    const float* sb = lds + kBBase + ST * kBStageDw;
-#pragma unroll
-    for (int gg = 0; gg < 2; ++gg)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) fb[set][gg * TN + j] = *reinterpret_cast<const f32x4*>(&sb[fb_off[half * 2 + gg] + j * 32 * RDW]);
-  };
-  auto mfmas = [&](int set) {
-#pragma unroll
-    for (int gg = 0; gg < 2; ++gg)
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8v, fa[set][gg * TM + i]),
-                                                             __builtin_bit_cast(f16x8v, fb[set][gg * TN + j]), acc[i][j], 0, 0, 0);
-  };
-
-  typedef std::integral_constant<int, 0> c0;
-  typedef std::integral_constant<int, 1> c1;
-  typedef std::integral_constant<int, 2> c2;
-  issue_halo();                          // chunk 0 (older than every B DMA below: a counted wait for a B tile covers it)
-  issue_b(c0{});
-  issue_halo();                          // chunk 1 lands while chunk 0 is multiplied
-  issue_b(c1{});
-  issue_b(c2{});
-  if constexpr (STAGES >= 4) issue_b(std::integral_constant<int, 3>{});
-  if constexpr (STAGES >= 5) issue_b(std::integral_constant<int, 4>{});
-  if constexpr (STAGES >= 6) issue_b(std::integral_constant<int, 5>{});
-  wait_vmcnt<(STAGES - 1) * GB>();       // halos + B tile 0 have landed (this wave's share)
-  // In the loop a halo is issued BEHIND the B tile of its slot: [B(s + 3)] [halo x 4].  vmcnt counts in issue order, so the two
-  // following waits -- for B(s + 2) and B(s + 3), both older than the halo -- may leave the halo's four DMAs in flight on top of
-  // the youngest B tile; the third wait (for B(s + 4), younger) retires it: three K-steps to land instead of one.
-  __builtin_amdgcn_s_barrier();
-  open_tap(0);
-  read_a(0, 0, lds);
-  read_b(c0{}, 0, 0);
-#define PSEG_HH_STEP(S)                                                                                                        \
-  {                                                                                                                            \
-    typedef std::integral_constant<int, (S)> cs;                                                                               \
-    typedef std::integral_constant<int, ((S) + 1) % STAGES> cs1;                                                               \
-    const float* hb_cur = lds + (c_chunk & 1) * kHaloDw;                                                                       \
-    read_a(1, 1, hb_cur);                                                                                                      \
-    read_b(cs{}, 1, 1);                                                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                                         \
-    mfmas(0);                                                                                                                  \
-    __builtin_amdgcn_sched_barrier(0);                                                                                         \
-    if (h_age < 2) wait_vmcnt<(STAGES - 2) * GB + GAH>(); /* ... a halo issued one / two slots ago may stay in flight */       \
-    else wait_vmcnt<(STAGES - 2) * GB>();              /* the next B tile (and any older halo) has landed */                   \
-    ++h_age;                                                                                                                   \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* this wave is done reading B stage S and this K-step's A rows */      \
-    __builtin_amdgcn_s_barrier();                                                                                              \
-    const bool new_chunk = c_tap == 8;                                                                                         \
-    if (new_chunk) {                                                                                                           \
-      c_tap = 0;                                                                                                               \
-      ++c_chunk;                                                                                                               \
-    } else {                                                                                                                   \
-      ++c_tap;                                                                                                                 \
-    }                                                                                                                          \
-    open_tap(c_tap);                                                                                                           \
-    read_a(0, 0, lds + (c_chunk & 1) * kHaloDw);       /* (stale bytes after the last step: never multiplied) */               \
-    read_b(cs1{}, 0, 0);                                                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                                                         \
-    issue_b(cs{});                                     /* B stage S is free now */                                             \
-    if (new_chunk && h_chunk < nchunks) {              /* the buffer of the chunk just finished is free: chunk + 2 -> it */    \
-      issue_halo();                                                                                                            \
-      h_age = 0;                                                                                                               \
-    }                                                                                                                          \
-    mfmas(1);                                                                                                                  \
-    __builtin_amdgcn_sched_barrier(0);                                                                                         \
-  }
-  for (int it = 0;;) {
-    PSEG_HH_STEP(0)
-    if (++it == n_steps) break;
-    PSEG_HH_STEP(1)
-    if (++it == n_steps) break;
-    PSEG_HH_STEP(2)
-    if (++it == n_steps) break;
-    if constexpr (STAGES >= 4) {
-      PSEG_HH_STEP(3)
-      if (++it == n_steps) break;
-    }
-    if constexpr (STAGES >= 5) {
-      PSEG_HH_STEP(4)
-      if (++it == n_steps) break;
-    }
-    if constexpr (STAGES >= 6) {
-      PSEG_HH_STEP(5)
-      if (++it == n_steps) break;
-    }
-  }
-#undef PSEG_HH_STEP
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // dummy DMAs must not land in the output patches
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-
-  // ---- epilogue: as gather_h_kernel (fp16 result, patch-ordered rows, fused BatchNorm statistics of the values as stored)
-  const int col_l = lane & 31;
-  {
-    float* patch = lds + wave * (32 * (WTN + 4));
-    const int col0 = n0 + wn * WTN;
-    int cv = p.N - col0;
-    cv = cv < 0 ? 0 : (cv > WTN ? WTN : cv);
-    auto rowmap = [&](int m) {
-      int b, ho, wo;
-      row_to_pixel(p, m, b, ho, wo);
-      return (b * p.Ho + ho) * p.Wo + wo;
-    };
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int row0 = m0 + wm * WTM + i * 32;
-      store_row32<TN>(acc[i], patch, p.y, false, p.ldy, row0, col0, 32, cv, nullptr, false, lane, rowmap);
-    }
-  }
-  if (p.stat != nullptr) {
-    auto rnd = [&](float v) -> float { return (float)(half_t)v; };
-    const int group = tile_m * WARPS_M + wm;
-    const long long gsz = (long long)p.stat_rows * p.N;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int col = n0 + wn * WTN + j * 32 + col_l;
-      const float k0 = __shfl(rnd(acc[0][j][0]), lane & 31, 64);
-      float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float dd = rnd(acc[i][j][r]) - k0;
-          s1 += dd;
-          s2 += dd * dd;
-        }
-      s1 += __shfl_xor(s1, 32, 64);
-      s2 += __shfl_xor(s2, 32, 64);
-      if (lane < 32 && col < p.N) {
-        const long long o = (long long)group * p.N + col;
-        p.stat[o] = k0;
-        p.stat[gsz + o] = s1;
-        p.stat[2 * gsz + o] = s2;
-      }
-    }
-  }
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// HALO-STAGED 3x3 with the filter as a RING OF TAPS, fp16 (round 5 -- the form of gather_f32_halo_kernel that paid in fp32, after the
-// lab kernel above lost: what it lost on was residency -- two halo buffers + a ring of whole-chunk tap tiles, 112-160 KB, ONE block
-// per CU).  An M tile is an 8 x 16 patch of output pixels; a 64-channel chunk of the A operand is DMA'd once, as the
-// (8 + 2d) x (16 + 2d) halo patch (23 / 30 KB for dilation 1 / 2), SINGLE-buffered; the nine taps read their fragments from it; the
-// chunk's filter slice goes through a three-stage ring of single taps ([BN columns][64 channels]: 16 / 8 KB).  78 KB (128 columns,
-// eight waves: two blocks per CU -- what gather_h_kernel has) / 54 KB (64 columns, four waves: two to three).  Operand bytes per
-// chunk and 128x128 tile: 30 + 144 KB instead of 288.  One barrier per tap, as gather_h_kernel has one per K-step.
-// Layouts (halo rows keyed on the halo column, filter rows as the ring kernels') and fragment reads as gather_f32_halo_kernel --
-// a 16-byte k-slot holds eight halves, v_mfma_f32_32x32x16_f16 takes one per operand.
-// Covers: 3x3, unit stride, dilation 1 or 2 with matching padding (forward / data gradient), channels % 64 == 0, maps of whole 8 x 16
-// patches, the 128x128 / 128x64 plan tiles with every tap live; bias / accumulate / fp32 or fp16 result / fused statistics as
-// gather_h_kernel.  LAB BUILD ONLY (PSEG_HCONV_HALO2=1 there): measured SLOWER than gather_h_kernel -- layer-4 3x3 d = 2 91 / 90 us against
-// 85 / 83, layer 3 35 / 32 against 29 / 26, layer 2 33 / 32 against 29 / 28, layer 1 48 / 42 against 41 / 42 (profiles/EXPERIMENTS.md
-// 5.14): a 64-channel chunk is nine taps of eight fp16 MFMAs per wave -- 1.1 us -- and the single halo buffer drains the DMA queue
-// at every chunk boundary; the fp32 kernel's chunk is four times as long.
-constexpr int kH2PH = 8, kH2PW = 16, kH2MaxRows = (kH2PH + 4) * (kH2PW + 4);        // 240 halo pixels at dilation 2 (180 at 1)
-template <int WARPS_N>
-__global__ __launch_bounds__(128 * WARPS_N, WARPS_N == 4 ? 4 : 3) void gather_hr_kernel(const HGatherParams hp) {
-  const GatherConvParams& p = hp.g;
-  set_wave_prio(p.prio);
-  constexpr int WARPS_M = 2, NW = WARPS_M * WARPS_N, BN = 32 * WARPS_N, TM = 2;
-  constexpr int RDW = 32;                                   // dwords per LDS row: 64 halves
-  constexpr int kA = 0, kB = kH2MaxRows * RDW, kRing = kB + 3 * BN * RDW;
-  constexpr int kEpi = NW * 32 * 36;
-  constexpr int kLds = kRing > kEpi ? kRing : kEpi;
-  __shared__ __attribute__((aligned(16))) float lds[kLds];
-  unsigned* ldsw = reinterpret_cast<unsigned*>(lds);
-  constexpr int GA = kH2MaxRows / 8 / NW + ((kH2MaxRows / 8) % NW != 0);      // halo row groups per wave: 4 (eight waves) / 8 (four)
-  constexpr int GB = BN / 8 / NW;                                              // row groups of one tap per wave: 2
-  static_assert(GB == 2, "two filter DMAs per wave and tap");
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WARPS_N, wn = wave % WARPS_N;
-  const int gridN = (p.N + BN - 1) / BN;
-  int bid = blockIdx.x;
-  bid = remap_tile(p.xcd_remap, bid, (int)gridDim.x);
-  const int tile_n = bid % gridN;
-  const int tile_m = bid / gridN;
-  const int m0 = tile_m * 128, n0 = tile_n * BN;
-  const int d = p.dstep < 0 ? -p.dstep : p.dstep;
-  const int HC = kH2PW + 2 * d, HROWS = (kH2PH + 2 * d) * HC;                 // halo columns / pixels
-  const int img = m0 / p.HoWo;
-  const int patch = (m0 - img * p.HoWo) / (kH2PH * kH2PW);
-  const int ph = patch / p.patches_per_row, pw = patch - ph * p.patches_per_row;
-  const int h0 = ph * kH2PH - d, w0 = pw * kH2PW - d;                           // image position of halo pixel (0, 0)
-
-  const __amdgpu_buffer_rsrc_t xr = make_rsrc(p.x, p.x_bytes);
-  const __amdgpu_buffer_rsrc_t wr = make_rsrc(p.w, p.w_bytes);
-  const int lrow = lane >> 3, lslot = lane & 7;
-  uint32_t a_off[GA], b_off[GB];
-#pragma unroll
-  for (int g = 0; g < GA; ++g) {
-    const int idx = 8 * (wave + NW * g) + lrow;
-    const int hr = idx / HC, hc = idx - hr * HC;
-    const int y = h0 + hr, x = w0 + hc;
-    const bool ok = idx < HROWS && (unsigned)y < (unsigned)p.Hi && (unsigned)x < (unsigned)p.Wi;
-    a_off[g] = ok ? (uint32_t)(((img * p.Hi + y) * p.Wi + x) * p.ldx) * 2u + (uint32_t)((lslot ^ ((hc >> 1) & 7)) * 16) : kOOB;
-  }
-#pragma unroll
-  for (int g = 0; g < GB; ++g) {
-    const int n = 8 * (wave + NW * g) + lrow;
-    b_off[g] = (n0 + n) < p.N ? (uint32_t)(n0 + n) * (uint32_t)p.K * 2u + (uint32_t)((lslot ^ ((n >> 1) & 7)) * 16) : kOOB;
-  }
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  auto issue_a = [&](int chunk) {
-    const uint32_t kc = (uint32_t)chunk * 128u;
-#pragma unroll
-    for (int g = 0; g < GA; ++g)
-      if (wave + NW * g < kH2MaxRows / 8)        // (wave-uniform)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_ptr)(ldsw + kA + 8 * (wave + NW * g) * RDW), 16,
-                                                 (int)(a_off[g] == kOOB ? kOOB : a_off[g] + kc), 0, 0, 0);
-  };
-  auto issue_b = [&](int chunk, int t) {
-    const uint32_t kc = (uint32_t)chunk * 128u + (uint32_t)(t * p.Cin) * 2u;
-#pragma unroll
-    for (int g = 0; g < GB; ++g)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_ptr)(ldsw + kB + ((t % 3) * BN + 8 * (wave + NW * g)) * RDW), 16,
-                                               (int)(b_off[g] == kOOB ? kOOB : b_off[g] + kc), 0, 0, 0);
-  };
-
-  f32x16 acc[TM][1];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.f;
-
-  const int frag_row = lane & 31, frag_h = lane >> 5;
-  const int pcol = frag_row & 15;
-  const int hbase = (2 * wm * TM + (frag_row >> 4) + d) * HC + (pcol + d);        // strip i: + 2 i rows
-  int a_col_dw[3], a_swz[3];
-#pragma unroll
-  for (int ts = 0; ts < 3; ++ts) {
-    const int os = p.off0 + ts * p.dstep;            // -d, 0, +d (forward) or +d, 0, -d (data gradient)
-    a_col_dw[ts] = os * RDW;
-    a_swz[ts] = ((pcol + d + os) >> 1) & 7;
-  }
-  const int b_frag = (wn * 32 + frag_row) * RDW, b_swz = (frag_row >> 1) & 7;
-  f32x4 fa[TM][4], fb[4];
-  auto read_a = [&](int t) {
-    const int tr = t / 3, ts = t - tr * 3;
-    const int orow = p.off0 + tr * p.dstep;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int arow = kA + (hbase + (2 * i + orow) * HC) * RDW + a_col_dw[ts];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) fa[i][q] = *reinterpret_cast<const f32x4*>(&lds[arow + (((2 * q + frag_h) ^ a_swz[ts]) << 2)]);
-    }
-  };
-  auto read_b = [&](int t) {
-    const int brow = kB + (t % 3) * BN * RDW + b_frag;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) fb[q] = *reinterpret_cast<const f32x4*>(&lds[brow + (((2 * q + frag_h) ^ b_swz) << 2)]);
-  };
-  auto mfmas = [&]() {
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-        acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8v, fa[i][q]), __builtin_bit_cast(f16x8v, fb[q]),
-                                                           acc[i][0], 0, 0, 0);
-  };
-
-  const int nchunks = p.Cin >> 6;
-  for (int c = 0; c < nchunks; ++c) {
-    issue_a(c);
-    issue_b(c, 0);
-    issue_b(c, 1);
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      // in order: the halo image and taps <= t have landed when at most one younger tap (GB DMAs) is outstanding
-      if (t < 8) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (t + 2 < 9) issue_b(c, t + 2);             // into the stage tap t - 1 was read from
-      read_a(t);
-      read_b(t);
-      __builtin_amdgcn_sched_barrier(0);
-      mfmas();
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();            // everybody is done reading: the next chunk (or the output patches) may land
-  }
-
-  // ---- epilogue: as gather_h_kernel (bias / accumulate / row map, fused BatchNorm statistics of the values as stored)
-  const int col_l = lane & 31;
-  const int row_h = (lane >> 5) * 4;
-  {
-    float* patchb = lds + wave * (32 * 36);
-    const int col0 = n0 + wn * 32;
-    int cv = p.N - col0;
-    cv = cv < 0 ? 0 : (cv > 32 ? 32 : cv);
-    auto rowmap = [&](int m) {
-      int b, ho, wo;
-      row_to_pixel(p, m, b, ho, wo);
-      return (b * p.Ho + ho) * p.Wo + wo;
-    };
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int row0 = m0 + wm * 64 + i * 32;
-      int rv = p.M - row0;
-      rv = rv < 0 ? 0 : (rv > 32 ? 32 : rv);
-      store_row32<1>(acc[i], patchb, p.y, hp.y_f32 != 0, p.ldy, row0, col0, rv, cv, p.bias, p.accumulate != 0, lane, rowmap);
-    }
-  }
-  if (p.stat != nullptr) {
-    const bool f32out = hp.y_f32 != 0;
-    auto rnd = [&](float v) -> float { return f32out ? v : (float)(half_t)v; };
-    const int group = tile_m * WARPS_M + wm;
-    const long long gsz = (long long)p.stat_rows * p.N;
-    const int col = n0 + wn * 32 + col_l;
-    const float k0 = __shfl(rnd(acc[0][0][0]), lane & 31, 64);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + row_h;
-        if (row < p.M) {
-          const float dd = rnd(acc[i][0][r]) - k0;
-          s1 += dd;
-          s2 += dd * dd;
-        }
-      }
-    s1 += __shfl_xor(s1, 32, 64);
-    s2 += __shfl_xor(s2, 32, 64);
-    if (lane < 32 && col < p.N) {
-      const long long o = (long long)group * p.N + col;
-      p.stat[o] = k0;
-      p.stat[gsz + o] = s1;
-      p.stat[2 * gsz + o] = s2;
-    }
-  }
-}
-#endif  // PSEG_LAB
 
 // ------------------------------------------------------------------------------------------------ weight gradient
 struct HWgradParams {
@@ -2056,16 +1516,12 @@ struct HTile {
   bool persistent;   // gather_hp_kernel is instantiated for it
   int bns_kb;        // K-steps (32 | 64) with which it carries the fused BatchNorm-backward sums: the tiles the Bottleneck and
                      // BasicBlock data gradients of the reference's models are planned onto
-  bool lab;          // lab build only: PSEG_HCONV_TILE = 1..4, in this order
 };
-constexpr HTile kHTiles[] = {{128, 128, 2, 4, true, 32 | 64, false}, {128, 64, 2, 2, true, 32 | 64, false},
-                             {64, 128, 2, 2, true, 0, false},        {128, 32, 4, 1, true, 32, false},
-                             {128, 128, 2, 2, true, 0, true},        {256, 128, 4, 2, true, 0, true},
-                             {256, 256, 2, 4, false, 0, true},       {256, 128, 4, 4, false, 0, true}};
-constexpr int kNumHTiles = (int)(sizeof(kHTiles) / sizeof(kHTiles[0])), kFirstLabHTile = 4;
+constexpr HTile kHTiles[] = {{128, 128, 2, 4, true, 32 | 64}, {128, 64, 2, 2, true, 32 | 64}, {64, 128, 2, 2, true, 0}, {128, 32, 4, 1, true, 32}};
+constexpr int kNumHTiles = (int)(sizeof(kHTiles) / sizeof(kHTiles[0]));
 
 static int h_tile_index(TileCfg t) {
-  for (int i = 0; i < kFirstLabHTile; ++i)
+  for (int i = 0; i < kNumHTiles; ++i)
     if (kHTiles[i].bm == t.bm && kHTiles[i].bn == t.bn) return i;
   return -1;
 }
@@ -2079,18 +1535,16 @@ constexpr long long h_ring_lds(const HTile& t, int kb, int st) {
 constexpr long long h_persistent_lds(const HTile& t, int kb, int st) {
   return (long long)st * (t.bm + t.bn) * kb * 2 + (long long)t.wm * t.wn * 32 * 72;
 }
-// the 256x256 tile only with the short K-step: its accumulators take 128 registers
-constexpr bool h_kb_ok(const HTile& t, int kb) { return !(t.bm == 256 && t.bn == 256 && kb == 64); }
 // (K-step, ring depth) pairs with a BNS = true instantiation: what the heuristics of select_gather_h give those data gradients
 constexpr bool h_bns_steps(int kb, int st, bool persistent) {
   return (kb == 32 && st == 3) || (kb == 64 && (st == 2 || (st == 3 && !persistent)));
 }
 constexpr bool h_ring_exists(const HTile& t, int kb, int st, bool bns) {
-  return (PSEG_LAB || !t.lab) && h_ring_lds(t, kb, st) <= kLdsBytes && h_kb_ok(t, kb) &&
+  return h_ring_lds(t, kb, st) <= kLdsBytes &&
          (!bns || ((t.bns_kb & kb) != 0 && h_bns_steps(kb, st, false)));
 }
 constexpr bool h_persistent_exists(const HTile& t, int kb, int st, bool bns) {      // (its ring is two or three deep)
-  return (PSEG_LAB || !t.lab) && t.persistent && st <= 3 && h_persistent_lds(t, kb, st) <= kLdsBytes &&
+  return t.persistent && st <= 3 && h_persistent_lds(t, kb, st) <= kLdsBytes &&
          (!bns || ((t.bns_kb & kb) != 0 && h_bns_steps(kb, st, true)));
 }
 
@@ -2128,7 +1582,7 @@ static TileCfg half_tile(TileCfg t) {
 
 // K-step (halves per LDS row) of a gather problem.  PSEG_HCONV_KB = 32 / 64 forces one.
 static int hconv_kb(int Cin, int K) {
-  static const int forced = env_int("PSEG_HCONV_KB", 0);
+  const int forced = cfg().hconv_kb;
   if (forced == 32 || forced == 64) return forced;
   if (Cin % 64 != 0) return 32;          // 32-channel layers stay on the hoisted (tap-uniform) addressing with the short step
   // measured (tools/bench_conv_half.py over PSEG_HCONV_KB x PSEG_HCONV_STAGES): the short step with a three-deep ring wins
@@ -2153,7 +1607,6 @@ struct HGatherChoice {
   int pstages;      // ... with a ring this deep
   bool ring;        // the gather_h_kernel instantiation exists (with the sums if asked)
   bool sums;        // the fused sums are asked for and a kernel that carries them takes the problem
-  int halo;         // lab build: 1 gather_hh_kernel, 2 gather_hr_kernel run instead
   int wave_rows() const { return tile >= 0 ? kHTiles[tile].wm : 2; }
   int stat_rows() const { return pl.gridM * wave_rows(); }
 };
@@ -2163,7 +1616,6 @@ static HGatherChoice select_gather_h(const HGatherProblem& q) {
   HGatherChoice c;
   const long long M = q.M;
   const int N = q.N, K = q.K;
-  [[maybe_unused]] const int taps = q.taps_h * q.taps_w;     // (lab kernels below)
   const int kb = c.kb = hconv_kb(q.Cin, K);
   const bool generic = q.Cin % kb != 0;
   // the plan: tile and row order from the shared planner (the schedules of the dilated convs carry over), never split-K.
@@ -2187,15 +1639,6 @@ static HGatherChoice select_gather_h(const HGatherProblem& q) {
     pl.banded = false;
   }
   c.tile = h_tile_index(t);
-#if PSEG_LAB
-  // experiments (tools/bench_conv_half.py): PSEG_HCONV_TILE = 1: 128x128 on four waves (64x64 wave tiles), 2: 256x128 on eight
-  // waves (64x64 wave tiles), 3: 256x256 on eight waves (128x64 wave tiles), 4: 256x128 on sixteen waves
-  const int forced_tile = cfg().hconv_tile;
-  if (forced_tile >= 1 && forced_tile <= 4 && !generic && !pl.banded && pl.patch_w == 0) {
-    c.tile = kFirstLabHTile + forced_tile - 1;
-    t = TileCfg{kHTiles[c.tile].bm, kHTiles[c.tile].bn};
-  }
-#endif
   pl.tile = t;
   pl.gridM = cdiv(M, t.bm);
   pl.gridN = cdiv(N, t.bn);
@@ -2209,39 +1652,12 @@ static HGatherChoice select_gather_h(const HGatherProblem& q) {
   // The stride-2 data gradient runs parity-homogeneous tiles on every tile shape, 3/4 of the taps skipped.
   c.order = gather_row_order(q, pl, !generic && !(t.bm == 128 && t.bn == 128), !generic);
   c.variant = generic ? 2 : (c.order.skip_taps != 0 ? 1 : 0);
-  c.halo = 0;
-#if PSEG_LAB
-  // halo-staged 3x3 (gather_hh_kernel): unit stride, dilation 1 / 2, channels in whole 64-chunks, maps of 8 x 16 patches, fp16
-  // result without bias / accumulation, and a plan whose statistics layout is the kernel's (128-row tiles, two wave rows).
-  // PSEG_HCONV_HALO=0: off.  With the filter as a ring of taps (gather_hr_kernel): 128x128 / 128x64 plan tiles, every tap live.
-  // PSEG_HCONV_HALO2=0: off.
-  static const int halo_on = env_int("PSEG_HCONV_HALO", 0), halo2_on = env_int("PSEG_HCONV_HALO2", 0);      // (opt-in)
-  const int adil = q.dstep < 0 ? -q.dstep : q.dstep;
-  const bool halo_shape = !q.bns && !generic && taps == 9 && q.taps_w == 3 && q.s_out == 1 && q.s_in == 1 && (adil == 1 || adil == 2) &&
-                          q.Cin % 64 == 0 && q.Hi == q.Ho && q.Wi == q.Wo && t.bm == 128 && (t.bn == 128 || t.bn == 64) &&
-                          c.order.row_perm == 0;
-  if (halo_on != 0 && halo_shape && (q.off0 == -adil || q.off0 == adil) && q.Ho % kHaloPH == 0 && q.Wo % kHaloPW == 0 && !q.y_f32 &&
-      !q.bias && !q.accumulate && N >= 64 && M % 128 == 0) {
-    c.halo = 1;
-    c.order.skip_taps = 0;
-    c.order.row_perm = 2;
-    c.order.patch_w = kHaloPW;
-    c.order.patch_hw = kHaloPH * kHaloPW;
-    c.order.patches_per_row = q.Wo / kHaloPW;
-  } else if (halo2_on != 0 && halo_shape && q.off0 == -q.dstep && q.Ho % kH2PH == 0 && q.Wo % kH2PW == 0 && c.order.skip_taps == 0) {
-    c.halo = 2;
-    c.order.row_perm = 2;
-    c.order.patch_w = kH2PW;
-    c.order.patch_hw = kH2PH * kH2PW;
-    c.order.patches_per_row = q.Wo / kH2PW;
-  }
-#endif
   // ring depth (PSEG_HCONV_STAGES forces 2 / 3 / 4); never deeper than the K loop is long
   // Measured: the short K-step always wants three stages (its blocks are small: four to eight stay resident anyway); the long
   // one only on narrow tiles with a deep contraction, where a deeper ring costs no resident block the grid needs -- the ASPP
   // convs (128x64 tiles, K = 18432: 237 -> 197 / 208 -> 151 us with three stages) and the classifier (128x32, K = 3456: 238 ->
   // 158 us with four); 128x128 tiles lose their second resident block to a third stage (layer-4 3x3: 89 -> 98 us).
-  static const int forced_stages = env_int("PSEG_HCONV_STAGES", 0);
+  const int forced_stages = cfg().hconv_stages;
   int stages = 2;
   if (kb == 32) stages = 3;
   else if (t.bn == 32 && K >= 2048) stages = 4;
@@ -2256,11 +1672,12 @@ static HGatherChoice select_gather_h(const HGatherProblem& q) {
   // K-steps per tile -- 5-20 % faster, e.g. 64 -> 256 channels on 128x128 maps 41 -> 35 us = 4.8 TB/s of operand + result
   // traffic; the deep contractions lose 15-25 %: ring + patch leave one resident block per CU where gather_h_kernel holds two,
   // and with 32+ K-steps per tile there is no chain left to hide).  PSEG_HCONV_PERSIST=2 forces it everywhere it is valid.
+  constexpr int kPersistMaxKSteps = 24;
   const int persist = cfg().hconv_persist;
   const bool offered = persist != 0 && c.variant == 0 && !q.y_f32 && !q.bias && !q.accumulate &&
                        (c.order.row_perm == 0 || c.order.row_perm == 3) && pl.kt_total >= 1 &&
-                       (pl.kt_total <= cfg().hconv_persist_kt || persist == 2 || (pl.gridM * pl.gridN <= 256 && pl.kt_total <= 48));
-  c.persistent = offered && c.halo == 0 && c.tile >= 0 && h_persistent_exists(kHTiles[c.tile], kb, c.pstages, q.bns);
+                       (pl.kt_total <= kPersistMaxKSteps || persist == 2 || (pl.gridM * pl.gridN <= 256 && pl.kt_total <= 48));
+  c.persistent = offered && c.tile >= 0 && h_persistent_exists(kHTiles[c.tile], kb, c.pstages, q.bns);
   // (the sums come with the plain variant only: every tap live, channels in whole K-steps)
   c.ring = c.tile >= 0 && h_ring_exists(kHTiles[c.tile], kb, stages, q.bns) && !(q.bns && c.variant != 0);
   c.sums = q.bns && !q.y_f32 && !q.bias && !q.stats && !q.accumulate && (c.persistent || c.ring);
@@ -2298,10 +1715,8 @@ static bool launch_gather_hp_one(int ntiles, hipStream_t st, const HGatherParams
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gather_hp_kernel<BM, BN, WM, WN, KB, ST, BNS>, 64 * NW, 0) != hipSuccess ||
         per_cu < 1)
       return false;
-    const int by_lds = (int)(kLdsBytes / h_persistent_lds(HTile{BM, BN, WM, WN, true, 0, false}, KB, ST));
+    const int by_lds = (int)(kLdsBytes / h_persistent_lds(HTile{BM, BN, WM, WN, true, 0}, KB, ST));
     if (per_cu > by_lds) per_cu = by_lds;
-    static const int forced_bpc = env_int("PSEG_HCONV_PBPC", 0);
-    if (forced_bpc > 0 && forced_bpc < per_cu) per_cu = forced_bpc;
     resident = prop.multiProcessorCount * per_cu;
   }
   const int blocks = ntiles < resident ? ntiles : resident;
@@ -2390,33 +1805,11 @@ static int run_gather_h(const GatherGeom& g, const void* x, long long x_bytes, i
     p.bns_dg = bns->dg;
   }
   hp.y_f32 = y_f32;
-#if PSEG_LAB
-  static const int ablate = env_int("PSEG_HCONV_ABLATE", 0);
-  hp.ablate = ablate;
-#endif
   hp.cin_div = FastDiv((uint32_t)g.Cin);
   hp.kw_div = FastDiv((uint32_t)g.taps_w);
   hp.howo_div = FastDiv((uint32_t)p.HoWo);      // (after the pointwise rewrite of set_gather_geometry: HoWo = Wo = M there)
   hp.wo_div = FastDiv((uint32_t)p.Wo);
   hp.ntiles = pl.gridM * pl.gridN;
-#if PSEG_LAB
-  if (c.halo == 1) {
-    const dim3 hgrid((unsigned)((g.M / 128) * cdiv(g.N, 128)), 1, 1);
-    static const int hstages = env_int("PSEG_HCONV_HALO_STAGES", 6);
-    if (hstages <= 3) hipLaunchKernelGGL(gather_hh_kernel<3>, hgrid, dim3(512), 0, st, hp);
-    else if (hstages == 4) hipLaunchKernelGGL(gather_hh_kernel<4>, hgrid, dim3(512), 0, st, hp);
-    else if (hstages == 5) hipLaunchKernelGGL(gather_hh_kernel<5>, hgrid, dim3(512), 0, st, hp);
-    else hipLaunchKernelGGL(gather_hh_kernel<6>, hgrid, dim3(512), 0, st, hp);
-    PSEG_LAUNCH_CHECK();
-    return PSEG_OK;
-  }
-  if (c.halo == 2) {
-    if (pl.tile.bn == 128) hipLaunchKernelGGL(gather_hr_kernel<4>, dim3((unsigned)hp.ntiles), dim3(512), 0, st, hp);
-    else hipLaunchKernelGGL(gather_hr_kernel<2>, dim3((unsigned)hp.ntiles), dim3(256), 0, st, hp);
-    PSEG_LAUNCH_CHECK();
-    return PSEG_OK;
-  }
-#endif
   if (c.persistent && launch_persistent_h(c, bns != nullptr, st, hp)) {
     g_last_conv_kernel = PSEG_KERNEL_GATHER_H_PERSISTENT;
     PSEG_LAUNCH_CHECK();
@@ -2448,9 +1841,9 @@ struct HWgradChoice {
   WgradPixelOrder order;
   int tile;        // entry of kHWgradTiles; -1: a forced tile that nothing is instantiated for
   bool skip;       // the kernel's SKIP template flag
-  int stages;      // ring depth (2 .. 4; the 64-pixel K-step has no four-deep ring)
   int bkp;         // pixels per K-step, 32 / 64
 };
+constexpr int kHWgradStages = 2;      // ring depth of wgrad_h_kernel (select_wgrad_h says why)
 
 // The one place that picks the kernel of an fp16 weight gradient.  Pure: launches nothing, touches no device.
 static HWgradChoice select_wgrad_h(const WgradGeom& q) {
@@ -2466,15 +1859,13 @@ static HWgradChoice select_wgrad_h(const WgradGeom& q) {
   c.tile = -1;
   for (int i = 0; i < kNumHWgradTiles; ++i)
     if (kHWgradTiles[i].bm == c.pl.tile.bm && kHWgradTiles[i].bn == c.pl.tile.bn) c.tile = i;
-  // ring depth: as deep as keeps the blocks the grid wants resident (measured: tools/bench_conv_half.py, PSEG_HWGRAD_STAGES)
-  const int forced_st = cfg().hwgrad_stages;
-  c.stages = (forced_st >= 2 && forced_st <= 4) ? forced_st : 2;
+  // ring depth: always kHWgradStages = 2 -- a deeper ring costs the resident blocks the grid wants and measured slower on every
+  // layer (profiles/EXPERIMENTS.md, "Weight gradient: ring depth hurts, resident blocks help")
   // pixels per K-step: 32 halves the ring (four blocks per CU instead of two) and pays on the deep 3x3 layers -- ASPP 361 -> 298
   // / 294 -> 238 / 250 -> 216 us, layer-4 3x3 140 -> 111 -- while the short launches (bounded by their slab traffic and
   // their prologue / epilogue) do not care and the narrow classifier loses 10 % (tools/bench_conv_half.py, PSEG_HWGRAD_BKP)
   const int forced_bkp = cfg().hwgrad_bkp;
   c.bkp = (forced_bkp == 32 || forced_bkp == 64) ? forced_bkp : ((q.kh * q.kw > 1 && q.Cout >= 128 && q.K() >= 4096) ? 32 : 64);
-  if (c.bkp == 64 && c.stages > 3) c.stages = 3;
   return c;
 }
 
@@ -2483,12 +1874,11 @@ static void launch_wgrad_h(const HWgradChoice& c, dim3 grid, hipStream_t st, con
   auto launch = [&](auto tile, auto steps) {
     constexpr HWgradTile t = kHWgradTiles[decltype(tile)::value];
     using S = decltype(steps);
-    if constexpr (!(S::kb == 64 && S::st == 4)) {
-      if (c.skip) hipLaunchKernelGGL((wgrad_h_kernel<t.bm, t.bn, t.wm, t.wn, true, S::st, S::kb>), grid, dim3(256), 0, st, hp);
-      else hipLaunchKernelGGL((wgrad_h_kernel<t.bm, t.bn, t.wm, t.wn, false, S::st, S::kb>), grid, dim3(256), 0, st, hp);
-    }
+    if (c.skip) hipLaunchKernelGGL((wgrad_h_kernel<t.bm, t.bn, t.wm, t.wn, true, S::st, S::kb>), grid, dim3(256), 0, st, hp);
+    else hipLaunchKernelGGL((wgrad_h_kernel<t.bm, t.bn, t.wm, t.wn, false, S::st, S::kb>), grid, dim3(256), 0, st, hp);
   };
-  (void)((c.tile == I && (with_h_steps<I>(c.bkp, c.stages, launch), true)) || ...);
+  (void)((c.tile == I && (c.bkp == 32 ? launch(std::integral_constant<int, I>{}, HSteps<32, kHWgradStages>{})
+                                      : launch(std::integral_constant<int, I>{}, HSteps<64, kHWgradStages>{}), true)) || ...);
 }
 
 // validate, select, check the workspace, fill the parameters from the choice and launch, reduce the slabs.

@@ -2835,17 +2835,16 @@ struct F32Tile {
   int bm, bn, wm, wn;
   bool pw;       // persistent pointwise kernel
   int halo;      // halo-staged kernel: the lowest PSEG_CONV_HALO that takes the tile (0: not instantiated)
-  bool dma32;    // only with PSEG_CONV_DMA32 != 0
 };
-constexpr F32Tile kF32Tiles[] = {{128, 128, 2, 4, true, 0, false},
-                                 {128, 64, 2, 2, true, 2, false},
-                                 {64, 128, 2, 2, true, 0, false},
-                                 {128, 32, 4, 1, false, 1, true}};   // narrow outputs (HRNet's 32-channel branch, the 21-class classifier)
+constexpr F32Tile kF32Tiles[] = {{128, 128, 2, 4, true, 0},
+                                 {128, 64, 2, 2, true, 2},
+                                 {64, 128, 2, 2, true, 0},
+                                 {128, 32, 4, 1, false, 1}};   // narrow outputs (HRNet's 32-channel branch, the 21-class classifier)
 constexpr int kNumF32Tiles = (int)(sizeof(kF32Tiles) / sizeof(kF32Tiles[0]));
 
 static int f32_tile_index(TileCfg t) {
   for (int i = 0; i < kNumF32Tiles; ++i)
-    if (kF32Tiles[i].bm == t.bm && kF32Tiles[i].bn == t.bn && (!kF32Tiles[i].dma32 || cfg().conv_dma32 != 0)) return i;
+    if (kF32Tiles[i].bm == t.bm && kF32Tiles[i].bn == t.bn) return i;
   return -1;
 }
 
@@ -2867,6 +2866,7 @@ struct GatherProblem : GatherGeom {
   bool stats, bias, planes, bns, accumulate;   // fused statistics / bias / pre-split limb planes / fused BatchNorm-backward sums
 };
 
+constexpr int kPwMaxKSteps = 32;     // longest contraction, in K-steps, that the persistent pointwise kernel is offered
 constexpr int kGatherRefused = 0;    // GatherChoice::kernel: no kernel carries the limb planes / fused sums asked for
 
 // Everything run_gather decides before it launches; the queries read their answers off the same choice.
@@ -2887,10 +2887,9 @@ static GatherChoice select_gather(const GatherProblem& q) {
   DilGeom geom;
   const bool has_geom = dil_geom(geom, q.Ho, q.Wo, q.Hi, q.Wi, q.taps_h, q.taps_w, q.Cin, q.s_out, q.s_in, q.dstep, q.off0);
   // the 256x128 / 8-wave tile (one block per CU) of the limb kernels: measured 1 % SLOWER in the round-2 training step than
-  // two 128-row blocks per CU (mixed policy 35.85 vs 35.45 ms) -- opt-in (PSEG_CONV_BIG=1); the pre-split DMA kernel is
-  // built on it
-  const bool allow_big = !q.stats && (q.precision == 1 || q.precision == 3) &&
-                         (q.planes || cfg().conv_big != 0 || cfg().conv_forcebig != 0);
+  // two 128-row blocks per CU (mixed policy 35.85 vs 35.45 ms) -- only forced (PSEG_CONV_FORCEBIG); the pre-split DMA kernel
+  // is built on it
+  const bool allow_big = !q.stats && (q.precision == 1 || q.precision == 3) && (q.planes || cfg().conv_forcebig != 0);
   c.pl = plan_gather(q.M, q.N, q.K, allow_big, has_geom ? &geom : nullptr);
   const FwdPlan& pl = c.pl;
   const bool whole = q.Cin % BK == 0;    // whole K-steps inside a tap
@@ -2902,7 +2901,7 @@ static GatherChoice select_gather(const GatherProblem& q) {
   if (q.planes) {
     // the LDS-DMA limb kernel or nothing: whole K-steps inside a tap, the 256x128 tile, no split-K
     const bool ok = q.precision == 1 && !q.stats && !q.bias && !q.bns && pl.tile.bm == kDmaBM && pl.tile.bn == kDmaBN &&
-                    pl.splits == 1 && whole && q.N >= kDmaBN && cfg().conv_nodma == 0;
+                    pl.splits == 1 && whole && q.N >= kDmaBN;
     c.kernel = ok ? PSEG_KERNEL_GATHER_LIMB_DMA : kGatherRefused;
     return c;
   }
@@ -2910,8 +2909,7 @@ static GatherChoice select_gather(const GatherProblem& q) {
   const F32Tile& t = kF32Tiles[c.f32_tile];
   const bool sk = c.order.skip_taps != 0;
   const int taps = q.taps_h * q.taps_w;
-  static const int generic_on = env_int("PSEG_CONV_F32DMA_GENERIC", 1);
-  if (generic_on != 0 && !whole && q.Cin % 4 == 0 && !sk && (c.order.row_perm == 0 || c.order.row_perm == 3) && !q.bns) {
+  if (!whole && q.Cin % 4 == 0 && !sk && (c.order.row_perm == 0 || c.order.row_perm == 3) && !q.bns) {
     // channel counts off the K-step grid (stem, classifier data gradient, MobileNetV2 widths): the GENERIC form of the ring
     // kernel with per-slot (tap, channel) derivation; two-stage ring
     c.kernel = PSEG_KERNEL_GATHER_RING_GENERIC;
@@ -2929,8 +2927,8 @@ static GatherChoice select_gather(const GatherProblem& q) {
   if (!(whole && q.K % BK == 0 && taps <= 32 && !(cfg().conv_f32dma == 2 && sk))) return c;
   if (q.bns && q.accumulate) return c;      // (the fused sums are those of the tile written, not of what it is added to)
   // pointwise convs with short contractions and more tiles than the device holds blocks: the persistent kernel
-  // (PSEG_CONV_PW=0: off; PSEG_CONV_PW_KT: longest contraction, in K-steps, that takes it)
-  c.try_pw = t.pw && cfg().conv_pw != 0 && c.order.row_perm == 3 && !sk && pl.kt_total <= cfg().conv_pw_kt && cfg().conv_f32dma >= 2;
+  // (PSEG_CONV_PW=0: off)
+  c.try_pw = t.pw && cfg().conv_pw != 0 && c.order.row_perm == 3 && !sk && pl.kt_total <= kPwMaxKSteps && cfg().conv_f32dma >= 2;
   // narrow 3x3: the halo-staged kernel where the map is made of whole 8 x 16 patches (see gather_f32_halo_kernel)
   const int halo = cfg().conv_halo;
   if (halo != 0 && t.halo != 0 && (t.halo == 1 || halo >= t.halo) && !sk && taps == 9 && q.taps_w == 3 && q.s_out == 1 &&
@@ -2989,8 +2987,6 @@ static int launch_pw(int ntiles, hipStream_t st, const GatherConvParams& p) {
       constexpr long long lds_bytes = (2LL * (BM + BN) * 32 + WM * WN * 8 * (BN / WN + 4)) * 4;
       const int by_lds = (int)((160 * 1024) / lds_bytes);
       if (per_cu > by_lds) per_cu = by_lds;
-      static const int forced = env_int("PSEG_CONV_PW_BPC", 0);
-      if (forced > 0 && forced < per_cu) per_cu = forced;
       resident = prop.multiProcessorCount * per_cu;
     }
   }
@@ -3191,13 +3187,11 @@ struct WgradProblem : WgradGeom {
   bool concurrent;   // the launch shares the chip with another stream's kernels (see plan_wgrad)
 };
 
-constexpr int kWgradRefused = 0;     // WgradChoice::kernel: no kernel is instantiated for the (forced) tile
-
 // Everything run_wgrad decides before it launches; the queries read their answers off the same choice.
 struct WgradChoice {
   WgradPlan pl;            // (the halo kernel's 32 x 288 tile and grid included)
   WgradPixelOrder order;   // ... with the packed tap order and lpt_per
-  int kernel;              // PSEG_KERNEL_WGRAD_* that runs, or kWgradRefused
+  int kernel;              // PSEG_KERNEL_WGRAD_* that runs
   int dma_tile;            // entry of kWgradDmaTiles, -1: none
   bool skip;               // the kernel's SKIP template flag
 };
@@ -3232,18 +3226,17 @@ static WgradChoice select_wgrad(const WgradProblem& q) {
   c.dma_tile = wgrad_dma_tile_index(pl.tile);
   if (!dma || c.dma_tile < 0) {
     // register-staged / limb kernels, in the shared pixel order
-    const bool tile288 = q.precision == 0 && pl.tile.bm == 32 && pl.tile.bn == 288;   // (PSEG_WGRAD_BM / _BN with PSEG_WGRAD_F32DMA=0)
-    c.kernel = tile288 ? kWgradRefused : (q.precision == 0 ? PSEG_KERNEL_WGRAD_REGISTER : PSEG_KERNEL_WGRAD_LIMB);
+    // (never the 32 x 288 tile: plan_wgrad and the halo branch above give it to the LDS-DMA kernels only)
+    c.kernel = q.precision == 0 ? PSEG_KERNEL_WGRAD_REGISTER : PSEG_KERNEL_WGRAD_LIMB;
     c.skip = o.mode != kWgDense;
     return c;
   }
   // exact-fp32 weight gradient on the LDS-DMA kernel (8 waves, two blocks per CU); same tile, same split plan
   c.kernel = halo ? PSEG_KERNEL_WGRAD_HALO : PSEG_KERNEL_WGRAD_DMA;
-  static const int packed_on = env_int("PSEG_WGRAD_PACKED", 1);
   if (!o.patch_mode) {
     // a map that does not tile into 32-pixel patches: plain row-major pixel order instead of the register-staged kernel
     o.mode = kWgRowMajorDma;
-  } else if (o.can_skip && q.stride == 1 && taps <= 9 && packed_on != 0) {
+  } else if (o.can_skip && q.stride == 1 && taps <= 9) {
     // dilated conv: packed live rectangles instead of 32-pixel patches
     o.mode = kWgPacked;
     // longest-first order of the taps (live area, descending; ties keep the tap order: deterministic)
@@ -3336,8 +3329,6 @@ static int run_wgrad(const WgradProblem& q, const float* x, int ldx, const float
   set_wgrad_geometry(p, q, pl, c.order);
   const int rc = set_wgrad_output(p, pl, dw, accumulate, workspace, workspace_bytes, "conv2d_wgrad");
   if (rc != PSEG_OK) return rc;
-  PSEG_REQUIRE(c.kernel != kWgradRefused,
-               "conv2d_wgrad: the 32 x 288 tile runs on the LDS-DMA kernel only (PSEG_WGRAD_F32DMA=0 with PSEG_WGRAD_NARROW288=1?)");
   const dim3 grid((unsigned)(pl.gridM * pl.gridN), 1, (unsigned)pl.splits);
   g_last_conv_kernel = c.kernel;
   if (c.kernel == PSEG_KERNEL_WGRAD_HALO) {

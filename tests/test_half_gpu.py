@@ -283,8 +283,7 @@ def test_persistent_gather_matches_gather_h(ops, case, monkeypatch):
     """gather_hp_kernel (persistent blocks, continuous operand ring, transposed fp16 epilogue patch) against gather_h_kernel on
     the same launch: same K-step order, same fp32 accumulation, one rounding to fp16 -- the results must be BIT-IDENTICAL, forward
     (with the fused statistics) and data gradient, also where the planner would not pick the persistent kernel
-    (PSEG_HCONV_PERSIST=2: everywhere it is valid; deep contractions, dilated convs run dense) and on the alternative block
-    shapes (PSEG_HCONV_TILE: 128x128 on four waves, 256x128 on eight)."""
+    (PSEG_HCONV_PERSIST=2: everywhere it is valid; deep contractions, dilated convs run dense)."""
     from pytorch_segmentation_amd import _lib
     B, Cin, H, W, Cout, k, stride, pad, dil = case
     x, w, b, xa, w_h, b_raw, cin_p, cout_p, Ho, Wo = _setup(ops, case, False)
@@ -304,23 +303,20 @@ def test_persistent_gather_matches_gather_h(ops, case, monkeypatch):
     monkeypatch.setenv('PSEG_CONV_NOSKIP', '1')          # (both kernels dense: the persistent one has no tap skipping)
     res = {}
     ran = []
-    for tile in ('0', '1', '2'):
-        for persist in ('0', '2'):
-            monkeypatch.setenv('PSEG_HCONV_PERSIST', persist)
-            monkeypatch.setenv('PSEG_HCONV_TILE', tile)
-            _lib.clear_query_cache()
-            res[(tile, persist)] = run()
-            if tile == '0':
-                assert ran[-1] == (22 if persist == '2' else 21), (persist, ran)
-    for env in ('PSEG_HCONV_PERSIST', 'PSEG_HCONV_TILE', 'PSEG_CONV_NOSKIP'):
+    for persist in ('0', '2'):
+        monkeypatch.setenv('PSEG_HCONV_PERSIST', persist)
+        _lib.clear_query_cache()
+        res[persist] = run()
+        assert ran[-1] == (22 if persist == '2' else 21), (persist, ran)
+    for env in ('PSEG_HCONV_PERSIST', 'PSEG_CONV_NOSKIP'):
         monkeypatch.delenv(env)
     _lib.clear_query_cache()
-    ref = res[('0', '0')]
+    ref = res['0']
     assert_half_rounded(ops.Act(ref[0], B, Ho, Wo, cout_p, cout_p).to_nchw(Cout),
                         F.conv2d(x.double(), w.double(), None, stride, pad, dil), 'gather_h')
     for key, got in res.items():
         assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1]), key
-        # (statistics: the same values summed per wave-row group -- another tile shape groups other rows)
+        # (statistics: the same values summed per wave-row group)
         assert rel(got[2], ref[2]) < 1e-5 and rel(got[3], ref[3]) < 1e-5, key
 
 

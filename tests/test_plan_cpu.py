@@ -109,3 +109,29 @@ def test_wgrad_launches_are_written_once():
     assign = r'skip_rows\s*=[^=]'
     assert not re.search(assign, mfma) and not re.search(assign, half)
     assert len(re.findall(assign, common)) == 1 and re.search(assign, _body(common, 'static void set_wgrad_geometry('))
+
+
+def test_switches_are_read_in_one_place():
+    """cfg_load (conv_common.h) is the only reader of the conv planning switches: env_int( occurs in its own definition and in
+    cfg_load's body, nowhere else in conv_common.h and nowhere in conv_mfma.hip / conv_half.hip, which do not call getenv( either
+    -- so pseg_config_reload() reaches every switch and no plan, selection or launch helper keeps a per-process copy of one."""
+    mfma, half, common = _csrc('conv_mfma.hip'), _csrc('conv_half.hip'), _csrc('conv_common.h')
+    assert 'env_int(' not in mfma and 'env_int(' not in half
+    assert 'getenv(' not in mfma and 'getenv(' not in half
+    definition = _body(common, 'static int env_int(')
+    load = _body(common, 'inline void cfg_load(')
+    assert load.count('env_int(') >= 20
+    rest = common.replace(definition, '').replace(load, '')
+    assert 'env_int(' not in rest and 'getenv(' not in rest
+    assert common.count('getenv(') == 1 and 'getenv(' in definition
+
+
+def test_lab_build_is_gone():
+    """The fp16 conv lab build (measured-and-rejected kernels, ablation bits) is in no source under csrc/."""
+    csrc = os.path.join(os.path.dirname(HERE), 'pytorch_segmentation_amd', 'csrc')
+    names = [n for n in sorted(os.listdir(csrc)) if n.endswith(('.hip', '.h', '.py'))]
+    assert 'conv_half.hip' in names and 'build.py' in names
+    for n in names:
+        src = _csrc(n)
+        for gone in ('PSEG_LAB', 'PSEG_ABLATE', 'gather_hh_kernel', 'gather_hr_kernel'):
+            assert gone not in src, (n, gone)
