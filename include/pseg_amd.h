@@ -446,6 +446,31 @@ int pseg_ce_upsampled_fwd_bwd(const float* logits_lr, int ld, int B, int h, int 
 int64_t pseg_lovasz_workspace_bytes(int B, int C, int64_t HW);
 int pseg_lovasz_softmax_fwd_bwd(const float* logits, const int64_t* target, int B, int C, int64_t HW, int64_t ignore_index,
                                 float* dlogits, float* out, void* workspace, int64_t workspace_bytes, void* stream);
+/* pseg_ce_opts_fwd_bwd (csrc/ce_opts.hip): cross-entropy with per-class weights, label smoothing, the focal modulation and
+ *   online hard-pixel selection (OHEM), with its gradient.  logits fp32 NCHW [B][C][HW], target int64 [B][HW]; validity is
+ *   the predicate of pseg_ce_fwd_bwd, other targets that are not ignore_index are ignored and counted.  With z the logits
+ *   of a pixel, t its label, p = softmax(z), w = class_weight (device, [C], non-negative; NULL = all ones),
+ *   eps = label_smoothing, gamma = focal_gamma:
+ *       l = (1 - eps) w_t (-log p_t) + (eps / C) sum_c w_c (-log p_c)      (F.cross_entropy(weight=, label_smoothing=))
+ *       f = (1 - p_t)^gamma l                                               (the gradient flows through the factor)
+ *       df/dz_j = m [(1 - eps) w_t (p_j - d_jt) + (eps / C)(p_j sum_c w_c - w_j)] - l gamma (1 - p_t)^(gamma - 1) p_t (d_jt - p_j),
+ *   m = (1 - p_t)^gamma; 1 - p_t is formed from the sum of the other classes' exponentials.  Selection: keep_ratio == 1
+ *   keeps every valid pixel (no selection runs); otherwise k = clamp(ceil((double)keep_ratio * n_valid), 1, n_valid), tau =
+ *   the k-th largest f (the fp32 values the kernel computed, parked at 4 bytes per pixel in the workspace and selected on
+ *   the device by a four-round radix select), kept = valid pixels with f >= tau: ties at tau are all kept, n_kept >= k.
+ *   loss = sum_kept f / sum_kept w_t; dlogits ([B][C][HW], nullable) receives the gradient of that quotient with the kept
+ *   set held fixed, zero on every pixel that is not kept.  A zero divisor (no valid pixel, or every kept weight zero)
+ *   gives a NaN loss and an all-zero gradient.  loss_out[6] = [loss, n_valid, n_out_of_range, n_kept, tau (0 when
+ *   keep_ratio == 1), sum_kept w_t] (as floats).  Refused with PSEG_ERR_ARG: null logits / target / loss_out / workspace,
+ *   non-positive sizes, B * HW >= 2^31, a workspace below pseg_ce_opts_workspace_bytes(B, C, HW) or not 16-byte aligned,
+ *   label_smoothing outside [0, 1), keep_ratio outside (0, 1], focal_gamma other than 0 or a value in [1, 8] (for
+ *   0 < gamma < 1 the derivative of the factor is unbounded).  Deterministic: floating-point sums go through per-block
+ *   partials in a fixed order in double, atomics add integers only; no host synchronisation.  With keep_ratio == 1 the
+ *   call is one read of the logits and one write of dlogits after a targets-only pass for the divisor. */
+int64_t pseg_ce_opts_workspace_bytes(int B, int C, int64_t HW);
+int pseg_ce_opts_fwd_bwd(const float* logits, const int64_t* target, int B, int C, int64_t HW, int64_t ignore_index,
+                         const float* class_weight, float label_smoothing, float focal_gamma, float keep_ratio,
+                         float* dlogits, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream);
 int pseg_scale_inplace(float* x, int64_t n, const float* gscale, void* stream);
 int pseg_argmax(const float* logits, int B, int C, int64_t HW, int64_t* mask, void* stream);
 int pseg_confusion(const int64_t* pred, const int64_t* target, int64_t n, int C, int64_t* counters, void* stream);

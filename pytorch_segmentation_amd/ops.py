@@ -1151,6 +1151,27 @@ def ce_fwd_bwd(logits, target, want_grad=True, ignore_index=-100):
     return out, dl
 
 
+def ce_opts_fwd_bwd(logits, target, class_weight=None, label_smoothing=0.0, focal_gamma=0.0, keep_ratio=1.0, want_grad=True,
+                    ignore_index=-100):
+    """Cross-entropy with class weights, label smoothing, the focal factor and hard-pixel selection (pseg_ce_opts_fwd_bwd).
+    logits: contiguous NCHW fp32 cuda, target: NHW int64, class_weight: [C] fp32 on the logits' device or None.
+    -> (out[6] = [loss, n_valid, n_out_of_range_targets, n_kept, tau, sum of the kept pixels' weights], dlogits|None)."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.shape == (logits.shape[0],) + logits.shape[2:]
+    B, C, H, W = logits.shape
+    if class_weight is not None:
+        assert class_weight.device == logits.device and class_weight.dtype == torch.float32 and \
+            class_weight.is_contiguous() and class_weight.shape == (C,), 'class_weight: %d fp32 values on %s' % (C, logits.device)
+    dl = torch.empty_like(logits) if want_grad else None
+    out = torch.empty(6, dtype=torch.float32, device=logits.device)
+    nbytes = _lib.query('pseg_ce_opts_workspace_bytes', B, C, H * W)
+    ws = workspace.get(nbytes, logits.device)
+    _lib.call('pseg_ce_opts_fwd_bwd', logits.data_ptr(), target.data_ptr(), B, C, H * W, ignore_index, _ptr(class_weight),
+              float(label_smoothing), float(focal_gamma), float(keep_ratio), _ptr(dl), out.data_ptr(), ws.data_ptr(), nbytes,
+              _stream())
+    return out, dl
+
+
 # the Lovasz loss's sort buffers (hundreds of MiB at training sizes) get a cache of their own: allocated once per stream,
 # and the small scratch every conv shares stays small
 lovasz_workspace = _Workspace()

@@ -127,16 +127,98 @@ def _ce_lovasz_loss_fn(outputs, targets, model=None):
     return _CrossEntropyFn.apply(outputs, targets) + _LovaszSoftmaxFn.apply(outputs, targets, -100)
 
 
+class _CrossEntropyOptsFn(torch.autograd.Function):
+    """Cross-entropy with class weights, label smoothing, the focal factor and hard-pixel selection.  Built like
+    _CrossEntropyFn: forward runs pseg_ce_opts_fwd_bwd, which leaves the gradient with respect to the logits as well (the
+    kept set held fixed); backward only rescales it by the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, class_weight, label_smoothing, focal_gamma, keep_ratio, ignore_index):
+        need = logits.requires_grad
+        out, dl = ops.ce_opts_fwd_bwd(logits, targets, class_weight, label_smoothing, focal_gamma, keep_ratio, want_grad=need,
+                                      ignore_index=ignore_index)
+        if CHECK_LABELS and out[2].item() != 0:     # (host sync: debugging aid, off by default)
+            raise IndexError('%d target values are outside [0, %d) and are not ignore_index'
+                             % (int(out[2].item()), logits.shape[1]))
+        ctx.dl = dl
+        ctx.mark_non_differentiable()
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        dl = ctx.dl
+        ctx.dl = None
+        if dl is None:
+            return (None,) * 7
+        g = g.reshape(1) if g.dtype == torch.float32 else g.float().reshape(1)
+        ops.scale_inplace(dl, g.contiguous())
+        return (dl,) + (None,) * 6
+
+
+def _class_weight_on(class_weight, device):
+    """None, a sequence or a tensor -> None or a contiguous fp32 tensor on `device`."""
+    if class_weight is None:
+        return None
+    return torch.as_tensor(class_weight, dtype=torch.float32).to(device).contiguous()
+
+
+def weighted_cross_entropy_loss(outputs, targets, class_weight=None, label_smoothing=0.0, focal_gamma=0.0, keep_ratio=1.0,
+                                ignore_index=-100):
+    """Cross-entropy of NCHW logits with per-class weights and label smoothing (F.cross_entropy(weight=, label_smoothing=)
+    per pixel), times the focal factor (1 - p_t)^focal_gamma, averaged (weighted by the labels' class weights) over the
+    keep_ratio hardest valid pixels of the batch -- all of them at keep_ratio = 1.  One HIP call (pseg_ce_opts_fwd_bwd);
+    bit-reproducible."""
+    outputs, targets = _logits_at_target_size(outputs, targets)
+    w = _class_weight_on(class_weight, outputs.device)
+    if w is not None and w.numel() != outputs.shape[1]:
+        raise ValueError('class_weight has %d values for %d classes' % (w.numel(), outputs.shape[1]))
+    return _CrossEntropyOptsFn.apply(outputs, targets, w, float(label_smoothing), float(focal_gamma), float(keep_ratio),
+                                     ignore_index)
+
+
 LOSSES = {'ce': compute_loss, 'lovasz': _lovasz_loss_fn, 'ce+lovasz': _ce_lovasz_loss_fn}
+CE_OPTIONS = {'class_weight': None, 'label_smoothing': 0.0, 'focal_gamma': 0.0, 'keep_ratio': 1.0}
 
 
-def make_loss(name):
-    """'ce' | 'lovasz' | 'ce+lovasz' -> loss_fn(outputs, targets, model) for Trainer(loss_fn=...).  'ce' is compute_loss
-    itself (the Trainer's fused fast path keys on that object); the others go through the Trainer's autograd route."""
-    try:
-        return LOSSES[name]
-    except KeyError:
+def _configured_ce(name, opts):
+    """loss_fn(outputs, targets, model) of 'ce' / 'ce+lovasz' with the cross-entropy configured by `opts`"""
+    state = {'w': opts['class_weight'], 'device': None}
+    ls, fg, kr = float(opts['label_smoothing']), float(opts['focal_gamma']), float(opts['keep_ratio'])
+
+    def weight_on(device):      # moved to the logits' device once
+        if state['w'] is not None and state['device'] != device:
+            state['w'], state['device'] = _class_weight_on(state['w'], device), device
+        return state['w']
+
+    def _ce_opts_loss_fn(outputs, targets, model=None):
+        return weighted_cross_entropy_loss(outputs, targets, weight_on(outputs.device), ls, fg, kr)
+
+    def _ce_opts_lovasz_loss_fn(outputs, targets, model=None):
+        outputs, targets = _logits_at_target_size(outputs, targets)
+        return (weighted_cross_entropy_loss(outputs, targets, weight_on(outputs.device), ls, fg, kr)
+                + _LovaszSoftmaxFn.apply(outputs, targets, -100))
+
+    return _ce_opts_loss_fn if name == 'ce' else _ce_opts_lovasz_loss_fn
+
+
+def make_loss(name, **ce_options):
+    """'ce' | 'lovasz' | 'ce+lovasz' -> loss_fn(outputs, targets, model) for Trainer(loss_fn=...).  'ce' without options is
+    compute_loss itself (the Trainer's fused fast path keys on that object); everything else goes through the Trainer's
+    autograd route.  ce_options (class_weight=, label_smoothing=, focal_gamma=, keep_ratio=) configure the cross-entropy of
+    'ce' and 'ce+lovasz' (weighted_cross_entropy_loss); an option left at its default (None, 0, 0, 1) is not an option."""
+    if name not in LOSSES:
         raise ValueError('unknown loss %r (choose from %s)' % (name, ', '.join(sorted(LOSSES))))
+    unknown = sorted(set(ce_options) - set(CE_OPTIONS))
+    if unknown:
+        raise TypeError('unknown cross-entropy option(s) %s (choose from %s)' % (', '.join(unknown), ', '.join(sorted(CE_OPTIONS))))
+    opts = dict(CE_OPTIONS, **ce_options)
+    is_set = opts['class_weight'] is not None or any(float(opts[k]) != CE_OPTIONS[k] for k in
+                                                      ('label_smoothing', 'focal_gamma', 'keep_ratio'))
+    if not is_set:
+        return LOSSES[name]
+    if name == 'lovasz':
+        raise ValueError("the cross-entropy options do not apply to 'lovasz' (use 'ce' or 'ce+lovasz')")
+    return _configured_ce(name, opts)
 
 
 def predict_mask(outputs):

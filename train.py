@@ -4,7 +4,7 @@ on the MI355X HIP path.
 
     python3 train.py data/<custom> [--epochs N] [-s W H] [-bs N] [-a ACC] [--lr LR] [--adam] [--resume]
                      [--weights F] [--notest] [--nosave] [--model unet|deeplabv3plus] [--augment | --augment-full | --augment-warps]
-                     [--loss ce|lovasz|ce+lovasz]
+                     [--loss ce|lovasz|ce+lovasz] [--class-weights W0 W1 ...] [--label-smoothing E] [--focal-gamma G] [--ohem-keep R]
     python3 -m torch.distributed.run --nproc-per-node <n> train.py data/<custom>        # RCCL data parallel
 
 Differences from the reference that are visible here: the model is picked with --model (the reference edits
@@ -34,6 +34,8 @@ MODELS = {'deeplabv3plus': DeepLabV3Plus, 'unet': UNet, 'hrnet': HRNet}
 # what train() minimises: main() sets it from --loss (train()'s keyword surface is the reference's and stays as it is);
 # the validation loss test.py reports is cross-entropy whatever is chosen here
 LOSS_FN = compute_loss
+# --class-weights as given, or None: train() checks their number against the data set's classes
+CLASS_WEIGHTS = None
 
 
 def _loader(dataset, batch_size, num_workers, train=True):
@@ -60,6 +62,8 @@ def train(data_dir, epochs=100, img_size=(320, 320), batch_size=32, accumulate=2
     if not notest:
         val_data = CocoInstance(osp.join(data_dir, 'val.json'), img_size=list(img_size), augments=None, rect=rect)
         val_fetcher = Fetcher(_loader(val_data, batch_size, num_workers, train=False), post_fetch_fn=val_data.post_fetch_fn)
+    if CLASS_WEIGHTS is not None and len(CLASS_WEIGHTS) != len(train_data.classes):
+        raise ValueError('--class-weights has %d values, the data set has %d classes' % (len(CLASS_WEIGHTS), len(train_data.classes)))
     model = MODELS[model_name](len(train_data.classes))
     trainer = Trainer(model, train_fetcher, loss_fn=LOSS_FN, workdir='weights', accumulate=accumulate, adam=adam,
                       lr=lr, weights=weights, resume=resume, mixed_precision=mixed_precision)
@@ -110,13 +114,28 @@ def build_parser():
     ap.add_argument('--loss', choices=['ce', 'lovasz', 'ce+lovasz'], default='ce',
                     help='training objective: per-pixel cross-entropy, the Lovasz-softmax surrogate of the mean IoU '
                          '(classes present in the batch), or their sum')
+    ap.add_argument('--class-weights', type=float, nargs='+', default=None, metavar='W',
+                    help='per-class weights of the cross-entropy, one value per class (ce and ce+lovasz)')
+    ap.add_argument('--label-smoothing', type=float, default=0.0, metavar='E', help='label smoothing of the cross-entropy, in [0, 1)')
+    ap.add_argument('--focal-gamma', type=float, default=0.0, metavar='G',
+                    help='focal modulation (1 - p_t)^G of the cross-entropy: 0 (off) or a value in [1, 8]')
+    ap.add_argument('--ohem-keep', type=float, default=1.0, metavar='R',
+                    help='online hard-example mining: average the cross-entropy over the share R in (0, 1] of the valid '
+                         'pixels of a batch with the largest loss')
     return ap
 
 
+def loss_from_options(opt):
+    """(loss_fn, class weights or None) of the parsed --loss / --class-weights / --label-smoothing / --focal-gamma /
+    --ohem-keep; with none of the four given this is make_loss(opt.loss), as before"""
+    return make_loss(opt.loss, class_weight=opt.class_weights, label_smoothing=opt.label_smoothing,
+                     focal_gamma=opt.focal_gamma, keep_ratio=opt.ohem_keep), opt.class_weights
+
+
 def main():
-    global LOSS_FN
+    global LOSS_FN, CLASS_WEIGHTS
     opt = build_parser().parse_args()
-    LOSS_FN = make_loss(opt.loss)
+    LOSS_FN, CLASS_WEIGHTS = loss_from_options(opt)
 
     if os.environ.get('WORLD_SIZE'):
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
