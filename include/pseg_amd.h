@@ -58,7 +58,9 @@ extern "C" {
 #define PSEG_ACT_RELU 1
 #define PSEG_ACT_RELU6 2
 
-/* bumped whenever an existing prototype changes incompatibly or entry points are added; pseg_abi_version() returns the value the library was built with */
+/* bumped whenever an existing prototype changes incompatibly; pseg_abi_version() returns the value the library was built with.
+ * Entry points added since 14 (pseg_image_preprocess_views, pseg_softmax_views, pseg_seg_decode_ensemble) are purely
+ * additive and do not bump it: the loader checks every declared prototype against the library's exports by name. */
 #define PSEG_ABI_VERSION 14
 int pseg_abi_version(void);
 const char* pseg_last_error(void);
@@ -498,6 +500,51 @@ int pseg_image_preprocess(const uint8_t* src, int64_t src_bytes, const int64_t* 
                           float mean2, float std0, float std1, float std2, float* out, int oh, int ow, void* stream);
 int pseg_seg_decode(const float* logits, int B, int C, int h, int w, const int64_t* table, int64_t npix_total, uint8_t* mask,
                     uint8_t* rgb, const uint8_t* lut, void* stream);
+
+/* ------------------------------------------------------------------ test-time ensembling (csrc/infer.hip)
+ * Multi-scale and mirrored prediction, the evaluation protocol DeepLabV3+ and HRNet figures are published with.
+ * Scales: for a model input size (h, w) and scales s_1..s_S (1 <= S <= 8) the size at scale s is
+ *   (max(32, int(h*s/32)*32), max(32, int(w*s/32)*32)) -- the training loader's multi-scale rule; scales that give the
+ *   same size are merged by the host.
+ * Views: with flipping each scale has two views, the image and the image mirrored left-right; K = S * (2 or 1).
+ * Ensemble, for a photo of H x W:
+ *   P = sum over the views of bilinear(unmirror(softmax_c(logits_view)), (H, W), align_corners=False)
+ *   mask = argmax_c P, the first index winning ties.
+ * The sum is unweighted (the argmax does not see the 1/K).  One map at scale 1 without flipping is pseg_seg_decode's
+ * definition.
+ *
+ * pseg_image_preprocess_views: pseg_image_preprocess with `rows` table records of FOUR int64 {byte offset, H, W, flags};
+ *   several records may name the same photo; out is [rows,3,oh,ow].  Flag PSEG_VIEW_MIRROR mirrors the OUTPUT row:
+ *   out[r,c,y,x] is the unflagged value at column ow-1-x (the resampled result is mirrored, not the photo), so a
+ *   flagged record equals the unflagged one flipped along x bit for bit, and a record with flags 0 equals
+ *   pseg_image_preprocess bit for bit.  The table lives on the device, so the host states in `flag_mask` which flag bits
+ *   its records use: a flag_mask with unknown bits is refused on the host, and a record with a flag bit outside
+ *   flag_mask is skipped on the device like a record that leaves src.
+ * pseg_softmax_views: logits fp32 NCHW [n,C,h,w], n = B (pairs = 0) or 2B (pairs = 1: rows B..2B-1 are the logits of the
+ *   mirrored inputs of rows 0..B-1).  Writes the probability map [B,h,w,CP] fp32, pixel-major, at prob + prob_offset
+ *   (floats; prob 16-byte aligned, prob_offset a multiple of 4, the map inside prob_floats): CP = 8 for C <= 8,
+ *   otherwise C rounded up to a multiple of 4 (pseg_seg_decode's padding); lanes C..CP-1 are written as 0.
+ *   out[b,y,x,:] = softmax(logits[b,:,y,x]) (+ softmax(logits[B+b,:,y,w-1-x]) with pairs: the mirrored twin is
+ *   un-mirrored and added here -- bilinear resizing is linear, so this is the ensemble's sum).  One softmax per source
+ *   pixel and view.  1 <= C <= 256.
+ * pseg_seg_decode_ensemble: prob is the packed buffer of prob_floats floats holding S maps; maps is a device array of S
+ *   records of three int64 {float offset, h_s, w_s}, map s being [B,h_s,w_s,CP] as pseg_softmax_views writes it
+ *   (1 <= S <= 8).  table, npix_total, mask, rgb, lut as pseg_seg_decode: for each b,
+ *   mask[table[b].offset + y*W + x] = argmax_c sum_s bilinear(map_s[b], (H, W), align_corners=False)[y, x, c], uint8,
+ *   first index on ties, fp32 with pseg_seg_decode's tap geometry.  Hmax, Wmax: the largest H and W of the table; they
+ *   size the grid.  Skipped on the device, nothing read or written: a table record whose extent leaves the mask buffer or
+ *   whose H > Hmax or W > Wmax; and, if ANY map record leaves prob (or has a misaligned offset or a size outside
+ *   [1, 65535]), every image -- there is no ensemble without all its maps.  No C-channel tensor at photo size exists.
+ */
+#define PSEG_VIEW_MIRROR 1
+int pseg_image_preprocess_views(const uint8_t* src, int64_t src_bytes, const int64_t* table, int rows, int flag_mask, int bgr,
+                                float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh,
+                                int ow, void* stream);
+int pseg_softmax_views(const float* logits, int B, int pairs, int C, int h, int w, float* prob, int64_t prob_offset,
+                       int64_t prob_floats, void* stream);
+int pseg_seg_decode_ensemble(const float* prob, int64_t prob_floats, const int64_t* maps, int S, int B, int C, const int64_t* table,
+                             int64_t npix_total, int Hmax, int Wmax, uint8_t* mask, uint8_t* rgb, const uint8_t* lut,
+                             void* stream);
 
 /* ------------------------------------------------------------------ training augmentation (csrc/augment.hip)
  * The geometric and colour-affine part of the reference's online augmentation (utils/datasets.py:26-125, imgaug on the

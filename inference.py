@@ -2,13 +2,15 @@
 """Inference entry point with the reference's flags (reference inference.py:41-58) on the MI355X HIP path.
 
     python3 inference.py data/samples outputs --weights weights.pth [-s W H] [-nc N] [-bs N] [--model ...] [-mp]
-                         [--norm dataset|reference]
+                         [--norm dataset|reference] [--scales S [S ...]] [--flip]
 
 Every file of img_dir whose extension is in IMG_EXT (case-sensitive, as the reference) is segmented, in name order, and
 written to output_dir as <name>.png in VOC colours.  Photos are decoded with PIL (RGB); resizing, normalisation, softmax,
 the resize of the probabilities to each photo's size and the argmax run on the device (utils/inference.py), -bs photos
 per batch.  Unlike the reference, output_dir is created but never emptied: deleting a directory the user names is not
 something an inference tool should do.  --show is accepted and ignored (the reference never used it either).
+--scales and --flip turn on test-time ensembling: the class probabilities of every scale of the model input (sizes in
+multiples of 32), and with --flip of the left-right mirrored photo as well, are summed at the photo's size before the argmax.
 """
 import argparse
 import os
@@ -37,7 +39,7 @@ def load_image(path):
 
 
 def run(img_dir, output_dir, img_size, num_classes, weights, show=False, model_name='deeplabv3plus', batch_size=1,
-        half=False, norm='dataset'):
+        half=False, norm='dataset', scales=None, flip=False):
     if show:
         _warn_ignored('--show', 'the reference accepts it and never displays anything either')
     os.makedirs(output_dir, exist_ok=True)
@@ -47,10 +49,11 @@ def run(img_dir, output_dir, img_size, num_classes, weights, show=False, model_n
     model = model.cuda()
     model.eval()
     names = list_images(img_dir)
+    tta = {} if scales is None and not flip else {'scales': scales, 'flip': bool(flip)}
     for i in range(0, len(names), max(1, batch_size)):
         batch = names[i:i + max(1, batch_size)]
         imgs = [load_image(osp.join(img_dir, n)) for n in batch]
-        _, colored = inference(model, imgs, tuple(img_size), norm=norm, bgr=False, half=half, colors=PALETTE_RGB)
+        _, colored = inference(model, imgs, tuple(img_size), norm=norm, bgr=False, half=half, colors=PALETTE_RGB, **tta)
         for name, seg in zip(batch, colored):
             Image.fromarray(seg).save(osp.join(output_dir, osp.splitext(name)[0] + '.png'))
         print('%d/%d' % (min(i + batch_size, len(names)), len(names)), flush=True)
@@ -70,10 +73,13 @@ def main(argv=None):
     parser.add_argument('-mp', '--mix_precision', action='store_true', help='half-precision forward')
     parser.add_argument('--norm', choices=sorted(NORMS), default='dataset',
                         help="'dataset': the training loader's mean/std (default); 'reference': /255 as the reference")
+    parser.add_argument('--scales', type=float, nargs='+', default=None, metavar='S',
+                        help='test-time ensembling: factors on --img_size (sizes in multiples of 32), e.g. 0.5 1.0 1.5')
+    parser.add_argument('--flip', action='store_true', help='test-time ensembling: add the left-right mirrored view')
     opt = parser.parse_args(argv)
     print(opt)
     run(opt.img_dir, opt.output_dir, opt.img_size, opt.num_classes, opt.weights, opt.show, opt.model, opt.batch_size,
-        opt.mix_precision, opt.norm)
+        opt.mix_precision, opt.norm, opt.scales, opt.flip)
 
 
 if __name__ == '__main__':

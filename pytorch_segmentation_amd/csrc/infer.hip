@@ -10,6 +10,15 @@
 //    upper-left tap lies in the tile is written by that block alone.  No full-resolution C-channel value is ever stored.
 //    A thread walks one output column down its rows and keeps the column-lerped probabilities of the two source rows it
 //    sits between in registers (C <= 32): the LDS is read 2C floats per SOURCE row it enters, not 4C per output pixel.
+// Test-time ensembling (several scales, each optionally with its left-right mirrored twin) stands on three more kernels:
+//  - image_preprocess_views: image_preprocess with a flag word per table row; bit 0 mirrors the OUTPUT row, so one launch
+//    gives the plain and the mirrored model input of every photo at one scale.
+//  - softmax_views: logits [n,C,h,w] -> probabilities [B,h,w,CP], pixel-major, classes padded to CP with zeros; with
+//    pairs the mirrored twin (batch row B + b) is un-mirrored and added, so a flip pair costs no storage of its own.
+//  - seg_decode_ensemble: argmax_c of the SUM over the S maps of bilinear(map_s, (H, W)).  Ownership is by OUTPUT tile
+//    (maps of different resolutions share no source tiling); a thread owns a short column of output pixels and reads the
+//    four taps of each map as 16-byte vectors straight from L1/L2 -- neighbouring pixels share them -- instead of
+//    staging S footprints of S different shapes in LDS (an 8x down-scaled photo's footprint would not fit anyway).
 #include "common.h"
 
 #include <math.h>
@@ -230,6 +239,175 @@ __global__ __launch_bounds__(256) void seg_decode_kernel(const float* __restrict
   }
 }
 
+// ------------------------------------------------------------------ test-time ensembling
+// image_preprocess_kernel with a flag word per row {byte offset, H, W, flags}.  Bit 0: out[b,c,y,x] is the unflagged
+// value at column ow - 1 - x (the resampled result is mirrored, not the photo).  The arithmetic is that kernel's,
+// expression for expression, so an unflagged row gives its bits.
+__global__ __launch_bounds__(256) void image_preprocess_views_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
+                                                                     const int64_t* __restrict__ table, int flag_mask, int bgr,
+                                                                     Norm nm, float* __restrict__ out, int oh, int ow) {
+  const int b = blockIdx.z, oy = blockIdx.y;
+  const int ox = blockIdx.x * 256 + threadIdx.x;
+  if (ox >= ow) return;
+  const int64_t off = table[4 * b], H = table[4 * b + 1], W = table[4 * b + 2], flags = table[4 * b + 3];
+  if (!entry_ok(off, H, W, 3, src_bytes) || (flags & ~(int64_t)flag_mask) != 0) return;   // bad row: nothing read or written
+  const InAxis ay{(float)H / (float)oh, (int)H, oh}, ax{(float)W / (float)ow, (int)W, ow};
+  const int sx = (flags & PSEG_VIEW_MIRROR) ? ow - 1 - ox : ox;      // the column of the unmirrored result
+  int y0, y1, x0, x1;
+  float ly0, ly1, lx0, lx1;
+  taps(ay, oy, y0, y1, ly0, ly1);
+  taps(ax, sx, x0, x1, lx0, lx1);
+  const uint8_t* p = src + off;
+  const uint8_t* p00 = p + ((int64_t)y0 * W + x0) * 3;
+  const uint8_t* p01 = p + ((int64_t)y0 * W + x1) * 3;
+  const uint8_t* p10 = p + ((int64_t)y1 * W + x0) * 3;
+  const uint8_t* p11 = p + ((int64_t)y1 * W + x1) * 3;
+  const int64_t plane = (int64_t)oh * ow;
+  float* o = out + (int64_t)b * 3 * plane + (int64_t)oy * ow + ox;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int cs = bgr ? 2 - k : k;
+    const float v = ly0 * (lx0 * (float)p00[cs] + lx1 * (float)p01[cs]) + ly1 * (lx0 * (float)p10[cs] + lx1 * (float)p11[cs]);
+    float q = floorf(v + 0.5f);
+    q = q < 0.f ? 0.f : (q > 255.f ? 255.f : q);
+    o[k * plane] = (q - nm.mean[k]) / nm.std[k];
+  }
+}
+
+// A block owns PX consecutive pixels of one source row (PX a power of two, 4 * PX <= 256).  The logits of the run -- and,
+// with pairs, of the mirrored run of batch row B + b, stored un-mirrored -- go to LDS pixel-major (global reads: consecutive
+// lanes, consecutive x of one class plane); four lanes share a pixel's softmax; the tile is then exactly the run's
+// [PX][CP] stretch of the output and leaves as 16-byte vectors.
+__global__ __launch_bounds__(256) void softmax_views_kernel(const float* __restrict__ logits, int B, int pairs, int C, int CP,
+                                                            int h, int w, int PX, int px_shift, int runs, float* __restrict__ out) {
+  extern __shared__ f32x4 T4[];
+  float* T = reinterpret_cast<float*>(T4);
+  const int tid = threadIdx.x;
+  const int run = blockIdx.x % runs, row = blockIdx.x / runs;      // row = b * h + y
+  const int b = row / h, y = row - b * h;
+  const int x0 = run * PX, npx = min(PX, w - x0);
+  const int64_t plane = (int64_t)h * w;
+  const int views = pairs ? 2 : 1;
+  for (int v = 0; v < views; ++v) {
+    const float* lb = logits + ((int64_t)(v * B + b) * C) * plane + (int64_t)y * w;
+    float* Tv = T + v * PX * CP;
+    for (int i = tid; i < C * PX; i += 256) {
+      const int c = i >> px_shift, px = i & (PX - 1);
+      if (px < npx) {
+        const int x = x0 + px;
+        Tv[px * CP + c] = lb[c * plane + (v ? w - 1 - x : x)];
+      }
+    }
+  }
+  __syncthreads();
+  const int n4 = CP / 4;
+  const int px = tid >> 2, q = tid & 3;
+  if (px < npx) {                                                    // whole quads take the branch together
+    for (int v = 0; v < views; ++v) {
+      f32x4* t = T4 + (v * PX + px) * n4;
+      float m = -INFINITY;
+      for (int j = q; j < n4; j += 4) {
+        const f32x4 u = t[j];
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (4 * j + e < C) m = fmaxf(m, u[e]);
+      }
+      m = fmaxf(m, __shfl_xor(m, 1, 64));
+      m = fmaxf(m, __shfl_xor(m, 2, 64));
+      // sixteen partial sums per pixel (four lanes x four vector lanes), combined as a tree: at C = 256 a partial adds 16
+      // terms, not 256 -- the rounding of one long running sum alone would use up the 4 ulp the map is held to
+      f32x4 s4 = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j = q; j < n4; j += 4) {
+        f32x4 u = t[j];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) u[e] = 4 * j + e < C ? expf(u[e] - m) : 0.f;
+        s4 += u;
+        t[j] = u;
+      }
+      float s = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+      s += __shfl_xor(s, 1, 64);
+      s += __shfl_xor(s, 2, 64);
+      for (int j = q; j < n4; j += 4) t[j] = t[j] / s;     // correctly rounded division: half an ulp less than * (1 / s)
+    }
+  }
+  __syncthreads();
+  f32x4* o = reinterpret_cast<f32x4*>(out) + ((int64_t)row * w + x0) * n4;
+  for (int i = tid; i < npx * n4; i += 256) o[i] = pairs ? T4[i] + T4[PX * n4 + i] : T4[i];
+}
+
+constexpr int kEnsTileW = 64, kEnsTileH = 16, kEnsMaxMaps = 8;
+
+__device__ __forceinline__ bool map_ok(int64_t off, int64_t h, int64_t w, int B, int CP, int64_t cap) {
+  return off >= 0 && (off & 3) == 0 && h >= 1 && w >= 1 && h <= 65535 && w <= 65535 && off + (int64_t)B * h * w * CP <= cap;
+}
+
+// A block owns a kEnsTileW x kEnsTileH rectangle of one image's pixels; a wave owns one row of it at a time (64 mask
+// bytes per store), a thread the pixels of its column in rows wave, wave + 4, ...  Per chunk of at most 32 classes the
+// bilinear samples of the S maps are summed in registers, then the running best is updated: classes are independent.
+__global__ __launch_bounds__(256) void seg_decode_ensemble_kernel(const float* __restrict__ prob, int64_t prob_floats,
+                                                                  const int64_t* __restrict__ maps, int S, int B, int C, int CP,
+                                                                  const int64_t* __restrict__ table, int64_t npix_cap,
+                                                                  int Hmax, int Wmax, uint8_t* __restrict__ mask,
+                                                                  uint8_t* __restrict__ rgb, const uint8_t* __restrict__ lut) {
+  const int b = blockIdx.z;
+  const int64_t off = table[3 * b], H = table[3 * b + 1], W = table[3 * b + 2];
+  if (!entry_ok(off, H, W, 1, npix_cap) || H > Hmax || W > Wmax) return;       // bad row: nothing read or written
+  const int oy_base = blockIdx.y * kEnsTileH, ox = blockIdx.x * kEnsTileW + (threadIdx.x & 63);
+  if (oy_base >= H || blockIdx.x * kEnsTileW >= W) return;                     // ragged batch: block-uniform exit
+  for (int s = 0; s < S; ++s)                                                  // one bad map: no ensemble, nothing written
+    if (!map_ok(maps[3 * s], maps[3 * s + 1], maps[3 * s + 2], B, CP, prob_floats)) return;
+  if (ox >= W) return;
+  const int n4 = CP / 4;
+  uint8_t* mb = mask + off;
+  uint8_t* rb = rgb ? rgb + 3 * off : nullptr;
+  const int oy_end = min(oy_base + kEnsTileH, (int)H);
+  for (int oy = oy_base + (threadIdx.x >> 6); oy < oy_end; oy += 4) {
+    float best = -1.f;
+    int bi = 0;
+    for (int c0 = 0; c0 < CP; c0 += 32) {
+      f32x4 acc[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int s = 0; s < S; ++s) {
+        const int64_t moff = maps[3 * s];
+        const int h = (int)maps[3 * s + 1], w = (int)maps[3 * s + 2];
+        const InAxis ay{(float)h / (float)H, h, (int)H}, ax{(float)w / (float)W, w, (int)W};
+        int y0, y1, x0, x1;
+        float ly0, ly1, lx0, lx1;
+        taps(ay, oy, y0, y1, ly0, ly1);
+        taps(ax, ox, x0, x1, lx0, lx1);
+        const f32x4* mp = reinterpret_cast<const f32x4*>(prob + moff) + (int64_t)b * h * w * n4 + c0 / 4;
+        const f32x4* a0 = mp + ((int64_t)y0 * w + x0) * n4;
+        const f32x4* a1 = mp + ((int64_t)y0 * w + x1) * n4;
+        const f32x4* b0 = mp + ((int64_t)y1 * w + x0) * n4;
+        const f32x4* b1 = mp + ((int64_t)y1 * w + x1) * n4;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+          if (c0 + 4 * k < CP) acc[k] += ly0 * (lx0 * a0[k] + lx1 * a1[k]) + ly1 * (lx0 * b0[k] + lx1 * b1[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        if (c0 + 4 * k < CP) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if (c0 + 4 * k + e < C && acc[k][e] > best) {   // strict: the first index wins ties
+              best = acc[k][e];
+              bi = c0 + 4 * k + e;
+            }
+          }
+        }
+      }
+    }
+    const int64_t o = (int64_t)oy * W + ox;
+    mb[o] = (uint8_t)bi;
+    if (rb) {
+      rb[3 * o] = lut[3 * bi];
+      rb[3 * o + 1] = lut[3 * bi + 1];
+      rb[3 * o + 2] = lut[3 * bi + 2];
+    }
+  }
+}
+
 }  // namespace pseg
 
 using namespace pseg;
@@ -274,6 +452,69 @@ int pseg_seg_decode(const float* logits, int B, int C, int h, int w, const int64
   else
     hipLaunchKernelGGL(seg_decode_kernel<32>, dim3(tiles_x * tiles_y, B), dim3(256), lds, st, logits, C, CP, h, w, TH, TW,
                        tiles_x, table, npix_total, mask, rgb, lut);
+  PSEG_LAUNCH_CHECK();
+  return PSEG_OK;
+}
+
+int pseg_image_preprocess_views(const uint8_t* src, int64_t src_bytes, const int64_t* table, int rows, int flag_mask, int bgr,
+                                float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh,
+                                int ow, void* stream) {
+  PSEG_REQUIRE(src && table && out, "image_preprocess_views: null pointer");
+  PSEG_REQUIRE((flag_mask & ~PSEG_VIEW_MIRROR) == 0, "image_preprocess_views: unknown flag bits 0x%x (known: PSEG_VIEW_MIRROR = 1)",
+               (unsigned)(flag_mask & ~PSEG_VIEW_MIRROR));
+  PSEG_REQUIRE(rows >= 1 && rows <= 65535, "image_preprocess_views: %d table rows outside [1, 65535]", rows);
+  PSEG_REQUIRE(oh >= 1 && oh <= 65535 && ow >= 1 && ow <= 65535, "image_preprocess_views: output size %dx%d outside [1, 65535]", oh,
+               ow);
+  PSEG_REQUIRE(src_bytes >= 3, "image_preprocess_views: src_bytes %lld holds no pixel", (long long)src_bytes);
+  PSEG_REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "image_preprocess_views: std must be non-zero");
+  Norm nm{{mean0, mean1, mean2}, {std0, std1, std2}};
+  hipLaunchKernelGGL(image_preprocess_views_kernel, dim3(cdiv(ow, 256), oh, rows), dim3(256), 0, (hipStream_t)stream, src,
+                     src_bytes, table, flag_mask, bgr ? 1 : 0, nm, out, oh, ow);
+  PSEG_LAUNCH_CHECK();
+  return PSEG_OK;
+}
+
+int pseg_softmax_views(const float* logits, int B, int pairs, int C, int h, int w, float* prob, int64_t prob_offset,
+                       int64_t prob_floats, void* stream) {
+  PSEG_REQUIRE(logits && prob, "softmax_views: null pointer");
+  PSEG_REQUIRE(pairs == 0 || pairs == 1, "softmax_views: pairs %d has unknown flag bits (0: plain rows, 1: plain + mirrored)", pairs);
+  PSEG_REQUIRE(C >= 1 && C <= 256, "softmax_views: %d classes; 1 <= C <= 256 supported", C);
+  PSEG_REQUIRE(B >= 1 && B <= 65535, "softmax_views: batch %d outside [1, 65535]", B);
+  PSEG_REQUIRE(h >= 1 && w >= 1 && h <= 65535 && w <= 65535, "softmax_views: logit size %dx%d outside [1, 65535]", h, w);
+  const int CP = C <= 8 ? 8 : (C + 3) / 4 * 4;
+  PSEG_REQUIRE(((uintptr_t)prob & 15) == 0 && prob_offset >= 0 && (prob_offset & 3) == 0,
+               "softmax_views: the probability buffer and the map's offset must be 16-byte aligned");
+  PSEG_REQUIRE(prob_offset + (int64_t)B * h * w * CP <= prob_floats,
+               "softmax_views: map [%d,%d,%d,%d] at float offset %lld leaves the buffer of %lld floats", B, h, w, CP,
+               (long long)prob_offset, (long long)prob_floats);
+  // pixels per block: both views of a run fit 32 KiB of LDS
+  const int PX = CP <= 64 ? 64 : (CP <= 128 ? 32 : 16), px_shift = PX == 64 ? 6 : (PX == 32 ? 5 : 4);
+  const int runs = cdiv(w, PX);
+  const long long blocks = (long long)B * h * runs;
+  PSEG_REQUIRE(blocks <= 0x7fffffffLL, "softmax_views: %lld blocks exceed the grid", blocks);
+  const size_t lds = (size_t)(pairs ? 2 : 1) * PX * CP * sizeof(float);
+  hipLaunchKernelGGL(softmax_views_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, logits, B, pairs, C, CP, h,
+                     w, PX, px_shift, runs, prob + prob_offset);
+  PSEG_LAUNCH_CHECK();
+  return PSEG_OK;
+}
+
+int pseg_seg_decode_ensemble(const float* prob, int64_t prob_floats, const int64_t* maps, int S, int B, int C, const int64_t* table,
+                             int64_t npix_total, int Hmax, int Wmax, uint8_t* mask, uint8_t* rgb, const uint8_t* lut,
+                             void* stream) {
+  PSEG_REQUIRE(prob && maps && table && mask, "seg_decode_ensemble: null pointer");
+  PSEG_REQUIRE((rgb == nullptr) == (lut == nullptr), "seg_decode_ensemble: rgb and lut come together");
+  PSEG_REQUIRE(S >= 1 && S <= kEnsMaxMaps, "seg_decode_ensemble: %d maps; 1 <= S <= %d supported", S, kEnsMaxMaps);
+  PSEG_REQUIRE(C >= 1 && C <= 256, "seg_decode_ensemble: %d classes; 1 <= C <= 256 supported (the mask is uint8)", C);
+  PSEG_REQUIRE(B >= 1 && B <= 65535, "seg_decode_ensemble: batch %d outside [1, 65535]", B);
+  PSEG_REQUIRE(Hmax >= 1 && Wmax >= 1 && Hmax <= 65535 && Wmax <= 65535, "seg_decode_ensemble: largest image %dx%d outside [1, 65535]",
+               Hmax, Wmax);
+  PSEG_REQUIRE(((uintptr_t)prob & 15) == 0, "seg_decode_ensemble: the probability buffer must be 16-byte aligned");
+  PSEG_REQUIRE(prob_floats >= 8 && npix_total >= 1, "seg_decode_ensemble: prob_floats %lld, npix_total %lld", (long long)prob_floats,
+               (long long)npix_total);
+  const int CP = C <= 8 ? 8 : (C + 3) / 4 * 4;
+  hipLaunchKernelGGL(seg_decode_ensemble_kernel, dim3(cdiv(Wmax, kEnsTileW), cdiv(Hmax, kEnsTileH), B), dim3(256), 0,
+                     (hipStream_t)stream, prob, prob_floats, maps, S, B, C, CP, table, npix_total, Hmax, Wmax, mask, rgb, lut);
   PSEG_LAUNCH_CHECK();
   return PSEG_OK;
 }

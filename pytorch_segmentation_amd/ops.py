@@ -1268,6 +1268,68 @@ def seg_decode(logits, table, npix_total, lut=None, out=None):
     return mask, rgb
 
 
+VIEW_MIRROR = 1         # PSEG_VIEW_MIRROR: flag bit of image_preprocess_views' table rows
+ENSEMBLE_MAX_MAPS = 8   # probability maps one seg_decode_ensemble call sums
+
+
+def class_pad(C):
+    """Floats per pixel of a probability map (softmax_views / seg_decode_ensemble): 8 for C <= 8, else C rounded up to 4."""
+    return 8 if C <= 8 else (C + 3) // 4 * 4
+
+
+def image_preprocess_views(src, table, oh, ow, mean, std, bgr, flag_mask=VIEW_MIRROR):
+    """image_preprocess with one flag word per table row (pseg_image_preprocess_views): table is an int64 device tensor
+    [R,4] of {byte offset, H, W, flags}, several rows may name one photo, -> fp32 [R,3,oh,ow].  A row flagged VIEW_MIRROR
+    is the unflagged result flipped along x, bit for bit; a row with flags 0 is image_preprocess's, bit for bit.
+    flag_mask: the flag bits the rows use -- unknown bits are refused, rows with bits outside it are skipped."""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
+    assert table.device == src.device and table.dtype == torch.int64 and table.is_contiguous() and table.dim() == 2
+    assert table.shape[1] == 4 and len(mean) == 3 and len(std) == 3
+    R = table.shape[0]
+    out = torch.empty(R, 3, oh, ow, dtype=torch.float32, device=src.device)
+    _lib.call('pseg_image_preprocess_views', src.data_ptr(), src.numel(), table.data_ptr(), R, int(flag_mask), int(bool(bgr)),
+              *[float(m) for m in mean], *[float(v) for v in std], out.data_ptr(), oh, ow, _stream())
+    return out
+
+
+def softmax_views(logits, prob, offset, pairs=False):
+    """NCHW fp32 logits [n,C,h,w] -> the probability map [B,h,w,class_pad(C)] (pixel-major, pad lanes 0) written into the
+    flat fp32 device tensor prob at float offset `offset` (a multiple of 4) (pseg_softmax_views).  pairs: n = 2B, rows
+    B..2B-1 are the logits of the mirrored inputs of rows 0..B-1; each is un-mirrored and added to its twin's softmax.
+    -> the map as a [B,h,w,CP] view of prob."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
+    assert prob.device == logits.device and prob.dtype == torch.float32 and prob.is_contiguous() and prob.dim() == 1
+    n, C, h, w = logits.shape
+    assert not pairs or n % 2 == 0
+    B = n // 2 if pairs else n
+    CP = class_pad(C)
+    _lib.call('pseg_softmax_views', logits.data_ptr(), B, int(bool(pairs)), C, h, w, prob.data_ptr(), int(offset), prob.numel(),
+              _stream())
+    return prob[offset:offset + B * h * w * CP].view(B, h, w, CP)
+
+
+def seg_decode_ensemble(prob, maps, B, C, table, npix_total, max_hw, lut=None, out=None):
+    """Per-image uint8 masks argmax_c sum_s bilinear(map_s, (H, W)) (pseg_seg_decode_ensemble), first index on ties.  prob:
+    the flat fp32 device tensor softmax_views filled; maps: int64 device tensor [S,3] of {float offset, h_s, w_s}, S <=
+    ENSEMBLE_MAX_MAPS; table: int64 device tensor [B,3] of {pixel offset, H, W}; max_hw = (largest H, largest W) of the
+    table (it sizes the grid; larger images are skipped).  npix_total, lut, out and the result are seg_decode's."""
+    assert prob.is_cuda and prob.dtype == torch.float32 and prob.is_contiguous() and prob.dim() == 1
+    assert maps.device == prob.device and maps.dtype == torch.int64 and maps.is_contiguous()
+    assert maps.dim() == 2 and maps.shape[1] == 3
+    assert table.device == prob.device and table.dtype == torch.int64 and table.is_contiguous() and table.shape == (B, 3)
+    nbytes = npix_total * (1 if lut is None else 4)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=prob.device)
+    assert out.device == prob.device and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == nbytes
+    mask, rgb = out[:npix_total], None
+    if lut is not None:
+        assert lut.device == prob.device and lut.dtype == torch.uint8 and lut.is_contiguous() and lut.shape == (256, 3)
+        rgb = out[npix_total:].view(npix_total, 3)
+    _lib.call('pseg_seg_decode_ensemble', prob.data_ptr(), prob.numel(), maps.data_ptr(), maps.shape[0], B, C, table.data_ptr(),
+              npix_total, int(max_hw[0]), int(max_hw[1]), mask.data_ptr(), _ptr(rgb), _ptr(lut), _stream())
+    return mask, rgb
+
+
 AUGMENT_ROW = 24        # PSEG_AUGMENT_ROW: floats per sample of augment_batch's parameter table (layout: include/pseg_amd.h)
 
 

@@ -10,7 +10,19 @@ copy) and receives masks and colours in ONE device-to-host copy.
 Normalisation is a decision, not a copy: ``norm='dataset'`` (default) applies the loader's MEAN / STD -- what weights
 trained with train.py expect; ``norm='reference'`` divides by 255 only, as the reference's inference does although its
 own training normalised with mean / std.
+
+Test-time ensembling (``scales=``, ``flip=``): the class probabilities of several scales, each optionally with its
+left-right mirrored twin, are summed at the photo's size before the argmax -- the evaluation protocol DeepLabV3+ and HRNet
+figures are published with.  The size at scale s of a model input (h, w) is ``(max(32, int(h*s/32)*32), max(32,
+int(w*s/32)*32))``, the training loader's multi-scale rule (``tta_sizes``); scales that give the same size are merged.  Per
+scale one ``ops.image_preprocess_views`` launch makes the plain and the mirrored inputs, one forward runs, and
+``ops.softmax_views`` adds a pair's two softmaxes (the twin un-mirrored) into one map of a packed buffer; one
+``ops.seg_decode_ensemble`` then sums the bilinear samples of all maps per photo pixel and takes the argmax, first index
+on ties.  The sum is unweighted.
 """
+import math
+import warnings
+
 import numpy as np
 import torch
 
@@ -42,17 +54,87 @@ def lut_of(colors):
     return lut
 
 
+def tta_sizes(h, w, scales):
+    """The distinct (h_s, w_s) of a model input (h, w) at `scales`, in first-seen order: the training loader's multi-scale
+    rule, sizes in multiples of 32.  Scales must be finite and > 0; scales that give the same size are merged with a
+    warning; at most ops.ENSEMBLE_MAX_MAPS sizes."""
+    scales = [float(s) for s in scales]
+    if not scales:
+        raise ValueError('scales is empty')
+    sizes = []
+    for s in scales:
+        if not math.isfinite(s) or s <= 0:
+            raise ValueError('scales must be finite and > 0; got %r' % (s,))
+        hw = (max(32, int(h * s / 32) * 32), max(32, int(w * s / 32) * 32))
+        if hw in sizes:
+            warnings.warn('scale %g gives the model input size %dx%d of an earlier scale; merged' % (s, hw[0], hw[1]),
+                          RuntimeWarning, stacklevel=3)
+        else:
+            sizes.append(hw)
+    if len(sizes) > ops.ENSEMBLE_MAX_MAPS:
+        raise ValueError('%d distinct sizes; at most %d scales are ensembled' % (len(sizes), ops.ENSEMBLE_MAX_MAPS))
+    return sizes
+
+
+def map_offsets(B, sizes):
+    """-> (pixel offset of each scale's [B,h_s,w_s] map in the packed buffer, pixels in all); times ops.class_pad(C) = floats"""
+    cells = [B * hs * ws for hs, ws in sizes]
+    return [sum(cells[:i]) for i in range(len(cells))], sum(cells)
+
+
+class Ensemble:
+    """The packed probability maps of one batch: ``add`` each scale's logits in the order of `sizes`, then ``decode``.
+    dmaps (optional): int64 device tensor [S,3] of {PIXEL offset (map_offsets), h_s, w_s} that travelled with the caller's
+    own host-to-device copy; it is turned into float offsets in place once the class count is known.  Without it the
+    table is built and copied at the first ``add``.  The buffer is sized once, at the first ``add``."""
+
+    def __init__(self, B, sizes, pairs, dmaps=None):
+        assert 1 <= len(sizes) <= ops.ENSEMBLE_MAX_MAPS
+        self.B, self.sizes, self.pairs, self.dmaps = B, list(sizes), bool(pairs), dmaps
+        self.offsets, self.cells = map_offsets(B, self.sizes)
+        self.prob, self.C, self.CP, self.n = None, None, None, 0
+
+    def add(self, logits):
+        n, C, hs, ws = logits.shape
+        assert self.n < len(self.sizes) and (hs, ws) == self.sizes[self.n] and n == self.B * (2 if self.pairs else 1)
+        if self.prob is None:
+            self.C, self.CP = C, ops.class_pad(C)
+            self.prob = torch.empty(self.cells * self.CP, dtype=torch.float32, device=logits.device)
+            if self.dmaps is None:
+                rows = [[o * self.CP, hs_, ws_] for o, (hs_, ws_) in zip(self.offsets, self.sizes)]
+                self.dmaps = torch.tensor(rows, dtype=torch.int64).to(logits.device)
+            else:
+                self.dmaps[:, 0] *= self.CP         # device arithmetic on S numbers: no host round trip
+        assert C == self.C
+        ops.softmax_views(logits.contiguous(), self.prob, self.offsets[self.n] * self.CP, self.pairs)
+        self.n += 1
+
+    def decode(self, table, npix_total, max_hw, lut=None, out=None):
+        assert self.n == len(self.sizes)
+        return ops.seg_decode_ensemble(self.prob, self.dmaps, self.B, self.C, table, npix_total, max_hw, lut, out)
+
+
 @torch.no_grad()
-def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=False, colors=None):
+def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=False, colors=None, scales=None, flip=False):
     """The reference's contract: ``imgs`` is a list of uint8 H x W x 3 photos (numpy arrays, or CPU or device tensors),
     ``img_size`` = (w, h) of the model input as cv2.resize takes it; returns one int64 numpy H x W mask per photo, at
     that photo's own size.  ``bgr=True``: the photos are cv2.imread output (B, G, R).  ``half=True``: the forward runs
     under the half-precision policy.  ``colors``: an [N, 3] uint8 palette -- then returns (masks, images) with images[i]
-    = colors[masks[i]] as uint8 H x W x 3 (classes >= N black)."""
+    = colors[masks[i]] as uint8 H x W x 3 (classes >= N black).
+
+    ``scales`` (a sequence of factors on the model input size, see ``tta_sizes``) and ``flip`` (add every scale's
+    left-right mirrored view) turn on test-time ensembling: mask = argmax_c of the unweighted sum, over all views, of the
+    un-mirrored softmax resized bilinearly (align_corners=False) to the photo's size; first index on ties.  ``scales`` None
+    or (1.0,) without ``flip`` is the single forward above, bit for bit."""
     if norm not in NORMS:
         raise ValueError('norm must be one of %s' % sorted(NORMS))
     mean, std = NORMS[norm]
     w, h = int(img_size[0]), int(img_size[1])
+    flip = bool(flip)
+    if scales is not None:
+        scales = tuple(float(s) for s in scales)
+    tta = flip or (scales is not None and scales != (1.0,))
+    sizes = tta_sizes(h, w, scales if scales is not None else (1.0,)) if tta else None
     photos = [_photo(im) for im in imgs]
     if not photos:
         return ([], []) if colors is not None else []
@@ -60,6 +142,10 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
     if device.type != 'cuda':
         raise RuntimeError('inference() runs on the HIP path: move the model to the GPU first')
     B = len(photos)
+    if tta:
+        if B * (2 if flip else 1) > 65535:
+            raise ValueError('%d photos x %d views exceed 65535 rows per launch' % (B, 2 if flip else 1))
+        return _inference_ensemble(model, photos, h, w, sizes, flip, mean, std, bgr, half, colors, device)
     sizes = np.array([(H, W) for _, H, W in photos], dtype=np.int64)
     npix = sizes[:, 0] * sizes[:, 1]
     pix_off = np.concatenate([[0], np.cumsum(npix)[:-1]])
@@ -89,6 +175,61 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
     ops.seg_decode(logits.contiguous(), dtables[1], total_pix, lut, out=out)
 
     # one device-to-host copy of masks (and colours)
+    host = torch.empty(out.numel(), dtype=torch.uint8, pin_memory=True)
+    host.copy_(out, non_blocking=True)
+    torch.cuda.current_stream(device).synchronize()
+    hv = host.numpy()
+    masks = [hv[o:o + H * W].reshape(H, W).astype(np.int64) for o, (H, W) in zip(pix_off, sizes)]
+    if colors is None:
+        return masks
+    rgb = hv[total_pix:]
+    return masks, [rgb[3 * o:3 * (o + H * W)].reshape(H, W, 3).copy() for o, (H, W) in zip(pix_off, sizes)]
+
+
+def _inference_ensemble(model, photos, h, w, view_sizes, flip, mean, std, bgr, half, colors, device):
+    """inference() with several views: the same single staging buffer (now also carrying the view table and the map
+    table) and the same single copy back; per scale one preprocess launch, one forward, one softmax launch."""
+    B, S, V = len(photos), len(view_sizes), 2 if flip else 1
+    sizes = np.array([(H, W) for _, H, W in photos], dtype=np.int64)
+    npix = sizes[:, 0] * sizes[:, 1]
+    pix_off = np.concatenate([[0], np.cumsum(npix)[:-1]])
+    total_pix = int(npix.sum())
+    views = np.zeros((V * B, 4), dtype=np.int64)               # rows 0..B-1 plain, rows B..2B-1 mirrored
+    views[:, 0], views[:, 1], views[:, 2] = np.tile(3 * pix_off, V), np.tile(sizes[:, 0], V), np.tile(sizes[:, 1], V)
+    views[B:, 3] = ops.VIEW_MIRROR
+    decode = np.zeros((B, 3), dtype=np.int64)
+    decode[:, 0], decode[:, 1], decode[:, 2] = pix_off, sizes[:, 0], sizes[:, 1]
+    maps = np.zeros((S, 3), dtype=np.int64)                    # pixel offsets: Ensemble scales them by the class padding
+    maps[:, 0], maps[:, 1:] = map_offsets(B, view_sizes)[0], np.array(view_sizes, dtype=np.int64)
+    heads = [views.reshape(-1), decode.reshape(-1), maps.reshape(-1)]
+    head = 8 * sum(t.size for t in heads)
+
+    staging = torch.empty(head + 3 * total_pix, dtype=torch.uint8, pin_memory=True)
+    sv = staging.numpy()
+    sv[:head] = np.concatenate(heads).view(np.uint8)
+    for (img, _, _), o in zip(photos, pix_off):
+        if isinstance(img, np.ndarray):
+            sv[head + 3 * o:head + 3 * (o + img.shape[0] * img.shape[1])] = np.ascontiguousarray(img).reshape(-1)
+    dbuf = staging.to(device, non_blocking=True)
+    for (img, _, _), o in zip(photos, pix_off):
+        if isinstance(img, torch.Tensor):
+            dbuf[head + 3 * o:head + 3 * (o + img.shape[0] * img.shape[1])].copy_(img.to(device).reshape(-1))
+    words = dbuf[:head].view(torch.int64)
+    dviews = words[:views.size].view(V * B, 4)
+    ddecode = words[views.size:views.size + decode.size].view(B, 3)
+    dmaps = words[views.size + decode.size:].view(S, 3)
+
+    ens = Ensemble(B, view_sizes, flip, dmaps)
+    for hs, ws in view_sizes:
+        x = ops.image_preprocess_views(dbuf[head:], dviews, hs, ws, mean, std, bgr)
+        logits = _forward(model, x, half)
+        del x
+        ens.add(logits)
+        del logits                                             # released before the next scale's forward
+    lut = None if colors is None else torch.from_numpy(lut_of(colors)).to(device)
+    out = torch.empty(total_pix * (1 if lut is None else 4), dtype=torch.uint8, device=device)
+    ens.decode(ddecode, total_pix, (int(sizes[:, 0].max()), int(sizes[:, 1].max())), lut, out=out)
+
     host = torch.empty(out.numel(), dtype=torch.uint8, pin_memory=True)
     host.copy_(out, non_blocking=True)
     torch.cuda.current_stream(device).synchronize()

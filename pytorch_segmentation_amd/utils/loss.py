@@ -226,6 +226,38 @@ def predict_mask(outputs):
     return ops.argmax(outputs.contiguous())
 
 
+@torch.no_grad()
+def predict_mask_ensemble(model, inputs, out_hw, scales=(1.0,), flip=False, view_logits=None):
+    """Test-time-ensembled prediction for an already normalised device batch [B,3,H,W]: int64 [B,out_h,out_w] =
+    argmax_c of the unweighted sum, over the views, of the un-mirrored softmax resized bilinearly (align_corners=False) to
+    out_hw; first index on ties.  Views: ``inputs`` resized (F.interpolate bilinear, align_corners=False; the identity at
+    its own size) to every size of ``tta_sizes(H, W, scales)``, each also flipped along x with ``flip``.  The softmaxes
+    and the resize-sum-argmax are ops.softmax_views / ops.seg_decode_ensemble.  view_logits (optional): a dict that
+    receives {(h_s, w_s): that scale's logits}."""
+    import torch.nn.functional as F
+    from .inference import Ensemble, tta_sizes
+    if not inputs.is_cuda:
+        raise RuntimeError('predict_mask_ensemble runs on the HIP path only (got %s)' % inputs.device)
+    B, _, H, W = inputs.shape
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    sizes = tta_sizes(H, W, scales)
+    if B * (2 if flip else 1) > 65535:
+        raise ValueError('%d images x %d views exceed 65535 rows per launch' % (B, 2 if flip else 1))
+    ens = Ensemble(B, sizes, flip)
+    for hs, ws in sizes:
+        x = inputs if (hs, ws) == (H, W) else F.interpolate(inputs, (hs, ws), mode='bilinear', align_corners=False)
+        if flip:
+            x = torch.cat([x, torch.flip(x, [3])], 0)
+        logits = model(x.contiguous()).float()
+        if view_logits is not None:
+            view_logits[(hs, ws)] = logits
+        ens.add(logits)
+        del logits, x
+    table = torch.tensor([[b * oh * ow, oh, ow] for b in range(B)], dtype=torch.int64).to(inputs.device)
+    mask, _ = ens.decode(table, B * oh * ow, (oh, ow))
+    return mask.view(B, oh, ow).long()
+
+
 def update_class_counts(counters, predicted, targets):
     """Accumulate per-class tp / fn / fp (reference test.py:34-46) into the int64 device tensor counters[3][C]
     with one kernel instead of 3*C host synchronisations."""

@@ -2,11 +2,14 @@
 """Evaluation entry point with the reference's flags (reference test.py:76-105) on the MI355X HIP path.
 
     python3 test.py data/<custom>/val.json --weights weights/best.pt [-s W H] [-bs N] [--model deeplabv3plus|unet]
+                    [--scales S [S ...]] [--flip]
 
 `test(model, fetcher)` keeps the reference's contract: evaluates in eval mode without gradients, prints per-class
 (or the five worst classes') targets / precision / recall / IoU / F1 and returns the mean IoU.  The per-class
 tp/fn/fp bookkeeping runs as one device kernel per batch instead of 3 host synchronisations per class, and the
-distributed reduction is a single [3, num_classes] all-reduce.
+distributed reduction is a single [3, num_classes] all-reduce.  With --scales / --flip the counted prediction is the
+test-time ensemble (utils.predict_mask_ensemble: summed class probabilities of every scale and mirrored view at the target
+size); the printed loss stays that of the plain forward.
 """
 import argparse
 
@@ -15,15 +18,17 @@ from torch.utils.data import DataLoader
 
 from pytorch_segmentation_amd.models import DeepLabV3Plus, HRNet, UNet
 from pytorch_segmentation_amd.utils import (Fetcher, all_reduce_counters, broadcast_buffers, compute_loss, compute_metrics,
-                                            predict_mask, update_class_counts)
+                                            predict_mask, predict_mask_ensemble, update_class_counts)
 from pytorch_segmentation_amd.utils.datasets import CocoDataset
 
 MODELS = {'deeplabv3plus': DeepLabV3Plus, 'unet': UNet, 'hrnet': HRNet}
 
 
 @torch.no_grad()
-def test(model, fetcher):
+def test(model, fetcher, scales=None, flip=False):
     model.eval()
+    tta = scales is not None or flip
+    scales = (1.0,) if scales is None else tuple(scales)
     # distributed evaluation sums per-class counters over the ranks (reference test.py:51-58): they must all come from ONE
     # model, so every replica takes rank 0's BatchNorm running statistics first (DistributedDataParallel's broadcast_buffers)
     broadcast_buffers(model, 0)
@@ -32,13 +37,22 @@ def test(model, fetcher):
     counters = None
     loss_sum, batches = None, 0
     for inputs, targets in fetcher:
-        outputs = model(inputs)
+        if tta:
+            view_logits = {}
+            predicted = predict_mask_ensemble(model, inputs, targets.shape[1:], scales, flip, view_logits)
+            # the loss of the plain forward: the scale-1.0 unmirrored view, or one extra forward without scale 1.0
+            outputs = view_logits.get(tuple(inputs.shape[2:]))
+            del view_logits
+            outputs = model(inputs) if outputs is None else outputs[:inputs.shape[0]]
+        else:
+            outputs = model(inputs)
+            predicted = None
         loss = compute_loss(outputs, targets, model)
         loss_sum = loss if loss_sum is None else loss_sum + loss
         batches += 1
         if counters is None:
             counters = torch.zeros(3, nc, dtype=torch.int64, device=outputs.device)
-        update_class_counts(counters, predict_mask(outputs), targets)
+        update_class_counts(counters, predict_mask(outputs) if predicted is None else predicted, targets)
     if counters is None:
         return 0.0
     all_reduce_counters(counters)
@@ -65,6 +79,9 @@ def main():
     ap.add_argument('-bs', '--batch-size', type=int, default=32)
     ap.add_argument('--num-workers', type=int, default=4)
     ap.add_argument('--model', choices=sorted(MODELS), default='deeplabv3plus')
+    ap.add_argument('--scales', type=float, nargs='+', default=None, metavar='S',
+                    help='test-time ensembling: factors on the input size (sizes in multiples of 32), e.g. 0.5 1.0 1.5')
+    ap.add_argument('--flip', action='store_true', help='test-time ensembling: add the left-right mirrored view')
     opt = ap.parse_args()
     data = CocoDataset(opt.val, img_size=opt.img_size, augments=None, rect=opt.rect)
     loader = DataLoader(data, batch_size=opt.batch_size, pin_memory=True, num_workers=opt.num_workers)
@@ -72,7 +89,7 @@ def main():
     model = MODELS[opt.model](len(data.classes))
     if opt.weights:
         model.load_state_dict(torch.load(opt.weights, map_location='cpu')['model'])
-    print('metrics: %8g' % test(model.cuda(), fetcher))
+    print('metrics: %8g' % test(model.cuda(), fetcher, opt.scales, opt.flip))
 
 
 if __name__ == '__main__':
