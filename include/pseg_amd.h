@@ -59,7 +59,8 @@ extern "C" {
 #define PSEG_ACT_RELU6 2
 
 /* bumped whenever an existing prototype changes incompatibly; pseg_abi_version() returns the value the library was built with.
- * Entry points added since 14 (pseg_image_preprocess_views, pseg_softmax_views, pseg_seg_decode_ensemble) are purely
+ * Entry points added since 14 (pseg_image_preprocess_views, pseg_softmax_views, pseg_seg_decode_ensemble, and the
+ * connected-region calls pseg_regions_workspace_bytes, pseg_mask_label, pseg_mask_regions, pseg_mask_clean) are purely
  * additive and do not bump it: the loader checks every declared prototype against the library's exports by name. */
 #define PSEG_ABI_VERSION 14
 int pseg_abi_version(void);
@@ -545,6 +546,54 @@ int pseg_softmax_views(const float* logits, int B, int pairs, int C, int h, int 
 int pseg_seg_decode_ensemble(const float* prob, int64_t prob_floats, const int64_t* maps, int S, int B, int C, const int64_t* table,
                              int64_t npix_total, int Hmax, int Wmax, uint8_t* mask, uint8_t* rgb, const uint8_t* lut,
                              void* stream);
+
+/* ------------------------------------------------------------------ connected regions of the masks (csrc/regions.hip)
+ * The step after the argmax: label the connected regions of each mask, describe them, and clean the mask.  mask, table,
+ * npix_total, Hmax and Wmax are pseg_seg_decode_ensemble's: a packed buffer of npix_total uint8 pixels under a device table
+ * of B records {pixel offset, H, W}.  A record whose extent leaves the buffer, or whose H > Hmax or W > Wmax, is skipped on
+ * the device: nothing is read or written for it.  Hmax * Wmax < 2^31 (labels are int32), otherwise PSEG_ERR_ARG.  A
+ * component is a maximal connected set of pixels of one class value; every value 0..255 is a class, background included.
+ * Integer arithmetic only (integer atomics, no floating point anywhere), a fixed number of launches, no host
+ * synchronisation.  These entry points are additive: PSEG_ABI_VERSION does not move.
+ *
+ * pseg_regions_workspace_bytes(npix_total, max_regions): bytes of the 16-byte aligned workspace the three calls below take
+ *   (-1 for arguments out of range).  It holds one int32 and one byte per pixel, the scan's block sums and the
+ *   (photo, class) table of largest_only for min(npix_total, PSEG_REGIONS_MAX_LARGEST_BATCH) photos; records are the
+ *   caller's buffer, so max_regions does not add to it.
+ * pseg_mask_label: connectivity 4 or 8.  labels (int32, npix_total words, at the mask's packed offsets):
+ *   labels[offset + y*W + x] = y0*W + x0 of the first pixel, in raster order, of that pixel's component -- the canonical
+ *   labelling, equal element for element to any correct one.  Three launches: a union-find over PSEG_REGIONS_TILE x
+ *   PSEG_REGIONS_TILE tiles (origin at the photo's corner) in LDS, the union of the pixel pairs across tile borders in
+ *   global memory (atomicMin toward the smaller index, retried), and a pass that points every pixel at its root.  The
+ *   workspace is not used by this call (ws may be null).
+ * pseg_mask_regions: one record of PSEG_REGION_WORDS int64 per component, in the order (photo, label) -- the exclusive scan
+ *   of the root flags labels[p] == p along the packed buffer (so table offsets must ascend with the photo index for the
+ *   order to be by photo).  Words: [0] photo * 256 + class, [1] label, [2] area, [3] x0, [4] y0, [5] x1, [6] y1 (the
+ *   bounding box, inclusive), [7] Sx, [8] Sy, [9] Sxx, [10] Sxy, [11] Syy = sums over the component's pixels of x, y, x*x,
+ *   x*y, y*y with x, y measured from the PHOTO's corner (pixel (0, 0) contributes nothing).  Bound: with H * W < 2^31 and
+ *   H, W <= 65535, Sxx <= H * (W-1)W(2W-1)/6 < (H*W) * W^2 / 3 < 2^31 * 2^32 / 3 < 2^62, likewise Syy, and
+ *   Sxy <= (H(H-1)/2) * (W(W-1)/2) < (H*W)^2 / 4 < 2^60: every sum stays inside int64.  count[0] (int64) receives the
+ *   full number of components; only records 0 .. min(count, max_regions) - 1 are written.  npix_total < 2^31.
+ * pseg_mask_clean: a component is SMALL if its area < min_area; with largest_only != 0 a component of class >= 1 is also
+ *   small unless it is the largest component of its class in its photo (equal areas: the smaller label wins; then
+ *   B <= PSEG_REGIONS_MAX_LARGEST_BATCH).  Every pixel of a small component takes the class found by this walk: from the
+ *   component's first pixel step to the pixel above it, or, in the top row, to the pixel left of it; if that pixel's
+ *   component is small too, go on from ITS first pixel; a component whose first pixel is the photo's corner keeps its
+ *   class.  Labels strictly decrease along the walk; it is one serial walk per component.  mask_out may equal mask.  rgb
+ *   (nullable, 3 * npix_total bytes) receives lut[3*c .. 3*c+2] of the cleaned class c, as pseg_seg_decode's.  min_area <= 1
+ *   without largest_only copies the mask (and colours it).  labels must be pseg_mask_label's result for mask.
+ */
+#define PSEG_REGIONS_TILE 32
+#define PSEG_REGION_WORDS 12
+#define PSEG_REGIONS_MAX_LARGEST_BATCH 4096
+int64_t pseg_regions_workspace_bytes(int64_t npix_total, int64_t max_regions);
+int pseg_mask_label(const uint8_t* mask, const int64_t* table, int B, int64_t npix_total, int Hmax, int Wmax, int connectivity,
+                    int* labels, void* ws, int64_t ws_bytes, void* stream);
+int pseg_mask_regions(const uint8_t* mask, const int* labels, const int64_t* table, int B, int64_t npix_total, int Hmax, int Wmax,
+                      int64_t max_regions, int64_t* records, int64_t* count, void* ws, int64_t ws_bytes, void* stream);
+int pseg_mask_clean(const uint8_t* mask, const int* labels, const int64_t* table, int B, int64_t npix_total, int Hmax, int Wmax,
+                    int64_t min_area, int largest_only, uint8_t* mask_out, uint8_t* rgb, const uint8_t* lut, void* ws,
+                    int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ training augmentation (csrc/augment.hip)
  * The geometric and colour-affine part of the reference's online augmentation (utils/datasets.py:26-125, imgaug on the

@@ -3,6 +3,7 @@
 
     python3 inference.py data/samples outputs --weights weights.pth [-s W H] [-nc N] [-bs N] [--model ...] [-mp]
                          [--norm dataset|reference] [--scales S [S ...]] [--flip]
+                         [--min-area N] [--connectivity {4,8}] [--largest-only] [--regions FILE.json]
 
 Every file of img_dir whose extension is in IMG_EXT (case-sensitive, as the reference) is segmented, in name order, and
 written to output_dir as <name>.png in VOC colours.  Photos are decoded with PIL (RGB); resizing, normalisation, softmax,
@@ -11,8 +12,13 @@ per batch.  Unlike the reference, output_dir is created but never emptied: delet
 something an inference tool should do.  --show is accepted and ignored (the reference never used it either).
 --scales and --flip turn on test-time ensembling: the class probabilities of every scale of the model input (sizes in
 multiples of 32), and with --flip of the left-right mirrored photo as well, are summed at the photo's size before the argmax.
+--min-area N drops connected regions of fewer than N pixels (specks take their surroundings' class, holes are filled),
+--largest-only keeps the largest region of every class but background, --connectivity chooses 4- or 8-neighbour regions
+(utils/regions.py); the PNGs show the cleaned masks.  --regions FILE.json writes {file name: [region, ...]} for the whole
+folder: class, area, bbox, centroid, angle, sides and label of every region of the (cleaned) mask.
 """
 import argparse
+import json
 import os
 import os.path as osp
 
@@ -39,7 +45,11 @@ def load_image(path):
 
 
 def run(img_dir, output_dir, img_size, num_classes, weights, show=False, model_name='deeplabv3plus', batch_size=1,
-        half=False, norm='dataset', scales=None, flip=False):
+        half=False, norm='dataset', scales=None, flip=False, min_area=0, connectivity=8, largest_only=False, regions=None):
+    if min_area < 0:
+        raise ValueError('--min-area must be >= 0; got %d' % min_area)
+    if connectivity not in (4, 8):
+        raise ValueError('--connectivity must be 4 or 8; got %r' % (connectivity,))
     if show:
         _warn_ignored('--show', 'the reference accepts it and never displays anything either')
     os.makedirs(output_dir, exist_ok=True)
@@ -50,13 +60,22 @@ def run(img_dir, output_dir, img_size, num_classes, weights, show=False, model_n
     model.eval()
     names = list_images(img_dir)
     tta = {} if scales is None and not flip else {'scales': scales, 'flip': bool(flip)}
+    if min_area > 1 or largest_only or regions:
+        tta.update(min_area=min_area, connectivity=connectivity, largest_only=bool(largest_only), regions=bool(regions))
+    found = {}
     for i in range(0, len(names), max(1, batch_size)):
         batch = names[i:i + max(1, batch_size)]
         imgs = [load_image(osp.join(img_dir, n)) for n in batch]
-        _, colored = inference(model, imgs, tuple(img_size), norm=norm, bgr=False, half=half, colors=PALETTE_RGB, **tta)
+        result = inference(model, imgs, tuple(img_size), norm=norm, bgr=False, half=half, colors=PALETTE_RGB, **tta)
+        colored = result[1]
+        if regions:
+            found.update(zip(batch, result[2]))
         for name, seg in zip(batch, colored):
             Image.fromarray(seg).save(osp.join(output_dir, osp.splitext(name)[0] + '.png'))
         print('%d/%d' % (min(i + batch_size, len(names)), len(names)), flush=True)
+    if regions:
+        with open(regions, 'w') as f:
+            json.dump(found, f)
     return names
 
 
@@ -76,10 +95,18 @@ def main(argv=None):
     parser.add_argument('--scales', type=float, nargs='+', default=None, metavar='S',
                         help='test-time ensembling: factors on --img_size (sizes in multiples of 32), e.g. 0.5 1.0 1.5')
     parser.add_argument('--flip', action='store_true', help='test-time ensembling: add the left-right mirrored view')
+    parser.add_argument('--min-area', type=int, default=0, metavar='N',
+                        help='drop connected regions of fewer than N pixels (they take the class of the region above them)')
+    parser.add_argument('--connectivity', type=int, choices=[4, 8], default=8, help='neighbours that connect a region')
+    parser.add_argument('--largest-only', action='store_true', help='keep only the largest region of every class >= 1')
+    parser.add_argument('--regions', type=str, default=None, metavar='FILE.json',
+                        help='write {file name: [region, ...]} (class, area, bbox, centroid, angle, sides, label)')
     opt = parser.parse_args(argv)
+    if opt.min_area < 0:
+        parser.error('--min-area must be >= 0')
     print(opt)
     run(opt.img_dir, opt.output_dir, opt.img_size, opt.num_classes, opt.weights, opt.show, opt.model, opt.batch_size,
-        opt.mix_precision, opt.norm, opt.scales, opt.flip)
+        opt.mix_precision, opt.norm, opt.scales, opt.flip, opt.min_area, opt.connectivity, opt.largest_only, opt.regions)
 
 
 if __name__ == '__main__':

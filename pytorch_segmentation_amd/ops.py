@@ -1330,6 +1330,82 @@ def seg_decode_ensemble(prob, maps, B, C, table, npix_total, max_hw, lut=None, o
     return mask, rgb
 
 
+REGIONS_TILE = 32       # PSEG_REGIONS_TILE: tile edge of mask_label's LDS union-find (tiles start at the photo's corner)
+REGION_WORDS = 12       # PSEG_REGION_WORDS: int64 per record of mask_regions (layout: include/pseg_amd.h)
+REGIONS_MAX_LARGEST_BATCH = 4096   # PSEG_REGIONS_MAX_LARGEST_BATCH: photos per mask_clean call with largest_only
+
+# the regions calls' scratch (5 bytes per mask pixel): its own buffer, like the Lovasz loss's
+regions_workspace = _Workspace()
+
+
+def _regions_args(mask, table, npix_total, max_hw):
+    assert mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.dim() == 1
+    assert mask.numel() == npix_total
+    assert table.device == mask.device and table.dtype == torch.int64 and table.is_contiguous()
+    assert table.dim() == 2 and table.shape[1] == 3
+    Hmax, Wmax = int(max_hw[0]), int(max_hw[1])
+    nbytes = _lib.query('pseg_regions_workspace_bytes', int(npix_total), 0)
+    assert nbytes >= 0, 'npix_total %d out of range' % npix_total
+    return table.shape[0], Hmax, Wmax, nbytes, regions_workspace.get(nbytes, mask.device)
+
+
+def mask_label(mask, table, npix_total, max_hw, connectivity=8, out=None):
+    """Connected-component labels of a packed batch of uint8 masks (pseg_mask_label).  mask: flat uint8 device tensor of
+    npix_total pixels; table: int64 device tensor [B,3] of {pixel offset, H, W}; max_hw = (largest H, largest W) of the
+    table.  -> int32 tensor [npix_total]: at each pixel, y*W + x of the first pixel (raster order) of its component, within
+    its own photo.  connectivity: 4 or 8.  Words outside every valid record are left as they are (out) or undefined."""
+    B, Hmax, Wmax, nbytes, ws = _regions_args(mask, table, npix_total, max_hw)
+    if out is None:
+        out = torch.empty(npix_total, dtype=torch.int32, device=mask.device)
+    assert out.device == mask.device and out.dtype == torch.int32 and out.is_contiguous() and out.numel() == npix_total
+    _lib.call('pseg_mask_label', mask.data_ptr(), table.data_ptr(), B, npix_total, Hmax, Wmax, int(connectivity),
+              out.data_ptr(), ws.data_ptr(), nbytes, _stream())
+    return out
+
+
+def mask_regions(mask, labels, table, npix_total, max_hw, max_regions, records=None, count=None):
+    """One record of REGION_WORDS int64 per component, in (photo, label) order (pseg_mask_regions; word layout in
+    include/pseg_amd.h).  -> (records int64 [max_regions, REGION_WORDS], count int64 [1]): count is the full number of
+    components, only the first min(count, max_regions) records are written.  No host synchronisation: read count yourself."""
+    B, Hmax, Wmax, nbytes, ws = _regions_args(mask, table, npix_total, max_hw)
+    assert labels.device == mask.device and labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == npix_total
+    max_regions = int(max_regions)
+    assert max_regions >= 0
+    if records is None:
+        records = torch.empty(max_regions, REGION_WORDS, dtype=torch.int64, device=mask.device)
+    if count is None:
+        count = torch.empty(1, dtype=torch.int64, device=mask.device)
+    assert records.device == mask.device and records.dtype == torch.int64 and records.is_contiguous()
+    assert records.numel() >= max_regions * REGION_WORDS
+    assert count.device == mask.device and count.dtype == torch.int64 and count.numel() >= 1
+    _lib.call('pseg_mask_regions', mask.data_ptr(), labels.data_ptr(), table.data_ptr(), B, npix_total, Hmax, Wmax, max_regions,
+              records.data_ptr() if max_regions else 0, count.data_ptr(), ws.data_ptr(), nbytes, _stream())
+    return records, count
+
+
+def mask_clean(mask, labels, table, npix_total, max_hw, min_area=0, largest_only=False, lut=None, out=None):
+    """Drop the small components of a labelled packed mask (pseg_mask_clean): a component below min_area pixels -- and, with
+    largest_only, every component of a class >= 1 but the largest of its class in its photo -- takes the class of the
+    region above (in the top row: left of) its first pixel, followed through further small components.  out (optional):
+    one uint8 device tensor of npix_total (x 4 with lut) bytes for the cleaned mask, then its colours, as seg_decode's;
+    it may start at mask's own storage (in place).  -> (mask_out, rgb or None)."""
+    B, Hmax, Wmax, nbytes, ws = _regions_args(mask, table, npix_total, max_hw)
+    assert labels.device == mask.device and labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == npix_total
+    if int(min_area) < 0:
+        raise ValueError('min_area must be >= 0; got %r' % (min_area,))
+    total = npix_total * (1 if lut is None else 4)
+    if out is None:
+        out = torch.empty(total, dtype=torch.uint8, device=mask.device)
+    assert out.device == mask.device and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == total
+    mask_out, rgb = out[:npix_total], None
+    if lut is not None:
+        assert lut.device == mask.device and lut.dtype == torch.uint8 and lut.is_contiguous() and lut.shape == (256, 3)
+        rgb = out[npix_total:].view(npix_total, 3)
+    _lib.call('pseg_mask_clean', mask.data_ptr(), labels.data_ptr(), table.data_ptr(), B, npix_total, Hmax, Wmax, int(min_area),
+              int(bool(largest_only)), mask_out.data_ptr(), _ptr(rgb), _ptr(lut), ws.data_ptr(), nbytes, _stream())
+    return mask_out, rgb
+
+
 AUGMENT_ROW = 24        # PSEG_AUGMENT_ROW: floats per sample of augment_batch's parameter table (layout: include/pseg_amd.h)
 
 

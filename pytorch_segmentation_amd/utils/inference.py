@@ -115,7 +115,8 @@ class Ensemble:
 
 
 @torch.no_grad()
-def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=False, colors=None, scales=None, flip=False):
+def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=False, colors=None, scales=None, flip=False,
+              min_area=0, connectivity=8, largest_only=False, regions=False):
     """The reference's contract: ``imgs`` is a list of uint8 H x W x 3 photos (numpy arrays, or CPU or device tensors),
     ``img_size`` = (w, h) of the model input as cv2.resize takes it; returns one int64 numpy H x W mask per photo, at
     that photo's own size.  ``bgr=True``: the photos are cv2.imread output (B, G, R).  ``half=True``: the forward runs
@@ -125,7 +126,20 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
     ``scales`` (a sequence of factors on the model input size, see ``tta_sizes``) and ``flip`` (add every scale's
     left-right mirrored view) turn on test-time ensembling: mask = argmax_c of the unweighted sum, over all views, of the
     un-mirrored softmax resized bilinearly (align_corners=False) to the photo's size; first index on ties.  ``scales`` None
-    or (1.0,) without ``flip`` is the single forward above, bit for bit."""
+    or (1.0,) without ``flip`` is the single forward above, bit for bit.
+
+    ``min_area`` (> 1), ``largest_only`` and ``regions`` turn on the connected-region post-processing (utils/regions.py) on
+    the device mask, after the decode of either route and before the single copy back: regions of fewer than ``min_area``
+    pixels -- with ``largest_only`` also every region of a class >= 1 but its class's largest in the photo -- take the
+    class of the region above their first pixel (``connectivity`` 4 or 8); the colours are those of the cleaned mask.
+    ``regions=True`` appends one more result: per photo, a list of dicts {class, area, bbox, centroid, angle, sides, label}
+    of the regions of the cleaned mask (utils.regions.region_dicts).  With all four at their defaults none of this runs."""
+    min_area = int(min_area)
+    if min_area < 0:
+        raise ValueError('min_area must be >= 0; got %d' % min_area)
+    if connectivity not in (4, 8):
+        raise ValueError('connectivity must be 4 or 8; got %r' % (connectivity,))
+    post = (min_area, int(connectivity), bool(largest_only), bool(regions)) if min_area > 1 or largest_only or regions else None
     if norm not in NORMS:
         raise ValueError('norm must be one of %s' % sorted(NORMS))
     mean, std = NORMS[norm]
@@ -137,7 +151,8 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
     sizes = tta_sizes(h, w, scales if scales is not None else (1.0,)) if tta else None
     photos = [_photo(im) for im in imgs]
     if not photos:
-        return ([], []) if colors is not None else []
+        empty = ([], []) if colors is not None else []
+        return empty if not regions else (empty + ([],) if colors is not None else (empty, []))
     device = next(model.parameters()).device
     if device.type != 'cuda':
         raise RuntimeError('inference() runs on the HIP path: move the model to the GPU first')
@@ -145,7 +160,7 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
     if tta:
         if B * (2 if flip else 1) > 65535:
             raise ValueError('%d photos x %d views exceed 65535 rows per launch' % (B, 2 if flip else 1))
-        return _inference_ensemble(model, photos, h, w, sizes, flip, mean, std, bgr, half, colors, device)
+        return _inference_ensemble(model, photos, h, w, sizes, flip, mean, std, bgr, half, colors, device, post)
     sizes = np.array([(H, W) for _, H, W in photos], dtype=np.int64)
     npix = sizes[:, 0] * sizes[:, 1]
     pix_off = np.concatenate([[0], np.cumsum(npix)[:-1]])
@@ -172,7 +187,12 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
     logits = _forward(model, x, half)
     lut = None if colors is None else torch.from_numpy(lut_of(colors)).to(device)
     out = torch.empty(total_pix * (1 if lut is None else 4), dtype=torch.uint8, device=device)
-    ops.seg_decode(logits.contiguous(), dtables[1], total_pix, lut, out=out)
+    if post is None:
+        ops.seg_decode(logits.contiguous(), dtables[1], total_pix, lut, out=out)
+        records = None
+    else:                                                       # decode without the palette: mask_clean writes the colours
+        ops.seg_decode(logits.contiguous(), dtables[1], total_pix, None, out=out[:total_pix])
+        records = _postprocess(out, dtables[1], total_pix, sizes, lut, post)
 
     # one device-to-host copy of masks (and colours)
     host = torch.empty(out.numel(), dtype=torch.uint8, pin_memory=True)
@@ -181,12 +201,30 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
     hv = host.numpy()
     masks = [hv[o:o + H * W].reshape(H, W).astype(np.int64) for o, (H, W) in zip(pix_off, sizes)]
     if colors is None:
-        return masks
+        return _with_regions(masks, records, post, B)
     rgb = hv[total_pix:]
-    return masks, [rgb[3 * o:3 * (o + H * W)].reshape(H, W, 3).copy() for o, (H, W) in zip(pix_off, sizes)]
+    images = [rgb[3 * o:3 * (o + H * W)].reshape(H, W, 3).copy() for o, (H, W) in zip(pix_off, sizes)]
+    return _with_regions((masks, images), records, post, B)
 
 
-def _inference_ensemble(model, photos, h, w, view_sizes, flip, mean, std, bgr, half, colors, device):
+def _postprocess(out, table, total_pix, sizes, lut, post):
+    """the connected-region pass on the decoded device mask (imported here: the default route never loads it)"""
+    from .regions import postprocess
+    min_area, connectivity, largest_only, want_regions = post
+    return postprocess(out, table, total_pix, (int(sizes[:, 0].max()), int(sizes[:, 1].max())), lut, min_area, connectivity,
+                       largest_only, want_regions)
+
+
+def _with_regions(result, records, post, B):
+    """result as it is, or with the per-photo region lists appended when regions=True asked for them"""
+    if post is None or not post[3]:
+        return result
+    from .regions import region_dicts
+    lists = region_dicts(records, B)
+    return result + (lists,) if isinstance(result, tuple) else (result, lists)
+
+
+def _inference_ensemble(model, photos, h, w, view_sizes, flip, mean, std, bgr, half, colors, device, post=None):
     """inference() with several views: the same single staging buffer (now also carrying the view table and the map
     table) and the same single copy back; per scale one preprocess launch, one forward, one softmax launch."""
     B, S, V = len(photos), len(view_sizes), 2 if flip else 1
@@ -228,7 +266,12 @@ def _inference_ensemble(model, photos, h, w, view_sizes, flip, mean, std, bgr, h
         del logits                                             # released before the next scale's forward
     lut = None if colors is None else torch.from_numpy(lut_of(colors)).to(device)
     out = torch.empty(total_pix * (1 if lut is None else 4), dtype=torch.uint8, device=device)
-    ens.decode(ddecode, total_pix, (int(sizes[:, 0].max()), int(sizes[:, 1].max())), lut, out=out)
+    if post is None:
+        ens.decode(ddecode, total_pix, (int(sizes[:, 0].max()), int(sizes[:, 1].max())), lut, out=out)
+        records = None
+    else:
+        ens.decode(ddecode, total_pix, (int(sizes[:, 0].max()), int(sizes[:, 1].max())), None, out=out[:total_pix])
+        records = _postprocess(out, ddecode, total_pix, sizes, lut, post)
 
     host = torch.empty(out.numel(), dtype=torch.uint8, pin_memory=True)
     host.copy_(out, non_blocking=True)
@@ -236,9 +279,10 @@ def _inference_ensemble(model, photos, h, w, view_sizes, flip, mean, std, bgr, h
     hv = host.numpy()
     masks = [hv[o:o + H * W].reshape(H, W).astype(np.int64) for o, (H, W) in zip(pix_off, sizes)]
     if colors is None:
-        return masks
+        return _with_regions(masks, records, post, B)
     rgb = hv[total_pix:]
-    return masks, [rgb[3 * o:3 * (o + H * W)].reshape(H, W, 3).copy() for o, (H, W) in zip(pix_off, sizes)]
+    images = [rgb[3 * o:3 * (o + H * W)].reshape(H, W, 3).copy() for o, (H, W) in zip(pix_off, sizes)]
+    return _with_regions((masks, images), records, post, B)
 
 
 def _forward(model, x, half):

@@ -2,14 +2,16 @@
 """Evaluation entry point with the reference's flags (reference test.py:76-105) on the MI355X HIP path.
 
     python3 test.py data/<custom>/val.json --weights weights/best.pt [-s W H] [-bs N] [--model deeplabv3plus|unet]
-                    [--scales S [S ...]] [--flip]
+                    [--scales S [S ...]] [--flip] [--min-area N] [--connectivity {4,8}] [--largest-only]
 
 `test(model, fetcher)` keeps the reference's contract: evaluates in eval mode without gradients, prints per-class
 (or the five worst classes') targets / precision / recall / IoU / F1 and returns the mean IoU.  The per-class
 tp/fn/fp bookkeeping runs as one device kernel per batch instead of 3 host synchronisations per class, and the
 distributed reduction is a single [3, num_classes] all-reduce.  With --scales / --flip the counted prediction is the
 test-time ensemble (utils.predict_mask_ensemble: summed class probabilities of every scale and mirrored view at the target
-size); the printed loss stays that of the plain forward.
+size); the printed loss stays that of the plain forward.  With --min-area / --largest-only the counted prediction is the
+cleaned mask (utils/regions.py: small connected regions dropped) of either route, so the effect of a threshold on the mIoU
+can be read off; the loss again stays as it is.
 """
 import argparse
 
@@ -25,8 +27,13 @@ MODELS = {'deeplabv3plus': DeepLabV3Plus, 'unet': UNet, 'hrnet': HRNet}
 
 
 @torch.no_grad()
-def test(model, fetcher, scales=None, flip=False):
+def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, largest_only=False):
     model.eval()
+    if min_area < 0:
+        raise ValueError('min_area must be >= 0; got %d' % min_area)
+    if connectivity not in (4, 8):
+        raise ValueError('connectivity must be 4 or 8; got %r' % (connectivity,))
+    clean = min_area > 1 or largest_only
     tta = scales is not None or flip
     scales = (1.0,) if scales is None else tuple(scales)
     # distributed evaluation sums per-class counters over the ranks (reference test.py:51-58): they must all come from ONE
@@ -34,6 +41,8 @@ def test(model, fetcher, scales=None, flip=False):
     broadcast_buffers(model, 0)
     classes = fetcher.loader.dataset.classes
     nc = len(classes)
+    if clean and nc > 256:
+        raise ValueError('mask cleanup handles at most 256 classes; the dataset has %d' % nc)
     counters = None
     loss_sum, batches = None, 0
     for inputs, targets in fetcher:
@@ -52,7 +61,12 @@ def test(model, fetcher, scales=None, flip=False):
         batches += 1
         if counters is None:
             counters = torch.zeros(3, nc, dtype=torch.int64, device=outputs.device)
-        update_class_counts(counters, predict_mask(outputs) if predicted is None else predicted, targets)
+        if predicted is None:
+            predicted = predict_mask(outputs)
+        if clean:
+            from pytorch_segmentation_amd.utils.regions import clean_predictions
+            predicted = clean_predictions(predicted, min_area, connectivity, largest_only)
+        update_class_counts(counters, predicted, targets)
     if counters is None:
         return 0.0
     all_reduce_counters(counters)
@@ -82,14 +96,21 @@ def main():
     ap.add_argument('--scales', type=float, nargs='+', default=None, metavar='S',
                     help='test-time ensembling: factors on the input size (sizes in multiples of 32), e.g. 0.5 1.0 1.5')
     ap.add_argument('--flip', action='store_true', help='test-time ensembling: add the left-right mirrored view')
+    ap.add_argument('--min-area', type=int, default=0, metavar='N',
+                    help='evaluate the masks with connected regions of fewer than N pixels dropped')
+    ap.add_argument('--connectivity', type=int, choices=[4, 8], default=8, help='neighbours that connect a region')
+    ap.add_argument('--largest-only', action='store_true', help='keep only the largest region of every class >= 1')
     opt = ap.parse_args()
+    if opt.min_area < 0:
+        ap.error('--min-area must be >= 0')
     data = CocoDataset(opt.val, img_size=opt.img_size, augments=None, rect=opt.rect)
     loader = DataLoader(data, batch_size=opt.batch_size, pin_memory=True, num_workers=opt.num_workers)
     fetcher = Fetcher(loader, post_fetch_fn=data.post_fetch_fn)
     model = MODELS[opt.model](len(data.classes))
     if opt.weights:
         model.load_state_dict(torch.load(opt.weights, map_location='cpu')['model'])
-    print('metrics: %8g' % test(model.cuda(), fetcher, opt.scales, opt.flip))
+    print('metrics: %8g' % test(model.cuda(), fetcher, opt.scales, opt.flip, opt.min_area, opt.connectivity,
+                                  opt.largest_only))
 
 
 if __name__ == '__main__':
