@@ -91,7 +91,7 @@ constexpr uint32_t kOOB = 0x80000000u;
 // pass every kernel of the serial chain starts as the youngest wave on CUs that hold blocks of a long-running weight
 // gradient: a BatchNorm reduction took 83 us beside one against 18 alone.  Helper passes of the serial chain (BatchNorm,
 // pooling / resize, depthwise convs, copies) raise their waves to priority 3 on entry; data gradients run at 1
-// (set_wave_prio, conv_mfma.hip); weight gradients and the slab reductions on their stream stay at 0.
+// (set_wave_prio, conv_gather.hip); weight gradients and the slab reductions on their stream stay at 0.
 // -DPSEG_NO_PRIO=1 builds the library without any of it (A/B measurements: PSEG_LIB_PATH selects the library file).
 #if defined(PSEG_NO_PRIO) && PSEG_NO_PRIO
 #define PSEG_HELPER_PRIO() ((void)0)

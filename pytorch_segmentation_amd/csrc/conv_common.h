@@ -1,5 +1,5 @@
-// Shared by the conv translation units (conv_mfma.hip: fp32 / limb arithmetic; conv_half.hip: fp16 storage + single-pass
-// fp16 MFMA): the parameter blocks of the gather / weight-gradient kernels, GEMM-row orders (patch / parity / liveness-class
+// Shared by the conv translation units (conv_gather.hip, conv_wgrad.hip: fp32 / limb arithmetic; conv_half.hip: fp16 storage +
+// single-pass fp16 MFMA): the parameter blocks of the gather / weight-gradient kernels, GEMM-row orders (patch / parity / liveness-class
 // sorted), XCD-aware tile order, the LDS-staged epilogue, and the host-side planners (tile choice, split choice, dilated-conv
 // tap-skipping schedules).  Everything here is `static` / `inline`: each translation unit gets its own copy of the code, the
 // planning overrides read from the environment (cfg()) are shared (inline variables).
@@ -8,6 +8,9 @@
 
 #include <stdio.h>
 #include <stdlib.h>
+
+#include <type_traits>
+#include <utility>
 
 namespace pseg {
 
@@ -1013,7 +1016,7 @@ struct WgradPixelOrder {
 };
 
 // What every weight-gradient kernel can run: kWgDense, kWgSkipRows or kWgSkipPatches (the exact-fp32 LDS-DMA kernel's own orders
-// are select_wgrad's, conv_mfma.hip).  tile_bn: columns of the plan's tile.
+// are select_wgrad's, conv_wgrad.hip).  tile_bn: columns of the plan's tile.
 static WgradPixelOrder wgrad_pixel_order(const WgradGeom& g, int tile_bn) {
   WgradPixelOrder o{};
   o.can_skip = g.dil >= 4 && g.kh * g.kw > 1 && g.Cin % tile_bn == 0 && cfg().conv_noskip == 0;
@@ -1096,8 +1099,35 @@ static int set_wgrad_output(WgradParams& p, const WgradPlan& pl, float* dw, int 
   return PSEG_OK;
 }
 
-// fixed-order slab reductions (kernels in conv_mfma.hip)
+// fixed-order slab reductions (kernels in conv_wgrad.hip)
 int launch_slab_reduce(const float* slabs, long long slab_stride, int nslab, float* out, int ld, long long M, int N,
                        const float* bias, int accumulate, hipStream_t st);
+
+// the register-staged kernel families (gather_conv_kernel, wgrad_kernel, wgrad_limb_kernel): one instantiation per tile
+template <typename P, typename F, int NTILES>
+static int launch_tiles(const F (&fns)[2][NTILES], bool skip, TileCfg c, dim3 grid, const P& p, hipStream_t st) {
+  int idx = -1;
+  if (c.bm == 128 && c.bn == 128) idx = 0;
+  else if (c.bm == 128 && c.bn == 64) idx = 1;
+  else if (c.bm == 128 && c.bn == 32) idx = 2;
+  else if (c.bm == 64 && c.bn == 128) idx = 3;
+  else if (c.bm == 32 && c.bn == 128) idx = 4;
+  else if (c.bm == 256 && c.bn == 128 && NTILES > 5) idx = 5;   // 8 waves
+  if (idx < 0 || fns[skip ? 1 : 0][idx] == nullptr) {
+    set_error("no kernel for tile %dx%d", c.bm, c.bn);
+    return PSEG_ERR_ARG;
+  }
+  hipLaunchKernelGGL(fns[skip ? 1 : 0][idx], grid, dim3(c.bm == 256 ? 512 : 256), 0, st, p);
+  PSEG_LAUNCH_CHECK();
+  return PSEG_OK;
+}
+
+// f(std::integral_constant<int, i>) for entry i of a table of N: the entry's fields are then template arguments
+template <typename F, int... I>
+static void with_index(int i, F&& f, std::integer_sequence<int, I...>) {
+  (void)((i == I && (f(std::integral_constant<int, I>{}), true)) || ...);
+}
+
+static int waves_m(TileCfg t) { return t.bm == 256 ? 4 : (t.bn == 32 ? 4 : (t.bm == 32 ? 1 : 2)); }
 
 }  // namespace pseg

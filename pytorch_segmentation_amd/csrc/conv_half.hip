@@ -4,7 +4,7 @@
 //
 //  gather_h_kernel   forward and data gradient: C[M = pixels][N] = A[M][K] * Bw[N][K]^T, both operands K-contiguous fp16.
 //     Same implicit-GEMM formulation, GEMM-row orders (patch / parity / liveness-class sorted), tap skipping and fused
-//     BatchNorm statistics as gather_f32_dma_kernel (conv_mfma.hip); tiles go global -> LDS by `buffer_load_dwordx4 ... lds`
+//     BatchNorm statistics as gather_f32_dma_kernel (conv_gather.hip); tiles go global -> LDS by `buffer_load_dwordx4 ... lds`
 //     into a two-stage ring of [rows][64 halves = 128 B] images (16-byte k-slot XOR (row >> 1) & 7, applied on the source
 //     side), one ds_read_b128 = the 8 consecutive k of one MFMA operand.  Output fp16 (or fp32 for the class logits, which
 //     the loss reads), written in 16-byte pieces through a wave-private LDS patch.
@@ -18,9 +18,6 @@
 //     split, reduced in a fixed order by the same slab kernels as the fp32 path (bit-reproducible).
 #include "conv_common.h"
 #include "half_io.h"
-
-#include <type_traits>
-#include <utility>
 
 namespace pseg {
 
@@ -1562,13 +1559,9 @@ static void with_h_steps(int kb, int st, F&& f) {
   else if (st == 3) f(tile, HSteps<64, 3>{});
   else f(tile, HSteps<64, 4>{});
 }
-template <typename F, int... I>
-static void with_h_kernel(int tile, int kb, int st, F&& f, std::integer_sequence<int, I...>) {
-  (void)((tile == I && (with_h_steps<I>(kb, st, f), true)) || ...);
-}
 template <typename F>
 static void with_h_kernel(int tile, int kb, int st, F&& f) {
-  with_h_kernel(tile, kb, st, f, std::make_integer_sequence<int, kNumHTiles>{});
+  with_index(tile, [&](auto t) { with_h_steps<decltype(t)::value>(kb, st, f); }, std::make_integer_sequence<int, kNumHTiles>{});
 }
 
 // the planner's tile -> one of the default entries of kHTiles

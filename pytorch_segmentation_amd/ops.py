@@ -661,7 +661,7 @@ def _conv2d_dgrad_one(dy, wT_raw, dx, kh, kw, stride, pad, dil, accumulate=False
             part = torch.empty(2, rows, Cin, dtype=torch.float32, device=dx.device)
             c0, cs = co.data_ptr(), co.shape[1] * 4
             p0 = part.data_ptr()
-            # (the rows query and the launch read one kernel choice: select_gather in conv_mfma.hip)
+            # (the rows query and the launch read one kernel choice: select_gather in conv_gather.hip)
             _lib.call('pseg_conv2d_dgrad_bnstat', dy.ptr, dy.ld, wT_raw.data_ptr(), dx.ptr, dx.ld, dx.B, dx.H, dx.W, Cin, dy.H,
                       dy.W, Cout, kh, kw, stride, pad, dil, y.ptr, y.ld, c0, c0 + cs, c0 + 2 * cs, c0 + 3 * cs, act,
                       p0, p0 + rows * Cin * 4, rows, _stream())

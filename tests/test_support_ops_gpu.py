@@ -265,7 +265,7 @@ def test_amax_batch_is_exactly_abs_max_per_job(ops, lib, counts):
 def split_planes_contract(x):
     """include/pseg_amd.h: hi = bf16(x), lo = bf16(x - hi), as uint16 bit patterns (int16 storage).
 
-    The kernel converts with `(__bf16)value` (pack_bf16 in csrc/conv_mfma.hip: v_cvt_pk_bf16_f32), which rounds to nearest,
+    The kernel converts with `(__bf16)value` (pack_bf16 in csrc/conv_limb.h: v_cvt_pk_bf16_f32), which rounds to nearest,
     ties to even -- the rounding of torch's `.bfloat16()`; x - hi is exact in fp32 (hi carries the leading 8 bits of x).
     Hand-checked on the CPU (value -> hi, lo):
         1.0                  -> 0x3F80, 0x0000      (zero low limb)
