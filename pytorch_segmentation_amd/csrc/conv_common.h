@@ -1,5 +1,5 @@
-// Shared by the conv translation units (conv_gather.hip, conv_wgrad.hip: fp32 / limb arithmetic; conv_half.hip: fp16 storage +
-// single-pass fp16 MFMA): the parameter blocks of the gather / weight-gradient kernels, GEMM-row orders (patch / parity / liveness-class
+// Shared by the conv translation units (conv_gather.hip, conv_wgrad.hip: fp32 / limb arithmetic; conv_half_gather.hip,
+// conv_half_wgrad.hip: fp16 storage + single-pass fp16 MFMA): the parameter blocks of the gather / weight-gradient kernels, GEMM-row orders (patch / parity / liveness-class
 // sorted), XCD-aware tile order, the LDS-staged epilogue, and the host-side planners (tile choice, split choice, dilated-conv
 // tap-skipping schedules).  Everything here is `static` / `inline`: each translation unit gets its own copy of the code, the
 // planning overrides read from the environment (cfg()) are shared (inline variables).
@@ -925,6 +925,60 @@ static void set_gather_geometry(GatherConvParams& p, const GatherGeom& g, const 
     p.HoWo = (int)g.M;
   }
   if (o.row_perm == 4) p.band = pl.band;
+}
+
+// BatchNorm-backward partial sums fused into a data gradient (pseg_conv2d_dgrad_bnstat[_h]; GatherConvParams::bns_*): the
+// producing layer's y (fp32 or fp16), its fp32 coefficient rows, where the [rows][N] partial sums go
+struct BnsArgs {
+  const void* y;
+  int ldy;
+  const float *mean, *invstd, *scale, *shift;
+  int act;
+  float *db, *dg;
+  int rows;
+};
+
+// the bns_* fields of a launch: the caller's, or null / zero without the fused sums
+static void set_bns_params(GatherConvParams& p, const BnsArgs* bns) {
+  static const BnsArgs none{};
+  const BnsArgs& a = bns != nullptr ? *bns : none;
+  p.bns_y = static_cast<const float*>(a.y);
+  p.bns_ldy = a.ldy;
+  p.bns_mean = a.mean;
+  p.bns_invstd = a.invstd;
+  p.bns_scale = a.scale;
+  p.bns_shift = a.shift;
+  p.bns_act = a.act;
+  p.bns_db = a.db;
+  p.bns_dg = a.dg;
+}
+
+// the forward problem of a query that knows Ho / Wo only: the smallest input that gives them
+static GatherGeom fwd_stats_geom(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int stride, int pad, int dil) {
+  const int H = (Ho - 1) * stride - 2 * pad + dil * (kh - 1) + 1, W = (Wo - 1) * stride - 2 * pad + dil * (kw - 1) + 1;
+  return fwd_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil);
+}
+
+// Argument checks the fp32 and fp16 entry points share; `name` is the entry point's, for the message.
+// pseg_conv2d_fwd[_h]: the geometry, and Ho / Wo against H / W
+static int check_fwd_geometry(const char* name, int H, int W, int Ho, int Wo, int kh, int kw, int stride, int pad, int dil) {
+  PSEG_REQUIRE(stride >= 1 && dil >= 1 && pad >= 0 && kh >= 1 && kw >= 1, "%s: bad geometry", name);
+  PSEG_REQUIRE(Ho == (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1,
+               "%s: Ho/Wo (%d,%d) inconsistent with H/W (%d,%d) k=%dx%d s=%d p=%d d=%d", name, Ho, Wo, H, W, kh, kw, stride, pad, dil);
+  return PSEG_OK;
+}
+
+// pseg_conv2d_dgrad_bnstat[_h]: pointers, geometry, activation, alignment; granule = elements of y_prev per 16 bytes (4 or 8)
+static int check_dgrad_bnstat_args(const char* name, int granule, const void* dy, const void* wT, const void* dx, int Cin, int stride,
+                                   int pad, int dil, const BnsArgs& a) {
+  PSEG_REQUIRE(dy && wT && dx && a.y && a.mean && a.invstd && a.scale && a.shift && a.db && a.dg, "%s: null pointer", name);
+  PSEG_REQUIRE(stride >= 1 && dil >= 1 && pad >= 0, "%s: bad geometry", name);
+  PSEG_REQUIRE(a.act == PSEG_ACT_NONE || a.act == PSEG_ACT_RELU || a.act == PSEG_ACT_RELU6, "%s: unknown activation", name);
+  PSEG_REQUIRE(a.ldy % granule == 0 && a.ldy >= Cin && ((uintptr_t)a.y & 15) == 0 && ((uintptr_t)a.db & 15) == 0 &&
+                   ((uintptr_t)a.dg & 15) == 0 && ((uintptr_t)a.mean & 15) == 0 && ((uintptr_t)a.invstd & 15) == 0 &&
+                   ((uintptr_t)a.scale & 15) == 0 && ((uintptr_t)a.shift & 15) == 0,
+               "%s: y_prev / coefficient / partial pointers must be 16-byte aligned, ldy_prev %% %d == 0", name, granule);
+  return PSEG_OK;
 }
 
 struct WgradPlan {

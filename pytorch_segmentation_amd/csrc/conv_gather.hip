@@ -1542,20 +1542,6 @@ struct LimbPlanes {
   long long xp_bytes, wp_bytes;
 };
 
-// BatchNorm-backward partial sums fused into a data gradient (GatherConvParams::bns_*)
-struct BnsArgs {
-  const float* y;
-  int ldy;
-  const float* mean;
-  const float* invstd;
-  const float* scale;
-  const float* shift;
-  int act;
-  float* db;
-  float* dg;
-  int rows;
-};
-
 // The tiles of the exact-fp32 LDS-DMA kernels, stated once: select_gather reads from this table what each family covers, the
 // launch helpers below map an entry to template arguments.  gather_f32_dma_kernel (plain and GENERIC) is instantiated for every
 // entry, gather_f32_pw_kernel / gather_f32_halo_kernel for those marked.  Threads per block = 64 * wm * wn.
@@ -1791,28 +1777,13 @@ static int run_gather(const GatherGeom& g, const float* x, long long x_bytes, in
   p.xh = p.xl = p.wh = p.wl = nullptr;
   p.xp_bytes = p.wp_bytes = 0;
   p.ldxp = 0;
-  p.bns_y = nullptr;
-  p.bns_ldy = 0;
-  p.bns_mean = p.bns_invstd = p.bns_scale = p.bns_shift = nullptr;
-  p.bns_act = 0;
-  p.bns_db = p.bns_dg = nullptr;
-  if (bns != nullptr) {
-    // only the exact-fp32 LDS-DMA kernels carry the fused sums: the caller asked pseg_conv2d_dgrad_bnstat_rows first
-    if (c.kernel == kGatherRefused || bns->rows != c.stat_rows()) {
-      set_error("conv: the fused BatchNorm-backward sums are not available for this data gradient (M=%lld N=%d K=%d, rows %d)", M,
-                N, K, bns->rows);
-      return PSEG_ERR_ARG;
-    }
-    p.bns_y = bns->y;
-    p.bns_ldy = bns->ldy;
-    p.bns_mean = bns->mean;
-    p.bns_invstd = bns->invstd;
-    p.bns_scale = bns->scale;
-    p.bns_shift = bns->shift;
-    p.bns_act = bns->act;
-    p.bns_db = bns->db;
-    p.bns_dg = bns->dg;
+  // only the exact-fp32 LDS-DMA kernels carry the fused sums: the caller asked pseg_conv2d_dgrad_bnstat_rows first
+  if (bns != nullptr && (c.kernel == kGatherRefused || bns->rows != c.stat_rows())) {
+    set_error("conv: the fused BatchNorm-backward sums are not available for this data gradient (M=%lld N=%d K=%d, rows %d)", M, N,
+              K, bns->rows);
+    return PSEG_ERR_ARG;
   }
+  set_bns_params(p, bns);
   const bool reg = c.kernel == PSEG_KERNEL_GATHER_REGISTER;     // the one kernel with every arithmetic; the others are fixed
   p.precision = reg ? precision : (c.kernel == PSEG_KERNEL_GATHER_LIMB_DMA ? 1 : 0);
   p.amax_a = reg ? amax_a : nullptr;
@@ -1898,8 +1869,7 @@ int pseg_debug_conv_trace(void* buffer) {
 
 // the choice of a forward conv with fused statistics (the queries know Ho / Wo only: the smallest input that gives them)
 static GatherChoice select_fwd_stats(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int stride, int pad, int dil) {
-  const int H = (Ho - 1) * stride - 2 * pad + dil * (kh - 1) + 1, W = (Wo - 1) * stride - 2 * pad + dil * (kw - 1) + 1;
-  return select_gather(GatherProblem{fwd_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil), PSEG_PREC_FP32, true, false,
+  return select_gather(GatherProblem{fwd_stats_geom(B, Ho, Wo, Cin, Cout, kh, kw, stride, pad, dil), PSEG_PREC_FP32, true, false,
                                      false, false, false});
 }
 
@@ -1924,10 +1894,8 @@ int pseg_conv2d_fwd(const float* x, int ldx, const float* w, const float* bias, 
                     int precision, const float* amax_x, const float* amax_w, float* stat, void* workspace,
                     int64_t workspace_bytes, void* stream) {
   PSEG_REQUIRE(x && w && y, "conv2d_fwd: null pointer");
-  PSEG_REQUIRE(stride >= 1 && dil >= 1 && pad >= 0 && kh >= 1 && kw >= 1, "conv2d_fwd: bad geometry");
-  PSEG_REQUIRE(Ho == (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1,
-               "conv2d_fwd: Ho/Wo (%d,%d) inconsistent with H/W (%d,%d) k=%dx%d s=%d p=%d d=%d", Ho, Wo, H, W, kh, kw,
-               stride, pad, dil);
+  const int rc = check_fwd_geometry("conv2d_fwd", H, W, Ho, Wo, kh, kw, stride, pad, dil);
+  if (rc != PSEG_OK) return rc;
   PSEG_REQUIRE(precision >= 0 && precision <= 3, "conv2d_fwd: precision must be one of PSEG_PREC_*");
   return run_gather(fwd_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil), x, nhwc_bytes(B, H, W, Cin, ldx), ldx, w, y, ldy,
                     bias, stat, accumulate, precision, (const unsigned*)amax_x, (const unsigned*)amax_w, workspace,
@@ -1960,18 +1928,12 @@ int pseg_conv2d_dgrad_bnstat(const float* dy, int ldy, const float* wT, float* d
                              int Wo, int Cout, int kh, int kw, int stride, int pad, int dil, const float* y_prev, int ldy_prev,
                              const float* mean, const float* invstd, const float* scale, const float* shift, int act,
                              float* part_db, float* part_dg, int part_rows, void* stream) {
-  PSEG_REQUIRE(dy && wT && dx && y_prev && mean && invstd && scale && shift && part_db && part_dg,
-               "conv2d_dgrad_bnstat: null pointer");
-  PSEG_REQUIRE(stride >= 1 && dil >= 1 && pad >= 0, "conv2d_dgrad_bnstat: bad geometry");
-  PSEG_REQUIRE(act == PSEG_ACT_NONE || act == PSEG_ACT_RELU || act == PSEG_ACT_RELU6, "conv2d_dgrad_bnstat: unknown activation");
-  PSEG_REQUIRE(ldy_prev % 4 == 0 && ldy_prev >= Cin && ((uintptr_t)y_prev & 15) == 0 && ((uintptr_t)part_db & 15) == 0 &&
-                   ((uintptr_t)part_dg & 15) == 0 && ((uintptr_t)mean & 15) == 0 && ((uintptr_t)invstd & 15) == 0 &&
-                   ((uintptr_t)scale & 15) == 0 && ((uintptr_t)shift & 15) == 0,
-               "conv2d_dgrad_bnstat: y_prev / coefficient / partial pointers must be 16-byte aligned, ldy_prev %% 4 == 0");
+  const BnsArgs bns{y_prev, ldy_prev, mean, invstd, scale, shift, act, part_db, part_dg, part_rows};
+  const int rc = check_dgrad_bnstat_args("conv2d_dgrad_bnstat", 4, dy, wT, dx, Cin, stride, pad, dil, bns);
+  if (rc != PSEG_OK) return rc;
   PSEG_REQUIRE(part_rows > 0 && part_rows == pseg_conv2d_dgrad_bnstat_rows(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil),
                "conv2d_dgrad_bnstat: part_rows (%d) is not pseg_conv2d_dgrad_bnstat_rows() of this problem (0 = not covered)",
                part_rows);
-  const BnsArgs bns{y_prev, ldy_prev, mean, invstd, scale, shift, act, part_db, part_dg, part_rows};
   return run_gather(dgrad_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil), dy, nhwc_bytes(B, Ho, Wo, Cout, ldy), ldy, wT,
                     dx, ldx, nullptr, nullptr, 0, PSEG_PREC_FP32, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, nullptr, &bns);
 }

@@ -654,34 +654,30 @@ def _conv2d_dgrad_one(dy, wT_raw, dx, kh, kw, stride, pad, dil, accumulate=False
     skips its reduction pass."""
     Cout, Cin = dy.C, dx.C
     assert wT_raw.numel() == Cout * kh * kw * Cin
-    if bn is not None and FUSE_BN_BWD and not dy.half and not accumulate and _prec(precision, True) == PREC_FP32:
-        rows = _lib.query('pseg_conv2d_dgrad_bnstat_rows', dx.B, dx.H, dx.W, Cin, dy.H, dy.W, Cout, kh, kw, stride, pad, dil)
+
+    def fused_sums(sfx):
+        """The data gradient with the layer's partial sums, fp32 ('') or fp16 ('_h'); False where no kernel carries them."""
         y, co, act = bn
-        if rows > 0 and y.C == Cin and y.M == dx.M and not y.half:
-            part = torch.empty(2, rows, Cin, dtype=torch.float32, device=dx.device)
-            c0, cs = co.data_ptr(), co.shape[1] * 4
-            p0 = part.data_ptr()
-            # (the rows query and the launch read one kernel choice: select_gather in conv_gather.hip)
-            _lib.call('pseg_conv2d_dgrad_bnstat', dy.ptr, dy.ld, wT_raw.data_ptr(), dx.ptr, dx.ld, dx.B, dx.H, dx.W, Cin, dy.H,
-                      dy.W, Cout, kh, kw, stride, pad, dil, y.ptr, y.ld, c0, c0 + cs, c0 + 2 * cs, c0 + 3 * cs, act,
-                      p0, p0 + rows * Cin * 4, rows, _stream())
-            dx.bnpart = BnPart(part, rows, y.ptr)
-            return
+        rows = _lib.query('pseg_conv2d_dgrad_bnstat_rows' + sfx, dx.B, dx.H, dx.W, Cin, dy.H, dy.W, Cout, kh, kw, stride, pad, dil)
+        if not (rows > 0 and y.C == Cin and y.M == dx.M and y.half == (sfx == '_h')):
+            return False
+        part = torch.empty(2, rows, Cin, dtype=torch.float32, device=dx.device)
+        c0, cs = co.data_ptr(), co.shape[1] * 4
+        p0 = part.data_ptr()
+        # (the rows query and the launch read one kernel choice: select_gather in conv_gather.hip, select_gather_h in
+        # conv_half_gather.hip)
+        _lib.call('pseg_conv2d_dgrad_bnstat' + sfx, dy.ptr, dy.ld, wT_raw.data_ptr(), dx.ptr, dx.ld, dx.B, dx.H, dx.W, Cin, dy.H,
+                  dy.W, Cout, kh, kw, stride, pad, dil, y.ptr, y.ld, c0, c0 + cs, c0 + 2 * cs, c0 + 3 * cs, act,
+                  p0, p0 + rows * Cin * 4, rows, _stream())
+        dx.bnpart = BnPart(part, rows, y.ptr)
+        return True
+
+    if bn is not None and FUSE_BN_BWD and not dy.half and not accumulate and _prec(precision, True) == PREC_FP32 and fused_sums(''):
+        return
     if dy.half:
         assert wT_raw.dtype == torch.float16 and dx.half
-        if bn is not None and FUSE_BN_BWD_H and not accumulate:
-            y, co, act = bn
-            rows = _lib.query('pseg_conv2d_dgrad_bnstat_rows_h', dx.B, dx.H, dx.W, Cin, dy.H, dy.W, Cout, kh, kw, stride, pad, dil)
-            if rows > 0 and y.C == Cin and y.M == dx.M and y.half:
-                part = torch.empty(2, rows, Cin, dtype=torch.float32, device=dx.device)
-                c0, cs = co.data_ptr(), co.shape[1] * 4
-                p0 = part.data_ptr()
-                # (the rows query and the launch read one kernel choice: select_gather_h in conv_half.hip)
-                _lib.call('pseg_conv2d_dgrad_bnstat_h', dy.ptr, dy.ld, wT_raw.data_ptr(), dx.ptr, dx.ld, dx.B, dx.H, dx.W, Cin,
-                          dy.H, dy.W, Cout, kh, kw, stride, pad, dil, y.ptr, y.ld, c0, c0 + cs, c0 + 2 * cs, c0 + 3 * cs, act,
-                          p0, p0 + rows * Cin * 4, rows, _stream())
-                dx.bnpart = BnPart(part, rows, y.ptr)
-                return
+        if bn is not None and FUSE_BN_BWD_H and not accumulate and fused_sums('_h'):
+            return
         _lib.call('pseg_conv2d_dgrad_h', dy.ptr, dy.ld, wT_raw.data_ptr(), dx.ptr, dx.ld, dx.B, dx.H, dx.W, Cin, dy.H, dy.W,
                   Cout, kh, kw, stride, pad, dil, int(accumulate), _stream())
         return

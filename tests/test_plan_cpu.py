@@ -2,7 +2,8 @@
 query (tests/plan_queries.py) for a few hundred conv problems, under the default environment, PSEG_CONV_NOSKIP=1,
 PSEG_HCONV_PERSIST=0 / 2 and PSEG_WGRAD_F32DMA=0 / PSEG_WGRAD_NARROW256=0 / PSEG_WGRAD_BPC=2, written by tools/plan_table.py with
 the library of the commit BEFORE the kernel selection was gathered into select_gather / select_wgrad (conv_gather.hip, conv_wgrad.hip) and
-select_gather_h / select_wgrad_h (conv_half.hip): the PSEG_WGRAD_* tables with the commit before the weight gradient's was.
+select_gather_h / select_wgrad_h (conv_half_gather.hip, conv_half_wgrad.hip): the PSEG_WGRAD_* tables with the commit before the
+weight gradient's was.
 A selection that moves changes the statistics layout, the fused-sum rows, a split count or a workspace size, and shows here
 without a GPU."""
 import json
@@ -56,6 +57,11 @@ def _csrc(name):
 
 
 FP32_UNITS = ('conv_gather.hip', 'conv_wgrad.hip', 'core.hip')     # the fp32 / limb conv units and the library's core
+HALF_UNITS = ('conv_half_gather.hip', 'conv_half_wgrad.hip', 'conv_half.h')     # the fp16 conv units and what they share
+
+
+def _half():
+    return ''.join(map(_csrc, HALF_UNITS))
 
 
 def test_gather_selection_is_written_once():
@@ -73,11 +79,13 @@ def test_gather_selection_is_written_once():
 
 
 def test_half_gather_selection_is_written_once():
-    """conv_half.hip has one selection, select_gather_h: no dry run of the launch path behind the fused-sums query, no second or
-    third derivation of the statistics layout, no launch ladders -- and the selection asks the device nothing."""
-    src = open(os.path.join(os.path.dirname(HERE), 'pytorch_segmentation_amd', 'csrc', 'conv_half.hip')).read()
+    """The fp16 gather side (conv_half_gather.hip) has one selection, select_gather_h, and the other fp16 files none: no dry run
+    of the launch path behind the fused-sums query, no second or third derivation of the statistics layout, no launch ladders
+    anywhere in them -- and the selection asks the device nothing."""
     for gone in ('bns_query', 'plan_fwd_stats_h', 'plan_run_h', 'PSEG_H_LAUNCH', 'PSEG_HP_LAUNCH'):
-        assert gone not in src, gone
+        assert gone not in _half(), gone
+    src = _csrc('conv_half_gather.hip')
+    assert 'select_gather_h(' not in _csrc('conv_half_wgrad.hip') + _csrc('conv_half.h')
     start = src.index('static HGatherChoice select_gather_h(')
     body = src[start:src.index('\n}\n', start)]
     assert 'return c;' in body and len(body.splitlines()) > 40
@@ -90,7 +98,7 @@ def _body(src, head):
 
 
 @pytest.mark.parametrize('name,head', [('conv_wgrad.hip', 'static WgradChoice select_wgrad('),
-                                       ('conv_half.hip', 'static HWgradChoice select_wgrad_h(')])
+                                       ('conv_half_wgrad.hip', 'static HWgradChoice select_wgrad_h(')])
 def test_wgrad_selection_is_pure(name, head):
     """The weight gradient's kernel is picked in one function per number format, which launches nothing and asks the device
     nothing; the launch path and the queries (_splits, _slabs, _workspace_bytes) all go through it."""
@@ -101,14 +109,15 @@ def test_wgrad_selection_is_pure(name, head):
     fn = head[head.index('select_wgrad'):-1]
     assert len(re.findall(r'\b%s\(' % fn, src)) >= 4                   # its definition, the launch path, both queries
     assert not re.search(r'\bplan_wgrad(_h)?\(', src.replace(body, ''))  # no plan of anyone's own beside it
-    for other in ('conv_gather.hip', 'core.hip'):                       # ... nor a selection or a plan in the other fp32 units
+    # ... nor a selection or a plan in the other fp32 units, the fp16 gather unit or the fp16 units' header
+    for other in ('conv_gather.hip', 'core.hip', 'conv_half_gather.hip', 'conv_half.h'):
         assert not re.search(r'\b(select|plan)_wgrad(_h)?\(', _csrc(other)), other
 
 
 def test_wgrad_launches_are_written_once():
-    """No launch macros in conv_half.hip; the slab reduction is launched from launch_slab_reduce alone (the batch kernel is
+    """No launch macros in the fp16 conv units; the slab reduction is launched from launch_slab_reduce alone (the batch kernel is
     another kernel); WgradParams::skip_rows is assigned by set_wgrad_geometry (conv_common.h) and nowhere else."""
-    fp32, half, common = ''.join(map(_csrc, FP32_UNITS)), _csrc('conv_half.hip'), _csrc('conv_common.h')
+    fp32, half, common = ''.join(map(_csrc, FP32_UNITS)), _half(), _csrc('conv_common.h')
     assert 'PSEG_HW_LAUNCH' not in half
     launches = [m.start() for m in re.finditer(r'hipLaunchKernelGGL\(\s*\(?slab_reduce_kernel\b', fp32 + half + common)]
     assert len(launches) == 1
@@ -121,10 +130,10 @@ def test_wgrad_launches_are_written_once():
 
 def test_switches_are_read_in_one_place():
     """cfg_load (conv_common.h) is the only reader of the conv planning switches: env_int( occurs in its own definition and in
-    cfg_load's body, nowhere else in conv_common.h and nowhere in conv_gather.hip / conv_wgrad.hip / core.hip / conv_half.hip, which
-    do not call getenv( either -- so pseg_config_reload() reaches every switch and no plan, selection or launch helper keeps a
+    cfg_load's body, nowhere else in conv_common.h and nowhere in conv_gather.hip / conv_wgrad.hip / core.hip / the fp16 units
+    (conv_half_gather.hip, conv_half_wgrad.hip, conv_half.h), which do not call getenv( either -- so pseg_config_reload() reaches every switch and no plan, selection or launch helper keeps a
     per-process copy of one."""
-    fp32, half, common = ''.join(map(_csrc, FP32_UNITS)), _csrc('conv_half.hip'), _csrc('conv_common.h')
+    fp32, half, common = ''.join(map(_csrc, FP32_UNITS)), _half(), _csrc('conv_common.h')
     assert 'env_int(' not in fp32 and 'env_int(' not in half
     assert 'getenv(' not in fp32 and 'getenv(' not in half
     definition = _body(common, 'static int env_int(')
@@ -139,8 +148,10 @@ def test_lab_build_is_gone():
     """The fp16 conv lab build (measured-and-rejected kernels, ablation bits) is in no source under csrc/."""
     csrc = os.path.join(os.path.dirname(HERE), 'pytorch_segmentation_amd', 'csrc')
     names = [n for n in sorted(os.listdir(csrc)) if n.endswith(('.hip', '.h', '.py'))]
-    assert 'conv_half.hip' in names and 'build.py' in names and set(FP32_UNITS) <= set(names)
+    assert 'conv_half.hip' not in names and 'build.py' in names and set(FP32_UNITS + HALF_UNITS) <= set(names)
     assert sorted(n for n in names if n.endswith('.hip')) == sorted(csrc_build.SOURCES)     # every unit is built, none is left behind
+    # ... and every header is a dependency of the build
+    assert sorted(n for n in names if n.endswith('.h')) == sorted(h for h in csrc_build.HEADERS if os.sep not in h)
     for n in names:
         src = _csrc(n)
         for gone in ('PSEG_LAB', 'PSEG_ABLATE', 'gather_hh_kernel', 'gather_hr_kernel'):

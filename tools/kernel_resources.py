@@ -1,5 +1,5 @@
 """Register / LDS / occupancy table of the kernels of one HIP source (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: python tools/kernel_resources.py conv_half.hip [name filter]   (or a saved remark file ending in .txt)"""
+usage: python tools/kernel_resources.py conv_half_gather.hip [name filter]   (or a saved remark file ending in .txt)"""
 import os
 import re
 import subprocess
