@@ -5,7 +5,9 @@
 //    models/deeplabv3plus.py:34-37,40-43, models/unet.py:30-55, utils/utils.py:18-20).  Source index and
 //    weights follow ATen's area_pixel_compute_source_index in fp32.  Backward is a GATHER over the output
 //    pixels that touch an input pixel (fixed summation order, no float atomics).
-//  - maxpool 3x3/s2 of the ResNet stem, backward via saved window positions (first maximum wins, as ATen).
+//  - maxpool 3x3/s2 of the ResNet stem, backward via saved window positions (first maximum wins, as ATen; a NaN tap is
+//    always taken -- ATen's `val > maxval || isnan(val)` -- so a NaN anywhere in a window reaches the output, and a window
+//    of -inf keeps its first in-map tap).
 #include "common.h"
 #include "half_io.h"
 
@@ -446,7 +448,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ 
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          if (!any || v[e] > best[e]) {
+          if (!any || v[e] > best[e] || v[e] != v[e]) {
             best[e] = v[e];
             pos[e] = (uint32_t)(r * p.k + s);
           }
@@ -739,7 +741,11 @@ int pseg_bilinear_bwd(const float* dy, int ldy, int B, int Hi, int Wi, int C, fl
     if (workspace != nullptr && workspace_bytes >= tmp_elems * 4 && tmp_elems < (1LL << 31) && al16(workspace)) {
       // separable two-pass form (scratch: pseg_bilinear_bwd_workspace_bytes)
       const long long nrows = (long long)B * C * Ho;
-      // taps per output column after trimming: <= 2*ceil(Wo/Wi) + 1
+      // taps per output column after trimming: <= 2*ceil(Wo/Wi) + 1 without align_corners; with it the count follows
+      // 2*(Wo-1)/(Wi-1) and passes this estimate by one at Wi = 4, Wo = 20 (12 real taps for an estimate of 11).  Over every
+      // width the LDS pass accepts, the fp32 weights never span more than kMaxTaps columns (enumerated on the CPU:
+      // tests/test_resize_ref_cpu.py), which is what the LDS kernel -- it has no in-place fallback -- relies on.
+      // (tests/test_pool_resize_gpu.py keeps a copy of the condition below to place its cases: change both together.)
       const int taps = 2 * ((Wo + Wi - 1) / Wi) + 1;
       if (Wi <= 256 && Wo <= 2048 && Wo % 4 == 0 && al16(dy) && taps <= kMaxTaps) {
         const int RB = 8192 / Wo;                                  // rows per block (32 KB of LDS)
