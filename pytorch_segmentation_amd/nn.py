@@ -18,20 +18,13 @@ Parameters are ordinary ``nn.Parameter``s with the reference's names / shapes (s
 reference and the oracle); their storage lives in the arena (arena.py) in kernel-native layout.
 """
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
 
 from . import ops
-from .ops import ACT_NONE, ACT_RELU, ACT_RELU6, Act
-
-
-def _round4(n):
-    return (n + 3) // 4 * 4
-
-
-def _round8(n):
-    return (n + 7) // 8 * 8
+from .ops import ACT_NONE, ACT_RELU, ACT_RELU6, Act, _round4, _round8
 
 
 class Env:
@@ -167,31 +160,6 @@ class Conv2d(nn.Conv2d):
             raise RuntimeError('fp16 filter copies are missing: call ParamArena.prepare_half() before a half-precision pass')
         return wh, wT
 
-    def _fwd_half(self, x, env, out, want_stats, out_f32):
-        assert x.C == self.cin_h, 'conv expects %d (padded) input channels, got %d' % (self.cin_h, x.C)
-        Ho, Wo = self.out_hw(x.H, x.W)
-        y = out if out is not None else Act.empty(x.B, Ho, Wo, self.cout_h, x.device,
-                                                  dtype=torch.float32 if out_f32 else torch.float16)
-        assert (y.B, y.H, y.W, y.C) == (x.B, Ho, Wo, self.cout_h)
-        kh, kw = self.kernel_size
-        s, p, d = self.stride[0], self.padding[0], self.dilation[0]
-        stats = None
-        if self.depthwise:
-            assert self.bias is None, 'depthwise conv with bias is not on the hot path'
-            # the depthwise kernels read the fp32 filter / write the gradient straight in the arena, padded to 4 channels, while
-            # fp16 activations are padded to 8: a width with C % 8 == 4 would read and write past the filter segment
-            # (MobileNetV2's widths are multiples of 8; anything else is refused rather than mis-addressed)
-            if self.cin_h != self.cin_p:
-                raise NotImplementedError('depthwise conv with %d channels under the half policy: channel count must be a '
-                                          'multiple of 8' % self.in_channels)
-            ops.dwconv_fwd(x, _raw(self, 'weight')[0], y, kh, s, p)      # (fp32 filter, fp16 activations)
-            if want_stats:
-                stats = ops.col_stats(y)
-        else:
-            b = self._bias_h() if self.bias is not None else None
-            stats = ops.conv2d_fwd(x, self._half_filters()[0], b, y, kh, kw, s, p, d, want_stats=want_stats)
-        return y, stats, (x if env.save else None)
-
     def _bias_h(self):
         """fp32 bias padded to the fp16 path's output channels (zeros beyond the arena's padding)."""
         b = _raw(self, 'bias')[0]
@@ -204,34 +172,74 @@ class Conv2d(nn.Conv2d):
         ops.copy2d(Act(b, 1, 1, 1, self.cout_p, self.cout_p), Act(pad, 1, 1, 1, self.cout_p, self.cout_h))
         return pad
 
+    # What differs between the two storage types -- fp32 activations (every policy but 'half') and fp16 ones -- is stated in the
+    # next three helpers; fwd and bwd are written once.
+    def _channels(self, half):
+        """(input, output) channels as the activations carry them: padded to fours in fp32, to eights in fp16"""
+        return (self.cin_h, self.cout_h) if half else (self.cin_p, self.cout_p)
+
+    def _fwd_operands(self, x, env):
+        """-> (filter, bias, arithmetic arguments) of the dense forward conv for x's storage type"""
+        if x.half:      # the fp16 filter copy; one arithmetic
+            return self._half_filters()[0], (self._bias_h() if self.bias is not None else None), {}
+        w = _raw(self, 'weight')[0]
+        b = _raw(self, 'bias')[0] if self.bias is not None else None
+        fprec = env.fwd_prec if self.limb_pays else ops.PREC_FP32
+        if fprec != ops.PREC_FP16X3:
+            return w, b, dict(precision=fprec)
+        # fp16-limb forward: both operands are scaled by an exact power of two from their max|.| bound
+        wam = getattr(self, '_wamax_view', None) if env.wamax_fresh else None
+        return w, b, dict(precision=fprec, amax_x=x.amax if x.amax is not None else ops.amax_of(x),
+                          amax_w=wam if wam is not None else ops.amax_of(w))
+
+    def _filter_T(self, w, half, env):
+        """the [Cin][taps][Cout] filter the data gradient reads: the arena's copy when it is fresh, else transposed here"""
+        if half:
+            return self._half_filters()[1]
+        wT = getattr(self, '_wT_view', None) if env.wT_fresh else None
+        if wT is None:
+            kh, kw = self.kernel_size
+            wT = ops.filter_transpose(w, self.cout_p, kh * kw, self.cin_p)
+        return wT
+
+    @staticmethod
+    def _bn_for_dgrad(bn_prev, dx, dx_accumulate):
+        """(y, co, act) of the BatchNorm layer below for ops.conv2d_dgrad(bn=...) when dx is exactly that layer's dz -- nothing
+        else adds to it, the layer runs on batch statistics and recomputes its activation mask from y -- else None"""
+        if bn_prev is None or dx_accumulate:
+            return None
+        y = bn_prev.y
+        if bn_prev.z is None and bn_prev.mask is None and bn_prev.use_batch and y.C == dx.C and y.M == dx.M:
+            return y, bn_prev.co, bn_prev.act
+        return None
+
     def fwd(self, x, env, out=None, want_stats=False, out_f32=False):
         """x: Act with C == padded in_channels.  Returns (y, stats|None, saved).
         out_f32 (half-precision policy only): write y as fp32 (the class logits, which the loss reads)."""
-        if x.half:
-            return self._fwd_half(x, env, out, want_stats, out_f32)
-        assert x.C == self.cin_p, 'conv expects %d (padded) input channels, got %d' % (self.cin_p, x.C)
-        w, _ = _raw(self, 'weight')
-        b = _raw(self, 'bias')[0] if self.bias is not None else None
+        half = x.half
+        cin, cout = self._channels(half)
+        assert x.C == cin, 'conv expects %d (padded) input channels, got %d' % (cin, x.C)
         Ho, Wo = self.out_hw(x.H, x.W)
-        y = out if out is not None else Act.empty(x.B, Ho, Wo, self.cout_p, x.device)
-        assert (y.B, y.H, y.W, y.C) == (x.B, Ho, Wo, self.cout_p)
+        y = out if out is not None else Act.empty(x.B, Ho, Wo, cout, x.device,
+                                                  dtype=torch.float16 if half and not out_f32 else torch.float32)
+        assert (y.B, y.H, y.W, y.C) == (x.B, Ho, Wo, cout)
         kh, kw = self.kernel_size
         s, p, d = self.stride[0], self.padding[0], self.dilation[0]
         stats = None
         if self.depthwise:
-            assert b is None, 'depthwise conv with bias is not on the hot path'
-            ops.dwconv_fwd(x, w, y, kh, s, p)
+            assert self.bias is None, 'depthwise conv with bias is not on the hot path'
+            # the depthwise kernels read the fp32 filter / write the gradient straight in the arena, padded to 4 channels, while
+            # fp16 activations are padded to 8: a width with C % 8 == 4 would read and write past the filter segment
+            # (MobileNetV2's widths are multiples of 8; anything else is refused rather than mis-addressed)
+            if half and self.cin_h != self.cin_p:
+                raise NotImplementedError('depthwise conv with %d channels under the half policy: channel count must be a '
+                                          'multiple of 8' % self.in_channels)
+            ops.dwconv_fwd(x, _raw(self, 'weight')[0], y, kh, s, p)      # (fp32 filter, whatever the activations are)
             if want_stats:
                 stats = ops.col_stats(y)
         else:
-            am = {}
-            fprec = env.fwd_prec if self.limb_pays else ops.PREC_FP32
-            if fprec == ops.PREC_FP16X3:
-                # fp16-limb forward: both operands are scaled by an exact power of two from their max|.| bound
-                wam = getattr(self, '_wamax_view', None) if env.wamax_fresh else None
-                am = dict(amax_x=x.amax if x.amax is not None else ops.amax_of(x),
-                          amax_w=wam if wam is not None else ops.amax_of(w))
-            stats = ops.conv2d_fwd(x, w, b, y, kh, kw, s, p, d, want_stats=want_stats, precision=fprec, **am)
+            w, b, arith = self._fwd_operands(x, env)
+            stats = ops.conv2d_fwd(x, w, b, y, kh, kw, s, p, d, want_stats=want_stats, **arith)
         return y, stats, (x if env.save else None)
 
     def wants_dy_planes(self, x, env):
@@ -249,6 +257,48 @@ class Conv2d(nn.Conv2d):
         Ho, Wo = self.out_hw(x.H, x.W)
         return ops.dgrad_planes_ok_shape(x.B, x.H, x.W, self.cin_p, Ho, Wo, self.cout_p, kh, kw, s, p, d)
 
+    def _wgrad(self, x, dy, env, forks, concurrent):
+        """The weight gradient (+ bias gradient) into the gradient arena -- under the half policy from fp16 operands, scaled by the
+        loss scale, which the optimiser divides out -- on the auxiliary stream when `forks`; then the grad_ready callback."""
+        side = ops.fork_aux(x.device) if forks else None
+        # (depthwise weight gradients are forked too, since round 4: in the MobileNetV2 UNet they were 17 launches of the serial
+        # backward chain -- 0.18 ms of a 3.6 ms replayed step)
+        if side is not None:
+            with torch.cuda.stream(side):
+                self._wgrad_launches(x, dy, env, concurrent)
+            x.t.record_stream(side)     # the caching allocator must not hand these blocks out again before the
+            dy.t.record_stream(side)    # auxiliary stream is done with them
+        else:
+            self._wgrad_launches(x, dy, env, concurrent)
+        if env.grad_ready is not None:
+            env.grad_ready(self)
+
+    def _wgrad_launches(self, x, dy, env, concurrent):
+        dw = _raw(self, 'weight')[1]
+        kh, kw = self.kernel_size
+        s, p, d = self.stride[0], self.padding[0], self.dilation[0]
+        if self.depthwise:
+            ops.dwconv_wgrad(x, dy, dw, kh, s, p, accumulate=env.accumulate)
+        else:
+            # the fp16 path's channel padding may differ from the arena's (3-channel stem, 2-class classifier): the gradient then
+            # goes into a scratch, and its arena-shaped corner (first cout_p rows, first cin_p channels of every tap) is copied /
+            # added into the arena
+            cin, cout = self._channels(x.half)
+            padded = (cin, cout) != (self.cin_p, self.cout_p)
+            # The slab pool is skipped (a) for a gradient that a reducer picks up layer by layer, which must be complete when this
+            # call returns, and (b) under `half` when the fp16 padding differs from the arena's: the pool folds into the arena
+            pool = env.slab_pool if (env.grad_ready is None and not padded) else None
+            bprec = env.bwd_prec if self.limb_pays else ops.PREC_FP32      # (the fp16 kernels have one arithmetic and ignore it)
+            into = torch.empty(cout * kh * kw * cin, dtype=torch.float32, device=x.device) if padded else dw
+            ops.conv2d_wgrad(x, dy, into, kh, kw, s, p, d, accumulate=env.accumulate and not padded, precision=bprec, pool=pool,
+                             concurrent=concurrent)
+            if padded:
+                rows = self.cout_p * kh * kw
+                ops.copy2d(Act(into, 1, 1, rows, self.cin_p, cin), Act(dw.view(-1), 1, 1, rows, self.cin_p, self.cin_p),
+                           accumulate=env.accumulate)
+        if self.bias is not None:
+            ops.col_sum(dy, _raw(self, 'bias')[1], accumulate=env.accumulate, C=self.cout_p)
+
     def bwd(self, dy, saved, env, need_dx=True, dx_out=None, dx_accumulate=False, bn_prev=None, wgrad_on_main=False,
             wgrad_concurrent=None):
         """Enqueue wgrad (+bias grad) into the gradient arena and, if asked, dgrad.  Returns dx or None.
@@ -256,124 +306,31 @@ class Conv2d(nn.Conv2d):
         stem: the last kernel of backward, meant to run beside the auxiliary stream's queue).  wgrad_concurrent: how the launch is
         PLANNED -- True: as one that runs beside another stream's kernels (one resident block per CU, half the slabs), False: as one
         that runs alone, None: concurrent exactly when it is forked.  (both are arguments now; the shared Env flag is
-        not toggled around the call any more.)
-        bn_prev: the saved state of the BatchNorm2d whose output (after its activation) is this conv's input, when this conv is
-        that output's ONLY consumer and the layer has no residual -- dx is then exactly that layer's dz, and the data gradient
-        computes its backward partial sums on the way out (ops.conv2d_dgrad(bn=...); BatchNorm2d.bwd picks them up)."""
+        not toggled around the call any more.)  The fp16 weight gradient has one plan: wgrad_concurrent does not reach it.
+        bn_prev: the saved state (BnSaved) of the BatchNorm2d whose output (after its activation) is this conv's input, when this
+        conv is that output's ONLY consumer and the layer has no residual -- dx is then exactly that layer's dz, and the data
+        gradient computes its backward partial sums on the way out (ops.conv2d_dgrad(bn=...); BatchNorm2d.bwd picks them up)."""
         x = saved
-        if x.half:
-            return self._bwd_half(dy, x, env, need_dx, dx_out, dx_accumulate, bn_prev, wgrad_on_main)
-        w, dw = _raw(self, 'weight')
+        half = x.half
+        cin, cout = self._channels(half)
+        assert not half or (dy.half and dy.C == cout)
         kh, kw = self.kernel_size
         s, p, d = self.stride[0], self.padding[0], self.dilation[0]
-        bprec = env.bwd_prec if self.limb_pays else ops.PREC_FP32
-        # (a gradient that a reducer picks up layer by layer must be complete when this call returns)
-        pool = env.slab_pool if env.grad_ready is None else None
-
-        forked = bool(env.overlap_wgrad and ops.OVERLAP_WGRAD)      # (the weight gradient runs beside the data gradients)
-        if wgrad_concurrent is not None:
-            forked = bool(wgrad_concurrent)
-        elif wgrad_on_main:
-            forked = False
-
-        def wgrad_body():
-            if self.depthwise:
-                ops.dwconv_wgrad(x, dy, dw, kh, s, p, accumulate=env.accumulate)
-            else:
-                ops.conv2d_wgrad(x, dy, dw, kh, kw, s, p, d, accumulate=env.accumulate, precision=bprec, pool=pool,
-                                 concurrent=forked)
-            if self.bias is not None:
-                ops.col_sum(dy, _raw(self, 'bias')[1], accumulate=env.accumulate)
-
-        def wgrad():
-            # (depthwise weight gradients too, since round 4: in the MobileNetV2 UNet they were 17 launches of the serial
-            # backward chain -- 0.18 ms of a 3.6 ms replayed step)
-            if env.overlap_wgrad and ops.OVERLAP_WGRAD and not wgrad_on_main:
-                side = ops.fork_aux(x.device)
-                with torch.cuda.stream(side):
-                    wgrad_body()
-                x.t.record_stream(side)     # the caching allocator must not hand these blocks out again before the
-                dy.t.record_stream(side)    # auxiliary stream is done with them
-            else:
-                wgrad_body()
-            if env.grad_ready is not None:
-                env.grad_ready(self)
+        forks = bool(env.overlap_wgrad and ops.OVERLAP_WGRAD and not wgrad_on_main)    # (it runs beside the data gradients)
+        concurrent = forks if wgrad_concurrent is None else bool(wgrad_concurrent)
 
         # Order on the device.  Default: the weight gradient is forked to the auxiliary stream BEFORE the data gradient is
         # enqueued.  PSEG_WGRAD_AFTER_DGRAD=1 forks it after (so that it would start when the data gradient -- matrix-pipe
         # bound like itself -- has finished and run beside the HBM-bound BatchNorm backward passes of the next layer down):
-        # measured no better, 51.0 -> 52.2 ms/step at the headline config, kept selectable.
-        late = need_dx and ops.WGRAD_AFTER_DGRAD
+        # measured no better, 51.0 -> 52.2 ms/step at the headline config, kept selectable.  Under `half` the switch has no
+        # effect (it was measured, and is wired, for the fp32 storage policies only).
+        late = need_dx and ops.WGRAD_AFTER_DGRAD and not half
         if not late:
-            wgrad()
+            self._wgrad(x, dy, env, forks, concurrent)
         if not need_dx:
             return None
-        dx = dx_out if dx_out is not None else Act.empty(x.B, x.H, x.W, self.cin_p, x.device)
-        if self.depthwise:
-            if dx_accumulate:
-                tmp = Act.empty(x.B, x.H, x.W, self.cin_p, x.device)
-                ops.dwconv_dgrad(dy, w, tmp, kh, s, p)
-                ops.copy2d(tmp, dx, accumulate=True)
-            else:
-                ops.dwconv_dgrad(dy, w, dx, kh, s, p)
-        else:
-            wT = getattr(self, '_wT_view', None) if env.wT_fresh else None
-            if wT is None:
-                wT = ops.filter_transpose(w, self.cout_p, kh * kw, self.cin_p)
-            if dy.planes is not None and bprec == ops.PREC_BF16X3 and ops.dgrad_planes_ok(dy, dx, kh, kw, s, p, d):
-                # dy arrived pre-split (BatchNorm backward wrote the limb planes): split the filter once, DMA kernel
-                wp = ops.split_planes(wT.view(self.cin_p, kh * kw * self.cout_p))
-                ops.conv2d_dgrad_planes(dy.planes, dy, wp, dx, kh, kw, s, p, d, accumulate=dx_accumulate)
-            else:
-                bn = None
-                if bn_prev is not None and not dx_accumulate:
-                    by, bz, bco, bact, use_batch, bmask = bn_prev
-                    if bz is None and bmask is None and use_batch and by.C == dx.C and by.M == dx.M:
-                        bn = (by, bco, bact)
-                ops.conv2d_dgrad(dy, wT, dx, kh, kw, s, p, d, accumulate=dx_accumulate, precision=bprec, bn=bn)
-        if late:
-            wgrad()
-        return dx
-
-    def _bwd_half(self, dy, x, env, need_dx, dx_out, dx_accumulate, bn_prev=None, wgrad_on_main=False):
-        """fp16 operands; the weight gradient lands in the fp32 gradient arena (scaled by the loss scale, which the
-        optimiser divides out)."""
-        assert dy.half and dy.C == self.cout_h
-        w, dw = _raw(self, 'weight')
-        kh, kw = self.kernel_size
-        s, p, d = self.stride[0], self.padding[0], self.dilation[0]
-        padded = (self.cin_h, self.cout_h) != (self.cin_p, self.cout_p)
-        pool = env.slab_pool if (env.grad_ready is None and not padded) else None
-
-        def wgrad_body():
-            if self.depthwise:
-                ops.dwconv_wgrad(x, dy, dw, kh, s, p, accumulate=env.accumulate)
-            elif padded:
-                # the fp16 path's channel padding differs from the arena's: gradient into a scratch, its arena-shaped
-                # corner (first cout_p rows, first cin_p channels of every tap) copied / added into the arena
-                taps = kh * kw
-                tmp = torch.empty(self.cout_h * taps * self.cin_h, dtype=torch.float32, device=x.device)
-                ops.conv2d_wgrad(x, dy, tmp, kh, kw, s, p, d, accumulate=False)
-                ops.copy2d(Act(tmp, 1, 1, self.cout_p * taps, self.cin_p, self.cin_h),
-                           Act(dw.view(-1), 1, 1, self.cout_p * taps, self.cin_p, self.cin_p), accumulate=env.accumulate)
-            else:
-                ops.conv2d_wgrad(x, dy, dw, kh, kw, s, p, d, accumulate=env.accumulate, pool=pool)
-            if self.bias is not None:
-                ops.col_sum(dy, _raw(self, 'bias')[1], accumulate=env.accumulate, C=self.cout_p)
-
-        if env.overlap_wgrad and ops.OVERLAP_WGRAD and not wgrad_on_main:
-            side = ops.fork_aux(x.device)
-            with torch.cuda.stream(side):
-                wgrad_body()
-            x.t.record_stream(side)
-            dy.t.record_stream(side)
-        else:
-            wgrad_body()
-        if env.grad_ready is not None:
-            env.grad_ready(self)
-        if not need_dx:
-            return None
-        dx = dx_out if dx_out is not None else Act.empty(x.B, x.H, x.W, self.cin_h, x.device, dtype=torch.float16)
+        w = _raw(self, 'weight')[0]
+        dx = dx_out if dx_out is not None else Act.empty(x.B, x.H, x.W, cin, x.device, dtype=x.dtype)
         if self.depthwise:
             if dx_accumulate:
                 tmp = dx.like()
@@ -382,12 +339,17 @@ class Conv2d(nn.Conv2d):
             else:
                 ops.dwconv_dgrad(dy, w, dx, kh, s, p)
         else:
-            bn = None
-            if bn_prev is not None and not dx_accumulate:
-                by, bz, bco, bact, use_batch, bmask = bn_prev
-                if bz is None and bmask is None and use_batch and by.C == dx.C and by.M == dx.M:
-                    bn = (by, bco, bact)
-            ops.conv2d_dgrad(dy, self._half_filters()[1], dx, kh, kw, s, p, d, accumulate=dx_accumulate, bn=bn)
+            bprec = env.bwd_prec if self.limb_pays else ops.PREC_FP32      # (ignored by the fp16 kernels)
+            wT = self._filter_T(w, half, env)
+            if dy.planes is not None and bprec == ops.PREC_BF16X3 and ops.dgrad_planes_ok(dy, dx, kh, kw, s, p, d):
+                # dy arrived pre-split (BatchNorm backward wrote the limb planes, fp32 storage only): split the filter once, DMA kernel
+                wp = ops.split_planes(wT.view(cin, kh * kw * cout))
+                ops.conv2d_dgrad_planes(dy.planes, dy, wp, dx, kh, kw, s, p, d, accumulate=dx_accumulate)
+            else:
+                ops.conv2d_dgrad(dy, wT, dx, kh, kw, s, p, d, accumulate=dx_accumulate, precision=bprec,
+                                 bn=self._bn_for_dgrad(bn_prev, dx, dx_accumulate))
+        if late:
+            self._wgrad(x, dy, env, forks, concurrent)
         return dx
 
     def forward(self, x):
@@ -405,6 +367,12 @@ class Conv2d(nn.Conv2d):
     @property
     def block_out_channels(self):
         return self.out_channels
+
+
+# What BatchNorm2d.fwd / .fwd_pooled keep for backward: the layer's input y; its output z where backward must re-read it (a
+# residual layer, eval mode), else None; the coefficient tensor [4][C]; the activation code; whether the batch's statistics
+# normalised; a residual layer's activation bitmask or None.  Conv2d.bwd(bn_prev=...) reads it too (the fused backward sums).
+BnSaved = namedtuple('BnSaved', 'y z co act use_batch mask')
 
 
 class BatchNorm2d(nn.BatchNorm2d):
@@ -431,48 +399,58 @@ class BatchNorm2d(nn.BatchNorm2d):
             module.num_batches_tracked += module._nbt_pending
             module._nbt_pending = 0
 
+    def _affine(self):
+        return (_raw(self, 'weight')[0], _raw(self, 'bias')[0]) if self.affine else (None, None)
+
+    def _batch_stats(self, y, stats):
+        """The batch-statistics preamble of fwd and fwd_pooled: -> (column partials of y -- computed here when the conv did not
+        hand them in --, the arguments of ops.bn_finalize / ops.bn_fwd_fused behind the count: gamma, beta, the running statistics
+        to update (training mode only), momentum, eps).  Counts the batch."""
+        g, b = self._affine()
+        if stats is None:
+            stats = ops.col_stats(y)
+        if y.M <= 1:
+            raise ValueError('Expected more than 1 value per channel when training, got input size %s'
+                             % ((y.B, self.num_features, y.H, y.W),))
+        mom = self.momentum
+        rm = rv = None
+        if self.track_running_stats and self.training:
+            rm, rv = self.running_mean, self.running_var
+            self.__dict__['_nbt_pending'] += 1      # (nn.Module.__setattr__ costs ~3 us per write)
+            if mom is None:  # cumulative moving average
+                mom = 1.0 / float(int(self.num_batches_tracked) + self._nbt_pending)
+        return stats, (g, b, rm, rv, mom if mom is not None else 0.0, self.eps)
+
+    @staticmethod
+    def _result(y, out, env):
+        z = out if out is not None else y.like()
+        if env.track_amax and z.amax is None:
+            z.amax = ops.new_amax(z.device)
+        return z
+
     def fwd(self, y, stats, env, act=ACT_NONE, residual=None, out=None):
-        """z = act(BN(y) (+ residual)).  `stats` are the column partials of y (training mode)."""
+        """z = act(BN(y) (+ residual)) -> (z, BnSaved | None).  `stats` are the column partials of y (training mode)."""
         C = self.num_features
         assert y.C == C and C % 4 == 0, 'BatchNorm2d HIP path needs C %% 4 == 0 (got %d)' % C
-        g = _raw(self, 'weight')[0] if self.affine else None
-        b = _raw(self, 'bias')[0] if self.affine else None
         use_batch = self.training or not self.track_running_stats
         mask = None
         if use_batch:
-            if stats is None:
-                stats = ops.col_stats(y)
-            if y.M <= 1:
-                raise ValueError('Expected more than 1 value per channel when training, got input size %s'
-                                 % ((y.B, C, y.H, y.W),))
-            mom = self.momentum
-            rm = self.running_mean if self.track_running_stats else None
-            rv = self.running_var if self.track_running_stats else None
-            if self.track_running_stats and self.training:
-                self.__dict__['_nbt_pending'] += 1      # (nn.Module.__setattr__ costs ~3 us per write)
-                if mom is None:  # cumulative moving average
-                    mom = 1.0 / float(int(self.num_batches_tracked) + self._nbt_pending)
-            z = out if out is not None else y.like()
-            if env.track_amax and z.amax is None:
-                z.amax = ops.new_amax(z.device)
+            stats, fin = self._batch_stats(y, stats)
+            z = self._result(y, out, env)
             if ops.bn_small_path(stats[1], y.M, C):
                 # small tensors: finalize + normalise + activation (+ residual) in ONE launch
-                co = ops.bn_fwd_fused(stats, y.M, g, b, rm if self.training else None, rv if self.training else None,
-                                      mom if mom is not None else 0.0, self.eps, y, act, z, residual=residual)
+                co = ops.bn_fwd_fused(stats, y.M, *fin, y, act, z, residual=residual)
             else:
-                co = ops.bn_finalize(stats, y.M, g, b, rm if self.training else None, rv if self.training else None,
-                                     mom if mom is not None else 0.0, self.eps)
+                co = ops.bn_finalize(stats, y.M, *fin)
                 # a residual layer's activation mask cannot be recomputed from y: keep it as one bit per element
                 mask = ops.bn_act_fwd(y, co, act, z, residual=residual,
                                       want_mask=residual is not None and env.save and ops.BN_MASK)
         else:
-            co = ops.bn_eval_coeffs(g, b, self.running_mean, self.running_var, self.eps)
-            z = out if out is not None else y.like()
-            if env.track_amax and z.amax is None:
-                z.amax = ops.new_amax(z.device)
+            co = ops.bn_eval_coeffs(*self._affine(), self.running_mean, self.running_var, self.eps)
+            z = self._result(y, out, env)
             ops.bn_act_fwd(y, co, act, z, residual=residual)
         # without a residual the backward kernels recompute the activation mask from y: z need not be re-read
-        saved = (y, z if (residual is not None or not use_batch) else None, co, act, use_batch, mask) if env.save else None
+        saved = BnSaved(y, z if (residual is not None or not use_batch) else None, co, act, use_batch, mask) if env.save else None
         return z, saved
 
     def fwd_pooled(self, y, stats, env, act, k, stride, pad):
@@ -484,37 +462,26 @@ class BatchNorm2d(nn.BatchNorm2d):
             return None
         C = self.num_features
         assert y.C == C and C % 4 == 0
-        g = _raw(self, 'weight')[0] if self.affine else None
-        b = _raw(self, 'bias')[0] if self.affine else None
-        if stats is None:
-            stats = ops.col_stats(y)
-        mom = self.momentum
-        rm = self.running_mean if self.track_running_stats else None
-        rv = self.running_var if self.track_running_stats else None
-        if self.track_running_stats and self.training:
-            self.__dict__['_nbt_pending'] += 1
-            if mom is None:
-                mom = 1.0 / float(int(self.num_batches_tracked) + self._nbt_pending)
-        co = ops.bn_finalize(stats, y.M, g, b, rm if self.training else None, rv if self.training else None,
-                             mom if mom is not None else 0.0, self.eps)
+        stats, fin = self._batch_stats(y, stats)
+        co = ops.bn_finalize(stats, y.M, *fin)
         Hp, Wp = ops.conv_out_size(y.H, k, stride, pad, 1), ops.conv_out_size(y.W, k, stride, pad, 1)
         p = y.new(y.B, Hp, Wp, C)
         arg = ops.bn_act_maxpool_fwd(y, co, act, p, k, stride, pad, want_argmax=env.save)
-        saved = (y, None, co, act, use_batch, None) if env.save else None
+        saved = BnSaved(y, None, co, act, use_batch, None) if env.save else None
         return p, arg, saved
 
     def bwd(self, dz, saved, env, dy_out=None, dres=None, res_accumulate=False, want_planes=False):
         """Returns dy (gradient w.r.t. the BN input).  dres (optional Act) receives the residual-branch gradient.
         want_planes: also write dy as bf16 limb planes (dy.planes) for the consumer conv's pre-split data gradient."""
-        y, z, co, act, use_batch, mask = saved
+        y, use_batch = saved.y, saved.use_batch
         dy = dy_out if dy_out is not None else y.like()
         dg = _raw(self, 'weight')[1] if self.affine else None
         db = _raw(self, 'bias')[1] if self.affine else None
         # eval mode (frozen running statistics): same two passes, with the statistics treated as constants --
         # dy = scale * dz * act', dgamma = sum(dz * act' * xhat), dbeta = sum(dz * act') (what autograd gives for
         # F.batch_norm(training=False))
-        ops.bn_act_bwd(dz, z, y, co, act, dy, dg, db, accumulate=env.accumulate, dres=dres,
-                       res_accumulate=res_accumulate, frozen=not use_batch, mask=mask, want_planes=want_planes,
+        ops.bn_act_bwd(dz, saved.z, y, saved.co, saved.act, dy, dg, db, accumulate=env.accumulate, dres=dres,
+                       res_accumulate=res_accumulate, frozen=not use_batch, mask=saved.mask, want_planes=want_planes,
                        part=dz.bnpart if use_batch else None)
         if env.grad_ready is not None:
             env.grad_ready(self)

@@ -327,6 +327,18 @@ def _ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
+def _pl(a):
+    """(pointer, pixel stride) of an optional Act: (0, 0) without one"""
+    return (0, 0) if a is None else (a.t.data_ptr(), a.ld)
+
+
+def _rows4(co):
+    """The four row pointers of a [4][C] coefficient tensor (mean, invstd, scale, shift), by arithmetic: indexing a tensor costs
+    ~2 us a time, and the callers run once per layer and step."""
+    c0, cs = co.data_ptr(), co.shape[1] * 4
+    return c0, c0 + cs, c0 + 2 * cs, c0 + 3 * cs
+
+
 class Act:
     """NHWC activation [B,H,W,C] with pixel stride ``ld`` (elements); ``t`` is a 1-D tensor whose first element is
     element (0,0,0,0) and which keeps the storage alive.  fp32 everywhere except under the half-precision (`-mp`)
@@ -572,30 +584,26 @@ def _conv2d_fwd_one(x, w_raw, bias_raw, y, kh, kw, stride, pad, dil, accumulate=
     assert w_raw.numel() == Cout * kh * kw * Cin and w_raw.is_contiguous()
     assert y.B == x.B and y.H == conv_out_size(x.H, kh, stride, pad, dil) and y.W == conv_out_size(x.W, kw, stride, pad, dil)
     dev = x.device
+    sfx = '_h' if x.half else ''
+    # (the fp16 kernels take no workspace: their statistics are always fused)
+    ws_bytes = 0 if x.half else _lib.query('pseg_conv2d_fwd_workspace_bytes', x.B, y.H, y.W, Cin, Cout, kh, kw)
+    fused = want_stats and ws_bytes == 0
+    st, rows, group = None, 0, 0
+    if fused:
+        geo = (x.B, y.H, y.W, Cin, Cout, kh, kw, stride, pad, dil)
+        rows = _lib.query('pseg_conv2d_stat_rows' + sfx, *geo)
+        group = _lib.query('pseg_conv2d_stat_group' + sfx, *geo)
+        st = torch.empty(3, rows, Cout, dtype=torch.float32, device=dev)
     if x.half:
         # half-precision path: fp16 operands, one fp16 MFMA pass, fp32 accumulate; y fp16 (or fp32: the class logits)
         assert w_raw.dtype == torch.float16, 'fp16 activations need the fp16 filter copy (ParamArena.prepare_half)'
-        geo = (x.B, y.H, y.W, Cin, Cout, kh, kw, stride, pad, dil)
-        st, rows, group = None, 0, 0
-        if want_stats:
-            rows = _lib.query('pseg_conv2d_stat_rows_h', *geo)
-            group = _lib.query('pseg_conv2d_stat_group_h', *geo)
-            st = torch.empty(3, rows, Cout, dtype=torch.float32, device=dev)
         _lib.call('pseg_conv2d_fwd_h', x.ptr, x.ld, w_raw.data_ptr(), _ptr(bias_raw), y.ptr, y.ld, int(not y.half), x.B,
                   x.H, x.W, Cin, y.H, y.W, Cout, kh, kw, stride, pad, dil, int(accumulate), _ptr(st), _stream())
-        return (st, rows, group) if want_stats else None
-    ws_bytes = _lib.query('pseg_conv2d_fwd_workspace_bytes', x.B, y.H, y.W, Cin, Cout, kh, kw)
-    ws = workspace.get(ws_bytes, dev) if ws_bytes else None
-    fused = want_stats and ws_bytes == 0
-    st = None
-    rows = group = 0
-    if fused:
-        rows = _lib.query('pseg_conv2d_stat_rows', x.B, y.H, y.W, Cin, Cout, kh, kw, stride, pad, dil)
-        group = _lib.query('pseg_conv2d_stat_group', x.B, y.H, y.W, Cin, Cout, kh, kw, stride, pad, dil)
-        st = torch.empty(3, rows, Cout, dtype=torch.float32, device=dev)
-    _lib.call('pseg_conv2d_fwd', x.ptr, x.ld, w_raw.data_ptr(), _ptr(bias_raw), y.ptr, y.ld, x.B, x.H, x.W, Cin,
-              y.H, y.W, Cout, kh, kw, stride, pad, dil, int(accumulate), _fwd_prec(precision, amax_x, amax_w),
-              _ptr(amax_x), _ptr(amax_w), _ptr(st), _ptr(ws), ws_bytes, _stream())
+    else:
+        ws = workspace.get(ws_bytes, dev) if ws_bytes else None
+        _lib.call('pseg_conv2d_fwd', x.ptr, x.ld, w_raw.data_ptr(), _ptr(bias_raw), y.ptr, y.ld, x.B, x.H, x.W, Cin,
+                  y.H, y.W, Cout, kh, kw, stride, pad, dil, int(accumulate), _fwd_prec(precision, amax_x, amax_w),
+                  _ptr(amax_x), _ptr(amax_w), _ptr(st), _ptr(ws), ws_bytes, _stream())
     if want_stats and not fused:
         return col_stats(y)
     return (st, rows, group) if want_stats else None
@@ -662,13 +670,11 @@ def _conv2d_dgrad_one(dy, wT_raw, dx, kh, kw, stride, pad, dil, accumulate=False
         if not (rows > 0 and y.C == Cin and y.M == dx.M and y.half == (sfx == '_h')):
             return False
         part = torch.empty(2, rows, Cin, dtype=torch.float32, device=dx.device)
-        c0, cs = co.data_ptr(), co.shape[1] * 4
         p0 = part.data_ptr()
         # (the rows query and the launch read one kernel choice: select_gather in conv_gather.hip, select_gather_h in
         # conv_half_gather.hip)
         _lib.call('pseg_conv2d_dgrad_bnstat' + sfx, dy.ptr, dy.ld, wT_raw.data_ptr(), dx.ptr, dx.ld, dx.B, dx.H, dx.W, Cin, dy.H,
-                  dy.W, Cout, kh, kw, stride, pad, dil, y.ptr, y.ld, c0, c0 + cs, c0 + 2 * cs, c0 + 3 * cs, act,
-                  p0, p0 + rows * Cin * 4, rows, _stream())
+                  dy.W, Cout, kh, kw, stride, pad, dil, y.ptr, y.ld, *_rows4(co), act, p0, p0 + rows * Cin * 4, rows, _stream())
         dx.bnpart = BnPart(part, rows, y.ptr)
         return True
 
@@ -796,43 +802,30 @@ def _conv2d_wgrad_one(x, dy, dw_raw, kh, kw, stride, pad, dil, accumulate=False,
     (pool.reduce(accumulate)), and dw_raw is complete only after that call.
     concurrent: the launch runs beside another stream's kernels (Conv2d.bwd forks it onto the weight-gradient stream): the
     exact-fp32 plan then keeps ONE resident block per CU (half the slabs); alone it is planned for two."""
-    cc = int(bool(concurrent))
     Cout, Cin = dy.C, x.C
     assert dw_raw.numel() == Cout * kh * kw * Cin and dw_raw.is_contiguous()
     if x.half:
-        # fp16 operands, fp32 gradient (the master gradient arena); same split / slab protocol as the fp32 path
+        # fp16 operands, fp32 gradient (the master gradient arena); one arithmetic, one plan
         assert dy.half and dw_raw.dtype == torch.float32
-        if pool is not None:
-            splits = _lib.query('pseg_conv2d_wgrad_splits_h', x.B, dy.H, dy.W, Cin, Cout, kh, kw)
-            if splits > 1:
-                slabs = pool.region(dw_raw, (x.B, x.H, x.W, dy.H, dy.W, kh, kw, stride, pad, dil, 'h'), splits)
-                if slabs is not None:
-                    _lib.call('pseg_conv2d_wgrad_slabs_h', x.ptr, x.ld, dy.ptr, dy.ld, slabs.data_ptr(), x.B, x.H, x.W, Cin,
-                              dy.H, dy.W, Cout, kh, kw, stride, pad, dil, slabs.numel() * 4, _stream())
-                    return
-                pool.reduce(accumulate)
-                accumulate = True
-        ws_bytes = _lib.query('pseg_conv2d_wgrad_workspace_bytes_h', x.B, dy.H, dy.W, Cin, Cout, kh, kw)
-        ws = workspace.get(ws_bytes, x.device) if ws_bytes else None
-        _lib.call('pseg_conv2d_wgrad_h', x.ptr, x.ld, dy.ptr, dy.ld, dw_raw.data_ptr(), x.B, x.H, x.W, Cin, dy.H, dy.W,
-                  Cout, kh, kw, stride, pad, dil, int(accumulate), _ptr(ws), ws_bytes, _stream())
-        return
+        sfx, extra, tag = '_h', (), ('h',)
+    else:
+        sfx = ''
+        extra = tag = (_prec(precision, True), int(bool(concurrent)))
     if pool is not None:
-        prec = _prec(precision, True)
-        splits = _lib.query('pseg_conv2d_wgrad_splits', x.B, dy.H, dy.W, Cin, Cout, kh, kw, prec, cc)
+        splits = _lib.query('pseg_conv2d_wgrad_splits' + sfx, x.B, dy.H, dy.W, Cin, Cout, kh, kw, *extra)
         if splits > 1:
-            slabs = pool.region(dw_raw, (x.B, x.H, x.W, dy.H, dy.W, kh, kw, stride, pad, dil, prec, cc), splits)
+            slabs = pool.region(dw_raw, (x.B, x.H, x.W, dy.H, dy.W, kh, kw, stride, pad, dil) + tag, splits)
             if slabs is not None:
-                _lib.call('pseg_conv2d_wgrad_slabs', x.ptr, x.ld, dy.ptr, dy.ld, slabs.data_ptr(), x.B, x.H, x.W, Cin,
-                          dy.H, dy.W, Cout, kh, kw, stride, pad, dil, prec, cc, slabs.numel() * 4, _stream())
+                _lib.call('pseg_conv2d_wgrad_slabs' + sfx, x.ptr, x.ld, dy.ptr, dy.ld, slabs.data_ptr(), x.B, x.H, x.W, Cin,
+                          dy.H, dy.W, Cout, kh, kw, stride, pad, dil, *extra, slabs.numel() * 4, _stream())
                 return
             # a second gradient for the same filter in one pass (shared weights): fold what is parked, then add
             pool.reduce(accumulate)
             accumulate = True
-    ws_bytes = _lib.query('pseg_conv2d_wgrad_workspace_bytes', x.B, dy.H, dy.W, Cin, Cout, kh, kw)
+    ws_bytes = _lib.query('pseg_conv2d_wgrad_workspace_bytes' + sfx, x.B, dy.H, dy.W, Cin, Cout, kh, kw)
     ws = workspace.get(ws_bytes, x.device) if ws_bytes else None
-    _lib.call('pseg_conv2d_wgrad', x.ptr, x.ld, dy.ptr, dy.ld, dw_raw.data_ptr(), x.B, x.H, x.W, Cin, dy.H, dy.W,
-              Cout, kh, kw, stride, pad, dil, int(accumulate), _prec(precision, True), cc, _ptr(ws), ws_bytes, _stream())
+    _lib.call('pseg_conv2d_wgrad' + sfx, x.ptr, x.ld, dy.ptr, dy.ld, dw_raw.data_ptr(), x.B, x.H, x.W, Cin, dy.H, dy.W,
+              Cout, kh, kw, stride, pad, dil, int(accumulate), *extra, _ptr(ws), ws_bytes, _stream())
 
 
 def _h(name, act):
@@ -873,10 +866,8 @@ def bn_finalize(stats, count, gamma, beta, running_mean, running_var, momentum, 
     co = torch.empty(4, C, dtype=torch.float32, device=st.device)
     ws_bytes = _lib.query('pseg_bn_finalize_workspace_bytes', rows, C)
     ws = workspace.get(ws_bytes, st.device) if ws_bytes else None
-    base, step = co.data_ptr(), C * 4      # (row pointers by arithmetic: indexing a tensor costs ~2 us a time)
     _lib.call('pseg_bn_finalize', st.data_ptr(), rows, group, count, C, _ptr(gamma), _ptr(beta),
-              _ptr(running_mean), _ptr(running_var), float(momentum), float(eps), base, base + step, base + 2 * step,
-              base + 3 * step, _ptr(ws), ws_bytes, _stream())
+              _ptr(running_mean), _ptr(running_var), float(momentum), float(eps), *_rows4(co), _ptr(ws), ws_bytes, _stream())
     return co
 
 
@@ -940,11 +931,8 @@ def bn_fwd_fused(stats, count, gamma, beta, running_mean, running_var, momentum,
     st, rows, group = stats
     C = st.shape[-1]
     co = torch.empty(4, C, dtype=torch.float32, device=st.device)
-    base, step = co.data_ptr(), C * 4
     args = (st.data_ptr(), rows, group, count, C, _ptr(gamma), _ptr(beta), _ptr(running_mean),
-            _ptr(running_var), float(momentum), float(eps), base, base + step, base + 2 * step, base + 3 * step,
-            y.ptr, y.ld, residual.ptr if residual is not None else 0, residual.ld if residual is not None else 0, act,
-            z.ptr, z.ld, y.M)
+            _ptr(running_var), float(momentum), float(eps), *_rows4(co), y.ptr, y.ld, *_pl(residual), act, z.ptr, z.ld, y.M)
     if y.half:
         _lib.call('pseg_bn_fwd_fused_h', *args, _stream())
     else:
@@ -956,7 +944,7 @@ def bn_eval_coeffs(gamma, beta, running_mean, running_var, eps):
     C = running_mean.numel()
     co = torch.empty(4, C, dtype=torch.float32, device=running_mean.device)
     _lib.call('pseg_bn_eval_coeffs', _ptr(gamma), _ptr(beta), running_mean.data_ptr(), running_var.data_ptr(),
-              float(eps), C, co[0].data_ptr(), co[1].data_ptr(), co[2].data_ptr(), co[3].data_ptr(), _stream())
+              float(eps), C, *_rows4(co), _stream())
     return co
 
 
@@ -978,12 +966,10 @@ def bn_act_fwd(y, co, act, z, residual=None, want_mask=False):
     assert z.M == y.M and z.C == y.C
     mu = sc = sh = 0
     if co is not None:
-        mu, step = co.data_ptr(), co.shape[1] * 4
-        sc, sh = mu + 2 * step, mu + 3 * step
+        mu, _, sc, sh = _rows4(co)
     mask = torch.empty(y.M * (y.C // 32), dtype=torch.int32, device=y.device) \
         if (want_mask and act != ACT_NONE and y.C % 32 == 0) else None
-    args = (y.ptr, y.ld, mu, sc, sh, residual.ptr if residual is not None else 0,
-            residual.ld if residual is not None else 0, act, z.ptr, z.ld, y.M, y.C)
+    args = (y.ptr, y.ld, mu, sc, sh, *_pl(residual), act, z.ptr, z.ld, y.M, y.C)
     if y.half:
         _lib.call('pseg_bn_act_fwd_h', *args, _ptr(mask), _stream())
     else:
@@ -1005,14 +991,12 @@ def bn_act_bwd(dz, z, y, co, act, dy, gamma_grad, beta_grad, accumulate=False, d
     else:
         rows = _lib.query('pseg_col_stats_rows', M, C)
         part = torch.empty(2, rows, C, dtype=torch.float32, device=dev)
-    zp, zld = (z.ptr, z.ld) if z is not None else (0, 0)
-    # row pointers by arithmetic (indexing a tensor costs ~2 us a time, and this function runs once per layer and step)
-    c0, cs = co.data_ptr(), co.shape[1] * 4
-    c1, c2, c3 = c0 + cs, c0 + 2 * cs, c0 + 3 * cs
+    zp, zld = _pl(z)
+    c0, c1, c2, c3 = _rows4(co)
     p0 = part.data_ptr()
     p1 = p0 + rows * C * 4
     dzp, dzl, yp, yl, dyp, dyl = dz.ptr, dz.ld, y.ptr, y.ld, dy.ptr, dy.ld
-    drp, drl = (dres.ptr, dres.ld) if dres is not None else (0, 0)
+    drp, drl = _pl(dres)
     st = _stream()
     if not fused:
         _lib.call(_h('pseg_bn_act_bwd_reduce', y), dzp, dzl, zp, zld, yp, yl, c0, c1, c2, c3, act, M, C, p0, p1, _ptr(mask), st)
@@ -1041,9 +1025,7 @@ def bn_act_bwd(dz, z, y, co, act, dy, gamma_grad, beta_grad, accumulate=False, d
 
 def act_bwd(dz, z, act, dy, scale=None, dres=None, res_accumulate=False):
     """dy = scale * dz * act'(z) (eval-mode BN / plain activation backward); optional dres = dz * act'(z)."""
-    _lib.call(_h('pseg_act_bwd', dz), dz.ptr, dz.ld, z.ptr if z is not None else 0, z.ld if z is not None else 0, _ptr(scale),
-              act, dy.ptr if dy is not None else 0, dy.ld if dy is not None else 0,
-              dres.ptr if dres is not None else 0, dres.ld if dres is not None else 0, int(res_accumulate), dz.M, dz.C,
+    _lib.call(_h('pseg_act_bwd', dz), dz.ptr, dz.ld, *_pl(z), _ptr(scale), act, *_pl(dy), *_pl(dres), int(res_accumulate), dz.M, dz.C,
               _stream())
 
 
@@ -1120,8 +1102,8 @@ def bn_act_maxpool_fwd(x, co, act, y, k, stride, pad, want_argmax=True):
     """y = maxpool(act(BN(x))) with BN's coefficient tensor `co` ([4][C]: mean, invstd, scale, shift) -- the activated map never exists
     (pseg_bn_act_maxpool_fwd; same values and argmax as bn_act_fwd + maxpool_fwd)."""
     arg = torch.empty(y.M * y.C, dtype=torch.uint8, device=x.device) if want_argmax else None
-    c0, cs = co.data_ptr(), co.shape[1] * 4
-    _lib.call(_h('pseg_bn_act_maxpool_fwd', x), x.ptr, x.ld, c0, c0 + 2 * cs, c0 + 3 * cs, act, x.B, x.H, x.W, x.C, y.ptr, y.ld,
+    mu, _, sc, sh = _rows4(co)
+    _lib.call(_h('pseg_bn_act_maxpool_fwd', x), x.ptr, x.ld, mu, sc, sh, act, x.B, x.H, x.W, x.C, y.ptr, y.ld,
               _ptr(arg), y.H, y.W, k, stride, pad, _stream())
     return arg
 
@@ -1209,7 +1191,7 @@ def ce_upsampled_fwd_bwd(lr, C, target, align_corners, want_grad=True, ignore_in
     nbytes = _lib.query('pseg_ce_upsampled_workspace_bytes', lr.B, lr.H, lr.W)
     ws = workspace.get(nbytes, lr.device)
     _lib.call('pseg_ce_upsampled_fwd_bwd', lr.ptr, lr.ld, lr.B, lr.H, lr.W, C, target.data_ptr(), H, W, int(align_corners),
-              ignore_index, dlr.ptr if dlr is not None else 0, dlr.ld if dlr is not None else 0, out.data_ptr(),
+              ignore_index, *_pl(dlr), out.data_ptr(),
               ws.data_ptr(), nbytes, _stream())
     return out, dlr
 

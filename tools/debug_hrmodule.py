@@ -91,12 +91,13 @@ def probe(seed=1, nb=3, S=16, i=1, j=2):
     oa, saved = m.fwd([Act.from_nchw(x.float().cuda()) for x in xs], env)
     for bi, blk in ((0, 'bn1'), (0, 'bn2'), (1, 'bn2'), (3, 'bn2')):
         sbk = saved[0][2][bi]
-        yb, zb, cob = (sbk[1] if blk == 'bn1' else sbk[3])[:3]
+        sbn = sbk[1] if blk == 'bn1' else sbk[3]      # (nn.BnSaved)
+        yb, cob = sbn.y, sbn.co
         bn = getattr(m.branches[2][bi], blk)
         preb = ((yb.view4() - cob[0]) * cob[2] + bn.bias.detach()).permute(0, 3, 1, 2).double().cpu()
         print('hip vs oracle64 at branches.2.%d.%s' % (bi, blk), (preb - grab['bn64/branches.2.%d.%s' % (bi, blk)]).abs().max().item())
     (sc, sb), tshape = saved[1][i][j]
-    y, z, co, act, ub = sb
+    y, z, co, act = sb.y, sb.z, sb.co, sb.act
     mean, invstd, scale, shift = co
     pre = (y.view4() - mean) * scale + m.fuse_layers[i][j][0].bn.bias.detach()
     pre = pre.permute(0, 3, 1, 2).double().cpu()
