@@ -166,7 +166,8 @@ int pseg_slab_reduce_block(void);
  * pattern), element strides as in the fp32 entry points, C % 8 == 0, ld % 8 == 0, 16-byte aligned bases; products are exact
  * (fp16 x fp16 on v_mfma_f32_32x32x16_f16) and every sum is fp32.
  * pseg_conv2d_fwd_h: y fp16, or fp32 when y_is_f32 (the class logits, which the loss reads in fp32); stat as pseg_conv2d_fwd
- *   with the row grouping of pseg_conv2d_stat_rows_h / _group_h (taken from the fp32 accumulators).  bias is fp32.
+ *   with the row grouping of pseg_conv2d_stat_rows_h / _group_h, taken over y AS STORED: an fp16 result is rounded before it is
+ *   summed (the layer normalises the values it reads back), an fp32 result is summed from the accumulators.  bias is fp32.
  * pseg_conv2d_dgrad_h: wT = the transposed fp16 filter [Cin][kh][kw][Cout].
  * pseg_conv2d_wgrad_h: dw fp32 [Cout][kh][kw][Cin] (the master gradient arena); split / slab protocol as pseg_conv2d_wgrad.
  * pseg_filter_prepare_h: every dense filter of a model in one launch, from the fp32 master weights: the fp16 copy AND the
@@ -186,8 +187,11 @@ int pseg_conv2d_dgrad_h(const pseg_half_t* dy, int ldy, const pseg_half_t* wT, p
                         int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil, int accumulate,
                         void* stream);
 /* pseg_conv2d_dgrad_bnstat_h: pseg_conv2d_dgrad_bnstat for the fp16 tensors (dx overwritten; y_prev fp16 with ldy_prev % 8 == 0;
- * the sums are taken over dx AS STORED, i.e. rounded to fp16, like pseg_bn_act_bwd_reduce_h reading it back).  Every fp16 gather
- * kernel carries the epilogue: pseg_conv2d_dgrad_bnstat_rows_h is 0 only for an invalid problem. */
+ * the sums are taken over dx AS STORED, i.e. rounded to fp16, like pseg_bn_act_bwd_reduce_h reading it back).  The plain
+ * instantiations of the tiles and (K-step, ring depth) pairs the default plan gives such data gradients carry the epilogue;
+ * pseg_conv2d_dgrad_bnstat_rows_h is 0 for an invalid problem AND for one whose kernel does not (tap-skipping, channels off the
+ * K-step grid, a forced tile / K-step / ring depth outside that set): the caller then runs pseg_conv2d_dgrad_h and the layer's
+ * own reduction pass, and pseg_conv2d_dgrad_bnstat_h refuses the problem -- never a launch without the sums. */
 int pseg_conv2d_dgrad_bnstat_rows_h(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
                                     int dil);
 int pseg_conv2d_dgrad_bnstat_h(const pseg_half_t* dy, int ldy, const pseg_half_t* wT, pseg_half_t* dx, int ldx, int B, int H, int W,
@@ -736,6 +740,12 @@ int pseg_debug_conv_trace(void* buffer);
 #define PSEG_KERNEL_GATHER_H 21              /* gather_h_kernel (fp16) */
 #define PSEG_KERNEL_GATHER_H_PERSISTENT 22   /* gather_hp_kernel (fp16) */
 int pseg_debug_last_conv_kernel(void);
+/* ... and, when that was an fp16 gather launch (codes 21 / 22: pseg_conv2d_fwd_h / _dgrad_h / _dgrad_bnstat_h), WHICH instantiation:
+ * out6 = {tile rows, tile columns, K-step in halves (32 | 64), ring depth as launched (after the clamp to the K loop's length;
+ * the persistent kernel's own depth, 2 | 3, when it ran), variant (0 plain, 1 tap-skipping, 2 channels off the K-step grid),
+ * 1 when the instantiation with the fused BatchNorm-backward sums ran}.  Zeros before the thread's first such launch.  A few
+ * host-side integer stores per launch, no device work; additive: PSEG_ABI_VERSION does not move. */
+int pseg_debug_last_gather_h(int* out6);
 
 /* ---- lane executor: a captured hipGraph replayed as plain launches on a few streams (csrc/lanes.hip) --------------------
  * The reference drives its step from Python through torch/apex (train.py:63-72 via pytorch_modules' Trainer); for the

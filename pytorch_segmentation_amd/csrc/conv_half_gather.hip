@@ -1190,6 +1190,14 @@ static const char* gather_size_error_h(const GatherGeom& g, long long x_bytes, i
   return nullptr;
 }
 
+// the instantiation the calling thread's last launch of run_gather_h ran (pseg_debug_last_gather_h): tile rows, tile columns,
+// K-step, ring depth as launched, variant, fused sums
+static thread_local int g_last_gather_h[6] = {0, 0, 0, 0, 0, 0};
+static void note_gather_h(const HGatherChoice& c, int depth, bool bns) {
+  const int rec[6] = {c.pl.tile.bm, c.pl.tile.bn, c.kb, depth, c.variant, bns ? 1 : 0};
+  for (int i = 0; i < 6; ++i) g_last_gather_h[i] = rec[i];
+}
+
 // validate, select, fill the parameters from the choice and launch
 static int run_gather_h(const GatherGeom& g, const void* x, long long x_bytes, int ldx, const void* w, void* y, int ldy, int y_f32,
                         const float* bias, float* stat, int accumulate, hipStream_t st, const BnsArgs* bns = nullptr) {
@@ -1231,6 +1239,7 @@ static int run_gather_h(const GatherGeom& g, const void* x, long long x_bytes, i
   hp.ntiles = pl.gridM * pl.gridN;
   if (c.persistent && launch_persistent_h(c, bns != nullptr, st, hp)) {
     g_last_conv_kernel = PSEG_KERNEL_GATHER_H_PERSISTENT;
+    note_gather_h(c, c.pstages, bns != nullptr);
     PSEG_LAUNCH_CHECK();
     return PSEG_OK;
   }
@@ -1241,6 +1250,7 @@ static int run_gather_h(const GatherGeom& g, const void* x, long long x_bytes, i
   }
   launch_ring_h(c, bns != nullptr, st, hp);
   g_last_conv_kernel = PSEG_KERNEL_GATHER_H;
+  note_gather_h(c, c.stages, bns != nullptr);
   PSEG_LAUNCH_CHECK();
   return PSEG_OK;
 }
@@ -1308,6 +1318,12 @@ int pseg_conv2d_dgrad_bnstat_h(const pseg_half_t* dy, int ldy, const pseg_half_t
                "conv2d_dgrad_bnstat_h: part_rows (%d) is not pseg_conv2d_dgrad_bnstat_rows_h() of this problem", part_rows);
   return run_gather_h(dgrad_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil), dy, nhwc_bytes_h(B, Ho, Wo, Cout, ldy), ldy,
                       wT, dx, ldx, 0, nullptr, nullptr, 0, (hipStream_t)stream, &bns);
+}
+
+int pseg_debug_last_gather_h(int* out6) {
+  PSEG_REQUIRE(out6 != nullptr, "debug_last_gather_h: null pointer");
+  for (int i = 0; i < 6; ++i) out6[i] = g_last_gather_h[i];
+  return PSEG_OK;
 }
 
 int pseg_filter_prepare_h(const int64_t* jobs, int n, int64_t total_tiles, void* stream) {

@@ -19,6 +19,7 @@ def lib():
 def test_header_prototypes_all_exported(lib):
     protos = _lib.parse_header()
     assert len(protos) >= 41
+    assert 'pseg_debug_last_conv_kernel' in protos and 'pseg_debug_last_gather_h' in protos
     for name in protos:
         assert hasattr(lib, name), name
     out = subprocess.check_output(['nm', '-D', '--defined-only', _lib.LIB_PATH]).decode()
@@ -33,6 +34,9 @@ def test_abi_version_and_error_string(lib):
     assert rc == -1 and b'null' in lib.pseg_last_error()
     with pytest.raises(_lib.PsegError):
         _lib.call('pseg_fill', None, 0, 0.0, None)
+    # the debug record of the fp16 gather launches: zeros on a thread that has launched none
+    rec = (ctypes.c_int * 6)(*[7] * 6)
+    assert lib.pseg_debug_last_gather_h(rec) == 0 and list(rec) == [0] * 6
 
 
 def test_plan_queries_are_consistent(lib):
