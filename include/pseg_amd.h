@@ -725,8 +725,9 @@ int pseg_amax_batch(const int64_t* jobs, int n, int64_t total_blocks, float* out
  * (tools/conv_phases.py turns them into a phase table).  Debug builds only (-DPSEG_CONV_TRACE=1; the default build returns
  * an error for a non-NULL buffer): one global pointer, no stream ordering. */
 int pseg_debug_conv_trace(void* buffer);
-/* debug / tests: which kernel did the calling thread's LAST convolution entry point (pseg_conv2d_fwd / _dgrad* / _wgrad* and their
- * _h forms) enqueue?  A parity test of a specialised kernel can so assert that the kernel it means to test is the one that ran. */
+/* debug / tests: which kernel did the calling thread's LAST convolution entry point (pseg_conv2d_fwd / _dgrad* / _wgrad* /
+ * _wgrad_slabs and their _h forms, the fp16 weight gradient included: code 23) enqueue?  A parity test of a specialised kernel can
+ * so assert that the kernel it means to test is the one that ran. */
 #define PSEG_KERNEL_GATHER_REGISTER 1        /* gather_conv_kernel (register-staged; every precision, split-K) */
 #define PSEG_KERNEL_GATHER_LIMB_DMA 2        /* gather_limb_dma_kernel (pre-split bf16 planes) */
 #define PSEG_KERNEL_GATHER_RING 3            /* gather_f32_dma_kernel */
@@ -739,6 +740,7 @@ int pseg_debug_conv_trace(void* buffer);
 #define PSEG_KERNEL_WGRAD_HALO 14            /* wgrad_f32_halo_kernel */
 #define PSEG_KERNEL_GATHER_H 21              /* gather_h_kernel (fp16) */
 #define PSEG_KERNEL_GATHER_H_PERSISTENT 22   /* gather_hp_kernel (fp16) */
+#define PSEG_KERNEL_WGRAD_H 23               /* wgrad_h_kernel (fp16) */
 int pseg_debug_last_conv_kernel(void);
 /* ... and, when that was an fp16 gather launch (codes 21 / 22: pseg_conv2d_fwd_h / _dgrad_h / _dgrad_bnstat_h), WHICH instantiation:
  * out6 = {tile rows, tile columns, K-step in halves (32 | 64), ring depth as launched (after the clamp to the K loop's length;
@@ -746,6 +748,19 @@ int pseg_debug_last_conv_kernel(void);
  * 1 when the instantiation with the fused BatchNorm-backward sums ran}.  Zeros before the thread's first such launch.  A few
  * host-side integer stores per launch, no device work; additive: PSEG_ABI_VERSION does not move. */
 int pseg_debug_last_gather_h(int* out6);
+/* ... and, when that was a weight gradient (codes 11-14 and 23: pseg_conv2d_wgrad / _wgrad_slabs / _wgrad_h / _wgrad_slabs_h), WHICH
+ * launch: out11 = {kernel code, tile rows, tile columns, pixels per K-step (32 | 64 for fp16, 32 for the fp32 / limb kernels), the
+ * kernel's SKIP flag, pixel order (0 dense, 1 dead image rows skipped, 2 dead patches skipped, 3 packed live rectangles, 4 row-major
+ * on the LDS-DMA kernel), 1 when the pixels run in patch order, patch rows, patch columns, pixel splits, pixels per split}.
+ * Zeros before the thread's first such launch.  Host-side integer stores next to the launch, no device work.
+ * pseg_conv2d_wgrad_choice / _choice_h: the same record for the launch that WOULD run for a problem -- a pure function of the integer
+ * arguments and the PSEG_* planning switches, read off the selection the launch reads; no device needed.  Additive:
+ * PSEG_ABI_VERSION does not move. */
+int pseg_debug_last_wgrad(int* out11);
+int pseg_conv2d_wgrad_choice(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil,
+                             int precision, int concurrent, int* out11);
+int pseg_conv2d_wgrad_choice_h(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil,
+                               int* out11);
 
 /* ---- lane executor: a captured hipGraph replayed as plain launches on a few streams (csrc/lanes.hip) --------------------
  * The reference drives its step from Python through torch/apex (train.py:63-72 via pytorch_modules' Trainer); for the

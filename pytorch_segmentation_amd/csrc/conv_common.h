@@ -32,6 +32,9 @@ constexpr int RPP = 256 / CPR; // rows covered by one pass of the 256 threads
 // column; the lanes that share a column chunk are folded at the end (fixed order) and lane rr == 0 writes the wave's partial.
 // which kernel the calling thread's last convolution entry point enqueued (pseg_debug_last_conv_kernel; codes: pseg_amd.h)
 extern thread_local int g_last_conv_kernel;
+// ... and, for a weight gradient, the record of its launch (pseg_debug_last_wgrad; filled by wgrad_record below)
+constexpr int kWgradRecord = 11;
+extern thread_local int g_last_wgrad[kWgradRecord];
 
 struct BnsEpilogue {
   const float* y;
@@ -1099,6 +1102,14 @@ static WgradPixelOrder wgrad_pixel_order(const WgradGeom& g, int tile_bn) {
     if (o.patch_mode && o.can_skip) o.mode = kWgSkipPatches;
   }
   return o;
+}
+
+// The record of a weight-gradient choice (pseg_debug_last_wgrad, pseg_conv2d_wgrad_choice(_h); layout: pseg_amd.h): the plan and
+// the pixel order as the launch reads them, the kernel code, the pixels of a K-step and the SKIP flag as the selection holds them.
+static void wgrad_record(int* out, int kernel, const WgradPlan& pl, const WgradPixelOrder& o, int kstep_pixels, bool skip) {
+  const int rec[kWgradRecord] = {kernel, pl.tile.bm, pl.tile.bn, kstep_pixels, skip ? 1 : 0, o.mode, o.patch_mode, o.patch_h, o.patch_w,
+                                 pl.splits, pl.pix_per_split};
+  for (int i = 0; i < kWgradRecord; ++i) out[i] = rec[i];
 }
 
 // geometry, pixel split and pixel order of a launch (the operand pointers, their sizes and strides, and where the result goes

@@ -413,6 +413,9 @@ static HWgradChoice select_wgrad_h(const WgradGeom& q) {
   return c;
 }
 
+// the record of a choice (pseg_debug_last_wgrad, pseg_conv2d_wgrad_choice_h)
+static void record_wgrad_h(const HWgradChoice& c, int* out11) { wgrad_record(out11, PSEG_KERNEL_WGRAD_H, c.pl, c.order, c.bkp, c.skip); }
+
 template <int... I>
 static void launch_wgrad_h(const HWgradChoice& c, dim3 grid, hipStream_t st, const HWgradParams& hp, std::integer_sequence<int, I...>) {
   auto launch = [&](auto tile, auto steps) {
@@ -452,6 +455,8 @@ static int run_wgrad_h(const WgradGeom& q, const void* x, int ldx, const void* d
   const int rc = set_wgrad_output(p, pl, dw, accumulate, workspace, workspace_bytes, "conv2d_wgrad_h");
   if (rc != PSEG_OK) return rc;
   PSEG_REQUIRE(c.tile >= 0, "conv2d_wgrad_h: no kernel for tile %dx%d", pl.tile.bm, pl.tile.bn);
+  g_last_conv_kernel = PSEG_KERNEL_WGRAD_H;
+  record_wgrad_h(c, g_last_wgrad);
   launch_wgrad_h(c, dim3((unsigned)(pl.gridM * pl.gridN), 1, (unsigned)pl.splits), st, hp, std::make_integer_sequence<int, kNumHWgradTiles>{});
   PSEG_LAUNCH_CHECK();
   if (pl.splits > 1 && !defer)
@@ -474,6 +479,15 @@ static WgradGeom wgrad_query_problem_h(int B, int Ho, int Wo, int Cin, int Cout,
 int pseg_conv2d_wgrad_splits_h(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw) {
   if (B <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0) return 0;
   return select_wgrad_h(wgrad_query_problem_h(B, Ho, Wo, Cin, Cout, kh, kw)).pl.splits;
+}
+
+int pseg_conv2d_wgrad_choice_h(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil,
+                               int* out11) {
+  PSEG_REQUIRE(out11 != nullptr, "conv2d_wgrad_choice_h: null pointer");
+  PSEG_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Ho > 0 && Wo > 0 && Cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0 && dil > 0,
+               "conv2d_wgrad_choice_h: bad geometry");
+  record_wgrad_h(select_wgrad_h(WgradGeom{B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil}), out11);
+  return PSEG_OK;
 }
 
 int64_t pseg_conv2d_wgrad_workspace_bytes_h(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw) {

@@ -1254,6 +1254,9 @@ static WgradChoice select_wgrad(const WgradProblem& q) {
   return c;
 }
 
+// the record of a choice (pseg_debug_last_wgrad, pseg_conv2d_wgrad_choice): every kernel here takes 32 pixels per K-step
+static void record_wgrad(const WgradChoice& c, int* out11) { wgrad_record(out11, c.kernel, c.pl, c.order, BK, c.skip); }
+
 static void launch_wgrad_dma(const WgradChoice& c, dim3 grid, hipStream_t st, const WgradParams& p) {
   with_index(c.dma_tile, [&](auto tile) {
     constexpr WgradDmaTile t = kWgradDmaTiles[decltype(tile)::value];
@@ -1320,6 +1323,7 @@ static int run_wgrad(const WgradProblem& q, const float* x, int ldx, const float
   if (rc != PSEG_OK) return rc;
   const dim3 grid((unsigned)(pl.gridM * pl.gridN), 1, (unsigned)pl.splits);
   g_last_conv_kernel = c.kernel;
+  record_wgrad(c, g_last_wgrad);
   if (c.kernel == PSEG_KERNEL_WGRAD_HALO) {
     hipLaunchKernelGGL(wgrad_f32_halo_kernel<32>, grid, dim3(576), 0, st, p);
   } else if (c.kernel == PSEG_KERNEL_WGRAD_DMA) {
@@ -1356,6 +1360,16 @@ static WgradProblem wgrad_query_problem(int B, int Ho, int Wo, int Cin, int Cout
 int pseg_conv2d_wgrad_splits(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int precision, int concurrent) {
   if (B <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || precision < 0 || precision > 2) return 0;
   return select_wgrad(wgrad_query_problem(B, Ho, Wo, Cin, Cout, kh, kw, precision, concurrent)).pl.splits;
+}
+
+int pseg_conv2d_wgrad_choice(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil,
+                             int precision, int concurrent, int* out11) {
+  PSEG_REQUIRE(out11 != nullptr, "conv2d_wgrad_choice: null pointer");
+  PSEG_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Ho > 0 && Wo > 0 && Cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0 &&
+                   dil > 0 && precision >= 0 && precision <= 2,
+               "conv2d_wgrad_choice: bad geometry or precision");
+  record_wgrad(select_wgrad(WgradProblem{{B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil}, precision, concurrent != 0}), out11);
+  return PSEG_OK;
 }
 
 int64_t pseg_conv2d_wgrad_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int kh, int kw) {

@@ -9,6 +9,7 @@ namespace pseg {
 
 static thread_local char g_err[512] = "";
 thread_local int g_last_conv_kernel = 0;      // pseg_debug_last_conv_kernel (conv_common.h)
+thread_local int g_last_wgrad[kWgradRecord] = {};      // pseg_debug_last_wgrad (conv_common.h)
 void set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -23,6 +24,11 @@ extern "C" {
 
 int pseg_abi_version(void) { return PSEG_ABI_VERSION; }
 int pseg_debug_last_conv_kernel(void) { return pseg::g_last_conv_kernel; }
+int pseg_debug_last_wgrad(int* out11) {
+  PSEG_REQUIRE(out11 != nullptr, "debug_last_wgrad: null pointer");
+  for (int i = 0; i < pseg::kWgradRecord; ++i) out11[i] = pseg::g_last_wgrad[i];
+  return PSEG_OK;
+}
 int pseg_config_reload(void) {
   pseg::cfg_load();
   return PSEG_OK;

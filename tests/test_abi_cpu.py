@@ -18,8 +18,9 @@ def lib():
 
 def test_header_prototypes_all_exported(lib):
     protos = _lib.parse_header()
-    assert len(protos) >= 41
+    assert len(protos) >= 141
     assert 'pseg_debug_last_conv_kernel' in protos and 'pseg_debug_last_gather_h' in protos
+    assert {'pseg_debug_last_wgrad', 'pseg_conv2d_wgrad_choice', 'pseg_conv2d_wgrad_choice_h'} <= set(protos)
     for name in protos:
         assert hasattr(lib, name), name
     out = subprocess.check_output(['nm', '-D', '--defined-only', _lib.LIB_PATH]).decode()

@@ -2,11 +2,14 @@
 dispatches).  Tolerance: 1e-3 relative to the tensor's max magnitude is the contract (BASELINE.json north_star);
 fp32 MFMA + fp32 accumulate lands around 1e-6..1e-5, so the asserts use TOL = 1e-4 to catch indexing bugs that a
 loose bound would hide.  Integer outputs (argmax, counts) are bit-exact."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import wgrad_cases
 from oracle import fill
 
 pytestmark = pytest.mark.gpu
@@ -508,6 +511,12 @@ def test_conv2d_wgrad_launch_families(ops, case, monkeypatch, fresh_plans):
         dw = torch.empty(cout_p, 3, 3, cin_p, device='cuda')
         ops.conv2d_wgrad(xa, gya, dw, 3, 3, 1, dil, dil, precision=P)
         assert ran() == kernel
+        # ... on the tile and in the pixel order meant (pseg_debug_last_wgrad; tests/wgrad_cases.py)
+        rec = (ctypes.c_int * 11)()
+        assert _lib.load().pseg_debug_last_wgrad(rec) == 0
+        tile, skip, order = wgrad_cases.FAMILY_RECORDS[name]
+        assert (rec[0], (rec[1], rec[2]), rec[3], rec[4], rec[5]) == (kernel, tile, 32, skip, order), tuple(rec)
+        assert rec[9] == (min(B, 3) if deferred else 1)
         assert rel(nchw(dw), ref64) < tol
         if cout_p > Cout:
             assert dw[Cout:].abs().max().item() == 0.0
