@@ -761,6 +761,25 @@ int pseg_conv2d_wgrad_choice(int B, int H, int W, int Cin, int Ho, int Wo, int C
                              int precision, int concurrent, int* out11);
 int pseg_conv2d_wgrad_choice_h(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil,
                                int* out11);
+/* ... and, when that was an exact-fp32 or limb gather launch (codes 1-6: pseg_conv2d_fwd / _dgrad / _dgrad_bnstat / _dgrad_planes),
+ * WHICH instantiation: out13 = {kernel code as launched (5 only when the persistent kernel accepted the problem), tile rows, tile
+ * columns, the arithmetic the kernel ran with (PSEG_PREC_*: the caller's on the register-staged kernel, BF16X3 on the pre-split
+ * limb kernel, FP32 on the LDS-DMA kernels whatever was asked for), the kernel's SKIP flag, ring depth (2 | 3; 0 off the ring
+ * kernel), 1 for the ring kernel's GENERIC form, row order (GatherConvParams::row_perm: 0 row-major, 1 parity classes, 2 pixel
+ * patches, 3 a 1x1 conv's 1 x M image, 4 rows sorted by liveness class), patch rows, patch columns (0 off the patch order), K
+ * splits, 1 when the launch carried the fused BatchNorm-backward sums (on the persistent kernel: its BNS instantiation), 1 when the
+ * problem was offered to the persistent pointwise kernel first}.  Zeros before the thread's first such launch; a refused call
+ * leaves it alone.  Host-side integer stores next to the launch, no device work.
+ * pseg_conv2d_gather_choice: the same record for the launch that WOULD run -- dgrad: 0 the forward conv, 1 the data gradient of the
+ * conv so described; precision: the caller's PSEG_PREC_*; stats / bias / planes / bns / accumulate: fused statistics, a bias, the
+ * pre-split limb planes, the fused BatchNorm-backward sums and accumulation asked for.  A pure function of its integer arguments and
+ * the PSEG_* planning switches, read off the selection the launch reads; no device needed.  The kernel code is the tile-per-block
+ * one, with the last field 1 where the persistent kernel is tried first (it declines by device occupancy), and 0 where the launch
+ * would be refused on the choice alone (limb planes or fused sums no kernel carries, fused statistics of a plan that splits K, a
+ * forced tile without an instantiation in this arithmetic).  Additive: PSEG_ABI_VERSION does not move. */
+int pseg_debug_last_gather(int* out13);
+int pseg_conv2d_gather_choice(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil,
+                              int dgrad, int precision, int stats, int bias, int planes, int bns, int accumulate, int* out13);
 
 /* ---- lane executor: a captured hipGraph replayed as plain launches on a few streams (csrc/lanes.hip) --------------------
  * The reference drives its step from Python through torch/apex (train.py:63-72 via pytorch_modules' Trainer); for the

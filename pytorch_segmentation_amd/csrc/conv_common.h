@@ -1169,15 +1169,20 @@ int launch_slab_reduce(const float* slabs, long long slab_stride, int nslab, flo
                        const float* bias, int accumulate, hipStream_t st);
 
 // the register-staged kernel families (gather_conv_kernel, wgrad_kernel, wgrad_limb_kernel): one instantiation per tile
+// (the column of a tile in their tables, -1 for a tile they do not have)
+static int tile_slot(TileCfg c, int ntiles) {
+  if (c.bm == 128 && c.bn == 128) return 0;
+  if (c.bm == 128 && c.bn == 64) return 1;
+  if (c.bm == 128 && c.bn == 32) return 2;
+  if (c.bm == 64 && c.bn == 128) return 3;
+  if (c.bm == 32 && c.bn == 128) return 4;
+  if (c.bm == 256 && c.bn == 128 && ntiles > 5) return 5;   // 8 waves
+  return -1;
+}
+
 template <typename P, typename F, int NTILES>
 static int launch_tiles(const F (&fns)[2][NTILES], bool skip, TileCfg c, dim3 grid, const P& p, hipStream_t st) {
-  int idx = -1;
-  if (c.bm == 128 && c.bn == 128) idx = 0;
-  else if (c.bm == 128 && c.bn == 64) idx = 1;
-  else if (c.bm == 128 && c.bn == 32) idx = 2;
-  else if (c.bm == 64 && c.bn == 128) idx = 3;
-  else if (c.bm == 32 && c.bn == 128) idx = 4;
-  else if (c.bm == 256 && c.bn == 128 && NTILES > 5) idx = 5;   // 8 waves
+  const int idx = tile_slot(c, NTILES);
   if (idx < 0 || fns[skip ? 1 : 0][idx] == nullptr) {
     set_error("no kernel for tile %dx%d", c.bm, c.bn);
     return PSEG_ERR_ARG;

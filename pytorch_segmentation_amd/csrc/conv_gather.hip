@@ -1653,6 +1653,44 @@ static GatherChoice select_gather(const GatherProblem& q) {
   return c;
 }
 
+// The register-staged kernel: five tiles x SKIP x four arithmetics; the 256x128 tile (8 waves, one block per CU) exists for the
+// LDS-staging-bound two-limb variants.  [SKIP][tile_slot]; nullptr = not instantiated.
+typedef void (*GatherFn)(const GatherConvParams);
+typedef GatherFn GatherFnTable[2][6];
+static const GatherFnTable& register_kernels(int precision) {
+#define PSEG_GATHER_ROW(SK, PR, BIG)                                                                   \
+  {gather_conv_kernel<128, 128, 2, 2, SK, PR>, gather_conv_kernel<128, 64, 2, 2, SK, PR>,              \
+   gather_conv_kernel<128, 32, 4, 1, SK, PR>, gather_conv_kernel<64, 128, 2, 2, SK, PR>,               \
+   gather_conv_kernel<32, 128, 1, 4, SK, PR>, BIG}
+  static const GatherFnTable fns32 = {PSEG_GATHER_ROW(false, 0, nullptr), PSEG_GATHER_ROW(true, 0, nullptr)};
+  static const GatherFnTable fnsb3 = {PSEG_GATHER_ROW(false, 1, (gather_conv_kernel<256, 128, 4, 2, false, 1>)),
+                                      PSEG_GATHER_ROW(true, 1, (gather_conv_kernel<256, 128, 4, 2, true, 1>))};
+  static const GatherFnTable fnsb6 = {PSEG_GATHER_ROW(false, 2, nullptr), PSEG_GATHER_ROW(true, 2, nullptr)};
+  static const GatherFnTable fnsh3 = {PSEG_GATHER_ROW(false, 3, (gather_conv_kernel<256, 128, 4, 2, false, 3>)),
+                                      PSEG_GATHER_ROW(true, 3, (gather_conv_kernel<256, 128, 4, 2, true, 3>))};
+#undef PSEG_GATHER_ROW
+  return precision == 3 ? fnsh3 : precision == 2 ? fnsb6 : precision == 1 ? fnsb3 : fns32;
+}
+
+// The record of a gather choice (pseg_debug_last_gather, pseg_conv2d_gather_choice; layout: pseg_amd.h): tile, SKIP flag, ring
+// depth, GENERIC flag, row order and K split as the launch reads them off the choice; `kernel` and `precision` as launched (the
+// pointwise kernel's code once it accepted; the arithmetic the kernel runs with, not the caller's request).
+constexpr int kGatherRecord = 13;
+static thread_local int g_last_gather[kGatherRecord] = {};
+static void gather_record(int* out, const GatherChoice& c, int kernel, int precision, bool bns) {
+  const bool ring = kernel == PSEG_KERNEL_GATHER_RING || kernel == PSEG_KERNEL_GATHER_RING_GENERIC;
+  const bool patches = c.order.row_perm == 2;
+  const int rec[kGatherRecord] = {kernel, c.pl.tile.bm, c.pl.tile.bn, precision, c.order.skip_taps != 0 ? 1 : 0, ring ? c.stages : 0,
+                                  c.generic ? 1 : 0, c.order.row_perm, patches ? c.order.patch_hw / c.order.patch_w : 0,
+                                  patches ? c.order.patch_w : 0, c.pl.splits, bns ? 1 : 0, c.try_pw ? 1 : 0};
+  for (int i = 0; i < kGatherRecord; ++i) out[i] = rec[i];
+}
+
+// the arithmetic a choice runs with: the register-staged kernel has every one, the others are fixed
+static int gather_precision(const GatherChoice& c, int precision) {
+  return c.kernel == PSEG_KERNEL_GATHER_REGISTER ? precision : (c.kernel == PSEG_KERNEL_GATHER_LIMB_DMA ? 1 : 0);
+}
+
 template <int I, bool SKIP, int STAGES, bool GENERIC>
 static void launch_ring_as(dim3 grid, hipStream_t st, const GatherConvParams& p) {
   constexpr F32Tile t = kF32Tiles[I];
@@ -1785,7 +1823,7 @@ static int run_gather(const GatherGeom& g, const float* x, long long x_bytes, in
   }
   set_bns_params(p, bns);
   const bool reg = c.kernel == PSEG_KERNEL_GATHER_REGISTER;     // the one kernel with every arithmetic; the others are fixed
-  p.precision = reg ? precision : (c.kernel == PSEG_KERNEL_GATHER_LIMB_DMA ? 1 : 0);
+  p.precision = gather_precision(c, precision);
   p.amax_a = reg ? amax_a : nullptr;
   p.amax_b = reg ? amax_b : nullptr;
   if (reg && precision == 3 && (amax_a == nullptr || amax_b == nullptr)) {
@@ -1807,6 +1845,7 @@ static int run_gather(const GatherGeom& g, const float* x, long long x_bytes, in
   }
   if (c.try_pw && launch_pointwise(c, st, p) == 0) {
     g_last_conv_kernel = PSEG_KERNEL_GATHER_POINTWISE;
+    gather_record(g_last_gather, c, PSEG_KERNEL_GATHER_POINTWISE, p.precision, bns != nullptr);
     PSEG_LAUNCH_CHECK();
     return PSEG_OK;
   }
@@ -1828,26 +1867,14 @@ static int run_gather(const GatherGeom& g, const float* x, long long x_bytes, in
       launch_halo(c, grid, st, p);
       break;
     default: {
-      typedef void (*Kfn)(const GatherConvParams);
-#define PSEG_GATHER_ROW(SK, PR, BIG)                                                                   \
-  {gather_conv_kernel<128, 128, 2, 2, SK, PR>, gather_conv_kernel<128, 64, 2, 2, SK, PR>,              \
-   gather_conv_kernel<128, 32, 4, 1, SK, PR>, gather_conv_kernel<64, 128, 2, 2, SK, PR>,               \
-   gather_conv_kernel<32, 128, 1, 4, SK, PR>, BIG}
-      // the 256x128 tile (8 waves, one block per CU) exists for the LDS-staging-bound two-limb variants
-      static const Kfn fns32[2][6] = {PSEG_GATHER_ROW(false, 0, nullptr), PSEG_GATHER_ROW(true, 0, nullptr)};
-      static const Kfn fnsb3[2][6] = {PSEG_GATHER_ROW(false, 1, (gather_conv_kernel<256, 128, 4, 2, false, 1>)),
-                                      PSEG_GATHER_ROW(true, 1, (gather_conv_kernel<256, 128, 4, 2, true, 1>))};
-      static const Kfn fnsb6[2][6] = {PSEG_GATHER_ROW(false, 2, nullptr), PSEG_GATHER_ROW(true, 2, nullptr)};
-      static const Kfn fnsh3[2][6] = {PSEG_GATHER_ROW(false, 3, (gather_conv_kernel<256, 128, 4, 2, false, 3>)),
-                                      PSEG_GATHER_ROW(true, 3, (gather_conv_kernel<256, 128, 4, 2, true, 3>))};
-#undef PSEG_GATHER_ROW
-      const auto& fns = precision == 3 ? fnsh3 : precision == 2 ? fnsb6 : precision == 1 ? fnsb3 : fns32;
-      const int rc = launch_tiles<GatherConvParams, Kfn, 6>(fns, p.skip_taps != 0, pl.tile, grid, p, st);
+      const int rc = launch_tiles<GatherConvParams, GatherFn, 6>(register_kernels(precision), p.skip_taps != 0, pl.tile, grid, p, st);
       if (rc != PSEG_OK) return rc;
+      gather_record(g_last_gather, c, c.kernel, p.precision, false);
       if (pl.splits > 1) return launch_slab_reduce((const float*)workspace, M * N, pl.splits, y, ldy, M, N, bias, accumulate, st);
       return PSEG_OK;
     }
   }
+  gather_record(g_last_gather, c, c.kernel, p.precision, bns != nullptr);
   PSEG_LAUNCH_CHECK();
   return PSEG_OK;
 }
@@ -1969,6 +1996,38 @@ int pseg_conv2d_dgrad_planes(const uint16_t* dy_hi, const uint16_t* dy_lo, int l
   // (x / w of run_gather are unused on this path; pass the planes for the alignment checks)
   return run_gather(g, reinterpret_cast<const float*>(dy_hi), 16, 4, reinterpret_cast<const float*>(wT_hi), dx, ldx, nullptr,
                     nullptr, accumulate, PSEG_PREC_BF16X3, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, &pln);
+}
+
+int pseg_debug_last_gather(int* out13) {
+  PSEG_REQUIRE(out13 != nullptr, "debug_last_gather: null pointer");
+  for (int i = 0; i < kGatherRecord; ++i) out13[i] = g_last_gather[i];
+  return PSEG_OK;
+}
+
+int pseg_conv2d_gather_choice(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil,
+                              int dgrad, int precision, int stats, int bias, int planes, int bns, int accumulate, int* out13) {
+  PSEG_REQUIRE(out13 != nullptr, "conv2d_gather_choice: null pointer");
+  PSEG_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Ho > 0 && Wo > 0 && Cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0 &&
+                   dil > 0 && precision >= 0 && precision <= 3 && (dgrad ? Cout : Cin) % 4 == 0 &&
+                   (long long)B * (dgrad ? H * (long long)W : Ho * (long long)Wo) < (1LL << 31),
+               "conv2d_gather_choice: bad geometry or precision (the gathered channels come in fours)");
+  if (!dgrad) {
+    const int rc = check_fwd_geometry("conv2d_gather_choice", H, W, Ho, Wo, kh, kw, stride, pad, dil);
+    if (rc != PSEG_OK) return rc;
+  }
+  const GatherGeom g = dgrad ? dgrad_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil)
+                             : fwd_geom(B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil);
+  // the problem run_gather builds from the same arguments, and its choice
+  GatherChoice c = select_gather(GatherProblem{g, precision, stats != 0, bias != 0, planes != 0, bns != 0, accumulate != 0});
+  // what run_gather refuses on the choice alone: fused statistics of a plan that splits K, a tile the register-staged kernel is
+  // not instantiated for in this arithmetic
+  if (stats != 0 && c.pl.splits > 1) c.kernel = kGatherRefused;
+  if (c.kernel == PSEG_KERNEL_GATHER_REGISTER) {
+    const int slot = tile_slot(c.pl.tile, 6);
+    if (slot < 0 || register_kernels(precision)[c.order.skip_taps != 0 ? 1 : 0][slot] == nullptr) c.kernel = kGatherRefused;
+  }
+  gather_record(out13, c, c.kernel, gather_precision(c, precision), bns != 0 && c.kernel != kGatherRefused);
+  return PSEG_OK;
 }
 
 // All filters of a model in ONE launch: jobs[j] = {w, wT, Cout, taps, Cin, first 32x32 tile of job j} (6 x int64, device

@@ -18,9 +18,10 @@ def lib():
 
 def test_header_prototypes_all_exported(lib):
     protos = _lib.parse_header()
-    assert len(protos) >= 141
+    assert len(protos) >= 143
     assert 'pseg_debug_last_conv_kernel' in protos and 'pseg_debug_last_gather_h' in protos
     assert {'pseg_debug_last_wgrad', 'pseg_conv2d_wgrad_choice', 'pseg_conv2d_wgrad_choice_h'} <= set(protos)
+    assert {'pseg_debug_last_gather', 'pseg_conv2d_gather_choice'} <= set(protos)
     for name in protos:
         assert hasattr(lib, name), name
     out = subprocess.check_output(['nm', '-D', '--defined-only', _lib.LIB_PATH]).decode()
@@ -38,6 +39,9 @@ def test_abi_version_and_error_string(lib):
     # the debug record of the fp16 gather launches: zeros on a thread that has launched none
     rec = (ctypes.c_int * 6)(*[7] * 6)
     assert lib.pseg_debug_last_gather_h(rec) == 0 and list(rec) == [0] * 6
+    # ... and of the exact-fp32 / limb ones
+    rec = (ctypes.c_int * 13)(*[7] * 13)
+    assert lib.pseg_debug_last_gather(rec) == 0 and list(rec) == [0] * 13
 
 
 def test_plan_queries_are_consistent(lib):

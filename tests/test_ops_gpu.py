@@ -30,6 +30,15 @@ def rel(a, b):
     return ((a - b).abs().max() / (b.abs().max() + 1e-30)).item()
 
 
+def gather_record():
+    """pseg_debug_last_gather: (kernel, tile rows, tile columns, arithmetic, SKIP, ring depth, GENERIC, row_perm, patch rows, patch
+    columns, K splits, fused sums, offered to the persistent kernel) of this thread's last exact-fp32 / limb gather launch"""
+    from pytorch_segmentation_amd import _lib
+    rec = (ctypes.c_int * 13)()
+    assert _lib.load().pseg_debug_last_gather(rec) == 0
+    return tuple(rec)
+
+
 def to_act(ops, x, Cpad=None):
     return ops.Act.from_nchw(x.cuda(), Cpad)
 
@@ -309,10 +318,14 @@ def test_conv2d_f32_dma_variant(ops, case, monkeypatch, fresh_plans):
     def run():
         ya = ops.Act.empty(B, Ho, Wo, cout_p, 'cuda')
         st = ops.conv2d_fwd(xa, w_raw, b_raw, ya, k, k, stride, pad, dil, want_stats=b_raw is None, precision=ops.PREC_FP32)
+        recs.append(gather_record())
         dxa = ops.Act.empty(B, H, W, cin_p, 'cuda')
         ops.conv2d_dgrad(gya, wT, dxa, k, k, stride, pad, dil, precision=ops.PREC_FP32)
+        recs.append(gather_record())
         co = ops.bn_finalize(st, ya.M, None, None, None, None, 0.0, 1e-5) if st is not None else None
         return ya.to_nchw(Cout), dxa.to_nchw(Cin), co
+
+    recs = []
 
     monkeypatch.setenv('PSEG_CONV_F32DMA', '0')      # register-staged kernel
     _lib.clear_query_cache()
@@ -325,6 +338,13 @@ def test_conv2d_f32_dma_variant(ops, case, monkeypatch, fresh_plans):
         assert rel(y1, y0) < 2e-6 and rel(d1, d0) < 2e-6, mode
         if c0 is not None:
             assert rel(c1[0], c0[0]) < 1e-5 and rel(c1[1], c0[1]) < 1e-5
+        # which instantiation ran (pseg_debug_last_gather): the register-staged run's tile, SKIP flag and K splits -- the plan does
+        # not depend on the switch -- and, on the ring kernel (3; 4 = its GENERIC form, always two stages), the ring depth asked for
+        for reg, dma in zip(recs[:2], recs[-2:]):
+            assert reg[0] == 1 and reg[5] == 0 and dma[1:3] == reg[1:3] and dma[4] == reg[4] and dma[10] == reg[10], (mode, reg, dma)
+            assert dma[0] in ((1,) if reg[10] > 1 or (dma[1], dma[2]) == (32, 128) else (3, 4, 5, 6)), (mode, dma)
+            if dma[0] == 3:
+                assert dma[5] == (3 if mode == '1' else 2), (mode, dma)
     monkeypatch.delenv('PSEG_CONV_F32DMA')
     _lib.clear_query_cache()
 
@@ -372,10 +392,12 @@ def test_conv2d_halo_staged_narrow_3x3(ops, case, bn, monkeypatch, fresh_plans):
         ya = ops.Act.empty(B, H, W, Cp, 'cuda')
         st = ops.conv2d_fwd(xa, w_raw, b_raw, ya, 3, 3, 1, 1, 1, want_stats=True, precision=ops.PREC_FP32)
         ran.append(_lib.load().pseg_debug_last_conv_kernel())
+        recs.append(gather_record())
         cof = ops.bn_finalize(st, ya.M, None, None, None, None, 0.0, 1e-5)
         d_plain = ops.Act.empty(B, H, W, Cin, 'cuda')
         ops.conv2d_dgrad(gya, wT, d_plain, 3, 3, 1, 1, 1, precision=ops.PREC_FP32)
         ran.append(_lib.load().pseg_debug_last_conv_kernel())
+        recs.append(gather_record())
         d_acc = to_act(ops, base)
         ops.conv2d_dgrad(gya, wT, d_acc, 3, 3, 1, 1, 1, accumulate=True, precision=ops.PREC_FP32)
         d_bn = ops.Act.empty(B, H, W, Cin, 'cuda')
@@ -384,7 +406,7 @@ def test_conv2d_halo_staged_narrow_3x3(ops, case, bn, monkeypatch, fresh_plans):
         assert (d_bn.bnpart is not None) == (Cp % 32 == 0)
         return ya, cof.clone(), d_plain, d_acc, d_bn, d_bn.bnpart.part.sum(1) if d_bn.bnpart is not None else None
 
-    ran = []
+    ran, recs = [], []
     monkeypatch.setenv('PSEG_CONV_HALO', '0')
     _lib.clear_query_cache()
     ref = run()
@@ -395,6 +417,10 @@ def test_conv2d_halo_staged_narrow_3x3(ops, case, bn, monkeypatch, fresh_plans):
     # 6 = the halo-staged kernel -- forward always; the data gradient gathers dy, whose padded channel count must be % 32
     assert ran[0] == 3 and ran[2] == 6, ran
     assert ran[1] == (3 if Cp % 32 == 0 else 4) and ran[3] == (6 if Cp % 32 == 0 else 4), ran
+    # ... on the forced tile, without SKIP: the ring kernels two stages deep in row-major order, the halo kernel in its 8 x 16 patches
+    # (pseg_debug_last_gather)
+    assert [r[0] for r in recs] == ran and all(r[1:3] == (128, bn) and r[4] == 0 and r[10] == 1 for r in recs), recs
+    assert all(r[5:10] == ((0, 0, 2, 8, 16) if r[0] == 6 else (2, int(r[0] == 4), 0, 0, 0)) for r in recs), recs
     for env in ('PSEG_CONV_HALO', 'PSEG_CONV_BM', 'PSEG_CONV_BN', 'PSEG_CONV_SPLITK'):
         monkeypatch.delenv(env)
     _lib.clear_query_cache()
@@ -598,6 +624,7 @@ def test_conv2d_persistent_pointwise_kernel(ops, case, grid, tile, monkeypatch, 
         ya = ops.Act.empty(B, H, W, Cout, 'cuda')
         st = ops.conv2d_fwd(xa, w_raw, None, ya, 1, 1, 1, 0, 1, want_stats=True, precision=ops.PREC_FP32)
         ran.append(_lib.load().pseg_debug_last_conv_kernel())
+        recs.append(gather_record())
         cof = ops.bn_finalize(st, ya.M, None, None, None, None, 0.0, 1e-5)
         d_plain = ops.Act.empty(B, H, W, Cin, 'cuda')
         ops.conv2d_dgrad(gya, wT, d_plain, 1, 1, 1, 0, 1, precision=ops.PREC_FP32)
@@ -608,7 +635,7 @@ def test_conv2d_persistent_pointwise_kernel(ops, case, grid, tile, monkeypatch, 
         part = d_bn.bnpart.part.sum(1) if d_bn.bnpart is not None else None
         return ya.t.clone(), cof.clone(), d_plain.t.clone(), d_acc.t.clone(), d_bn.t.clone(), part
 
-    ran = []
+    ran, recs = [], []
     monkeypatch.setenv('PSEG_CONV_PW', '0')
     _lib.clear_query_cache()
     ref = run()
@@ -624,6 +651,10 @@ def test_conv2d_persistent_pointwise_kernel(ops, case, grid, tile, monkeypatch, 
     _lib.clear_query_cache()
     if tile is not None:       # (a forced tile is one the persistent kernel takes: 5 = it ran, 3 = the tile-per-block ring kernel)
         assert ran == [3, 5], ran
+        # ... on that tile, the 1 x M image of a 1x1, no SKIP, one split: the ring kernel two stages deep and not offered to the
+        # persistent kernel, the persistent kernel after the offer (pseg_debug_last_gather)
+        assert [r[0] for r in recs] == ran and all(r[1:3] == tile and r[4] == 0 and r[7] == 3 and r[10] == 1 for r in recs), recs
+        assert (recs[0][5], recs[0][12]) == (2, 0) and (recs[1][5], recs[1][12]) == (0, 1), recs
     assert rel(ops.Act(got[0], B, H, W, Cout, Cout).to_nchw(), F.conv2d(x, w)) < TOL
     assert torch.equal(got[0], ref[0]) and torch.equal(got[2], ref[2]) and torch.equal(got[3], ref[3]) and torch.equal(got[4], ref[4])
     assert rel(got[1][0], ref[1][0]) < 1e-5 and rel(got[1][1], ref[1][1]) < 1e-5
