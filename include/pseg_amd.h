@@ -213,7 +213,9 @@ int pseg_convert2d(const void* x, int x_is_half, int ldx, void* y, int y_is_half
 /* fp16-storage variants of the bandwidth-bound passes: the same kernels instantiated on 2-byte activations (arguments and
  * semantics of the entry point without the suffix; statistics, per-channel vectors, filters of the depthwise convs and
  * every sum stay fp32; the amax / limb-plane arguments of the fp32 forms do not exist here).  Under `-mp` these halve the
- * bytes of the passes that are 40 % of a step's HBM traffic. */
+ * bytes of the passes that are 40 % of a step's HBM traffic.
+ * Every fp16 tensor needs ld % 8 == 0.  pseg_bn_act_fwd_h, pseg_bn_act_bwd_reduce_h and pseg_bn_act_bwd_apply_h work in lanes of
+ * eight channels and need C % 8 == 0 as well (refused with PSEG_ERR_ARG otherwise); the others here take C % 4 == 0. */
 int pseg_col_stats_h(const pseg_half_t* y, int ldy, int64_t M, int C, float* stat, void* stream);
 int pseg_bn_act_fwd_h(const pseg_half_t* y, int ldy, const float* mean, const float* scale, const float* shift,
                       const pseg_half_t* residual, int ldr, int act, pseg_half_t* z, int ldz, int64_t M, int C,
@@ -778,6 +780,21 @@ int pseg_conv2d_wgrad_choice_h(int B, int H, int W, int Cin, int Ho, int Wo, int
  * would be refused on the choice alone (limb planes or fused sums no kernel carries, fused statistics of a plan that splits K, a
  * forced tile without an instantiation in this arithmetic).  Additive: PSEG_ABI_VERSION does not move. */
 int pseg_debug_last_gather(int* out13);
+/* ... and the calling thread's last BatchNorm / activation / column-sum launch (csrc/norm_act.hip; these launches do not move
+ * pseg_debug_last_conv_kernel): out12 = {kernel, storage type (0 fp32, 1 fp16), V = channels per lane, NR = rows (row groups, for the
+ * finalize kernels) in flight per lane, MODE, LANES, block x, block y, grid x, grid y, rows per group R (statistics, reduce) or rows
+ * per block RB (apply, forward-rows, the fused kernels) or partial rows as the last kernel saw them (finalize, column reduce), 1
+ * when pseg_bn_finalize ran its two-stage merge first}.
+ *   kernel: 1 col_stats_kernel (MODE 1 shifted statistics, 0 plain sums: pseg_col_sum, whose record is this launch's with LANES of
+ *   the col_reduce_kernel launch that followed), 2 bn_bwd_reduce_kernel, 3 stat_merge_kernel (never last), 4 bn_finalize_kernel,
+ *   5 bn_bwd_finalize_kernel, 6 col_reduce_kernel (on its own: the depthwise weight gradient), 7 bn_eval_coeffs_kernel,
+ *   8 bn_act_fwd_kernel, 9 bn_act_fwd_rows_kernel, 10 bn_act_bwd_apply_kernel, 11 act_bwd_kernel, 12 copy2d_kernel,
+ *   13 bn_fwd_small_kernel (pseg_bn_fwd_fused), 14 bn_bwd_small_kernel (pseg_bn_bwd_fused).
+ *   MODE of the backward kernels: where act'(z) came from -- 0 no activation, 1 the bitmask, 2 the stored z, 3 recomputed from y.
+ *   LANES: row lanes of the finalize / reduce block (32 | 128; 32 inside the fused kernels), 0 elsewhere.
+ * Zeros before the thread's first such launch; a refused call leaves it alone.  Host-side integer stores next to the launch, no
+ * device work.  Additive: PSEG_ABI_VERSION does not move. */
+int pseg_debug_last_norm(int* out12);
 int pseg_conv2d_gather_choice(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil,
                               int dgrad, int precision, int stats, int bias, int planes, int bns, int accumulate, int* out13);
 

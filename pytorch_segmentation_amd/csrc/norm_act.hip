@@ -891,6 +891,24 @@ __global__ __launch_bounds__(256) void bn_bwd_small_kernel(
 // ------------------------------------------------------------------------------------------------ host
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// The record of the calling thread's last launch from this file (pseg_debug_last_norm; layout: pseg_amd.h): which kernel, on
+// which storage type, in which instantiation and launch shape.  A few integer stores beside the launch; nothing reads it back.
+constexpr int kNormRecord = 12;
+enum NormKernel {
+  kNormColStats = 1, kNormBwdReduce, kNormStatMerge, kNormFinalize, kNormBwdFinalize, kNormColReduce, kNormEvalCoeffs,
+  kNormActFwd, kNormActFwdRows, kNormBwdApply, kNormActBwd, kNormCopy2d, kNormFwdSmall, kNormBwdSmall
+};
+static thread_local int g_last_norm[kNormRecord] = {};
+
+static void norm_record(int kernel, int half, int V, int NR, int mode, int lanes, dim3 block, dim3 grid, int rows,
+                        int two_stage = 0) {
+  const int rec[kNormRecord] = {kernel, half, V, NR, mode, lanes, (int)block.x, (int)block.y, (int)grid.x, (int)grid.y,
+                                rows, two_stage};
+  for (int i = 0; i < kNormRecord; ++i) g_last_norm[i] = rec[i];
+}
+template <typename T>
+constexpr int is_half() { return sizeof(T) == 2 ? 1 : 0; }
+
 // V: channels per lane (4; 8 for the fp16 streaming passes)
 static void stat_block(int C, dim3& block, dim3& grid, long long M, int R, int V = 4) {
   const int cv = C / V;
@@ -925,6 +943,8 @@ int launch_col_reduce(const float* part, int rows, int C, float* out, int accumu
     hipLaunchKernelGGL(col_reduce_kernel<kFinLanes>, dim3(cdiv(C, kFinCh)), dim3(kFinCh * kFinLanes), 0, st, part, rows, C,
                        out, accumulate);
   PSEG_LAUNCH_CHECK();
+  const int lanes = rows >= kFinWideRows ? kFinLanesWide : kFinLanes;
+  norm_record(kNormColReduce, 0, 1, 0, 0, lanes, dim3(kFinCh * lanes), dim3(cdiv(C, kFinCh)), rows);
   return PSEG_OK;
 }
 
@@ -932,6 +952,11 @@ int launch_col_reduce(const float* part, int rows, int C, float* out, int accumu
 // ------------------------------------------------------------------------------------------------ entry points, by storage type
 template <typename T>
 static bool ld_ok(int ld) { return ld % (sizeof(T) == 2 ? 8 : 4) == 0; }
+
+// the streaming BatchNorm passes work in lanes of lane_channels<T>() channels: an fp16 tensor with C % 8 == 4 would have its last
+// lane load and store four channels past C (in the reduce pass: past the end of the partials)
+#define EW_LANE_CHECK(name, T, C) \
+  PSEG_REQUIRE((C) % lane_channels<T>() == 0, name ": fp16 tensors need C %% 8 == 0 (C=%d)", (int)(C))
 
 template <typename T>
 static int col_stats_impl(const T* y, int ldy, int64_t M, int C, float* stat, void* stream) {
@@ -944,6 +969,7 @@ static int col_stats_impl(const T* y, int ldy, int64_t M, int C, float* stat, vo
   hipLaunchKernelGGL((col_stats_kernel<true, T>), grid, block, 0, (hipStream_t)stream, y, ldy, (long long)M, C, R, stat,
                      (long long)cdiv(M, R) * C);
   PSEG_LAUNCH_CHECK();
+  norm_record(kNormColStats, is_half<T>(), 4, 4, 1, 0, block, grid, R);
   return PSEG_OK;
 }
 
@@ -963,6 +989,7 @@ static int bn_fwd_fused_impl(const float* stat, int rows, int group, int64_t cou
                      C, gamma, beta, running_mean, running_var, momentum, eps, mean, invstd, scale, shift, y, ldy, residual,
                      ldr, act, z, ldz, (long long)M, (unsigned*)amax_z);
   PSEG_LAUNCH_CHECK();
+  norm_record(kNormFwdSmall, is_half<T>(), 4, 1, 0, kFinLanes, dim3(256), grid, kSmallRowsPerBlock);
   return PSEG_OK;
 }
 
@@ -984,6 +1011,8 @@ static int bn_bwd_fused_impl(const float* part_db, const float* part_dg, int row
                      (long long)count, C, dgamma, dbeta, accumulate, frozen, dz, lddz, z, ldz, y, ldy, mean, invstd, scale,
                      shift, act, dy, lddy, dres, lddres, res_accumulate, (long long)M);
   PSEG_LAUNCH_CHECK();
+  norm_record(kNormBwdSmall, is_half<T>(), 4, 1, act == PSEG_ACT_NONE ? 0 : (z != nullptr ? 2 : 3), kFinLanes, dim3(256), grid,
+              kSmallRowsPerBlock);
   return PSEG_OK;
 }
 
@@ -996,6 +1025,7 @@ static int bn_act_fwd_impl(const T* y, int ldy, const float* mean, const float* 
   PSEG_REQUIRE((scale == nullptr) == (shift == nullptr) && (scale == nullptr) == (mean == nullptr),
                "bn_act_fwd: mean/scale/shift must come together");
   EW_COMMON_CHECKS("bn_act_fwd", M, C);
+  EW_LANE_CHECK("bn_act_fwd", T, C);
   PSEG_REQUIRE(ld_ok<T>(ldy) && ld_ok<T>(ldz) && (!residual || ld_ok<T>(ldr)) && al16(y) && al16(z) && al16(residual) &&
                    al16(mean) && al16(scale) && al16(shift),
                "bn_act_fwd: alignment");
@@ -1019,12 +1049,14 @@ static int bn_act_fwd_impl(const T* y, int ldy, const float* mean, const float* 
       hipLaunchKernelGGL((bn_act_fwd_rows_kernel<kNR, T, V>), grid, block, 0, (hipStream_t)stream, y, ldy, mean, scale, shift,
                          residual, ldr, act, z, ldz, (long long)M, C, RB, mask_out);
       PSEG_LAUNCH_CHECK();
+      norm_record(kNormActFwdRows, 1, V, kNR, 0, 0, block, grid, RB);
       return PSEG_OK;
     }
   }
   hipLaunchKernelGGL((bn_act_fwd_kernel<T, V>), dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, y, ldy, mean, scale,
                      shift, residual, ldr, act, z, ldz, total, FastDiv((uint32_t)(C / V)), (unsigned*)amax_z, mask_out);
   PSEG_LAUNCH_CHECK();
+  norm_record(kNormActFwd, is_half<T>(), V, 1, 0, 0, dim3(256), dim3(ew_grid(total)), 0);
   return PSEG_OK;
 }
 
@@ -1036,6 +1068,7 @@ static int bn_act_bwd_reduce_impl(const T* dz, int lddz, const T* z, int ldz, co
   PSEG_REQUIRE(act == PSEG_ACT_NONE || z || mask || (scale && shift), "bn_act_bwd_reduce: activation needs z, mask or scale/shift");
   PSEG_REQUIRE(mask == nullptr || C % 32 == 0, "bn_act_bwd_reduce: mask needs C %% 32 == 0");
   EW_COMMON_CHECKS("bn_act_bwd_reduce", M, C);
+  EW_LANE_CHECK("bn_act_bwd_reduce", T, C);
   PSEG_REQUIRE(ld_ok<T>(lddz) && ld_ok<T>(ldy) && (!z || ld_ok<T>(ldz)) && al16(dz) && al16(z) && al16(y), "bn_act_bwd_reduce: alignment");
   dim3 block, grid;
   const int R = stat_group(M, C);
@@ -1055,6 +1088,7 @@ static int bn_act_bwd_reduce_impl(const T* dz, int lddz, const T* z, int ldz, co
   }
 #undef PSEG_BWD_REDUCE
   PSEG_LAUNCH_CHECK();
+  norm_record(kNormBwdReduce, is_half<T>(), V, V == 8 ? 2 : 4, mode, 0, block, grid, R);
   return PSEG_OK;
 }
 
@@ -1071,6 +1105,7 @@ static int bn_act_bwd_apply_impl(const T* dz, int lddz, const T* z, int ldz, con
   PSEG_REQUIRE(act == PSEG_ACT_NONE || z || mask || shift, "bn_act_bwd_apply: activation needs z, mask or shift");
   PSEG_REQUIRE(mask == nullptr || C % 32 == 0, "bn_act_bwd_apply: mask needs C %% 32 == 0");
   EW_COMMON_CHECKS("bn_act_bwd_apply", M, C);
+  EW_LANE_CHECK("bn_act_bwd_apply", T, C);
   PSEG_REQUIRE(ld_ok<T>(lddz) && ld_ok<T>(ldy) && ld_ok<T>(lddy) && (!z || ld_ok<T>(ldz)) && (!dres || ld_ok<T>(lddres)) &&
                    al16(dz) && al16(z) && al16(y) && al16(dy) && al16(dres),
                "bn_act_bwd_apply: alignment");
@@ -1098,6 +1133,7 @@ static int bn_act_bwd_apply_impl(const T* dz, int lddz, const T* z, int ldz, con
   }
 #undef PSEG_BWD_APPLY
   PSEG_LAUNCH_CHECK();
+  norm_record(kNormBwdApply, is_half<T>(), V, kNR, mode, 0, block, grid, RB);
   return PSEG_OK;
 }
 
@@ -1114,6 +1150,7 @@ static int act_bwd_impl(const T* dz, int lddz, const T* z, int ldz, const float*
   hipLaunchKernelGGL(act_bwd_kernel<T>, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, dz, lddz, z, ldz, scale, act,
                      dy, lddy, dres, lddres, res_accumulate, total, FastDiv((uint32_t)(C / 4)));
   PSEG_LAUNCH_CHECK();
+  norm_record(kNormActBwd, is_half<T>(), 4, 1, act == PSEG_ACT_NONE ? 0 : 2, 0, dim3(256), dim3(ew_grid(total)), 0);
   return PSEG_OK;
 }
 
@@ -1135,7 +1172,10 @@ static int col_sum_impl(const T* dy, int ldy, int64_t M, int C, float* out, int 
   hipLaunchKernelGGL((col_stats_kernel<false, T>), grid, block, 0, (hipStream_t)stream, dy, ldy, (long long)M, C, R,
                      (float*)workspace, 0LL);
   PSEG_LAUNCH_CHECK();
-  return launch_col_reduce((const float*)workspace, rows, C, out, accumulate, (hipStream_t)stream);
+  const int rc = launch_col_reduce((const float*)workspace, rows, C, out, accumulate, (hipStream_t)stream);
+  // two launches: the record is the column-sum kernel's, with the lanes of the reduction that followed it
+  if (rc == PSEG_OK) norm_record(kNormColStats, is_half<T>(), 4, 4, 0, rows >= kFinWideRows ? kFinLanesWide : kFinLanes, block, grid, R);
+  return rc;
 }
 
 template <typename T>
@@ -1147,6 +1187,7 @@ static int copy2d_impl(const T* x, int ldx, T* y, int ldy, int64_t M, int C, int
   hipLaunchKernelGGL(copy2d_kernel<T>, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, accumulate,
                      total, FastDiv((uint32_t)(C / 4)));
   PSEG_LAUNCH_CHECK();
+  norm_record(kNormCopy2d, is_half<T>(), 4, 1, 0, 0, dim3(256), dim3(ew_grid(total)), 0);
   return PSEG_OK;
 }
 
@@ -1158,6 +1199,12 @@ using namespace pseg;
 #define HPM(p) reinterpret_cast<half_t*>(p)
 
 extern "C" {
+
+int pseg_debug_last_norm(int* out12) {
+  PSEG_REQUIRE(out12 != nullptr, "debug_last_norm: null pointer");
+  for (int i = 0; i < kNormRecord; ++i) out12[i] = g_last_norm[i];
+  return PSEG_OK;
+}
 
 int pseg_col_stats_rows(int64_t M, int C) { return cdiv(M, stat_group(M, C)); }
 
@@ -1184,6 +1231,7 @@ int pseg_bn_finalize(const float* stat, int rows, int group, int64_t count, int 
   PSEG_REQUIRE(rows > 0 && group > 0 && count > 0 && C > 0, "bn_finalize: bad sizes");
   PSEG_REQUIRE((long long)rows * group >= count, "bn_finalize: %d groups of %d rows do not cover %lld rows", rows, group,
                (long long)count);
+  int two_stage = 0;
   if (rows > kTwoStageRows) {
     const int64_t need = pseg_bn_finalize_workspace_bytes(rows, C);
     if (!workspace || workspace_bytes < need) {
@@ -1197,6 +1245,7 @@ int pseg_bn_finalize(const float* stat, int rows, int group, int64_t count, int 
     stat = (const float*)workspace;
     rows = out_rows;
     group *= kMergePer;
+    two_stage = 1;
   }
   if (rows >= kFinWideRows)
     hipLaunchKernelGGL(bn_finalize_kernel<kFinLanesWide>, dim3(cdiv(C, kFinCh)), dim3(kFinCh * kFinLanesWide), 0,
@@ -1207,6 +1256,10 @@ int pseg_bn_finalize(const float* stat, int rows, int group, int64_t count, int 
                        (hipStream_t)stream, stat, rows, group, (long long)count, C, gamma, beta, running_mean, running_var,
                        momentum, eps, mean, invstd, scale, shift);
   PSEG_LAUNCH_CHECK();
+  {
+    const int lanes = rows >= kFinWideRows ? kFinLanesWide : kFinLanes;
+    norm_record(kNormFinalize, 0, 1, 4, 0, lanes, dim3(kFinCh * lanes), dim3(cdiv(C, kFinCh)), rows, two_stage);
+  }
   return PSEG_OK;
 }
 
@@ -1260,6 +1313,7 @@ int pseg_bn_eval_coeffs(const float* gamma, const float* beta, const float* runn
   hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, gamma, beta,
                      running_mean, running_var, eps, C, mean, invstd, scale, shift);
   PSEG_LAUNCH_CHECK();
+  norm_record(kNormEvalCoeffs, 0, 1, 1, 0, 0, dim3(256), dim3(cdiv(C, 256)), 0);
   return PSEG_OK;
 }
 
@@ -1300,6 +1354,10 @@ int pseg_bn_bwd_finalize(const float* part_db, const float* part_dg, int rows, i
                        (hipStream_t)stream, part_db, part_dg, rows, (long long)count, C, dgamma, dbeta, accumulate, frozen, c1,
                        c2);
   PSEG_LAUNCH_CHECK();
+  {
+    const int lanes = rows >= kFinWideRows ? kFinLanesWide : kFinLanes;
+    norm_record(kNormBwdFinalize, 0, 1, 4, 0, lanes, dim3(kFinCh * lanes), dim3(cdiv(C, kFinCh)), rows);
+  }
   return PSEG_OK;
 }
 

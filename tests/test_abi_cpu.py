@@ -18,10 +18,11 @@ def lib():
 
 def test_header_prototypes_all_exported(lib):
     protos = _lib.parse_header()
-    assert len(protos) >= 143
+    assert len(protos) >= 144
     assert 'pseg_debug_last_conv_kernel' in protos and 'pseg_debug_last_gather_h' in protos
     assert {'pseg_debug_last_wgrad', 'pseg_conv2d_wgrad_choice', 'pseg_conv2d_wgrad_choice_h'} <= set(protos)
     assert {'pseg_debug_last_gather', 'pseg_conv2d_gather_choice'} <= set(protos)
+    assert 'pseg_debug_last_norm' in protos
     for name in protos:
         assert hasattr(lib, name), name
     out = subprocess.check_output(['nm', '-D', '--defined-only', _lib.LIB_PATH]).decode()
@@ -42,6 +43,9 @@ def test_abi_version_and_error_string(lib):
     # ... and of the exact-fp32 / limb ones
     rec = (ctypes.c_int * 13)(*[7] * 13)
     assert lib.pseg_debug_last_gather(rec) == 0 and list(rec) == [0] * 13
+    # ... and of the BatchNorm / activation launches
+    rec = (ctypes.c_int * 12)(*[7] * 12)
+    assert lib.pseg_debug_last_norm(rec) == 0 and list(rec) == [0] * 12
 
 
 def test_plan_queries_are_consistent(lib):
