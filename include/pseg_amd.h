@@ -59,8 +59,9 @@ extern "C" {
 #define PSEG_ACT_RELU6 2
 
 /* bumped whenever an existing prototype changes incompatibly; pseg_abi_version() returns the value the library was built with.
- * Entry points added since 14 (pseg_image_preprocess_views, pseg_softmax_views, pseg_seg_decode_ensemble, and the
- * connected-region calls pseg_regions_workspace_bytes, pseg_mask_label, pseg_mask_regions, pseg_mask_clean) are purely
+ * Entry points added since 14 (pseg_image_preprocess_views, pseg_softmax_views, pseg_seg_decode_ensemble, the
+ * connected-region calls pseg_regions_workspace_bytes, pseg_mask_label, pseg_mask_regions, pseg_mask_clean, and the
+ * sliding-window calls pseg_image_preprocess_windows, pseg_seg_decode_windows) are purely
  * additive and do not bump it: the loader checks every declared prototype against the library's exports by name. */
 #define PSEG_ABI_VERSION 14
 int pseg_abi_version(void);
@@ -552,6 +553,51 @@ int pseg_softmax_views(const float* logits, int B, int pairs, int C, int h, int 
 int pseg_seg_decode_ensemble(const float* prob, int64_t prob_floats, const int64_t* maps, int S, int B, int C, const int64_t* table,
                              int64_t npix_total, int Hmax, int Wmax, uint8_t* mask, uint8_t* rgb, const uint8_t* lut,
                              void* stream);
+
+/* ------------------------------------------------------------------ sliding-window inference (csrc/infer.hip)
+ * A photo larger than the model input is not squeezed into it: the model runs on overlapping windows of its input size
+ * laid over the photo at its own (or a scaled) resolution, the class probabilities of the windows covering a pixel are
+ * averaged, and the argmax is taken.  Given: the window (h, w) = the model input size, a stride (sy, sx), scales
+ * s_1..s_S (1 <= S <= 8) and a photo of H x W.
+ * Working image at scale s: (Hs, Ws) = (max(1, int(H*s + 0.5)), max(1, int(W*s + 0.5))); the photo resampled with
+ *   pseg_image_preprocess's geometry and 8-bit rounding, exactly as that call gives it at oh = Hs, ow = Ws (at s = 1 the
+ *   photo itself, bit for bit: the taps degenerate to weights 1 / 0).
+ * Window grid of a working image: ny = ceil(max(Hs - h, 0) / sy) + 1 rows and nx = ceil(max(Ws - w, 0) / sx) + 1 columns;
+ *   window (i, j) has its origin at y0 = min(i*sy, max(Hs - h, 0)), x0 = min(j*sx, max(Ws - w, 0)): the last row and
+ *   column are shifted back inside the image, not hung over its edge; an image smaller than the window along an axis has
+ *   one window along it, whose positions outside the image hold the normalised value 0.0 (the mean colour) and are never
+ *   sampled by the decode.  Strides: ceil(h/2) <= sy <= h and ceil(w/2) <= sx <= w, so a pixel is covered by at most
+ *   3 windows per axis; the usual choice is (ceil(2h/3), ceil(2w/3)).
+ * Working probability: P_s(Y, X, c) = (sum over the windows covering (Y, X), in (i, j) order, of
+ *   p_win(Y - y0, X - x0, c)) / n(Y, X), p_win being the window's softmax (with mirroring: plus the un-mirrored softmax of
+ *   the mirrored window, what pseg_softmax_views writes with pairs), n the integer number of covering windows; fp32, the
+ *   division correctly rounded; the average is unweighted.
+ * Mask: mask(y, x) = argmax_c sum_s bilinear(P_s, (H, W), align_corners=False)[y, x, c] with pseg_seg_decode's tap
+ *   geometry, the first index winning ties, uint8; colours through the lut as in pseg_seg_decode.
+ *
+ * pseg_image_preprocess_windows: pseg_image_preprocess_views with `rows` table records of EIGHT int64 {byte offset, H, W,
+ *   flags, Hs, Ws, y0, x0}; out is [rows,3,oh,ow] with (oh, ow) the window: out[r,c,y,x] = the normalised working-image
+ *   value at (y0 + y, x0 + x), or 0.0f where that position lies outside Hs x Ws; PSEG_VIEW_MIRROR mirrors the output row as
+ *   in the views call.  The arithmetic is the views call's, so a record {.., flags, oh, ow, 0, 0} equals its row bit for
+ *   bit, and a window equals the crop of the record {.., 0, Hs, Ws, 0, 0} rendered at oh = Hs, ow = Ws bit for bit.
+ *   Skipped on the device, nothing read or written: a record whose photo leaves src, whose Hs or Ws is outside
+ *   [1, 65535], whose y0 or x0 is negative or >= Hs / Ws, or with a flag bit outside flag_mask.
+ * pseg_seg_decode_windows: groups is a device array of S * B records of three int64 {float offset, Hs, Ws}, scale-major
+ *   (record s * B + b: the windows of photo b at scale s), a group being [ny*nx, h, w, CP] as pseg_softmax_views writes
+ *   it, window (i, j) at index i*nx + j; ny and nx follow from the grid rule.  table, npix_total, Hmax, Wmax, mask, rgb
+ *   and lut are pseg_seg_decode_ensemble's.  Skipped on the device, nothing written: a photo whose table record leaves
+ *   the mask buffer or exceeds Hmax / Wmax, and a photo ANY of whose S group records leaves prob, has an offset that is
+ *   not a multiple of 4 or a size outside [1, 65535] (other photos are not affected).  PSEG_ERR_ARG: null pointers, S
+ *   outside [1, 8], C outside [1, 256], strides outside the limits above, non-positive sizes.  A gather by output tile:
+ *   per photo pixel and scale the covering windows' vectors are summed and divided per bilinear tap, the taps blended
+ *   and the scales accumulated in registers; no atomics, no C-channel tensor at working or photo size, deterministic.
+ */
+int pseg_image_preprocess_windows(const uint8_t* src, int64_t src_bytes, const int64_t* table, int rows, int flag_mask, int bgr,
+                                  float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh,
+                                  int ow, void* stream);
+int pseg_seg_decode_windows(const float* prob, int64_t prob_floats, const int64_t* groups, int S, int B, int C, int h, int w, int sy,
+                            int sx, const int64_t* table, int64_t npix_total, int Hmax, int Wmax, uint8_t* mask, uint8_t* rgb,
+                            const uint8_t* lut, void* stream);
 
 /* ------------------------------------------------------------------ connected regions of the masks (csrc/regions.hip)
  * The step after the argmax: label the connected regions of each mask, describe them, and clean the mask.  mask, table,

@@ -4,6 +4,7 @@
     python3 inference.py data/samples outputs --weights weights.pth [-s W H] [-nc N] [-bs N] [--model ...] [-mp]
                          [--norm dataset|reference] [--scales S [S ...]] [--flip]
                          [--min-area N] [--connectivity {4,8}] [--largest-only] [--regions FILE.json]
+                         [--slide [--stride SW SH] [--window-batch N]]
 
 Every file of img_dir whose extension is in IMG_EXT (case-sensitive, as the reference) is segmented, in name order, and
 written to output_dir as <name>.png in VOC colours.  Photos are decoded with PIL (RGB); resizing, normalisation, softmax,
@@ -16,6 +17,10 @@ multiples of 32), and with --flip of the left-right mirrored photo as well, are 
 --largest-only keeps the largest region of every class but background, --connectivity chooses 4- or 8-neighbour regions
 (utils/regions.py); the PNGs show the cleaned masks.  --regions FILE.json writes {file name: [region, ...]} for the whole
 folder: class, area, bbox, centroid, angle, sides and label of every region of the (cleaned) mask.
+--slide does not squeeze a photo into -s W H: the model runs on overlapping W x H windows (multiples of 32) laid over the
+photo at its own size -- with --scales over the photo scaled by each factor -- at --stride SW SH (default 2/3 of the
+window), the class probabilities of the windows covering a pixel are averaged and the argmax is taken; --window-batch N
+windows go through the model at a time (default: the photos of a batch).
 """
 import argparse
 import json
@@ -45,7 +50,10 @@ def load_image(path):
 
 
 def run(img_dir, output_dir, img_size, num_classes, weights, show=False, model_name='deeplabv3plus', batch_size=1,
-        half=False, norm='dataset', scales=None, flip=False, min_area=0, connectivity=8, largest_only=False, regions=None):
+        half=False, norm='dataset', scales=None, flip=False, min_area=0, connectivity=8, largest_only=False, regions=None,
+        slide=False, stride=None, window_batch=None):
+    if not slide and (stride is not None or window_batch is not None):
+        raise ValueError('--stride and --window-batch need --slide')
     if min_area < 0:
         raise ValueError('--min-area must be >= 0; got %d' % min_area)
     if connectivity not in (4, 8):
@@ -60,6 +68,8 @@ def run(img_dir, output_dir, img_size, num_classes, weights, show=False, model_n
     model.eval()
     names = list_images(img_dir)
     tta = {} if scales is None and not flip else {'scales': scales, 'flip': bool(flip)}
+    if slide:
+        tta.update(slide=True, stride=None if stride is None else tuple(stride), window_batch=window_batch)
     if min_area > 1 or largest_only or regions:
         tta.update(min_area=min_area, connectivity=connectivity, largest_only=bool(largest_only), regions=bool(regions))
     found = {}
@@ -101,12 +111,24 @@ def main(argv=None):
     parser.add_argument('--largest-only', action='store_true', help='keep only the largest region of every class >= 1')
     parser.add_argument('--regions', type=str, default=None, metavar='FILE.json',
                         help='write {file name: [region, ...]} (class, area, bbox, centroid, angle, sides, label)')
+    parser.add_argument('--slide', action='store_true',
+                        help='sliding-window inference: -s W H is the window (multiples of 32) laid over the photo at its own '
+                             'size; --scales then scale the photo')
+    parser.add_argument('--stride', type=int, nargs=2, default=None, metavar=('SW', 'SH'),
+                        help='with --slide: the window stride, between half the window and the window (default: 2/3 of it)')
+    parser.add_argument('--window-batch', type=int, default=None, metavar='N',
+                        help='with --slide: windows per forward (default: -bs)')
     opt = parser.parse_args(argv)
     if opt.min_area < 0:
         parser.error('--min-area must be >= 0')
+    if not opt.slide and (opt.stride is not None or opt.window_batch is not None):
+        parser.error('--stride and --window-batch need --slide')
+    if opt.window_batch is not None and opt.window_batch < 1:
+        parser.error('--window-batch must be >= 1')
     print(opt)
     run(opt.img_dir, opt.output_dir, opt.img_size, opt.num_classes, opt.weights, opt.show, opt.model, opt.batch_size,
-        opt.mix_precision, opt.norm, opt.scales, opt.flip, opt.min_area, opt.connectivity, opt.largest_only, opt.regions)
+        opt.mix_precision, opt.norm, opt.scales, opt.flip, opt.min_area, opt.connectivity, opt.largest_only, opt.regions,
+        opt.slide, opt.stride, opt.window_batch)
 
 
 if __name__ == '__main__':

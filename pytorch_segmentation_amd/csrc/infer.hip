@@ -19,6 +19,14 @@
 //    (maps of different resolutions share no source tiling); a thread owns a short column of output pixels and reads the
 //    four taps of each map as 16-byte vectors straight from L1/L2 -- neighbouring pixels share them -- instead of
 //    staging S footprints of S different shapes in LDS (an 8x down-scaled photo's footprint would not fit anyway).
+// Sliding-window inference (a photo larger than the model input is covered by overlapping windows of the input size at
+// the photo's own or a scaled resolution) generalises two of them:
+//  - image_preprocess_windows: image_preprocess_views whose output row is a window of the photo resampled to a working
+//    size (Hs, Ws), zero (the mean colour) beyond it.
+//  - seg_decode_windows: seg_decode_ensemble with, per scale, the windows' probability maps in place of one map: the value
+//    of a bilinear tap is the unweighted mean of the windows that cover it.  Still a gather by output tile -- no atomics and
+//    no C-channel canvas at working or photo size; the windows covering a tap depend only on its row or column, so a block
+//    works them out once for its 16 rows and 64 columns into LDS.
 #include "common.h"
 
 #include <math.h>
@@ -408,6 +416,203 @@ __global__ __launch_bounds__(256) void seg_decode_ensemble_kernel(const float* _
   }
 }
 
+// ------------------------------------------------------------------ sliding windows
+// Along one axis a working image of `in` pixels is covered by n = ceil(max(in - win, 0) / stride) + 1 windows of `win`
+// pixels; window i starts at min(i * stride, max(in - win, 0)): the last one is shifted back inside the image, and an
+// image shorter than the window has one window (whose positions beyond the image are never sampled).
+__device__ __forceinline__ int win_count(int in, int win, const FastDiv& st) {
+  const int m = in > win ? in - win : 0;
+  return (int)st.div((uint32_t)m + st.d - 1) + 1;
+}
+
+// The windows covering coordinate p (0 <= p < in), ascending, as (window index << 16 | coordinate inside the window);
+// -> their number: 1..3 under the stride limits ceil(win / 2) <= stride <= win the host enforces.
+__device__ __forceinline__ int win_cover(int p, int in, int win, const FastDiv& st, int n, uint32_t* out) {
+  const int m = in > win ? in - win : 0;
+  const int hi = p >= m ? n - 1 : (int)st.div((uint32_t)p);
+  const int lo = p < win ? 0 : (int)st.div((uint32_t)(p - win)) + 1;
+  const int c = min(hi - lo + 1, 3);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int i = lo + k;
+    out[k] = k < c ? ((uint32_t)i << 16) | (uint32_t)(p - min(i * (int)st.d, m)) : 0u;
+  }
+  return c;
+}
+
+// image_preprocess_views_kernel with rows {byte offset, H, W, flags, Hs, Ws, y0, x0}: the output row is the oh x ow window
+// at (y0, x0) of the photo resampled to Hs x Ws; positions beyond Hs x Ws hold 0.0f (the mean colour).  The arithmetic is
+// that kernel's, expression for expression: a row {.., oh, ow, 0, 0} gives its bits, and a window gives the bits of the
+// crop of the whole working image.
+__global__ __launch_bounds__(256) void image_preprocess_windows_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
+                                                                       const int64_t* __restrict__ table, int flag_mask, int bgr,
+                                                                       Norm nm, float* __restrict__ out, int oh, int ow) {
+  const int b = blockIdx.z, oy = blockIdx.y;
+  const int ox = blockIdx.x * 256 + threadIdx.x;
+  if (ox >= ow) return;
+  const int64_t* t = table + 8 * (int64_t)b;
+  const int64_t off = t[0], H = t[1], W = t[2], flags = t[3], Hs = t[4], Ws = t[5], wy = t[6], wx = t[7];
+  if (!entry_ok(off, H, W, 3, src_bytes) || (flags & ~(int64_t)flag_mask) != 0) return;   // bad row: nothing read or written
+  if (Hs < 1 || Ws < 1 || Hs > 65535 || Ws > 65535 || wy < 0 || wx < 0 || wy >= Hs || wx >= Ws) return;
+  const InAxis ay{(float)H / (float)(int)Hs, (int)H, (int)Hs}, ax{(float)W / (float)(int)Ws, (int)W, (int)Ws};
+  const int sx = (flags & PSEG_VIEW_MIRROR) ? ow - 1 - ox : ox;      // the column of the unmirrored window
+  const int Y = (int)wy + oy, X = (int)wx + sx;                      // position in the working image
+  const int64_t plane = (int64_t)oh * ow;
+  float* o = out + (int64_t)b * 3 * plane + (int64_t)oy * ow + ox;
+  if (Y >= (int)Hs || X >= (int)Ws) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[k * plane] = 0.f;
+    return;
+  }
+  int y0, y1, x0, x1;
+  float ly0, ly1, lx0, lx1;
+  taps(ay, Y, y0, y1, ly0, ly1);
+  taps(ax, X, x0, x1, lx0, lx1);
+  const uint8_t* p = src + off;
+  const uint8_t* p00 = p + ((int64_t)y0 * W + x0) * 3;
+  const uint8_t* p01 = p + ((int64_t)y0 * W + x1) * 3;
+  const uint8_t* p10 = p + ((int64_t)y1 * W + x0) * 3;
+  const uint8_t* p11 = p + ((int64_t)y1 * W + x1) * 3;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int cs = bgr ? 2 - k : k;
+    const float v = ly0 * (lx0 * (float)p00[cs] + lx1 * (float)p01[cs]) + ly1 * (lx0 * (float)p10[cs] + lx1 * (float)p11[cs]);
+    float q = floorf(v + 0.5f);
+    q = q < 0.f ? 0.f : (q > 255.f ? 255.f : q);
+    o[k * plane] = (q - nm.mean[k]) / nm.std[k];
+  }
+}
+
+// One bilinear tap pair of an output row or column at one scale: the upper tap's weight and, for the lower and the upper
+// tap, the windows that cover its working-image coordinate (win_cover); cnt = lower count | upper count << 2.
+struct WinTaps {
+  float l1;
+  int cnt;
+  uint32_t win[6];
+};
+
+// seg_decode_ensemble_kernel's tile and thread mapping, with the map of scale s replaced by the group of windows of
+// photo b at that scale: the value of a tap is the sum of the covering windows' vectors over their number.  A gather: no
+// atomics, no canvas.  What depends only on the tap's coordinate -- the taps of the tile's 16 rows and 64 columns at every
+// scale and the windows covering them -- is worked out once per block into LDS (20 KiB), not per pixel and class chunk;
+// the row entries are read wave-uniformly, the column entries by consecutive lanes.
+__global__ __launch_bounds__(256) void seg_decode_windows_kernel(const float* __restrict__ prob, int64_t prob_floats,
+                                                                 const int64_t* __restrict__ groups, int S, int B, int C, int CP,
+                                                                 int h, int w, FastDiv dsy, FastDiv dsx,
+                                                                 const int64_t* __restrict__ table, int64_t npix_cap, int Hmax,
+                                                                 int Wmax, uint8_t* __restrict__ mask, uint8_t* __restrict__ rgb,
+                                                                 const uint8_t* __restrict__ lut) {
+  constexpr int kEnt = kEnsTileH + kEnsTileW;
+  __shared__ WinTaps ent[kEnsMaxMaps * kEnt];
+  __shared__ int64_t goff[kEnsMaxMaps];
+  __shared__ int gnx[kEnsMaxMaps];
+  const int b = blockIdx.z;
+  const int64_t off = table[3 * b], H = table[3 * b + 1], W = table[3 * b + 2];
+  if (!entry_ok(off, H, W, 1, npix_cap) || H > Hmax || W > Wmax) return;       // bad row: nothing read or written
+  const int oy_base = blockIdx.y * kEnsTileH, ox_base = blockIdx.x * kEnsTileW;
+  if (oy_base >= H || ox_base >= W) return;                                    // ragged batch: block-uniform exit
+  for (int s = 0; s < S; ++s) {                                                // one bad group: this photo is not written
+    const int64_t* g = groups + 3 * ((int64_t)s * B + b);
+    const int64_t go = g[0], Hs = g[1], Ws = g[2];
+    if (go < 0 || (go & 3) != 0 || Hs < 1 || Ws < 1 || Hs > 65535 || Ws > 65535) return;
+    const int64_t cells = (int64_t)win_count((int)Hs, h, dsy) * h * ((int64_t)win_count((int)Ws, w, dsx) * w);
+    if (go + cells * CP > prob_floats) return;
+  }
+  const int tid = threadIdx.x;
+  for (int e = tid; e < S * kEnt; e += 256) {
+    const int s = e / kEnt, r = e - s * kEnt;
+    const int64_t* g = groups + 3 * ((int64_t)s * B + b);
+    const bool is_row = r < kEnsTileH;
+    const int o = is_row ? oy_base + r : ox_base + r - kEnsTileH;
+    const int in = (int)(is_row ? g[1] : g[2]), outn = (int)(is_row ? H : W), win = is_row ? h : w;
+    const FastDiv st = is_row ? dsy : dsx;
+    WinTaps t{0.f, 0, {0, 0, 0, 0, 0, 0}};
+    if (o < outn) {
+      const InAxis a{(float)in / (float)outn, in, outn};
+      int i0, i1;
+      float l0, l1;
+      taps(a, o, i0, i1, l0, l1);
+      const int n = win_count(in, win, st);
+      t.l1 = l1;
+      t.cnt = win_cover(i0, in, win, st, n, t.win) | win_cover(i1, in, win, st, n, t.win + 3) << 2;
+    }
+    ent[e] = t;
+    if (r == 0) {
+      goff[s] = g[0];
+      gnx[s] = win_count((int)g[2], w, dsx);
+    }
+  }
+  __syncthreads();
+  const int col = tid & 63, ox = ox_base + col;
+  if (ox >= W) return;
+  const int n4 = CP / 4;
+  uint8_t* mb = mask + off;
+  uint8_t* rb = rgb ? rgb + 3 * off : nullptr;
+  const int oy_end = min(oy_base + kEnsTileH, (int)H);
+  for (int oy = oy_base + (tid >> 6); oy < oy_end; oy += 4) {
+    float best = -1.f;
+    int bi = 0;
+    for (int c0 = 0; c0 < CP; c0 += 32) {
+      f32x4 acc[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int s = 0; s < S; ++s) {
+        const WinTaps* ey = ent + s * kEnt + (oy - oy_base);
+        const WinTaps* ex = ent + s * kEnt + kEnsTileH + col;
+        const f32x4* gp = reinterpret_cast<const f32x4*>(prob + goff[s]) + c0 / 4;
+        const int64_t nx = gnx[s];
+        const float ly1 = ey->l1, ly0 = 1.f - ly1, lx1 = ex->l1, lx0 = 1.f - lx1;
+        const int cy = ey->cnt, cx = ex->cnt;
+#pragma unroll
+        for (int ty = 0; ty < 2; ++ty) {
+#pragma unroll
+          for (int tx = 0; tx < 2; ++tx) {
+            const int ny_ = (cy >> (2 * ty)) & 3, nx_ = (cx >> (2 * tx)) & 3;
+            f32x4 t[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) t[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int i = 0; i < ny_; ++i) {                                    // the covering windows, in (i, j) order
+              const uint32_t uy = ey->win[3 * ty + i];
+              for (int j = 0; j < nx_; ++j) {
+                const uint32_t ux = ex->win[3 * tx + j];
+                const int64_t px = (((int64_t)(uy >> 16) * nx + (ux >> 16)) * h + (uy & 0xffffu)) * w + (ux & 0xffffu);
+                const f32x4* p = gp + px * n4;
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                  if (c0 + 4 * k < CP) t[k] += p[k];
+              }
+            }
+            const int n = ny_ * nx_;
+            const float cnt = (float)n, wgt = (ty ? ly1 : ly0) * (tx ? lx1 : lx0);
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+              if (c0 + 4 * k < CP) acc[k] += wgt * (n > 1 ? t[k] / cnt : t[k]);   // correctly rounded; / 1 is the identity
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        if (c0 + 4 * k < CP) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if (c0 + 4 * k + e < C && acc[k][e] > best) {   // strict: the first index wins ties
+              best = acc[k][e];
+              bi = c0 + 4 * k + e;
+            }
+          }
+        }
+      }
+    }
+    const int64_t o = (int64_t)oy * W + ox;
+    mb[o] = (uint8_t)bi;
+    if (rb) {
+      rb[3 * o] = lut[3 * bi];
+      rb[3 * o + 1] = lut[3 * bi + 1];
+      rb[3 * o + 2] = lut[3 * bi + 2];
+    }
+  }
+}
+
 }  // namespace pseg
 
 using namespace pseg;
@@ -515,6 +720,49 @@ int pseg_seg_decode_ensemble(const float* prob, int64_t prob_floats, const int64
   const int CP = C <= 8 ? 8 : (C + 3) / 4 * 4;
   hipLaunchKernelGGL(seg_decode_ensemble_kernel, dim3(cdiv(Wmax, kEnsTileW), cdiv(Hmax, kEnsTileH), B), dim3(256), 0,
                      (hipStream_t)stream, prob, prob_floats, maps, S, B, C, CP, table, npix_total, Hmax, Wmax, mask, rgb, lut);
+  PSEG_LAUNCH_CHECK();
+  return PSEG_OK;
+}
+
+int pseg_image_preprocess_windows(const uint8_t* src, int64_t src_bytes, const int64_t* table, int rows, int flag_mask, int bgr,
+                                  float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh,
+                                  int ow, void* stream) {
+  PSEG_REQUIRE(src && table && out, "image_preprocess_windows: null pointer");
+  PSEG_REQUIRE((flag_mask & ~PSEG_VIEW_MIRROR) == 0,
+               "image_preprocess_windows: unknown flag bits 0x%x (known: PSEG_VIEW_MIRROR = 1)",
+               (unsigned)(flag_mask & ~PSEG_VIEW_MIRROR));
+  PSEG_REQUIRE(rows >= 1 && rows <= 65535, "image_preprocess_windows: %d table rows outside [1, 65535]", rows);
+  PSEG_REQUIRE(oh >= 1 && oh <= 65535 && ow >= 1 && ow <= 65535, "image_preprocess_windows: window size %dx%d outside [1, 65535]",
+               oh, ow);
+  PSEG_REQUIRE(src_bytes >= 3, "image_preprocess_windows: src_bytes %lld holds no pixel", (long long)src_bytes);
+  PSEG_REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "image_preprocess_windows: std must be non-zero");
+  Norm nm{{mean0, mean1, mean2}, {std0, std1, std2}};
+  hipLaunchKernelGGL(image_preprocess_windows_kernel, dim3(cdiv(ow, 256), oh, rows), dim3(256), 0, (hipStream_t)stream, src,
+                     src_bytes, table, flag_mask, bgr ? 1 : 0, nm, out, oh, ow);
+  PSEG_LAUNCH_CHECK();
+  return PSEG_OK;
+}
+
+int pseg_seg_decode_windows(const float* prob, int64_t prob_floats, const int64_t* groups, int S, int B, int C, int h, int w, int sy,
+                            int sx, const int64_t* table, int64_t npix_total, int Hmax, int Wmax, uint8_t* mask, uint8_t* rgb,
+                            const uint8_t* lut, void* stream) {
+  PSEG_REQUIRE(prob && groups && table && mask, "seg_decode_windows: null pointer");
+  PSEG_REQUIRE((rgb == nullptr) == (lut == nullptr), "seg_decode_windows: rgb and lut come together");
+  PSEG_REQUIRE(S >= 1 && S <= kEnsMaxMaps, "seg_decode_windows: %d scales; 1 <= S <= %d supported", S, kEnsMaxMaps);
+  PSEG_REQUIRE(C >= 1 && C <= 256, "seg_decode_windows: %d classes; 1 <= C <= 256 supported (the mask is uint8)", C);
+  PSEG_REQUIRE(B >= 1 && B <= 65535, "seg_decode_windows: batch %d outside [1, 65535]", B);
+  PSEG_REQUIRE(h >= 1 && w >= 1 && h <= 65535 && w <= 65535, "seg_decode_windows: window size %dx%d outside [1, 65535]", h, w);
+  PSEG_REQUIRE(sy >= (h + 1) / 2 && sy <= h && sx >= (w + 1) / 2 && sx <= w,
+               "seg_decode_windows: stride %dx%d outside [ceil(h/2), h] x [ceil(w/2), w] of the %dx%d window", sy, sx, h, w);
+  PSEG_REQUIRE(Hmax >= 1 && Wmax >= 1 && Hmax <= 65535 && Wmax <= 65535, "seg_decode_windows: largest image %dx%d outside [1, 65535]",
+               Hmax, Wmax);
+  PSEG_REQUIRE(((uintptr_t)prob & 15) == 0, "seg_decode_windows: the probability buffer must be 16-byte aligned");
+  PSEG_REQUIRE(prob_floats >= 8 && npix_total >= 1, "seg_decode_windows: prob_floats %lld, npix_total %lld", (long long)prob_floats,
+               (long long)npix_total);
+  const int CP = C <= 8 ? 8 : (C + 3) / 4 * 4;
+  hipLaunchKernelGGL(seg_decode_windows_kernel, dim3(cdiv(Wmax, kEnsTileW), cdiv(Hmax, kEnsTileH), B), dim3(256), 0,
+                     (hipStream_t)stream, prob, prob_floats, groups, S, B, C, CP, h, w, FastDiv((uint32_t)sy), FastDiv((uint32_t)sx),
+                     table, npix_total, Hmax, Wmax, mask, rgb, lut);
   PSEG_LAUNCH_CHECK();
   return PSEG_OK;
 }

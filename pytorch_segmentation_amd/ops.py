@@ -1308,6 +1308,58 @@ def seg_decode_ensemble(prob, maps, B, C, table, npix_total, max_hw, lut=None, o
     return mask, rgb
 
 
+WINDOW_STRIDE = (2, 3)  # default stride of sliding windows: ceil(2/3 of the window) along each axis
+
+
+def window_stride_limits(win):
+    """(smallest, largest, default) stride of sliding windows of `win` pixels along one axis: ceil(win/2) <= stride <=
+    win, so that a pixel is covered by at most 3 windows per axis; default ceil(win * WINDOW_STRIDE)."""
+    num, den = WINDOW_STRIDE
+    return (win + 1) // 2, win, (num * win + den - 1) // den
+
+
+def image_preprocess_windows(src, table, oh, ow, mean, std, bgr, flag_mask=VIEW_MIRROR):
+    """image_preprocess_views whose output rows are windows (pseg_image_preprocess_windows): table is an int64 device
+    tensor [R,8] of {byte offset, H, W, flags, Hs, Ws, y0, x0}, -> fp32 [R,3,oh,ow] with out[r,c,y,x] = the normalised
+    value at (y0 + y, x0 + x) of the photo resampled to Hs x Ws, 0.0 beyond it.  A row {.., flags, oh, ow, 0, 0} is
+    image_preprocess_views' row, bit for bit; a window is the crop of the whole working image, bit for bit.  Rows whose
+    photo leaves src, with Hs / Ws outside [1, 65535], an origin outside the working image or flag bits outside flag_mask
+    are skipped."""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
+    assert table.device == src.device and table.dtype == torch.int64 and table.is_contiguous() and table.dim() == 2
+    assert table.shape[1] == 8 and len(mean) == 3 and len(std) == 3
+    R = table.shape[0]
+    out = torch.empty(R, 3, oh, ow, dtype=torch.float32, device=src.device)
+    _lib.call('pseg_image_preprocess_windows', src.data_ptr(), src.numel(), table.data_ptr(), R, int(flag_mask), int(bool(bgr)),
+              *[float(m) for m in mean], *[float(v) for v in std], out.data_ptr(), oh, ow, _stream())
+    return out
+
+
+def seg_decode_windows(prob, groups, B, C, window_hw, stride_hw, table, npix_total, max_hw, lut=None, out=None):
+    """Per-image uint8 masks argmax_c sum_s bilinear(P_s, (H, W)) (pseg_seg_decode_windows), P_s being the unweighted mean
+    of the probability maps of the sliding windows that cover a working-image pixel; first index on ties.  prob: the flat
+    fp32 device tensor softmax_views filled; groups: int64 device tensor [S,B,3] of {float offset, Hs, Ws}, S <=
+    ENSEMBLE_MAX_MAPS, the group of photo b at scale s being [ny*nx, h, w, class_pad(C)] in window order (i*nx + j);
+    window_hw = (h, w), stride_hw = (sy, sx) within window_stride_limits.  table, npix_total, max_hw, lut, out and the
+    result are seg_decode_ensemble's.  A photo with a bad table or group record is not written."""
+    assert prob.is_cuda and prob.dtype == torch.float32 and prob.is_contiguous() and prob.dim() == 1
+    assert groups.device == prob.device and groups.dtype == torch.int64 and groups.is_contiguous()
+    assert groups.dim() == 3 and groups.shape[1:] == (B, 3)
+    assert table.device == prob.device and table.dtype == torch.int64 and table.is_contiguous() and table.shape == (B, 3)
+    nbytes = npix_total * (1 if lut is None else 4)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=prob.device)
+    assert out.device == prob.device and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == nbytes
+    mask, rgb = out[:npix_total], None
+    if lut is not None:
+        assert lut.device == prob.device and lut.dtype == torch.uint8 and lut.is_contiguous() and lut.shape == (256, 3)
+        rgb = out[npix_total:].view(npix_total, 3)
+    _lib.call('pseg_seg_decode_windows', prob.data_ptr(), prob.numel(), groups.data_ptr(), groups.shape[0], B, C,
+              int(window_hw[0]), int(window_hw[1]), int(stride_hw[0]), int(stride_hw[1]), table.data_ptr(), npix_total,
+              int(max_hw[0]), int(max_hw[1]), mask.data_ptr(), _ptr(rgb), _ptr(lut), _stream())
+    return mask, rgb
+
+
 REGIONS_TILE = 32       # PSEG_REGIONS_TILE: tile edge of mask_label's LDS union-find (tiles start at the photo's corner)
 REGION_WORDS = 12       # PSEG_REGION_WORDS: int64 per record of mask_regions (layout: include/pseg_amd.h)
 REGIONS_MAX_LARGEST_BATCH = 4096   # PSEG_REGIONS_MAX_LARGEST_BATCH: photos per mask_clean call with largest_only

@@ -116,7 +116,7 @@ class Ensemble:
 
 @torch.no_grad()
 def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=False, colors=None, scales=None, flip=False,
-              min_area=0, connectivity=8, largest_only=False, regions=False):
+              min_area=0, connectivity=8, largest_only=False, regions=False, slide=False, stride=None, window_batch=None):
     """The reference's contract: ``imgs`` is a list of uint8 H x W x 3 photos (numpy arrays, or CPU or device tensors),
     ``img_size`` = (w, h) of the model input as cv2.resize takes it; returns one int64 numpy H x W mask per photo, at
     that photo's own size.  ``bgr=True``: the photos are cv2.imread output (B, G, R).  ``half=True``: the forward runs
@@ -133,7 +133,21 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
     pixels -- with ``largest_only`` also every region of a class >= 1 but its class's largest in the photo -- take the
     class of the region above their first pixel (``connectivity`` 4 or 8); the colours are those of the cleaned mask.
     ``regions=True`` appends one more result: per photo, a list of dicts {class, area, bbox, centroid, angle, sides, label}
-    of the regions of the cleaned mask (utils.regions.region_dicts).  With all four at their defaults none of this runs."""
+    of the regions of the cleaned mask (utils.regions.region_dicts).  With all four at their defaults none of this runs.
+
+    ``slide=True`` turns on sliding-window inference for photos larger than the model input: ``img_size`` is then the
+    WINDOW (both sides multiples of 32), laid over the photo at ``stride`` = (sw, sh) in ``img_size``'s order (between
+    half the window, rounded up, and the window; default ceil(2/3 of the window)) -- ``window_grid``; ``scales`` scale the
+    PHOTO (``work_size``), not the input.  mask = argmax_c of the sum, over the scales, of the bilinearly resized
+    (align_corners=False) working probability, which is the unweighted mean of the softmaxes (with ``flip``: softmax plus
+    un-mirrored softmax of the mirrored window) of the windows covering a working-image pixel.  Windows go through the
+    model at most ``window_batch`` at a time (default: the number of photos).  ``colors``, ``half`` and the region
+    options compose as on the other routes.  Without ``slide`` neither ``stride`` nor ``window_batch`` may be given."""
+    slide = bool(slide)
+    if not slide and (stride is not None or window_batch is not None):
+        raise ValueError('stride and window_batch belong to slide=True')
+    if window_batch is not None and int(window_batch) < 1:
+        raise ValueError('window_batch must be >= 1; got %r' % (window_batch,))
     min_area = int(min_area)
     if min_area < 0:
         raise ValueError('min_area must be >= 0; got %d' % min_area)
@@ -147,8 +161,14 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
     flip = bool(flip)
     if scales is not None:
         scales = tuple(float(s) for s in scales)
-    tta = flip or (scales is not None and scales != (1.0,))
+    tta = not slide and (flip or (scales is not None and scales != (1.0,)))
     sizes = tta_sizes(h, w, scales if scales is not None else (1.0,)) if tta else None
+    if slide:
+        if h < 32 or w < 32 or h % 32 or w % 32:
+            raise ValueError('slide=True takes a window whose sides are multiples of 32; got img_size (%d, %d)' % (w, h))
+        sy, sx = slide_strides(h, w, stride)
+        scales = scales if scales is not None else (1.0,)
+        slide_scales([], scales)                               # the scales alone: finite, > 0, at most 8
     photos = [_photo(im) for im in imgs]
     if not photos:
         empty = ([], []) if colors is not None else []
@@ -157,6 +177,9 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
     if device.type != 'cuda':
         raise RuntimeError('inference() runs on the HIP path: move the model to the GPU first')
     B = len(photos)
+    if slide:
+        return _inference_slide(model, photos, h, w, sy, sx, scales, flip, window_batch, mean, std, bgr, half, colors, device,
+                                post)
     if tta:
         if B * (2 if flip else 1) > 65535:
             raise ValueError('%d photos x %d views exceed 65535 rows per launch' % (B, 2 if flip else 1))
@@ -271,6 +294,145 @@ def _inference_ensemble(model, photos, h, w, view_sizes, flip, mean, std, bgr, h
         records = None
     else:
         ens.decode(ddecode, total_pix, (int(sizes[:, 0].max()), int(sizes[:, 1].max())), None, out=out[:total_pix])
+        records = _postprocess(out, ddecode, total_pix, sizes, lut, post)
+
+    host = torch.empty(out.numel(), dtype=torch.uint8, pin_memory=True)
+    host.copy_(out, non_blocking=True)
+    torch.cuda.current_stream(device).synchronize()
+    hv = host.numpy()
+    masks = [hv[o:o + H * W].reshape(H, W).astype(np.int64) for o, (H, W) in zip(pix_off, sizes)]
+    if colors is None:
+        return _with_regions(masks, records, post, B)
+    rgb = hv[total_pix:]
+    images = [rgb[3 * o:3 * (o + H * W)].reshape(H, W, 3).copy() for o, (H, W) in zip(pix_off, sizes)]
+    return _with_regions((masks, images), records, post, B)
+
+
+def work_size(H, W, s):
+    """(Hs, Ws) of an H x W photo at scale s for sliding-window inference: the photo's own size at 1.0"""
+    return max(1, int(H * s + 0.5)), max(1, int(W * s + 0.5))
+
+
+def window_grid(Hs, Ws, h, w, sy, sx):
+    """The windows of h x w at stride (sy, sx) over a working image of Hs x Ws -> ([(y0, x0), ...] in (i, j) order, (ny,
+    nx)): n = ceil(max(size - window, 0) / stride) + 1 per axis, window i at min(i * stride, max(size - window, 0)) -- the
+    last one is shifted back inside the image, and an image smaller than the window has one window along that axis."""
+    my, mx = max(Hs - h, 0), max(Ws - w, 0)
+    ny, nx = -(-my // sy) + 1, -(-mx // sx) + 1
+    ys, xs = [min(i * sy, my) for i in range(ny)], [min(j * sx, mx) for j in range(nx)]
+    return [(y0, x0) for y0 in ys for x0 in xs], (ny, nx)
+
+
+def slide_strides(h, w, stride=None):
+    """(sy, sx) for windows of h x w: `stride` = (sw, sh) in img_size's order, checked against ops.window_stride_limits;
+    None: the default of that rule"""
+    (ly, hy, dy), (lx, hx, dx) = ops.window_stride_limits(h), ops.window_stride_limits(w)
+    if stride is None:
+        return dy, dx
+    sx, sy = int(stride[0]), int(stride[1])
+    if not (ly <= sy <= hy and lx <= sx <= hx):
+        raise ValueError('stride (%d, %d) outside [%d, %d] x [%d, %d]: between half the window (rounded up) and the window'
+                         % (sx, sy, lx, hx, ly, hy))
+    return sy, sx
+
+
+def slide_scales(photo_sizes, scales):
+    """-> per kept scale the list of (Hs, Ws) of every photo.  Scales must be finite and > 0 and keep every working size
+    within 65535; a scale that gives EVERY photo the working size of an earlier scale is merged with a warning (as
+    tta_sizes does); at most ops.ENSEMBLE_MAX_MAPS scales."""
+    scales = [float(s) for s in scales]
+    if not scales:
+        raise ValueError('scales is empty')
+    kept = []
+    for s in scales:
+        if not math.isfinite(s) or s <= 0:
+            raise ValueError('scales must be finite and > 0; got %r' % (s,))
+        sizes = [work_size(H, W, s) for H, W in photo_sizes]
+        if any(Hs > 65535 or Ws > 65535 for Hs, Ws in sizes):
+            raise ValueError('scale %g takes a photo beyond 65535 pixels along an axis' % s)
+        if sizes and sizes in kept:
+            warnings.warn('scale %g gives every photo the working size of an earlier scale; merged' % s, RuntimeWarning,
+                          stacklevel=3)
+        else:
+            kept.append(sizes)
+    if len(kept) > ops.ENSEMBLE_MAX_MAPS:
+        raise ValueError('%d scales; at most %d scales are ensembled' % (len(kept), ops.ENSEMBLE_MAX_MAPS))
+    return kept
+
+
+def _inference_slide(model, photos, h, w, sy, sx, scales, flip, window_batch, mean, std, bgr, half, colors, device, post=None):
+    """inference(slide=True): the same single staging buffer (now also carrying the window table and the group table) and
+    the same single copy back; per chunk of windows one preprocess launch, one forward, one softmax launch, then ONE
+    decode.  The window table is staged chunk by chunk -- with flip a chunk is [n plain; n mirrored] -- so every chunk's
+    table is a slice of the staged words."""
+    B, V = len(photos), 2 if flip else 1
+    sizes = np.array([(H, W) for _, H, W in photos], dtype=np.int64)
+    npix = sizes[:, 0] * sizes[:, 1]
+    pix_off = np.concatenate([[0], np.cumsum(npix)[:-1]])
+    total_pix = int(npix.sum())
+    work = slide_scales([(int(H), int(W)) for H, W in sizes], scales)
+    S = len(work)
+    rows, groups = [], np.zeros((S, B, 3), dtype=np.int64)       # groups: window offsets, scaled to floats on the device
+    for s in range(S):
+        for b in range(B):
+            Hs, Ws = work[s][b]
+            groups[s, b] = (len(rows) * h * w, Hs, Ws)
+            rows += [(3 * pix_off[b], sizes[b, 0], sizes[b, 1], 0, Hs, Ws, y0, x0)
+                     for y0, x0 in window_grid(Hs, Ws, h, w, sy, sx)[0]]
+    rows = np.array(rows, dtype=np.int64)
+    N = len(rows)
+    step = min(max(1, int(window_batch) if window_batch is not None else B), 65535 // V)
+    chunks = [(a, min(a + step, N)) for a in range(0, N, step)]
+    staged = []
+    for a, e in chunks:
+        staged.append(rows[a:e])
+        if flip:
+            twin = rows[a:e].copy()
+            twin[:, 3] = ops.VIEW_MIRROR
+            staged.append(twin)
+    windows = np.concatenate(staged)
+    decode = np.zeros((B, 3), dtype=np.int64)
+    decode[:, 0], decode[:, 1], decode[:, 2] = pix_off, sizes[:, 0], sizes[:, 1]
+    heads = [windows.reshape(-1), decode.reshape(-1), groups.reshape(-1)]
+    head = 8 * sum(t.size for t in heads)
+
+    staging = torch.empty(head + 3 * total_pix, dtype=torch.uint8, pin_memory=True)
+    sv = staging.numpy()
+    sv[:head] = np.concatenate(heads).view(np.uint8)
+    for (img, _, _), o in zip(photos, pix_off):
+        if isinstance(img, np.ndarray):
+            sv[head + 3 * o:head + 3 * (o + img.shape[0] * img.shape[1])] = np.ascontiguousarray(img).reshape(-1)
+    dbuf = staging.to(device, non_blocking=True)
+    for (img, _, _), o in zip(photos, pix_off):
+        if isinstance(img, torch.Tensor):
+            dbuf[head + 3 * o:head + 3 * (o + img.shape[0] * img.shape[1])].copy_(img.to(device).reshape(-1))
+    words = dbuf[:head].view(torch.int64)
+    dwindows = words[:windows.size].view(V * N, 8)
+    ddecode = words[windows.size:windows.size + decode.size].view(B, 3)
+    dgroups = words[windows.size + decode.size:].view(S, B, 3)
+
+    prob = C = None
+    for a, e in chunks:
+        x = ops.image_preprocess_windows(dbuf[head:], dwindows[V * a:V * e], h, w, mean, std, bgr)
+        logits = _forward(model, x, half)
+        del x
+        if logits.shape[2:] != (h, w):
+            raise RuntimeError('the model returns %dx%d logits for a %dx%d window' % (tuple(logits.shape[2:]) + (h, w)))
+        if prob is None:
+            C = logits.shape[1]
+            CP = ops.class_pad(C)
+            prob = torch.empty(N * h * w * CP, dtype=torch.float32, device=device)
+            dgroups[:, :, 0] *= CP                             # device arithmetic on S * B numbers: no host round trip
+        ops.softmax_views(logits.contiguous(), prob, a * h * w * CP, flip)
+        del logits                                             # released before the next chunk's forward
+    lut = None if colors is None else torch.from_numpy(lut_of(colors)).to(device)
+    out = torch.empty(total_pix * (1 if lut is None else 4), dtype=torch.uint8, device=device)
+    max_hw = (int(sizes[:, 0].max()), int(sizes[:, 1].max()))
+    if post is None:
+        ops.seg_decode_windows(prob, dgroups, B, C, (h, w), (sy, sx), ddecode, total_pix, max_hw, lut, out=out)
+        records = None
+    else:
+        ops.seg_decode_windows(prob, dgroups, B, C, (h, w), (sy, sx), ddecode, total_pix, max_hw, None, out=out[:total_pix])
         records = _postprocess(out, ddecode, total_pix, sizes, lut, post)
 
     host = torch.empty(out.numel(), dtype=torch.uint8, pin_memory=True)

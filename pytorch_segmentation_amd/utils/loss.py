@@ -258,6 +258,53 @@ def predict_mask_ensemble(model, inputs, out_hw, scales=(1.0,), flip=False, view
     return mask.view(B, oh, ow).long()
 
 
+@torch.no_grad()
+def predict_mask_windows(model, inputs, out_hw, window_hw, stride_hw=None, scales=(1.0,), flip=False):
+    """Sliding-window prediction for an already normalised device batch [B,3,H,W]: int64 [B,out_h,out_w] = argmax_c of the
+    sum, over the scales, of the bilinearly resized (align_corners=False) working probability -- the unweighted mean of the
+    softmaxes (with ``flip``: plus the un-mirrored softmax of the mirrored window) of the windows covering a pixel of the
+    working image; first index on ties.  The working image at scale s is ``inputs`` resized (F.interpolate bilinear,
+    align_corners=False; the identity at 1.0) to ``work_size(H, W, s)``; the windows of ``window_hw`` = (h, w) at
+    ``stride_hw`` = (sy, sx) (default: 2/3 of the window, ``window_grid``) are slices of it, zero-padded where it is
+    smaller than the window; one forward per scale and image.  The softmaxes and the decode are ops.softmax_views /
+    ops.seg_decode_windows."""
+    import torch.nn.functional as F
+    from .inference import slide_scales, slide_strides, window_grid
+    if not inputs.is_cuda:
+        raise RuntimeError('predict_mask_windows runs on the HIP path only (got %s)' % inputs.device)
+    B, _, H, W = inputs.shape
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    h, w = int(window_hw[0]), int(window_hw[1])
+    sy, sx = slide_strides(h, w, None if stride_hw is None else (stride_hw[1], stride_hw[0]))
+    work = slide_scales([(H, W)] * B, scales)
+    grids = [window_grid(sizes[0][0], sizes[0][1], h, w, sy, sx)[0] for sizes in work]
+    if max(len(g) for g in grids) * (2 if flip else 1) > 65535:
+        raise ValueError('more than 65535 window rows per forward')
+    prob, CP, done, groups = None, None, 0, []
+    for sizes, grid in zip(work, grids):
+        Hs, Ws = sizes[0]
+        x = inputs if (Hs, Ws) == (H, W) else F.interpolate(inputs, (Hs, Ws), mode='bilinear', align_corners=False)
+        if Hs < h or Ws < w:
+            x = F.pad(x, (0, max(w - Ws, 0), 0, max(h - Hs, 0)))
+        for b in range(B):
+            wins = torch.stack([x[b, :, y0:y0 + h, x0:x0 + w] for y0, x0 in grid])
+            if flip:
+                wins = torch.cat([wins, torch.flip(wins, [3])], 0)
+            logits = model(wins.contiguous()).float()
+            if prob is None:
+                CP = ops.class_pad(logits.shape[1])
+                prob = torch.empty(sum(len(g) for g in grids) * B * h * w * CP, dtype=torch.float32, device=inputs.device)
+            groups.append([done * h * w * CP, Hs, Ws])
+            ops.softmax_views(logits.contiguous(), prob, done * h * w * CP, flip)
+            done += len(grid)
+            C = logits.shape[1]
+            del logits, wins
+    dgroups = torch.tensor(groups, dtype=torch.int64).view(len(work), B, 3).to(inputs.device)
+    table = torch.tensor([[b * oh * ow, oh, ow] for b in range(B)], dtype=torch.int64).to(inputs.device)
+    mask, _ = ops.seg_decode_windows(prob, dgroups, B, C, (h, w), (sy, sx), table, B * oh * ow, (oh, ow))
+    return mask.view(B, oh, ow).long()
+
+
 def update_class_counts(counters, predicted, targets):
     """Accumulate per-class tp / fn / fp (reference test.py:34-46) into the int64 device tensor counters[3][C]
     with one kernel instead of 3*C host synchronisations."""

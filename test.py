@@ -3,6 +3,7 @@
 
     python3 test.py data/<custom>/val.json --weights weights/best.pt [-s W H] [-bs N] [--model deeplabv3plus|unet]
                     [--scales S [S ...]] [--flip] [--min-area N] [--connectivity {4,8}] [--largest-only]
+                    [--window W H [--stride SW SH]]
 
 `test(model, fetcher)` keeps the reference's contract: evaluates in eval mode without gradients, prints per-class
 (or the five worst classes') targets / precision / recall / IoU / F1 and returns the mean IoU.  The per-class
@@ -11,7 +12,9 @@ distributed reduction is a single [3, num_classes] all-reduce.  With --scales / 
 test-time ensemble (utils.predict_mask_ensemble: summed class probabilities of every scale and mirrored view at the target
 size); the printed loss stays that of the plain forward.  With --min-area / --largest-only the counted prediction is the
 cleaned mask (utils/regions.py: small connected regions dropped) of either route, so the effect of a threshold on the mIoU
-can be read off; the loss again stays as it is.
+can be read off; the loss again stays as it is.  With --window W H the counted prediction is the sliding-window one
+(utils.predict_mask_windows: W x H windows at --stride over the images -s delivers, the probabilities of the windows covering
+a pixel averaged; --scales then scale the image, --flip adds every window's mirrored twin).
 """
 import argparse
 
@@ -20,15 +23,17 @@ from torch.utils.data import DataLoader
 
 from pytorch_segmentation_amd.models import DeepLabV3Plus, HRNet, UNet
 from pytorch_segmentation_amd.utils import (Fetcher, all_reduce_counters, broadcast_buffers, compute_loss, compute_metrics,
-                                            predict_mask, predict_mask_ensemble, update_class_counts)
+                                            predict_mask, predict_mask_ensemble, predict_mask_windows, update_class_counts)
 from pytorch_segmentation_amd.utils.datasets import CocoDataset
 
 MODELS = {'deeplabv3plus': DeepLabV3Plus, 'unet': UNet, 'hrnet': HRNet}
 
 
 @torch.no_grad()
-def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, largest_only=False):
+def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, largest_only=False, window=None, stride=None):
     model.eval()
+    if window is None and stride is not None:
+        raise ValueError('stride belongs to window=')
     if min_area < 0:
         raise ValueError('min_area must be >= 0; got %d' % min_area)
     if connectivity not in (4, 8):
@@ -46,7 +51,11 @@ def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, la
     counters = None
     loss_sum, batches = None, 0
     for inputs, targets in fetcher:
-        if tta:
+        if window is not None:                                 # sliding windows of (w, h) over the delivered batch
+            predicted = predict_mask_windows(model, inputs, targets.shape[1:], (window[1], window[0]),
+                                             None if stride is None else (stride[1], stride[0]), scales, flip)
+            outputs = model(inputs)                            # the loss stays that of the plain forward
+        elif tta:
             view_logits = {}
             predicted = predict_mask_ensemble(model, inputs, targets.shape[1:], scales, flip, view_logits)
             # the loss of the plain forward: the scale-1.0 unmirrored view, or one extra forward without scale 1.0
@@ -84,7 +93,7 @@ def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, la
     return miou.mean().item()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('val', type=str)
     ap.add_argument('--weights', type=str, default='')
@@ -100,9 +109,21 @@ def main():
                     help='evaluate the masks with connected regions of fewer than N pixels dropped')
     ap.add_argument('--connectivity', type=int, choices=[4, 8], default=8, help='neighbours that connect a region')
     ap.add_argument('--largest-only', action='store_true', help='keep only the largest region of every class >= 1')
-    opt = ap.parse_args()
+    ap.add_argument('--window', type=int, nargs=2, default=None, metavar=('W', 'H'),
+                    help='sliding-window evaluation: W x H windows over the images the loader delivers (-s); --scales then '
+                         'scale the image')
+    ap.add_argument('--stride', type=int, nargs=2, default=None, metavar=('SW', 'SH'),
+                    help='with --window: the window stride, between half the window and the window (default: 2/3 of it)')
+    opt = ap.parse_args(argv)
     if opt.min_area < 0:
         ap.error('--min-area must be >= 0')
+    if opt.stride is not None and opt.window is None:
+        ap.error('--stride needs --window')
+    return opt
+
+
+def main(argv=None):
+    opt = parse_args(argv)
     data = CocoDataset(opt.val, img_size=opt.img_size, augments=None, rect=opt.rect)
     loader = DataLoader(data, batch_size=opt.batch_size, pin_memory=True, num_workers=opt.num_workers)
     fetcher = Fetcher(loader, post_fetch_fn=data.post_fetch_fn)
@@ -110,7 +131,7 @@ def main():
     if opt.weights:
         model.load_state_dict(torch.load(opt.weights, map_location='cpu')['model'])
     print('metrics: %8g' % test(model.cuda(), fetcher, opt.scales, opt.flip, opt.min_area, opt.connectivity,
-                                  opt.largest_only))
+                                  opt.largest_only, opt.window, opt.stride))
 
 
 if __name__ == '__main__':
