@@ -427,8 +427,9 @@ int pseg_ce_fwd_bwd(const float* logits, const int64_t* target, int B, int C, in
 /* The same loss on bilinearly up-sampled logits WITHOUT the full-resolution tensor (models/deeplabv3plus.py:40-43 +
  * utils/utils.py:18-21): logits_lr is the fp32 NHWC [B,h,w] x ld tensor of class logits (C <= 24 classes in the first
  * channels, ld % 4 == 0), target the [B,H,W] labels; the loss is CE(interpolate(logits, (H, W), 'bilinear', align_corners),
- * target) and dlogits_lr ([B,h,w] x ldd, nullable) receives its gradient with respect to the LOW-resolution logits
- * (channels [C, ldd) are written as 0).  Deterministic (no floating-point atomics).  pseg_ce_upsampled_ok(...) != 0 says
+ * target) and dlogits_lr ([B,h,w] x ldd, nullable; ldd >= C, ldd % 4 == 0, 16-byte aligned: it is written 16 bytes at a
+ * time) receives its gradient with respect to the LOW-resolution logits (channels [C, ldd) are written as 0, also past the 24
+ * the kernels compute in).  loss_out as for pseg_ce_fwd_bwd; with no valid pixel the loss is NaN and the gradient 0.  Deterministic (no floating-point atomics).  pseg_ce_upsampled_ok(...) != 0 says
  * whether the scale factors are covered (about x4 or less per axis); otherwise use pseg_bilinear_fwd + pseg_ce_fwd_bwd +
  * pseg_bilinear_bwd. */
 int pseg_ce_upsampled_ok(int h, int w, int C, int H, int W, int align_corners);
@@ -841,6 +842,17 @@ int pseg_debug_last_gather(int* out13);
  * Zeros before the thread's first such launch; a refused call leaves it alone.  Host-side integer stores next to the launch, no
  * device work.  Additive: PSEG_ABI_VERSION does not move. */
 int pseg_debug_last_norm(int* out12);
+/* ... and the calling thread's last loss / mask / metric launch (csrc/loss.hip: pseg_ce_fwd_bwd, pseg_ce_upsampled_fwd_bwd,
+ * pseg_argmax, pseg_confusion, pseg_scale_inplace): out8 = {kernel, CMAX = the compile-time class bound (4 | 8 | 24 | 32 on
+ * ce_fused_kernel, 24 on the up-sampled kernels, 0 elsewhere), VEC = consecutive pixels (elements, for scale_inplace) per lane,
+ * grid x, block x, form of the up-sampled loss (0 none, 1 gather: ce_up_fused_kernel, 2 scatter: ce_up_scatter_kernel +
+ * ce_up_combine_kernel), per-block partials handed to the finish kernel (ce_finish_kernel; ce_up_finish_kernel behind the
+ * scatter form; 0 where none runs), 1 when a gradient was asked for (dlogits / dlogits_lr not NULL)}.
+ *   kernel: 1 ce_fused_kernel, 2 ce_generic_kernel, 3 ce_up_fused_kernel, 4 ce_up_scatter_kernel, 5 argmax_kernel,
+ *   6 confusion_kernel, 7 scale_inplace_kernel.
+ * Zeros before the thread's first such launch; a refused call leaves it alone.  Host-side integer stores next to the launch, from
+ * the variables the launch takes; no device work.  Additive: PSEG_ABI_VERSION does not move. */
+int pseg_debug_last_loss(int* out8);
 int pseg_conv2d_gather_choice(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil,
                               int dgrad, int precision, int stats, int bias, int planes, int bns, int accumulate, int* out13);
 

@@ -430,13 +430,15 @@ __global__ __launch_bounds__(kUpThreads) void ce_up_fused_kernel(const float* __
       const int r0 = s_rng[0][ii], r1 = s_rng[1][ii];
       for (int r = r0; r <= r1; ++r) acc += s_wy[r][ii] * *reinterpret_cast<const f32x4*>(&s_gx[(r * kUpRX + jj) * kUpCP + c4 * 4]);
       float* dp = dL + ((long long)(b * h + i) * w + j) * ldd + c4 * 4;
-      if (c4 * 4 + 3 < ldd) {
-        *reinterpret_cast<f32x4*>(dp) = acc;
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (c4 * 4 + k < ldd) dp[k] = acc[k];
-      }
+      if (c4 * 4 < ldd) *reinterpret_cast<f32x4*>(dp) = acc;     // (ldd % 4 == 0, host-checked; lanes at or past C hold 0)
+    }
+    // channels [kUpCP, ldd) of the tile's pixels: written as 0 (pseg_amd.h); no iterations at ldd <= kUpCP
+    const int pad4 = ldd > kUpCP ? (ldd - kUpCP) / 4 : 0;
+    for (int o = tid; o < kUpTY * kUpTX * pad4; o += kUpThreads) {
+      const int c4 = o % pad4, px = o / pad4;
+      const int i = i0 + px / kUpTX, j = j0 + px % kUpTX;
+      if (i >= h || j >= w) continue;
+      *reinterpret_cast<f32x4*>(dL + ((long long)(b * h + i) * w + j) * ldd + kUpCP + c4 * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
     }
   }
   lsum = wave_sum_d(lsum);
@@ -760,14 +762,13 @@ __global__ __launch_bounds__(256) void ce_up_combine_kernel(const float* __restr
     if (li == 0 && ti > 0 && lj == 0 && tj > 0) acc += entry(ti - 1, tj - 1, kSY, kSX);
     acc *= inv_n;
     float* dp = dL + ((long long)(b * h + i) * w + j) * ldd + c4 * 4;
-    if (c4 * 4 + 3 < ldd) {
-      *reinterpret_cast<f32x4*>(dp) = acc;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (c4 * 4 + k < ldd) dp[k] = acc[k];
-    }
+    if (c4 * 4 < ldd) *reinterpret_cast<f32x4*>(dp) = acc;     // (ldd % 4 == 0, host-checked; lanes at or past C hold 0)
   }
+  // channels [kUpCP, ldd): written as 0 (pseg_amd.h); no iterations at ldd <= kUpCP
+  const int pad4 = ldd > kUpCP ? (ldd - kUpCP) / 4 : 0;
+  const long long pad_total = (long long)B * h * w * pad4;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < pad_total; e += (long long)gridDim.x * 256)
+    *reinterpret_cast<f32x4*>(dL + (e / pad4) * ldd + kUpCP + (int)(e % pad4) * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
 template <int VEC>
@@ -824,11 +825,30 @@ static int capped_blocks(long long work_items, int cap) {
 
 constexpr int kCeMaxBlocks = 4096;
 
+// The record of the calling thread's last launch from this file (pseg_debug_last_loss; layout: pseg_amd.h): which kernel, in
+// which instantiation and launch shape, which form of the up-sampled loss, how many partials its finish kernel was handed.  A few
+// integer stores beside the launch, from the variables the launch itself takes; nothing reads it back.
+constexpr int kLossRecord = 8;
+enum LossKernel { kLossCeFused = 1, kLossCeGeneric, kLossCeUpFused, kLossCeUpScatter, kLossArgmax, kLossConfusion, kLossScaleInplace };
+static thread_local int g_last_loss[kLossRecord] = {};
+
+static void loss_record(int kernel, int cmax, int vec, dim3 grid, dim3 block, int form, const void* dlogits) {
+  const int rec[kLossRecord] = {kernel, cmax, vec, (int)grid.x, (int)block.x, form, 0, dlogits != nullptr ? 1 : 0};
+  for (int i = 0; i < kLossRecord; ++i) g_last_loss[i] = rec[i];
+}
+static void loss_record_finish(int nblocks) { g_last_loss[6] = nblocks; }
+
 }  // namespace pseg
 
 using namespace pseg;
 
 extern "C" {
+
+int pseg_debug_last_loss(int* out8) {
+  PSEG_REQUIRE(out8 != nullptr, "debug_last_loss: null pointer");
+  for (int i = 0; i < kLossRecord; ++i) out8[i] = g_last_loss[i];
+  return PSEG_OK;
+}
 
 int64_t pseg_ce_workspace_bytes(int64_t npix) {
   (void)npix;
@@ -858,8 +878,10 @@ int pseg_ce_fwd_bwd(const float* logits, const int64_t* target, int B, int C, in
   do {                                                                                                             \
     const long long groups = npix / VEC;                                                                           \
     blocks = capped_blocks(groups, kCeMaxBlocks);                                                                  \
-    hipLaunchKernelGGL((ce_fused_kernel<CMAX, VEC>), dim3(blocks), dim3(256), 0, st, logits, target, C,            \
+    const dim3 grid(blocks), block(256);                                                                           \
+    hipLaunchKernelGGL((ce_fused_kernel<CMAX, VEC>), grid, block, 0, st, logits, target, C,                        \
                        (long long)HW, groups, (long long)ignore_index, dlogits, (const CeHeader*)hdr, partial);    \
+    loss_record(kLossCeFused, CMAX, VEC, grid, block, 0, dlogits);                                                 \
   } while (0)
   if (C <= 4 && vec4) CE_LAUNCH(4, 4);
   else if (C <= 4) CE_LAUNCH(4, 1);
@@ -871,13 +893,16 @@ int pseg_ce_fwd_bwd(const float* logits, const int64_t* target, int B, int C, in
   else if (C <= 32) CE_LAUNCH(32, 1);
   else {
     blocks = capped_blocks(npix, kCeMaxBlocks);
-    hipLaunchKernelGGL(ce_generic_kernel, dim3(blocks), dim3(256), 0, st, logits, target, C, (long long)HW, npix,
+    const dim3 grid(blocks), block(256);
+    hipLaunchKernelGGL(ce_generic_kernel, grid, block, 0, st, logits, target, C, (long long)HW, npix,
                        (long long)ignore_index, dlogits, (const CeHeader*)hdr, partial);
+    loss_record(kLossCeGeneric, 0, 1, grid, block, 0, dlogits);
   }
 #undef CE_LAUNCH
   PSEG_LAUNCH_CHECK();
   hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)partial, blocks, (const CeHeader*)hdr,
                      loss_out);
+  loss_record_finish(blocks);
   PSEG_LAUNCH_CHECK();
   return PSEG_OK;
 }
@@ -922,7 +947,8 @@ int pseg_ce_upsampled_fwd_bwd(const float* logits_lr, int ld, int B, int h, int 
                "pseg_bilinear_fwd + pseg_ce_fwd_bwd): h=%d w=%d C=%d H=%d W=%d", h, w, C, H, W);
   PSEG_REQUIRE(ld % 4 == 0 && ld >= C && ((uintptr_t)logits_lr & 15) == 0, "ce_upsampled: logits need ld %% 4 == 0, ld >= C, "
                "16-byte alignment");
-  PSEG_REQUIRE(!dlogits_lr || ldd >= C, "ce_upsampled: ldd < C");
+  PSEG_REQUIRE(!dlogits_lr || (ldd >= C && ldd % 4 == 0 && ((uintptr_t)dlogits_lr & 15) == 0),
+               "ce_upsampled: dlogits_lr needs ldd >= C, ldd %% 4 == 0, 16-byte alignment (ldd = %d)", ldd);
   PSEG_REQUIRE(workspace_bytes >= pseg_ce_upsampled_workspace_bytes(B, h, w) && ((uintptr_t)workspace & 15) == 0,
                "ce_upsampled: workspace too small / misaligned");
   hipStream_t st = (hipStream_t)stream;
@@ -962,10 +988,13 @@ int pseg_ce_upsampled_fwd_bwd(const float* logits_lr, int ld, int B, int h, int 
     tiles_x = cdiv(w, kSX);
     blocks = (long long)B * tiles_y * tiles_x;
     float* patches = dlogits_lr ? (float*)((char*)workspace + ce_up_partial_bytes(B, h, w)) : nullptr;
-    hipLaunchKernelGGL(ce_up_scatter_kernel, dim3((unsigned)blocks), dim3(kSThreads), 0, st, logits_lr, ld, B, C, target, ay, ax,
+    const dim3 grid((unsigned)blocks), block(kSThreads);
+    hipLaunchKernelGGL(ce_up_scatter_kernel, grid, block, 0, st, logits_lr, ld, B, C, target, ay, ax,
                        (long long)ignore_index, patches, partial, tiles_y, tiles_x);
+    loss_record(kLossCeUpScatter, kUpCP, 1, grid, block, 2, dlogits_lr);
     PSEG_LAUNCH_CHECK();
     hipLaunchKernelGGL(ce_up_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)partial, (int)blocks, hdr, loss_out);
+    loss_record_finish((int)blocks);
     PSEG_LAUNCH_CHECK();
     if (dlogits_lr) {
       const long long total = (long long)B * h * w * (kUpCP / 4);
@@ -982,11 +1011,14 @@ int pseg_ce_upsampled_fwd_bwd(const float* logits_lr, int ld, int B, int h, int 
   hipLaunchKernelGGL(ce_count_kernel, dim3(capped_blocks(npix, 2048)), dim3(256), 0, st, target, npix,
                      (long long)ignore_index, C, hdr);
   PSEG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ce_up_fused_kernel, dim3((unsigned)blocks), dim3(kUpThreads), 0, st, logits_lr, ld, B, C, target, ay, ax,
+  const dim3 grid((unsigned)blocks), block(kUpThreads);
+  hipLaunchKernelGGL(ce_up_fused_kernel, grid, block, 0, st, logits_lr, ld, B, C, target, ay, ax,
                      (long long)ignore_index, dlogits_lr, ldd, (const CeHeader*)hdr, partial, tiles_y, tiles_x);
+  loss_record(kLossCeUpFused, kUpCP, 1, grid, block, 1, dlogits_lr);
   PSEG_LAUNCH_CHECK();
   hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)partial, (int)blocks, (const CeHeader*)hdr,
                      loss_out);
+  loss_record_finish((int)blocks);
   PSEG_LAUNCH_CHECK();
   return PSEG_OK;
 }
@@ -994,8 +1026,9 @@ int pseg_ce_upsampled_fwd_bwd(const float* logits_lr, int ld, int B, int h, int 
 int pseg_scale_inplace(float* x, int64_t n, const float* gscale, void* stream) {
   PSEG_REQUIRE(x && gscale && n > 0 && ((uintptr_t)x & 15) == 0, "scale_inplace: bad argument");
   const long long n4 = n / 4;
-  hipLaunchKernelGGL(scale_inplace_kernel, dim3(capped_blocks(n4 ? n4 : 1, 2048)), dim3(256), 0, (hipStream_t)stream, x,
-                     n4, (long long)n, gscale);
+  const dim3 grid(capped_blocks(n4 ? n4 : 1, 2048)), block(256);
+  hipLaunchKernelGGL(scale_inplace_kernel, grid, block, 0, (hipStream_t)stream, x, n4, (long long)n, gscale);
+  loss_record(kLossScaleInplace, 0, 4, grid, block, 0, nullptr);
   PSEG_LAUNCH_CHECK();
   return PSEG_OK;
 }
@@ -1003,12 +1036,15 @@ int pseg_scale_inplace(float* x, int64_t n, const float* gscale, void* stream) {
 int pseg_argmax(const float* logits, int B, int C, int64_t HW, int64_t* mask, void* stream) {
   PSEG_REQUIRE(logits && mask && B > 0 && C > 0 && HW > 0, "argmax: bad argument");
   const long long npix = (long long)B * HW;
+  const dim3 block(256);
   if (HW % 4 == 0 && ((uintptr_t)logits & 15) == 0) {
-    hipLaunchKernelGGL(argmax_kernel<4>, dim3(capped_blocks(npix / 4, 4096)), dim3(256), 0, (hipStream_t)stream, logits, C,
-                       (long long)HW, npix / 4, mask);
+    const dim3 grid(capped_blocks(npix / 4, 4096));
+    hipLaunchKernelGGL(argmax_kernel<4>, grid, block, 0, (hipStream_t)stream, logits, C, (long long)HW, npix / 4, mask);
+    loss_record(kLossArgmax, 0, 4, grid, block, 0, nullptr);
   } else {
-    hipLaunchKernelGGL(argmax_kernel<1>, dim3(capped_blocks(npix, 4096)), dim3(256), 0, (hipStream_t)stream, logits, C,
-                       (long long)HW, npix, mask);
+    const dim3 grid(capped_blocks(npix, 4096));
+    hipLaunchKernelGGL(argmax_kernel<1>, grid, block, 0, (hipStream_t)stream, logits, C, (long long)HW, npix, mask);
+    loss_record(kLossArgmax, 0, 1, grid, block, 0, nullptr);
   }
   PSEG_LAUNCH_CHECK();
   return PSEG_OK;
@@ -1017,8 +1053,10 @@ int pseg_argmax(const float* logits, int B, int C, int64_t HW, int64_t* mask, vo
 int pseg_confusion(const int64_t* pred, const int64_t* target, int64_t n, int C, int64_t* counters, void* stream) {
   PSEG_REQUIRE(pred && target && counters && n > 0, "confusion: bad argument");
   PSEG_REQUIRE(C > 0 && C <= kMaxConfusionClasses, "confusion: class count must be in [1, %d]", kMaxConfusionClasses);
-  hipLaunchKernelGGL(confusion_kernel, dim3(capped_blocks(n, 1024)), dim3(256), 0, (hipStream_t)stream, pred, target,
-                     (long long)n, C, (unsigned long long*)counters);
+  const dim3 grid(capped_blocks(n, 1024)), block(256);
+  hipLaunchKernelGGL(confusion_kernel, grid, block, 0, (hipStream_t)stream, pred, target, (long long)n, C,
+                     (unsigned long long*)counters);
+  loss_record(kLossConfusion, 0, 1, grid, block, 0, nullptr);
   PSEG_LAUNCH_CHECK();
   return PSEG_OK;
 }

@@ -22,7 +22,7 @@ def test_header_prototypes_all_exported(lib):
     assert 'pseg_debug_last_conv_kernel' in protos and 'pseg_debug_last_gather_h' in protos
     assert {'pseg_debug_last_wgrad', 'pseg_conv2d_wgrad_choice', 'pseg_conv2d_wgrad_choice_h'} <= set(protos)
     assert {'pseg_debug_last_gather', 'pseg_conv2d_gather_choice'} <= set(protos)
-    assert 'pseg_debug_last_norm' in protos
+    assert 'pseg_debug_last_norm' in protos and 'pseg_debug_last_loss' in protos
     for name in protos:
         assert hasattr(lib, name), name
     out = subprocess.check_output(['nm', '-D', '--defined-only', _lib.LIB_PATH]).decode()
@@ -46,6 +46,9 @@ def test_abi_version_and_error_string(lib):
     # ... and of the BatchNorm / activation launches
     rec = (ctypes.c_int * 12)(*[7] * 12)
     assert lib.pseg_debug_last_norm(rec) == 0 and list(rec) == [0] * 12
+    # ... and of the loss / mask / metric launches
+    rec = (ctypes.c_int * 8)(*[7] * 8)
+    assert lib.pseg_debug_last_loss(rec) == 0 and list(rec) == [0] * 8
 
 
 def test_plan_queries_are_consistent(lib):

@@ -1164,6 +1164,18 @@ def test_cross_entropy_on_upsampled_logits(ops, B, C, h, w, scale, ac, form, mon
     lr = to_act(ops, x, 24)
     assert ops.ce_upsampled_ok(lr, C, H, W, ac)
     out, dlr = ops.ce_upsampled_fwd_bwd(lr, C, t.cuda(), ac)
+    # the form that ran (pseg_debug_last_loss) is the one the host rule gives (tests/loss_cases.py).  `scatter` asks for the scatter
+    # kernel; [scatter-2-21-16-16-4-False] still runs the GATHER kernel: at x4 with align_corners=False the first tile owns 6 + 4
+    # destination rows, + 2 of slack = 12 > the 10 its LDS image holds (tests/test_loss_instances_gpu.py runs the scatter form with
+    # align_corners=False at x3)
+    import ctypes
+    import loss_cases as lc
+    from pytorch_segmentation_amd import _lib
+    rec = (ctypes.c_int * 8)()
+    assert _lib.load().pseg_debug_last_loss(rec) == 0
+    want_form = lc.up_form(h, w, H, W, int(ac), '1' if form == 'scatter' else '0')
+    assert rec[5] == want_form, 'meant to test %s, ran %s' % (lc.FORM_NAMES[want_form], lc.FORM_NAMES[rec[5]])
+    assert want_form == (lc.SCATTER if form == 'scatter' and ac else lc.GATHER)
     out2, dlr2 = ops.ce_upsampled_fwd_bwd(lr, C, t.cuda(), ac)
     assert torch.equal(out, out2) and torch.equal(dlr.t, dlr2.t)
     # (1) float64 autograd
