@@ -61,7 +61,8 @@ extern "C" {
 /* bumped whenever an existing prototype changes incompatibly; pseg_abi_version() returns the value the library was built with.
  * Entry points added since 14 (pseg_image_preprocess_views, pseg_softmax_views, pseg_seg_decode_ensemble, the
  * connected-region calls pseg_regions_workspace_bytes, pseg_mask_label, pseg_mask_regions, pseg_mask_clean, and the
- * sliding-window calls pseg_image_preprocess_windows, pseg_seg_decode_windows) are purely
+ * sliding-window calls pseg_image_preprocess_windows, pseg_seg_decode_windows, and the grouped optimiser calls
+ * pseg_grad_sumsq_workspace_bytes, pseg_grad_sumsq, pseg_opt_step_sgd, pseg_opt_step_adam) are purely
  * additive and do not bump it: the loader checks every declared prototype against the library's exports by name. */
 #define PSEG_ABI_VERSION 14
 int pseg_abi_version(void);
@@ -762,6 +763,53 @@ int pseg_adam_step(float* param, const float* grad, float* exp_avg, float* exp_a
                    float beta1, float beta2, float eps, float weight_decay, int decoupled, float grad_scale,
                    int step, void* stream);
 int pseg_fill(float* x, int64_t n, float value, void* stream);
+
+/* ---- grouped step: per-run learning-rate factor and weight decay, global-norm clipping, weight EMA (csrc/optim_groups.hip).
+ * Additive: PSEG_ABI_VERSION does not move.
+ *
+ * A RUN is a contiguous range of the arena whose floats share their hyper-parameters.  The table is an array of
+ * pseg_opt_run_t, ascending and disjoint, offset and count multiples of 4 (arena segments are: no 16-byte access straddles
+ * a run and there is no scalar tail).  first_block is the index of the run's first 256-thread block; the run owns the blocks
+ * up to the next run's first_block (the last one up to total_blocks), at least 1 and at most ceil(count / PSEG_OPT_RUN_SPAN):
+ * a block covers PSEG_OPT_RUN_SPAN floats per trip and strides by its run's block count.  `runs` is the table in DEVICE memory
+ * (what the kernel reads), `runs_host` the same table in HOST memory: every launch validates the host copy against n and
+ * total_blocks before anything is enqueued.
+ *
+ * pseg_grad_sumsq: clip_state[0] = (float)sqrt(sum of grad[i]^2), squares and sums in fp64, one partial per block into
+ *   `workspace` (pseg_grad_sumsq_workspace_bytes(n) bytes, at most 8 * PSEG_GRAD_SUMSQ_MAX_PARTIALS; 8-byte aligned), folded by a
+ *   second single-block launch in a fixed order.  The grid depends on n only, there is no atomic: bit-reproducible from call
+ *   to call.  n is a multiple of 4.
+ * pseg_opt_step_sgd / pseg_opt_step_adam, per element of run r, in the arithmetic of pseg_sgd_step / pseg_adam_step:
+ *     d = g * (gscale_eff * coef);  weight decay wd_r, coupled (d += wd_r * w) or `decoupled` (w *= 1 - lr_r * wd_r);
+ *     momentum / Nesterov, or the Adam moments;  w -= lr_r * d  (Adam: step_size = lr_r / bias_correction1),  lr_r = lr * lr_mult_r;
+ *     ema (nullable):  e = ema_decay * e + (1 - ema_decay) * w_new.
+ *   gscale_eff = grad_scale, times mp_state[1] when mp_state (nullable: the 8-float `-mp` state above) is given.
+ *   coef = 1 when max_norm == 0, else min(1, max_norm / (clip_state[0] * |gscale_eff| + 1e-6)) -- torch's clip_grad_norm_ with
+ *   error_if_nonfinite=False -- derived by every thread from the device state; one thread records clip_state[1] = coef,
+ *   clip_state[2] = clip_state[0] * |gscale_eff| (the norm of the unscaled gradients) and adds 1 to clip_state[3] when coef < 1.
+ *   clip_state: 4 floats on the device, required when max_norm > 0.
+ *   With mp_state: a raised found-inf flag (mp_state[3]) returns before anything is written -- parameters, moments, EMA and
+ *   clip_state[1..3] stay as they were; first step / bias corrections come from mp_state[4] (first_step / step are ignored).
+ *   Without it they come from the host: first_step as in pseg_sgd_step, step >= 1 as in pseg_adam_step (bias corrections in double).
+ *   A one-run table with lr_mult = 1, max_norm = 0 and ema = NULL reproduces pseg_sgd_step, pseg_sgd_step_mp, pseg_adam_step
+ *   and pseg_adam_step_mp bit for bit.  Refused with a message naming the check: null / misaligned (16 bytes) pointers, a
+ *   table that breaks a rule above, ema_decay outside [0, 1), max_norm < 0. */
+#define PSEG_OPT_RUN_SPAN 1024
+#define PSEG_GRAD_SUMSQ_MAX_PARTIALS 1024
+typedef struct {
+  int64_t offset, count, first_block;
+  float lr_mult, weight_decay;
+} pseg_opt_run_t;
+int64_t pseg_grad_sumsq_workspace_bytes(int64_t n);
+int pseg_grad_sumsq(const float* grad, int64_t n, void* workspace, int64_t workspace_bytes, float* clip_state, void* stream);
+int pseg_opt_step_sgd(float* param, const float* grad, float* momentum_buf, float* ema, int64_t n, const pseg_opt_run_t* runs,
+                      const pseg_opt_run_t* runs_host, int n_runs, int64_t total_blocks, float lr, float momentum, int nesterov,
+                      int decoupled, float grad_scale, int first_step, float max_norm, float ema_decay, float* clip_state,
+                      const float* mp_state, void* stream);
+int pseg_opt_step_adam(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                       const pseg_opt_run_t* runs, const pseg_opt_run_t* runs_host, int n_runs, int64_t total_blocks, float lr,
+                       float beta1, float beta2, float eps, int decoupled, float grad_scale, int step, float max_norm,
+                       float ema_decay, float* clip_state, const float* mp_state, void* stream);
 /* amax_inout[0] = max(amax_inout[0], max |x[m*ld + c]|), m < M, c < C (atomic on the float's bit pattern; zero it first) */
 int pseg_amax(const float* x, int64_t ld, int64_t M, int C, float* amax_inout, void* stream);
 /* max|.| of many contiguous float arrays in one launch (every conv filter of a model, once per step).  jobs: device array

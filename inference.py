@@ -4,7 +4,7 @@
     python3 inference.py data/samples outputs --weights weights.pth [-s W H] [-nc N] [-bs N] [--model ...] [-mp]
                          [--norm dataset|reference] [--scales S [S ...]] [--flip]
                          [--min-area N] [--connectivity {4,8}] [--largest-only] [--regions FILE.json]
-                         [--slide [--stride SW SH] [--window-batch N]]
+                         [--slide [--stride SW SH] [--window-batch N]] [--ema]
 
 Every file of img_dir whose extension is in IMG_EXT (case-sensitive, as the reference) is segmented, in name order, and
 written to output_dir as <name>.png in VOC colours.  Photos are decoded with PIL (RGB); resizing, normalisation, softmax,
@@ -51,7 +51,7 @@ def load_image(path):
 
 def run(img_dir, output_dir, img_size, num_classes, weights, show=False, model_name='deeplabv3plus', batch_size=1,
         half=False, norm='dataset', scales=None, flip=False, min_area=0, connectivity=8, largest_only=False, regions=None,
-        slide=False, stride=None, window_batch=None):
+        slide=False, stride=None, window_batch=None, ema=False):
     if not slide and (stride is not None or window_batch is not None):
         raise ValueError('--stride and --window-batch need --slide')
     if min_area < 0:
@@ -63,7 +63,9 @@ def run(img_dir, output_dir, img_size, num_classes, weights, show=False, model_n
     os.makedirs(output_dir, exist_ok=True)
     model = MODELS[model_name](num_classes)
     state_dict = torch.load(weights, map_location='cpu')
-    model.load_state_dict(state_dict['model'])
+    if ema and 'model_ema' not in state_dict:
+        raise KeyError("--ema: %s holds no 'model_ema' (it was not trained with --ema-decay)" % weights)
+    model.load_state_dict(state_dict['model_ema' if ema else 'model'])
     model = model.cuda()
     model.eval()
     names = list_images(img_dir)
@@ -118,6 +120,7 @@ def main(argv=None):
                         help='with --slide: the window stride, between half the window and the window (default: 2/3 of it)')
     parser.add_argument('--window-batch', type=int, default=None, metavar='N',
                         help='with --slide: windows per forward (default: -bs)')
+    parser.add_argument('--ema', action='store_true', help="use the averaged weights ('model_ema') of the checkpoint")
     opt = parser.parse_args(argv)
     if opt.min_area < 0:
         parser.error('--min-area must be >= 0')
@@ -128,7 +131,7 @@ def main(argv=None):
     print(opt)
     run(opt.img_dir, opt.output_dir, opt.img_size, opt.num_classes, opt.weights, opt.show, opt.model, opt.batch_size,
         opt.mix_precision, opt.norm, opt.scales, opt.flip, opt.min_area, opt.connectivity, opt.largest_only, opt.regions,
-        opt.slide, opt.stride, opt.window_batch)
+        opt.slide, opt.stride, opt.window_batch, opt.ema)
 
 
 if __name__ == '__main__':

@@ -10,11 +10,49 @@ view into a second one laid out identically.  That gives:
 * gradient buckets for the data-parallel all-reduce that are plain contiguous ranges of the gradient arena
   (no flatten / unflatten copies), in forward order so that backward completes them from the top down.
 """
+import numpy as np
 import torch
 
 
 def _round4(n):
     return (n + 3) // 4 * 4
+
+
+# ---- run tables of the grouped optimiser step (pseg_opt_run_t, include/pseg_amd.h)
+RUN_SPAN = 1024          # floats a 256-thread block covers per trip (PSEG_OPT_RUN_SPAN)
+# blocks per run: one per span, capped -- a run of the whole arena (no groups asked for) gets 4 blocks per CU, and a table
+# of a few hundred runs (no decay on norm parameters) stays at the ~40 k blocks its spans add up to
+RUN_BLOCK_CAP = 1024
+
+
+def run_blocks(count):
+    return max(1, min(RUN_BLOCK_CAP, (count + RUN_SPAN - 1) // RUN_SPAN))
+
+
+def make_runs(rows):
+    """rows of (offset, count, lr_mult, weight_decay), ascending -> the run table as a list of
+    (offset, count, first_block, lr_mult, weight_decay): neighbours that touch and share both values are fused, every run
+    gets run_blocks(count) blocks.  lr_mult and weight_decay are rounded to fp32, what the kernel receives."""
+    merged = []
+    for off, cnt, lm, wd in rows:
+        lm, wd = float(np.float32(lm)), float(np.float32(wd))
+        if merged and merged[-1][0] + merged[-1][1] == off and merged[-1][2] == lm and merged[-1][3] == wd:
+            merged[-1][1] += cnt
+        else:
+            merged.append([int(off), int(cnt), lm, wd])
+    table, blocks = [], 0
+    for off, cnt, lm, wd in merged:
+        table.append((off, cnt, blocks, lm, wd))
+        blocks += run_blocks(cnt)
+    return table
+
+
+def pack_runs(table):
+    """run table -> (numpy record array in the layout of pseg_opt_run_t, total blocks)"""
+    dt = np.dtype([('offset', '<i8'), ('count', '<i8'), ('first_block', '<i8'), ('lr_mult', '<f4'), ('weight_decay', '<f4')])
+    arr = np.array([tuple(r) for r in table], dtype=dt)
+    assert dt.itemsize == 32
+    return arr, int(table[-1][2] + run_blocks(table[-1][1]))
 
 
 class Segment:
@@ -40,6 +78,7 @@ def _layout(module, name, p):
 class ParamArena:
     def __init__(self, model, device):
         self.device = torch.device(device)
+        self._module_names = {id(m): n for n, m in model.named_modules()}     # state-dict prefixes, for runs()
         segs, seen, off = [], set(), 0
         for mod in model.modules():
             for name, p in mod._parameters.items():
@@ -173,6 +212,22 @@ class ParamArena:
 
     def zero_grad(self):
         self.grads.zero_()
+
+    def key_of(self, seg):
+        """state-dict key of a segment's parameter"""
+        prefix = self._module_names.get(id(seg.module), '')
+        return prefix + '.' + seg.name if prefix else seg.name
+
+    def runs(self, rule):
+        """The run table of the grouped optimiser step: ``rule(state_dict_key, module, name) -> (lr_mult, weight_decay)`` is
+        asked once per segment; neighbouring segments with equal answers fuse.  The table covers [0, numel) without gap or
+        overlap (a segment's padding floats belong to its run: they are zero, their gradients are zero, they stay zero).
+        -> list of (offset, count, first_block, lr_mult, weight_decay), see make_runs."""
+        rows = []
+        for seg in self.segments:
+            lm, wd = rule(self.key_of(seg), seg.module, seg.name)
+            rows.append((seg.offset, seg.numel, lm, wd))
+        return make_runs(rows)
 
     def range_of(self, module):
         """[begin, end) element range of the arena that holds ``module``'s own and descendant parameters."""

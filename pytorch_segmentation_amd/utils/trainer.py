@@ -17,6 +17,7 @@ input buffers and replay.  The optimiser launch stays outside the graph (its lea
 The optimiser hyper-parameters of the external Trainer are not observable from the reference tree; torch.optim
 defaults are used (SGD: momentum 0.9, no weight decay; Adam: betas (0.9, 0.999)) and can be overridden.
 """
+import contextlib
 import os
 
 import torch
@@ -27,6 +28,7 @@ from ..arena import prepare
 from ..nn import BatchNorm2d, Conv2d, Env
 from .dist import GradReducer, broadcast_buffers
 from .loss import compute_loss as _default_loss
+from .schedule import lr_at
 
 
 def _device():
@@ -54,14 +56,41 @@ class Fetcher:
 
 
 class FlatOptimizer:
-    """SGD(momentum) / Adam over the flat parameter arena: one kernel launch per step."""
+    """SGD(momentum) / Adam over the flat parameter arena: one kernel launch per step.
+
+    With any of `runs` (a run table of ParamArena.runs: per-run learning-rate factor and weight decay -- `weight_decay` is
+    then the table's), `max_grad_norm` (global-norm clip), `ema_decay` (fused moving average of the weights in `self.ema`)
+    or `decoupled` (AdamW / SGDW decay) the step is the grouped one (csrc/optim_groups.hip): [pseg_mp_check],
+    pseg_grad_sumsq when clipping, pseg_opt_step_*, [pseg_mp_update] -- one step launch, no host synchronisation.  With none
+    of them the calls are the ones this class always issued."""
 
     def __init__(self, arena, adam=False, lr=1e-3, momentum=0.9, weight_decay=0.0, nesterov=False,
-                 betas=(0.9, 0.999), eps=1e-8):
+                 betas=(0.9, 0.999), eps=1e-8, runs=None, max_grad_norm=0.0, ema_decay=0.0, decoupled=False):
         self.arena, self.adam, self.lr = arena, adam, lr
         self.momentum, self.weight_decay, self.nesterov = momentum, weight_decay, nesterov
         self.betas, self.eps = betas, eps
         self.steps = 0
+        self.sched_steps = 0      # step() calls so far, skipped `-mp` steps included: what a schedule counts (utils/schedule.py)
+        if max_grad_norm < 0:
+            raise ValueError('max_grad_norm must be >= 0 (0: no clipping); got %r' % (max_grad_norm,))
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError('ema_decay must be in [0, 1) (0: no EMA); got %r' % (ema_decay,))
+        self.max_grad_norm, self.ema_decay, self.decoupled = float(max_grad_norm), float(ema_decay), bool(decoupled)
+        self.grouped = runs is not None or self.max_grad_norm > 0 or self.ema_decay > 0 or self.decoupled
+        self.ema = self.clip_state = None
+        if self.grouped:
+            from .. import _lib
+            from ..arena import make_runs, pack_runs
+            self.runs = list(runs) if runs is not None else make_runs([(0, arena.numel, 1.0, weight_decay)])
+            # the table twice, from one array: the device copy the kernel reads, the host copy every launch is checked against
+            self._runs_host, self._run_blocks = pack_runs(self.runs)
+            self._runs_dev = torch.from_numpy(self._runs_host.view('uint8').copy()).to(arena.device)
+            self.clip_state = torch.zeros(4, dtype=torch.float32, device=arena.device)
+            if self.max_grad_norm > 0:
+                nbytes = _lib.query('pseg_grad_sumsq_workspace_bytes', arena.numel)
+                self._sumsq_ws = torch.empty(nbytes // 8, dtype=torch.float64, device=arena.device)
+            if self.ema_decay > 0:
+                self.ema = arena.params.detach().clone()
         # dynamic loss scaling of the half-precision policy (apex / torch.cuda.amp defaults)
         self.growth_factor, self.backoff_factor, self.growth_interval = 2.0, 0.5, 2000
         n, dev = arena.numel, arena.device
@@ -78,6 +107,9 @@ class FlatOptimizer:
         synchronisation (whether the step was applied is only known on the device: state[4] / state[5] count)."""
         a = self.arena
         self.steps += 1
+        self.sched_steps += 1
+        if self.grouped:
+            return self._grouped_step(grad_scale, mp_state)
         if mp_state is not None:
             from .. import _lib
             st, sp = ops._stream(), mp_state.data_ptr()
@@ -100,15 +132,56 @@ class FlatOptimizer:
             ops.sgd_step(a.params, a.grads, self.m, self.lr, self.momentum, self.weight_decay, self.nesterov,
                          grad_scale, self.steps == 1)
 
+    def _grouped_step(self, grad_scale, mp_state):
+        from .. import _lib
+        a, st = self.arena, ops._stream()
+        sp = mp_state.data_ptr() if mp_state is not None else None
+        clip = self.max_grad_norm > 0
+        if sp is not None:
+            _lib.call('pseg_mp_check', a.grads.data_ptr(), a.numel, sp, st)
+        if clip:
+            _lib.call('pseg_grad_sumsq', a.grads.data_ptr(), a.numel, self._sumsq_ws.data_ptr(), self._sumsq_ws.numel() * 8,
+                      self.clip_state.data_ptr(), st)
+        tail = (float(self.max_grad_norm), float(self.ema_decay), self.clip_state.data_ptr(), sp, st)
+        table = (a.numel, self._runs_dev.data_ptr(), self._runs_host.ctypes.data, len(self.runs), self._run_blocks)
+        if self.adam:
+            _lib.call('pseg_opt_step_adam', a.params.data_ptr(), a.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                      ops._ptr(self.ema), *table, float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                      int(self.decoupled), float(grad_scale), int(self.steps), *tail)
+        else:
+            _lib.call('pseg_opt_step_sgd', a.params.data_ptr(), a.grads.data_ptr(), ops._ptr(self.m), ops._ptr(self.ema),
+                      *table, float(self.lr), float(self.momentum), int(self.nesterov), int(self.decoupled), float(grad_scale),
+                      int(self.steps == 1), *tail)
+        if sp is not None:
+            _lib.call('pseg_mp_update', sp, float(self.growth_factor), float(self.backoff_factor), int(self.growth_interval),
+                      1.0, float(2 ** 24), st)
+
+    def clip_stats(self):
+        """(grouped step with clipping) host copy of the clip state: dict(norm, coef, steps_clipped) of the last applied
+        step.  Synchronises the host -- for logging and tests, not for the step."""
+        if self.clip_state is None:
+            return None
+        s = self.clip_state.detach().cpu().tolist()
+        return {'norm': s[2], 'coef': s[1], 'steps_clipped': int(s[3])}
+
     def state_dict(self):
-        return {'adam': self.adam, 'steps': self.steps, 'm': self.m, 'v': self.v, 'lr': self.lr}
+        sd = {'adam': self.adam, 'steps': self.steps, 'm': self.m, 'v': self.v, 'lr': self.lr, 'sched_steps': self.sched_steps}
+        if self.grouped:
+            sd.update(ema=self.ema, clip_state=self.clip_state)
+        return sd
 
     def load_state_dict(self, sd):
         self.steps = sd['steps']
+        self.sched_steps = sd.get('sched_steps', sd['steps'])
         if sd.get('m') is not None and self.m is not None:
             self.m.copy_(sd['m'])
         if sd.get('v') is not None and self.v is not None:
             self.v.copy_(sd['v'])
+        if self.ema is not None:
+            # (a checkpoint without averaged weights: the average starts from the weights it holds)
+            self.ema.copy_(sd['ema'] if sd.get('ema') is not None else self.arena.params)
+        if self.clip_state is not None and sd.get('clip_state') is not None:
+            self.clip_state.copy_(sd['clip_state'])
 
 
 FUSE_CE_UPSAMPLE = os.environ.get('PSEG_FUSE_CE_UPSAMPLE', '1') == '1'
@@ -272,7 +345,14 @@ class _StepGraph:
 class Trainer:
     def __init__(self, model, fetcher, loss_fn=None, workdir='weights', accumulate=1, adam=False, lr=1e-3,
                  weights='', resume=False, mixed_precision=False, momentum=0.9, weight_decay=0.0,
-                 bucket_bytes=32 << 20, device=None, graph=None, max_graphs=8):
+                 bucket_bytes=32 << 20, device=None, graph=None, max_graphs=8, no_decay_norm_bias=False, lr_mult=None,
+                 max_grad_norm=0.0, ema_decay=0.0, adamw=False, schedule=None, warmup_steps=0, total_steps=None,
+                 poly_power=0.9, min_lr=0.0):
+        # The training recipe around the step (all off by default; the optimiser then issues the calls it always did):
+        # no_decay_norm_bias: weight decay 0 for every BatchNorm2d parameter and every `bias`; lr_mult: {state-dict key
+        # prefix: factor on the learning rate}, first match wins ({'backbone.': 0.1}); max_grad_norm: global-norm clip;
+        # ema_decay: moving average of the weights (ema_weights(), 'model_ema' in checkpoints); adamw: decoupled weight
+        # decay; schedule 'poly' / 'cosine' with warmup_steps / total_steps / poly_power / min_lr (utils/schedule.py)
         # mixed_precision: the reference's -mp flag asks apex for fp16 compute with fp32 master weights and loss scaling
         # (train.py:70,102-105,138; README.md:12).  That is the `half` policy here: fp16 activations / gradients / filter
         # copies in HBM, every conv one fp16 MFMA pass with fp32 accumulation, BatchNorm statistics, the loss and the
@@ -291,7 +371,23 @@ class Trainer:
             sd = torch.load(weights, map_location='cpu')
             model.load_state_dict(sd['model'] if 'model' in sd else sd)
         self.arena = prepare(model, self.device)
-        self.optimizer = FlatOptimizer(self.arena, adam=adam, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        runs = None
+        if no_decay_norm_bias or lr_mult:
+            factors = list((lr_mult or {}).items())
+
+            def rule(key, module, name):
+                wd = 0.0 if (no_decay_norm_bias and (isinstance(module, torch.nn.BatchNorm2d) or name == 'bias')) \
+                    else weight_decay
+                return next((f for prefix, f in factors if key.startswith(prefix)), 1.0), wd
+            runs = self.arena.runs(rule)
+        self.optimizer = FlatOptimizer(self.arena, adam=adam, lr=lr, momentum=momentum, weight_decay=weight_decay, runs=runs,
+                                       max_grad_norm=max_grad_norm, ema_decay=ema_decay, decoupled=adamw)
+        self.base_lr = lr
+        self.schedule = None
+        if schedule is not None:
+            self.schedule = dict(schedule=schedule, total_steps=total_steps, warmup_steps=warmup_steps, poly_power=poly_power,
+                                 min_lr=min_lr)
+            lr_at(0, lr, **self.schedule)         # (refuses a bad combination here, not at the first step)
         owners = [(s.module, s.offset, s.numel) for s in self.arena.segments]
         self.reducer = GradReducer(self.arena.grads, owners, bucket_bytes=bucket_bytes)
         mp_policy = os.environ.get('PSEG_MP_POLICY', 'half')
@@ -395,12 +491,12 @@ class Trainer:
         dist.broadcast(self.arena.params, 0)
         if self.mp_state is not None:
             dist.broadcast(self.mp_state, 0)
-        for t in (self.optimizer.m, self.optimizer.v):
+        for t in (self.optimizer.m, self.optimizer.v, self.optimizer.ema, self.optimizer.clip_state):
             if t is not None:
                 dist.broadcast(t, 0)
-        steps = torch.tensor([self.optimizer.steps, self.epoch], dtype=torch.int64, device=self.device)
+        steps = torch.tensor([self.optimizer.steps, self.epoch, self.optimizer.sched_steps], dtype=torch.int64, device=self.device)
         dist.broadcast(steps, 0)
-        self.optimizer.steps, self.epoch = int(steps[0]), int(steps[1])
+        self.optimizer.steps, self.epoch, self.optimizer.sched_steps = int(steps[0]), int(steps[1]), int(steps[2])
         broadcast_buffers(self.model, 0)
 
     # ---- one optimisation micro-step; the optimiser fires every `accumulate` micro-batches (train.py:65)
@@ -462,6 +558,10 @@ class Trainer:
         self._micro += 1
         if last:
             self.reducer.finish()
+            if self.schedule is not None:
+                # (the optimiser launch is outside the captured step: its learning rate is a by-value argument)
+                self.optimizer.lr = lr_at(self.optimizer.sched_steps, self.base_lr, **self.schedule)
+            # (after the exchange every rank holds the same gradients: the clip norm needs no collective)
             self.optimizer.step(grad_scale=self.reducer.grad_scale / self.accumulate, mp_state=self.mp_state if self.env.half else None)
             self._micro = 0
         return loss
@@ -633,9 +733,37 @@ class Trainer:
         self.epoch += 1
         return (total / max(n, 1)).item() if total is not None else float('nan')
 
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the model computes with the averaged weights: the parameter arena and the EMA buffer are swapped
+        by device copies (every parameter is a view of the arena), and swapped back on exit.  BatchNorm running statistics are
+        the live model's.  Under the half policy the fp16 filter copies follow the swap.  No optimiser step inside."""
+        ema = self.optimizer.ema
+        if ema is None:
+            raise RuntimeError('ema_weights() needs Trainer(ema_decay=...) > 0')
+
+        def swap():
+            with torch.no_grad():
+                tmp = self.arena.params.clone()
+                self.arena.params.copy_(ema)
+                ema.copy_(tmp)
+            if self.env.half and getattr(self.arena, '_half_jobs', None) is not None:
+                self.arena.prepare_half()
+        swap()
+        try:
+            yield self.model
+        finally:
+            swap()
+
     def state(self):
         sd = {k: v.detach().contiguous().clone() for k, v in self.model.state_dict().items()}
         st = {'model': sd, 'epoch': self.epoch, 'metrics': self.metrics, 'optimizer': self.optimizer.state_dict()}
+        if self.optimizer.ema is not None:
+            # the averaged weights in the model's own keys and shapes (what test.py --ema / inference.py --ema load)
+            with self.ema_weights():
+                st['model_ema'] = {k: v.detach().contiguous().clone() for k, v in self.model.state_dict().items()}
+            st['optimizer'] = dict(st['optimizer'], ema=self.optimizer.ema.detach().clone(),
+                                   clip_state=self.optimizer.clip_state.detach().clone())
         if self.mp_state is not None:
             st['loss_scaler'] = self.mp_state.detach().cpu().clone()
             # the optimiser's host-side count includes steps the device skipped (overflow); what a resumed fp32 run needs is
@@ -673,6 +801,8 @@ class Trainer:
         self.metrics = st.get('metrics', 0)
         if 'optimizer' in st:
             self.optimizer.load_state_dict(st['optimizer'])
+        elif self.optimizer.ema is not None:
+            self.optimizer.ema.copy_(self.arena.params)
         if self.mp_state is not None:
             if 'loss_scaler' in st:
                 self.mp_state.copy_(st['loss_scaler'])

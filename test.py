@@ -3,7 +3,7 @@
 
     python3 test.py data/<custom>/val.json --weights weights/best.pt [-s W H] [-bs N] [--model deeplabv3plus|unet]
                     [--scales S [S ...]] [--flip] [--min-area N] [--connectivity {4,8}] [--largest-only]
-                    [--window W H [--stride SW SH]]
+                    [--window W H [--stride SW SH]] [--ema]
 
 `test(model, fetcher)` keeps the reference's contract: evaluates in eval mode without gradients, prints per-class
 (or the five worst classes') targets / precision / recall / IoU / F1 and returns the mean IoU.  The per-class
@@ -93,6 +93,15 @@ def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, la
     return miou.mean().item()
 
 
+def checkpoint_weights(checkpoint, ema=False, path='the checkpoint'):
+    """the state dict to evaluate: 'model', or with ema the averaged weights train.py --ema-decay saved as 'model_ema'"""
+    if not ema:
+        return checkpoint['model']
+    if 'model_ema' not in checkpoint:
+        raise KeyError("--ema: %s holds no 'model_ema' (it was not trained with --ema-decay)" % path)
+    return checkpoint['model_ema']
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('val', type=str)
@@ -114,6 +123,7 @@ def parse_args(argv=None):
                          'scale the image')
     ap.add_argument('--stride', type=int, nargs=2, default=None, metavar=('SW', 'SH'),
                     help='with --window: the window stride, between half the window and the window (default: 2/3 of it)')
+    ap.add_argument('--ema', action='store_true', help="evaluate the averaged weights ('model_ema') of the checkpoint")
     opt = ap.parse_args(argv)
     if opt.min_area < 0:
         ap.error('--min-area must be >= 0')
@@ -129,9 +139,13 @@ def main(argv=None):
     fetcher = Fetcher(loader, post_fetch_fn=data.post_fetch_fn)
     model = MODELS[opt.model](len(data.classes))
     if opt.weights:
-        model.load_state_dict(torch.load(opt.weights, map_location='cpu')['model'])
-    print('metrics: %8g' % test(model.cuda(), fetcher, opt.scales, opt.flip, opt.min_area, opt.connectivity,
-                                  opt.largest_only, opt.window, opt.stride))
+        model.load_state_dict(checkpoint_weights(torch.load(opt.weights, map_location='cpu'), opt.ema, opt.weights))
+    elif opt.ema:
+        raise ValueError('--ema needs --weights')
+    metrics = test(model.cuda(), fetcher, opt.scales, opt.flip, opt.min_area, opt.connectivity,
+                   opt.largest_only, opt.window, opt.stride)
+    print('metrics: %8g' % metrics)
+    return metrics
 
 
 if __name__ == '__main__':

@@ -5,6 +5,8 @@ on the MI355X HIP path.
     python3 train.py data/<custom> [--epochs N] [-s W H] [-bs N] [-a ACC] [--lr LR] [--adam] [--resume]
                      [--weights F] [--notest] [--nosave] [--model unet|deeplabv3plus] [--augment | --augment-full | --augment-warps]
                      [--loss ce|lovasz|ce+lovasz] [--class-weights W0 W1 ...] [--label-smoothing E] [--focal-gamma G] [--ohem-keep R]
+                     [--weight-decay WD] [--momentum M] [--adamw] [--no-decay-norm-bias] [--backbone-lr-mult F]
+                     [--clip-grad N] [--ema-decay D] [--schedule poly|cosine] [--warmup-steps N] [--min-lr LR]
     python3 -m torch.distributed.run --nproc-per-node <n> train.py data/<custom>        # RCCL data parallel
 
 Differences from the reference that are visible here: the model is picked with --model (the reference edits
@@ -36,6 +38,9 @@ MODELS = {'deeplabv3plus': DeepLabV3Plus, 'unet': UNet, 'hrnet': HRNet}
 LOSS_FN = compute_loss
 # --class-weights as given, or None: train() checks their number against the data set's classes
 CLASS_WEIGHTS = None
+# optimiser recipe: Trainer keywords main() fills from --weight-decay ... --min-lr (optim_from_options); empty = the
+# Trainer's defaults, as before.  'total_steps' is worked out in train() once the loader's length is known.
+OPTIM = {}
 
 
 def _loader(dataset, batch_size, num_workers, train=True):
@@ -65,15 +70,23 @@ def train(data_dir, epochs=100, img_size=(320, 320), batch_size=32, accumulate=2
     if CLASS_WEIGHTS is not None and len(CLASS_WEIGHTS) != len(train_data.classes):
         raise ValueError('--class-weights has %d values, the data set has %d classes' % (len(CLASS_WEIGHTS), len(train_data.classes)))
     model = MODELS[model_name](len(train_data.classes))
+    optim = dict(OPTIM)
+    if optim.get('schedule') is not None:
+        optim['total_steps'] = epochs * (len(train_fetcher) // max(1, accumulate))
     trainer = Trainer(model, train_fetcher, loss_fn=LOSS_FN, workdir='weights', accumulate=accumulate, adam=adam,
-                      lr=lr, weights=weights, resume=resume, mixed_precision=mixed_precision)
+                      lr=lr, weights=weights, resume=resume, mixed_precision=mixed_precision, **optim)
+    use_ema = optim.get('ema_decay', 0.0) > 0
     last_loss = None
     while trainer.epoch < epochs:
         last_loss = trainer.step()
         print('epoch %d: loss %g' % (trainer.epoch, last_loss))
         best = False
         if val_fetcher is not None:
-            metrics = test(trainer.model, val_fetcher)
+            if use_ema:         # the averaged weights are the ones scored, and the ones best.pt is chosen by
+                with trainer.ema_weights():
+                    metrics = test(trainer.model, val_fetcher)
+            else:
+                metrics = test(trainer.model, val_fetcher)
             if metrics > trainer.metrics:
                 best = True
                 print('save best, miou: %g' % metrics)
@@ -122,7 +135,48 @@ def build_parser():
     ap.add_argument('--ohem-keep', type=float, default=1.0, metavar='R',
                     help='online hard-example mining: average the cross-entropy over the share R in (0, 1] of the valid '
                          'pixels of a batch with the largest loss')
+    ap.add_argument('--weight-decay', type=float, default=None, metavar='WD', help='weight decay (default 0)')
+    ap.add_argument('--momentum', type=float, default=None, metavar='M', help='SGD momentum (default 0.9)')
+    ap.add_argument('--adamw', action='store_true', help='decoupled weight decay (AdamW with --adam, SGDW without)')
+    ap.add_argument('--no-decay-norm-bias', action='store_true', help='no weight decay on BatchNorm parameters and biases')
+    ap.add_argument('--backbone-lr-mult', type=float, default=None, metavar='F',
+                    help="factor on the learning rate of the parameters under 'backbone.' (e.g. 0.1 for a pretrained one)")
+    ap.add_argument('--clip-grad', type=float, default=0.0, metavar='N', help='clip the global gradient norm to N (0: off)')
+    ap.add_argument('--ema-decay', type=float, default=0.0, metavar='D',
+                    help='exponential moving average of the weights with decay D in [0, 1): validated, chosen as best.pt by, '
+                         "and saved as 'model_ema' (0: off)")
+    ap.add_argument('--schedule', choices=['poly', 'cosine'], default=None, help='learning-rate schedule over all epochs')
+    ap.add_argument('--warmup-steps', type=int, default=0, metavar='N', help='linear warm-up over the first N optimiser steps')
+    ap.add_argument('--min-lr', type=float, default=0.0, help='floor of the schedule')
     return ap
+
+
+def optim_from_options(opt):
+    """Trainer keywords of the parsed optimiser flags; {} when none is given"""
+    kw = {}
+    if opt.weight_decay is not None:
+        kw['weight_decay'] = opt.weight_decay
+    if opt.momentum is not None:
+        kw['momentum'] = opt.momentum
+    if opt.adamw:
+        kw['adamw'] = True
+    if opt.no_decay_norm_bias:
+        kw['no_decay_norm_bias'] = True
+    if opt.backbone_lr_mult is not None:
+        kw['lr_mult'] = {'backbone.': opt.backbone_lr_mult}
+    if opt.clip_grad < 0:
+        raise ValueError('--clip-grad must be >= 0; got %g' % opt.clip_grad)
+    if opt.clip_grad > 0:
+        kw['max_grad_norm'] = opt.clip_grad
+    if not 0.0 <= opt.ema_decay < 1.0:
+        raise ValueError('--ema-decay must be in [0, 1); got %g' % opt.ema_decay)
+    if opt.ema_decay > 0:
+        kw['ema_decay'] = opt.ema_decay
+    if opt.schedule is not None:
+        kw.update(schedule=opt.schedule, warmup_steps=opt.warmup_steps, min_lr=opt.min_lr)
+    elif opt.warmup_steps or opt.min_lr:
+        raise ValueError('--warmup-steps and --min-lr belong to --schedule')
+    return kw
 
 
 def loss_from_options(opt):
@@ -133,9 +187,10 @@ def loss_from_options(opt):
 
 
 def main():
-    global LOSS_FN, CLASS_WEIGHTS
+    global LOSS_FN, CLASS_WEIGHTS, OPTIM
     opt = build_parser().parse_args()
     LOSS_FN, CLASS_WEIGHTS = loss_from_options(opt)
+    OPTIM = optim_from_options(opt)
 
     if os.environ.get('WORLD_SIZE'):
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
