@@ -764,7 +764,7 @@ int pseg_adam_step(float* param, const float* grad, float* exp_avg, float* exp_a
                    int step, void* stream);
 int pseg_fill(float* x, int64_t n, float value, void* stream);
 
-/* ---- grouped step: per-run learning-rate factor and weight decay, global-norm clipping, weight EMA (csrc/optim_groups.hip).
+/* ---- grouped step: per-run learning-rate factor and weight decay, global-norm clipping, weight EMA (csrc/optim.hip).
  * Additive: PSEG_ABI_VERSION does not move.
  *
  * A RUN is a contiguous range of the arena whose floats share their hyper-parameters.  The table is an array of
@@ -779,7 +779,7 @@ int pseg_fill(float* x, int64_t n, float value, void* stream);
  *   `workspace` (pseg_grad_sumsq_workspace_bytes(n) bytes, at most 8 * PSEG_GRAD_SUMSQ_MAX_PARTIALS; 8-byte aligned), folded by a
  *   second single-block launch in a fixed order.  The grid depends on n only, there is no atomic: bit-reproducible from call
  *   to call.  n is a multiple of 4.
- * pseg_opt_step_sgd / pseg_opt_step_adam, per element of run r, in the arithmetic of pseg_sgd_step / pseg_adam_step:
+ * pseg_opt_step_sgd / pseg_opt_step_adam, per element of run r, by the kernel that pseg_sgd_step / pseg_adam_step launch too:
  *     d = g * (gscale_eff * coef);  weight decay wd_r, coupled (d += wd_r * w) or `decoupled` (w *= 1 - lr_r * wd_r);
  *     momentum / Nesterov, or the Adam moments;  w -= lr_r * d  (Adam: step_size = lr_r / bias_correction1),  lr_r = lr * lr_mult_r;
  *     ema (nullable):  e = ema_decay * e + (1 - ema_decay) * w_new.
@@ -791,8 +791,9 @@ int pseg_fill(float* x, int64_t n, float value, void* stream);
  *   With mp_state: a raised found-inf flag (mp_state[3]) returns before anything is written -- parameters, moments, EMA and
  *   clip_state[1..3] stay as they were; first step / bias corrections come from mp_state[4] (first_step / step are ignored).
  *   Without it they come from the host: first_step as in pseg_sgd_step, step >= 1 as in pseg_adam_step (bias corrections in double).
- *   A one-run table with lr_mult = 1, max_norm = 0 and ema = NULL reproduces pseg_sgd_step, pseg_sgd_step_mp, pseg_adam_step
- *   and pseg_adam_step_mp bit for bit.  Refused with a message naming the check: null / misaligned (16 bytes) pointers, a
+ *   pseg_sgd_step, pseg_sgd_step_mp, pseg_adam_step and pseg_adam_step_mp are this step over the whole arena as ONE run with
+ *   lr_mult = 1, max_norm = 0 and ema = NULL, passed to the kernel by value (no table; n need not be a multiple of 4): a
+ *   one-run table with those values gives their result bit for bit.  Refused with a message naming the check: null / misaligned (16 bytes) pointers, a
  *   table that breaks a rule above, ema_decay outside [0, 1), max_norm < 0. */
 #define PSEG_OPT_RUN_SPAN 1024
 #define PSEG_GRAD_SUMSQ_MAX_PARTIALS 1024

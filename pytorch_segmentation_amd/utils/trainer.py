@@ -60,7 +60,7 @@ class FlatOptimizer:
 
     With any of `runs` (a run table of ParamArena.runs: per-run learning-rate factor and weight decay -- `weight_decay` is
     then the table's), `max_grad_norm` (global-norm clip), `ema_decay` (fused moving average of the weights in `self.ema`)
-    or `decoupled` (AdamW / SGDW decay) the step is the grouped one (csrc/optim_groups.hip): [pseg_mp_check],
+    or `decoupled` (AdamW / SGDW decay) the step is the grouped one (csrc/optim.hip): [pseg_mp_check],
     pseg_grad_sumsq when clipping, pseg_opt_step_*, [pseg_mp_update] -- one step launch, no host synchronisation.  With none
     of them the calls are the ones this class always issued."""
 

@@ -1,4 +1,4 @@
-"""fp64 restatement of ONE grouped optimiser step (csrc/optim_groups.hip), and the same recipe through torch.optim.
+"""fp64 restatement of ONE grouped optimiser step (csrc/optim.hip), and the same recipe through torch.optim.
 
 grouped_step(): runs with their own learning-rate factor and weight decay, the global-norm clip of
 torch.nn.utils.clip_grad_norm_, SGD (momentum, Nesterov) or Adam / AdamW, the weight EMA and the `-mp` skip, written out

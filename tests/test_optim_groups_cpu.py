@@ -1,5 +1,5 @@
 """Host side of the grouped optimiser step: the fp64 restatement against torch.optim, the learning-rate schedules, the run
-tables of ParamArena.runs, the command-line flags, and the refusals of the entry points (csrc/optim_groups.hip).  No GPU."""
+tables of ParamArena.runs, the command-line flags, and the refusals of the entry points (csrc/optim.hip).  No GPU."""
 import math
 
 import numpy as np

@@ -58,7 +58,7 @@ def load(d):
         out.append((klass(n, phase), n, disp[k]['c']))
         if 'ce_fused_kernel' in n or 'ce_generic_kernel' in n or 'ce_up_fused_kernel' in n or 'ce_up_combine_kernel' in n:
             phase = 'bwd'
-        elif 'sgd_kernel' in n or 'adam_kernel' in n or 'sgd_mp_kernel' in n or 'adam_mp_kernel' in n:
+        elif 'sgd_kernel' in n or 'adam_kernel' in n:
             phase = 'fwd'
     return out
 

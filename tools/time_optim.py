@@ -4,6 +4,8 @@
 
 On random gradients, one FlatOptimizer.step() per call:
   * `pseg_sgd_step` (momentum 0.9) and `pseg_adam_step` as they stand: the baseline;
+  * `pseg_sgd_step_mp` / `pseg_adam_step_mp`: the baseline under the half-precision policy, FlatOptimizer.step(mp_state=...),
+    three launches (`pseg_mp_check`, the step, `pseg_mp_update`);
   * the grouped step (`pseg_opt_step_sgd` / `pseg_opt_step_adam`) with a ONE-run table, the configuration that reproduces the
     baseline bit for bit;
   * the grouped step with the model's real run table (no decay on BatchNorm parameters and biases, 0.1 on `backbone.`);
@@ -11,7 +13,8 @@ On random gradients, one FlatOptimizer.step() per call:
   * that with the norm pass (`pseg_grad_sumsq`, two launches) and the clip added.
 Each figure is the median over --iters single calls, each between its own pair of events, after warm-up; the variants
 alternate inside one loop so that they see the same machine.  Every row carries the bytes the call moves by count (SGD
-20 B / element: parameter and momentum read and written, gradient read; Adam 28; the EMA adds 8, the norm pass 4) and that
+20 B / element: parameter and momentum read and written, gradient read; Adam 28; the EMA adds 8, the norm pass and the
+`-mp` check 4 each) and that
 over the time against 6.3 TB/s.
 """
 import argparse
@@ -22,6 +25,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pytorch_segmentation_amd import _lib, ops  # noqa: E402
 from pytorch_segmentation_amd.arena import ParamArena, make_runs  # noqa: E402
 from pytorch_segmentation_amd.models import DeepLabV3Plus  # noqa: E402
 from pytorch_segmentation_amd.utils import FlatOptimizer  # noqa: E402
@@ -47,17 +51,21 @@ def main():
         return (0.1 if key.startswith('backbone.') else 1.0), wd
     real = arena.runs(rule)
     one = make_runs([(0, n, 1.0, 1e-4)])
+    mp_state = torch.zeros(8, dtype=torch.float32, device=arena.device)
+    _lib.call('pseg_mp_state_init', mp_state.data_ptr(), 2.0 ** 16, ops._stream())
     variants = {}
     for adam, tag, base_bytes in ((False, 'sgd', 20), (True, 'adam', 28)):
         kw = dict(adam=adam, lr=1e-3, weight_decay=1e-4)
         variants['pseg_%s_step' % tag] = (FlatOptimizer(arena, **kw), base_bytes, 1)
+        variants['pseg_%s_step_mp' % tag] = (FlatOptimizer(arena, **kw), base_bytes + 4, 3)
         variants['pseg_opt_step_%s, one run' % tag] = (FlatOptimizer(arena, runs=one, **kw), base_bytes, 1)
         variants['pseg_opt_step_%s, %d runs' % (tag, len(real))] = (FlatOptimizer(arena, runs=real, **kw), base_bytes, 1)
         variants['pseg_opt_step_%s, %d runs + ema' % (tag, len(real))] = \
             (FlatOptimizer(arena, runs=real, ema_decay=0.999, **kw), base_bytes + 8, 1)
         variants['pseg_opt_step_%s, %d runs + ema + norm' % (tag, len(real))] = \
             (FlatOptimizer(arena, runs=real, ema_decay=0.999, max_grad_norm=1.0, **kw), base_bytes + 12, 3)
-    med = timed_median({k: v[0].step for k, v in variants.items()}, opt.iters)
+    med = timed_median({k: (lambda o=v[0]: o.step(mp_state=mp_state)) if k.endswith('_mp') else v[0].step
+                        for k, v in variants.items()}, opt.iters)
     rows = []
     for k, (m, lo, hi) in med.items():
         _, bpe, launches = variants[k]
