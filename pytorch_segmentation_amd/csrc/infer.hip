@@ -10,7 +10,9 @@
 //    upper-left tap lies in the tile is written by that block alone.  No full-resolution C-channel value is ever stored.
 //    A thread walks one output column down its rows and keeps the column-lerped probabilities of the two source rows it
 //    sits between in registers (C <= 32): the LDS is read 2C floats per SOURCE row it enters, not 4C per output pixel.
-// Test-time ensembling (several scales, each optionally with its left-right mirrored twin) stands on three more kernels:
+// The three preprocess entry points are one kernel template over the table's row layout (3, 4 or 8 words) around one
+// sample-and-store body; a narrower row is the wider one with constants, so the plain route compiles without the others' work.
+// Test-time ensembling (several scales, each optionally with its left-right mirrored twin) stands on:
 //  - image_preprocess_views: image_preprocess with a flag word per table row; bit 0 mirrors the OUTPUT row, so one launch
 //    gives the plain and the mirrored model input of every photo at one scale.
 //  - softmax_views: logits [n,C,h,w] -> probabilities [B,h,w,CP], pixel-major, classes padded to CP with zeros; with
@@ -27,6 +29,9 @@
 //    of a bilinear tap is the unweighted mean of the windows that cover it.  Still a gather by output tile -- no atomics and
 //    no C-channel canvas at working or photo size; the windows covering a tap depend only on its row or column, so a block
 //    works them out once for its 16 rows and 64 columns into LDS.
+// The two kernels that own output tiles share their table-row check and ragged-batch exit (out_tile), their class scan
+// (scan_classes) and, with seg_decode, the pixel store (store_pixel); the inner loops stay each kernel's own.  The entry
+// points' argument checks are written once per family and take the entry point's name for their messages.
 #include "common.h"
 
 #include <math.h>
@@ -76,26 +81,37 @@ struct Norm {
   float mean[3], std[3];
 };
 
-__global__ __launch_bounds__(256) void image_preprocess_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
-                                                               const int64_t* __restrict__ table, int bgr, Norm nm,
-                                                               float* __restrict__ out, int oh, int ow) {
-  const int b = blockIdx.z, oy = blockIdx.y;
-  const int ox = blockIdx.x * 256 + threadIdx.x;
-  if (ox >= ow) return;
-  const int64_t off = table[3 * b], H = table[3 * b + 1], W = table[3 * b + 2];
-  if (!entry_ok(off, H, W, 3, src_bytes)) return;        // the host wrapper validates the table; never read outside src
-  const InAxis ay{(float)H / (float)oh, (int)H, oh}, ax{(float)W / (float)ow, (int)W, ow};
+// One table row in the terms of the widest layout.  kWords = 3: {byte offset, H, W}; 4: {.., flags}; 8: {.., flags, Hs, Ws,
+// y0, x0}.  What a narrower row does not carry is a constant: flags 0, the working image is the output, origin (0, 0).
+struct PreRow {
+  int64_t off, H, W, flags, Hs, Ws, wy, wx;
+};
+
+template <int kWords>
+__device__ __forceinline__ PreRow read_row(const int64_t* __restrict__ table, int b, int oh, int ow) {
+  const int64_t* t = table + kWords * (int64_t)b;
+  PreRow r{t[0], t[1], t[2], 0, oh, ow, 0, 0};
+  if constexpr (kWords >= 4) r.flags = t[3];
+  if constexpr (kWords == 8) {
+    r.Hs = t[4];
+    r.Ws = t[5];
+    r.wy = t[6];
+    r.wx = t[7];
+  }
+  return r;
+}
+
+// The four taps of position (Y, X) of the resampled photo p, blended, rounded to 8 bits, normalised -> o[k * plane]
+__device__ __forceinline__ void sample_store(const uint8_t* __restrict__ p, int64_t W, const InAxis& ay, const InAxis& ax, int Y,
+                                             int X, int bgr, const Norm& nm, float* __restrict__ o, int64_t plane) {
   int y0, y1, x0, x1;
   float ly0, ly1, lx0, lx1;
-  taps(ay, oy, y0, y1, ly0, ly1);
-  taps(ax, ox, x0, x1, lx0, lx1);
-  const uint8_t* p = src + off;
+  taps(ay, Y, y0, y1, ly0, ly1);
+  taps(ax, X, x0, x1, lx0, lx1);
   const uint8_t* p00 = p + ((int64_t)y0 * W + x0) * 3;
   const uint8_t* p01 = p + ((int64_t)y0 * W + x1) * 3;
   const uint8_t* p10 = p + ((int64_t)y1 * W + x0) * 3;
   const uint8_t* p11 = p + ((int64_t)y1 * W + x1) * 3;
-  const int64_t plane = (int64_t)oh * ow;
-  float* o = out + (int64_t)b * 3 * plane + (int64_t)oy * ow + ox;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int cs = bgr ? 2 - k : k;                      // the swap happens on load
@@ -106,8 +122,67 @@ __global__ __launch_bounds__(256) void image_preprocess_kernel(const uint8_t* __
   }
 }
 
+// out[b] = the oh x ow window at the row's origin of its photo resampled to the row's working size; bit 0 of the flags
+// mirrors the OUTPUT row (the resampled result, not the photo); positions beyond the working image hold 0.0f (the mean
+// colour).  The layout is a template parameter: the 3-word instantiation holds no flag test, no mirror select and no
+// beyond-the-image branch, the 4-word one no origin.  A bad row (the host wrapper validates the table) reads and writes
+// nothing.  With Hs = oh the scale (float)H / (float)(int)Hs is (float)H / (float)oh: a 4-word row gives the 3-word
+// row's bits, an 8-word row {.., oh, ow, 0, 0} the 4-word row's, and a window the bits of the crop of the working image.
+template <int kWords>
+__global__ __launch_bounds__(256) void image_preprocess_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
+                                                               const int64_t* __restrict__ table, int flag_mask, int bgr,
+                                                               Norm nm, float* __restrict__ out, int oh, int ow) {
+  const int b = blockIdx.z, oy = blockIdx.y;
+  const int ox = blockIdx.x * 256 + threadIdx.x;
+  if (ox >= ow) return;
+  const PreRow r = read_row<kWords>(table, b, oh, ow);
+  if (!entry_ok(r.off, r.H, r.W, 3, src_bytes)) return;
+  if constexpr (kWords >= 4)
+    if ((r.flags & ~(int64_t)flag_mask) != 0) return;
+  if constexpr (kWords == 8)
+    if (r.Hs < 1 || r.Ws < 1 || r.Hs > 65535 || r.Ws > 65535 || r.wy < 0 || r.wx < 0 || r.wy >= r.Hs || r.wx >= r.Ws) return;
+  const InAxis ay{(float)r.H / (float)(int)r.Hs, (int)r.H, (int)r.Hs}, ax{(float)r.W / (float)(int)r.Ws, (int)r.W, (int)r.Ws};
+  int sx = ox;                                                       // the column of the unmirrored result
+  if constexpr (kWords >= 4) sx = (r.flags & PSEG_VIEW_MIRROR) ? ow - 1 - ox : ox;
+  const int Y = (int)r.wy + oy, X = (int)r.wx + sx;                  // position in the working image
+  const int64_t plane = (int64_t)oh * ow;
+  float* o = out + (int64_t)b * 3 * plane + (int64_t)oy * ow + ox;
+  if constexpr (kWords == 8) {
+    if (Y >= (int)r.Hs || X >= (int)r.Ws) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) o[k * plane] = 0.f;
+      return;
+    }
+  }
+  sample_store(src + r.off, r.W, ay, ax, Y, X, bgr, nm, o, plane);
+}
+
 // ------------------------------------------------------------------ decode
 constexpr int kDecodeLdsFloats = 12288;   // 48 KiB of probabilities per block
+
+// Floats per pixel of a probability map: a multiple of 4 (a class chunk is a run of 16-byte vectors), at least 8
+static inline int class_pad(int C) { return C <= 8 ? 8 : (C + 3) / 4 * 4; }
+
+// The running argmax over classes c .. c + 3 of v; classes >= C are padding
+__device__ __forceinline__ void scan_classes(const f32x4& v, int c, int C, float& best, int& bi) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (c + e < C && v[e] > best) {   // strict: the first index wins ties
+      best = v[e];
+      bi = c + e;
+    }
+  }
+}
+
+// Pixel o of an image whose mask starts at mb and whose colours start at rb (null: mask only)
+__device__ __forceinline__ void store_pixel(uint8_t* mb, uint8_t* rb, const uint8_t* lut, int64_t o, int bi) {
+  mb[o] = (uint8_t)bi;
+  if (rb) {
+    rb[3 * o] = lut[3 * bi];
+    rb[3 * o + 1] = lut[3 * bi + 1];
+    rb[3 * o + 2] = lut[3 * bi + 2];
+  }
+}
 
 template <int CR>
 __global__ __launch_bounds__(256) void seg_decode_kernel(const float* __restrict__ logits, int C, int CP, int h, int w, int TH,
@@ -225,10 +300,12 @@ __global__ __launch_bounds__(256) void seg_decode_kernel(const float* __restrict
 #pragma unroll
         for (int k = 0; k < CR / 4; ++k) {
           if (c0 + 4 * k < C) {
+            // scan_classes, spelt out: through the helper (in any form tried: by reference, by value, loop-free) hipcc
+            // allocates 10 more VGPRs for this kernel and both instantiations lose a wave per SIMD
             const f32x4 v = ly0 * Qa[k] + ly1 * Qb[k];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              if (c0 + 4 * k + e < C && v[e] > best) {   // strict: the first index wins ties
+              if (c0 + 4 * k + e < C && v[e] > best) {
                 best = v[e];
                 bi = c0 + 4 * k + e;
               }
@@ -236,52 +313,12 @@ __global__ __launch_bounds__(256) void seg_decode_kernel(const float* __restrict
           }
         }
       }
-      const int64_t o = (int64_t)oy * W + ox;
-      mb[o] = (uint8_t)bi;
-      if (rb) {
-        rb[3 * o] = lut[3 * bi];
-        rb[3 * o + 1] = lut[3 * bi + 1];
-        rb[3 * o + 2] = lut[3 * bi + 2];
-      }
+      store_pixel(mb, rb, lut, (int64_t)oy * W + ox, bi);
     }
   }
 }
 
 // ------------------------------------------------------------------ test-time ensembling
-// image_preprocess_kernel with a flag word per row {byte offset, H, W, flags}.  Bit 0: out[b,c,y,x] is the unflagged
-// value at column ow - 1 - x (the resampled result is mirrored, not the photo).  The arithmetic is that kernel's,
-// expression for expression, so an unflagged row gives its bits.
-__global__ __launch_bounds__(256) void image_preprocess_views_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
-                                                                     const int64_t* __restrict__ table, int flag_mask, int bgr,
-                                                                     Norm nm, float* __restrict__ out, int oh, int ow) {
-  const int b = blockIdx.z, oy = blockIdx.y;
-  const int ox = blockIdx.x * 256 + threadIdx.x;
-  if (ox >= ow) return;
-  const int64_t off = table[4 * b], H = table[4 * b + 1], W = table[4 * b + 2], flags = table[4 * b + 3];
-  if (!entry_ok(off, H, W, 3, src_bytes) || (flags & ~(int64_t)flag_mask) != 0) return;   // bad row: nothing read or written
-  const InAxis ay{(float)H / (float)oh, (int)H, oh}, ax{(float)W / (float)ow, (int)W, ow};
-  const int sx = (flags & PSEG_VIEW_MIRROR) ? ow - 1 - ox : ox;      // the column of the unmirrored result
-  int y0, y1, x0, x1;
-  float ly0, ly1, lx0, lx1;
-  taps(ay, oy, y0, y1, ly0, ly1);
-  taps(ax, sx, x0, x1, lx0, lx1);
-  const uint8_t* p = src + off;
-  const uint8_t* p00 = p + ((int64_t)y0 * W + x0) * 3;
-  const uint8_t* p01 = p + ((int64_t)y0 * W + x1) * 3;
-  const uint8_t* p10 = p + ((int64_t)y1 * W + x0) * 3;
-  const uint8_t* p11 = p + ((int64_t)y1 * W + x1) * 3;
-  const int64_t plane = (int64_t)oh * ow;
-  float* o = out + (int64_t)b * 3 * plane + (int64_t)oy * ow + ox;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int cs = bgr ? 2 - k : k;
-    const float v = ly0 * (lx0 * (float)p00[cs] + lx1 * (float)p01[cs]) + ly1 * (lx0 * (float)p10[cs] + lx1 * (float)p11[cs]);
-    float q = floorf(v + 0.5f);
-    q = q < 0.f ? 0.f : (q > 255.f ? 255.f : q);
-    o[k * plane] = (q - nm.mean[k]) / nm.std[k];
-  }
-}
-
 // A block owns PX consecutive pixels of one source row (PX a power of two, 4 * PX <= 256).  The logits of the run -- and,
 // with pairs, of the mirrored run of batch row B + b, stored un-mirrored -- go to LDS pixel-major (global reads: consecutive
 // lanes, consecutive x of one class plane); four lanes share a pixel's softmax; the tile is then exactly the run's
@@ -349,6 +386,24 @@ __device__ __forceinline__ bool map_ok(int64_t off, int64_t h, int64_t w, int B,
   return off >= 0 && (off & 3) == 0 && h >= 1 && w >= 1 && h <= 65535 && w <= 65535 && off + (int64_t)B * h * w * CP <= cap;
 }
 
+// What the two kernels that own OUTPUT tiles do before their loops: image blockIdx.z's table row and the block's tile of it.
+struct OutTile {
+  int64_t off, H, W;
+  int oy_base, ox_base, oy_end;
+};
+
+// -> false, for the whole block, when the row is bad or above the stated maximum (nothing is read or written) or the tile
+// lies outside the image (ragged batch)
+__device__ __forceinline__ bool out_tile(const int64_t* __restrict__ table, int64_t npix_cap, int Hmax, int Wmax, OutTile& tile) {
+  const int b = blockIdx.z;
+  tile.off = table[3 * b], tile.H = table[3 * b + 1], tile.W = table[3 * b + 2];
+  if (!entry_ok(tile.off, tile.H, tile.W, 1, npix_cap) || tile.H > Hmax || tile.W > Wmax) return false;
+  tile.oy_base = blockIdx.y * kEnsTileH, tile.ox_base = blockIdx.x * kEnsTileW;
+  if (tile.oy_base >= tile.H || tile.ox_base >= tile.W) return false;
+  tile.oy_end = min(tile.oy_base + kEnsTileH, (int)tile.H);
+  return true;
+}
+
 // A block owns a kEnsTileW x kEnsTileH rectangle of one image's pixels; a wave owns one row of it at a time (64 mask
 // bytes per store), a thread the pixels of its column in rows wave, wave + 4, ...  Per chunk of at most 32 classes the
 // bilinear samples of the S maps are summed in registers, then the running best is updated: classes are independent.
@@ -357,19 +412,16 @@ __global__ __launch_bounds__(256) void seg_decode_ensemble_kernel(const float* _
                                                                   const int64_t* __restrict__ table, int64_t npix_cap,
                                                                   int Hmax, int Wmax, uint8_t* __restrict__ mask,
                                                                   uint8_t* __restrict__ rgb, const uint8_t* __restrict__ lut) {
-  const int b = blockIdx.z;
-  const int64_t off = table[3 * b], H = table[3 * b + 1], W = table[3 * b + 2];
-  if (!entry_ok(off, H, W, 1, npix_cap) || H > Hmax || W > Wmax) return;       // bad row: nothing read or written
-  const int oy_base = blockIdx.y * kEnsTileH, ox = blockIdx.x * kEnsTileW + (threadIdx.x & 63);
-  if (oy_base >= H || blockIdx.x * kEnsTileW >= W) return;                     // ragged batch: block-uniform exit
+  OutTile tile;
+  if (!out_tile(table, npix_cap, Hmax, Wmax, tile)) return;
+  const int b = blockIdx.z, ox = tile.ox_base + (threadIdx.x & 63);
   for (int s = 0; s < S; ++s)                                                  // one bad map: no ensemble, nothing written
     if (!map_ok(maps[3 * s], maps[3 * s + 1], maps[3 * s + 2], B, CP, prob_floats)) return;
-  if (ox >= W) return;
+  if (ox >= tile.W) return;
   const int n4 = CP / 4;
-  uint8_t* mb = mask + off;
-  uint8_t* rb = rgb ? rgb + 3 * off : nullptr;
-  const int oy_end = min(oy_base + kEnsTileH, (int)H);
-  for (int oy = oy_base + (threadIdx.x >> 6); oy < oy_end; oy += 4) {
+  uint8_t* mb = mask + tile.off;
+  uint8_t* rb = rgb ? rgb + 3 * tile.off : nullptr;
+  for (int oy = tile.oy_base + (threadIdx.x >> 6); oy < tile.oy_end; oy += 4) {
     float best = -1.f;
     int bi = 0;
     for (int c0 = 0; c0 < CP; c0 += 32) {
@@ -379,7 +431,7 @@ __global__ __launch_bounds__(256) void seg_decode_ensemble_kernel(const float* _
       for (int s = 0; s < S; ++s) {
         const int64_t moff = maps[3 * s];
         const int h = (int)maps[3 * s + 1], w = (int)maps[3 * s + 2];
-        const InAxis ay{(float)h / (float)H, h, (int)H}, ax{(float)w / (float)W, w, (int)W};
+        const InAxis ay{(float)h / (float)tile.H, h, (int)tile.H}, ax{(float)w / (float)tile.W, w, (int)tile.W};
         int y0, y1, x0, x1;
         float ly0, ly1, lx0, lx1;
         taps(ay, oy, y0, y1, ly0, ly1);
@@ -394,25 +446,10 @@ __global__ __launch_bounds__(256) void seg_decode_ensemble_kernel(const float* _
           if (c0 + 4 * k < CP) acc[k] += ly0 * (lx0 * a0[k] + lx1 * a1[k]) + ly1 * (lx0 * b0[k] + lx1 * b1[k]);
       }
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        if (c0 + 4 * k < CP) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            if (c0 + 4 * k + e < C && acc[k][e] > best) {   // strict: the first index wins ties
-              best = acc[k][e];
-              bi = c0 + 4 * k + e;
-            }
-          }
-        }
-      }
+      for (int k = 0; k < 8; ++k)
+        if (c0 + 4 * k < CP) scan_classes(acc[k], c0 + 4 * k, C, best, bi);
     }
-    const int64_t o = (int64_t)oy * W + ox;
-    mb[o] = (uint8_t)bi;
-    if (rb) {
-      rb[3 * o] = lut[3 * bi];
-      rb[3 * o + 1] = lut[3 * bi + 1];
-      rb[3 * o + 2] = lut[3 * bi + 2];
-    }
+    store_pixel(mb, rb, lut, (int64_t)oy * tile.W + ox, bi);
   }
 }
 
@@ -440,49 +477,6 @@ __device__ __forceinline__ int win_cover(int p, int in, int win, const FastDiv& 
   return c;
 }
 
-// image_preprocess_views_kernel with rows {byte offset, H, W, flags, Hs, Ws, y0, x0}: the output row is the oh x ow window
-// at (y0, x0) of the photo resampled to Hs x Ws; positions beyond Hs x Ws hold 0.0f (the mean colour).  The arithmetic is
-// that kernel's, expression for expression: a row {.., oh, ow, 0, 0} gives its bits, and a window gives the bits of the
-// crop of the whole working image.
-__global__ __launch_bounds__(256) void image_preprocess_windows_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
-                                                                       const int64_t* __restrict__ table, int flag_mask, int bgr,
-                                                                       Norm nm, float* __restrict__ out, int oh, int ow) {
-  const int b = blockIdx.z, oy = blockIdx.y;
-  const int ox = blockIdx.x * 256 + threadIdx.x;
-  if (ox >= ow) return;
-  const int64_t* t = table + 8 * (int64_t)b;
-  const int64_t off = t[0], H = t[1], W = t[2], flags = t[3], Hs = t[4], Ws = t[5], wy = t[6], wx = t[7];
-  if (!entry_ok(off, H, W, 3, src_bytes) || (flags & ~(int64_t)flag_mask) != 0) return;   // bad row: nothing read or written
-  if (Hs < 1 || Ws < 1 || Hs > 65535 || Ws > 65535 || wy < 0 || wx < 0 || wy >= Hs || wx >= Ws) return;
-  const InAxis ay{(float)H / (float)(int)Hs, (int)H, (int)Hs}, ax{(float)W / (float)(int)Ws, (int)W, (int)Ws};
-  const int sx = (flags & PSEG_VIEW_MIRROR) ? ow - 1 - ox : ox;      // the column of the unmirrored window
-  const int Y = (int)wy + oy, X = (int)wx + sx;                      // position in the working image
-  const int64_t plane = (int64_t)oh * ow;
-  float* o = out + (int64_t)b * 3 * plane + (int64_t)oy * ow + ox;
-  if (Y >= (int)Hs || X >= (int)Ws) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[k * plane] = 0.f;
-    return;
-  }
-  int y0, y1, x0, x1;
-  float ly0, ly1, lx0, lx1;
-  taps(ay, Y, y0, y1, ly0, ly1);
-  taps(ax, X, x0, x1, lx0, lx1);
-  const uint8_t* p = src + off;
-  const uint8_t* p00 = p + ((int64_t)y0 * W + x0) * 3;
-  const uint8_t* p01 = p + ((int64_t)y0 * W + x1) * 3;
-  const uint8_t* p10 = p + ((int64_t)y1 * W + x0) * 3;
-  const uint8_t* p11 = p + ((int64_t)y1 * W + x1) * 3;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int cs = bgr ? 2 - k : k;
-    const float v = ly0 * (lx0 * (float)p00[cs] + lx1 * (float)p01[cs]) + ly1 * (lx0 * (float)p10[cs] + lx1 * (float)p11[cs]);
-    float q = floorf(v + 0.5f);
-    q = q < 0.f ? 0.f : (q > 255.f ? 255.f : q);
-    o[k * plane] = (q - nm.mean[k]) / nm.std[k];
-  }
-}
-
 // One bilinear tap pair of an output row or column at one scale: the upper tap's weight and, for the lower and the upper
 // tap, the windows that cover its working-image coordinate (win_cover); cnt = lower count | upper count << 2.
 struct WinTaps {
@@ -506,11 +500,9 @@ __global__ __launch_bounds__(256) void seg_decode_windows_kernel(const float* __
   __shared__ WinTaps ent[kEnsMaxMaps * kEnt];
   __shared__ int64_t goff[kEnsMaxMaps];
   __shared__ int gnx[kEnsMaxMaps];
-  const int b = blockIdx.z;
-  const int64_t off = table[3 * b], H = table[3 * b + 1], W = table[3 * b + 2];
-  if (!entry_ok(off, H, W, 1, npix_cap) || H > Hmax || W > Wmax) return;       // bad row: nothing read or written
-  const int oy_base = blockIdx.y * kEnsTileH, ox_base = blockIdx.x * kEnsTileW;
-  if (oy_base >= H || ox_base >= W) return;                                    // ragged batch: block-uniform exit
+  OutTile tile;
+  if (!out_tile(table, npix_cap, Hmax, Wmax, tile)) return;
+  const int b = blockIdx.z, oy_base = tile.oy_base, ox_base = tile.ox_base;
   for (int s = 0; s < S; ++s) {                                                // one bad group: this photo is not written
     const int64_t* g = groups + 3 * ((int64_t)s * B + b);
     const int64_t go = g[0], Hs = g[1], Ws = g[2];
@@ -524,19 +516,19 @@ __global__ __launch_bounds__(256) void seg_decode_windows_kernel(const float* __
     const int64_t* g = groups + 3 * ((int64_t)s * B + b);
     const bool is_row = r < kEnsTileH;
     const int o = is_row ? oy_base + r : ox_base + r - kEnsTileH;
-    const int in = (int)(is_row ? g[1] : g[2]), outn = (int)(is_row ? H : W), win = is_row ? h : w;
+    const int in = (int)(is_row ? g[1] : g[2]), outn = (int)(is_row ? tile.H : tile.W), win = is_row ? h : w;
     const FastDiv st = is_row ? dsy : dsx;
-    WinTaps t{0.f, 0, {0, 0, 0, 0, 0, 0}};
+    WinTaps wt{0.f, 0, {0, 0, 0, 0, 0, 0}};
     if (o < outn) {
       const InAxis a{(float)in / (float)outn, in, outn};
       int i0, i1;
       float l0, l1;
       taps(a, o, i0, i1, l0, l1);
       const int n = win_count(in, win, st);
-      t.l1 = l1;
-      t.cnt = win_cover(i0, in, win, st, n, t.win) | win_cover(i1, in, win, st, n, t.win + 3) << 2;
+      wt.l1 = l1;
+      wt.cnt = win_cover(i0, in, win, st, n, wt.win) | win_cover(i1, in, win, st, n, wt.win + 3) << 2;
     }
-    ent[e] = t;
+    ent[e] = wt;
     if (r == 0) {
       goff[s] = g[0];
       gnx[s] = win_count((int)g[2], w, dsx);
@@ -544,12 +536,11 @@ __global__ __launch_bounds__(256) void seg_decode_windows_kernel(const float* __
   }
   __syncthreads();
   const int col = tid & 63, ox = ox_base + col;
-  if (ox >= W) return;
+  if (ox >= tile.W) return;
   const int n4 = CP / 4;
-  uint8_t* mb = mask + off;
-  uint8_t* rb = rgb ? rgb + 3 * off : nullptr;
-  const int oy_end = min(oy_base + kEnsTileH, (int)H);
-  for (int oy = oy_base + (tid >> 6); oy < oy_end; oy += 4) {
+  uint8_t* mb = mask + tile.off;
+  uint8_t* rb = rgb ? rgb + 3 * tile.off : nullptr;
+  for (int oy = oy_base + (tid >> 6); oy < tile.oy_end; oy += 4) {
     float best = -1.f;
     int bi = 0;
     for (int c0 = 0; c0 < CP; c0 += 32) {
@@ -591,26 +582,52 @@ __global__ __launch_bounds__(256) void seg_decode_windows_kernel(const float* __
         }
       }
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        if (c0 + 4 * k < CP) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            if (c0 + 4 * k + e < C && acc[k][e] > best) {   // strict: the first index wins ties
-              best = acc[k][e];
-              bi = c0 + 4 * k + e;
-            }
-          }
-        }
-      }
+      for (int k = 0; k < 8; ++k)
+        if (c0 + 4 * k < CP) scan_classes(acc[k], c0 + 4 * k, C, best, bi);
     }
-    const int64_t o = (int64_t)oy * W + ox;
-    mb[o] = (uint8_t)bi;
-    if (rb) {
-      rb[3 * o] = lut[3 * bi];
-      rb[3 * o + 1] = lut[3 * bi + 1];
-      rb[3 * o + 2] = lut[3 * bi + 2];
-    }
+    store_pixel(mb, rb, lut, (int64_t)oy * tile.W + ox, bi);
   }
+}
+
+// ------------------------------------------------------------------ host checks shared by the entry points (name: theirs)
+// kWords = 3: `rows` is the batch and there is no flag word; `what` names the output ("output" / "window")
+template <int kWords>
+static int launch_preprocess(const char* name, const char* what, const uint8_t* src, int64_t src_bytes, const int64_t* table,
+                             int rows, int flag_mask, int bgr, const Norm& nm, float* out, int oh, int ow, void* stream) {
+  PSEG_REQUIRE(src && table && out, "%s: null pointer", name);
+  if (kWords == 3) {
+    PSEG_REQUIRE(rows >= 1 && rows <= 65535, "%s: batch %d outside [1, 65535]", name, rows);
+  } else {
+    PSEG_REQUIRE((flag_mask & ~PSEG_VIEW_MIRROR) == 0, "%s: unknown flag bits 0x%x (known: PSEG_VIEW_MIRROR = 1)", name,
+                 (unsigned)(flag_mask & ~PSEG_VIEW_MIRROR));
+    PSEG_REQUIRE(rows >= 1 && rows <= 65535, "%s: %d table rows outside [1, 65535]", name, rows);
+  }
+  PSEG_REQUIRE(oh >= 1 && oh <= 65535 && ow >= 1 && ow <= 65535, "%s: %s size %dx%d outside [1, 65535]", name, what, oh, ow);
+  PSEG_REQUIRE(src_bytes >= 3, "%s: src_bytes %lld holds no pixel", name, (long long)src_bytes);
+  PSEG_REQUIRE(nm.std[0] != 0.f && nm.std[1] != 0.f && nm.std[2] != 0.f, "%s: std must be non-zero", name);
+  hipLaunchKernelGGL(image_preprocess_kernel<kWords>, dim3(cdiv(ow, 256), oh, rows), dim3(256), 0, (hipStream_t)stream, src,
+                     src_bytes, table, flag_mask, bgr ? 1 : 0, nm, out, oh, ow);
+  PSEG_LAUNCH_CHECK();
+  return PSEG_OK;
+}
+
+// The decode entry points' checks after their null-pointer test; S maps or scales (`noun`), none for the plain decode
+static int check_decode(const char* name, const uint8_t* rgb, const uint8_t* lut, int S, const char* noun, int C, int B) {
+  PSEG_REQUIRE((rgb == nullptr) == (lut == nullptr), "%s: rgb and lut come together", name);
+  if (noun) PSEG_REQUIRE(S >= 1 && S <= kEnsMaxMaps, "%s: %d %s; 1 <= S <= %d supported", name, S, noun, kEnsMaxMaps);
+  PSEG_REQUIRE(C >= 1 && C <= 256, "%s: %d classes; 1 <= C <= 256 supported (the mask is uint8)", name, C);
+  PSEG_REQUIRE(B >= 1 && B <= 65535, "%s: batch %d outside [1, 65535]", name, B);
+  return PSEG_OK;
+}
+
+// ... and those of the two that read the packed probability buffer and size their grid by the largest image
+static int check_packed(const char* name, const float* prob, int64_t prob_floats, int64_t npix_total, int Hmax, int Wmax) {
+  PSEG_REQUIRE(Hmax >= 1 && Wmax >= 1 && Hmax <= 65535 && Wmax <= 65535, "%s: largest image %dx%d outside [1, 65535]", name, Hmax,
+               Wmax);
+  PSEG_REQUIRE(((uintptr_t)prob & 15) == 0, "%s: the probability buffer must be 16-byte aligned", name);
+  PSEG_REQUIRE(prob_floats >= 8 && npix_total >= 1, "%s: prob_floats %lld, npix_total %lld", name, (long long)prob_floats,
+               (long long)npix_total);
+  return PSEG_OK;
 }
 
 }  // namespace pseg
@@ -621,28 +638,18 @@ extern "C" {
 
 int pseg_image_preprocess(const uint8_t* src, int64_t src_bytes, const int64_t* table, int B, int bgr, float mean0, float mean1,
                           float mean2, float std0, float std1, float std2, float* out, int oh, int ow, void* stream) {
-  PSEG_REQUIRE(src && table && out, "image_preprocess: null pointer");
-  PSEG_REQUIRE(B >= 1 && B <= 65535, "image_preprocess: batch %d outside [1, 65535]", B);
-  PSEG_REQUIRE(oh >= 1 && oh <= 65535 && ow >= 1 && ow <= 65535, "image_preprocess: output size %dx%d outside [1, 65535]", oh, ow);
-  PSEG_REQUIRE(src_bytes >= 3, "image_preprocess: src_bytes %lld holds no pixel", (long long)src_bytes);
-  PSEG_REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "image_preprocess: std must be non-zero");
-  Norm nm{{mean0, mean1, mean2}, {std0, std1, std2}};
-  hipLaunchKernelGGL(image_preprocess_kernel, dim3(cdiv(ow, 256), oh, B), dim3(256), 0, (hipStream_t)stream, src, src_bytes,
-                     table, bgr ? 1 : 0, nm, out, oh, ow);
-  PSEG_LAUNCH_CHECK();
-  return PSEG_OK;
+  return launch_preprocess<3>("image_preprocess", "output", src, src_bytes, table, B, 0, bgr,
+                              Norm{{mean0, mean1, mean2}, {std0, std1, std2}}, out, oh, ow, stream);
 }
 
 int pseg_seg_decode(const float* logits, int B, int C, int h, int w, const int64_t* table, int64_t npix_total, uint8_t* mask,
                     uint8_t* rgb, const uint8_t* lut, void* stream) {
   PSEG_REQUIRE(logits && table && mask, "seg_decode: null pointer");
-  PSEG_REQUIRE((rgb == nullptr) == (lut == nullptr), "seg_decode: rgb and lut come together");
-  PSEG_REQUIRE(C >= 1 && C <= 256, "seg_decode: %d classes; 1 <= C <= 256 supported (the mask is uint8)", C);
-  PSEG_REQUIRE(B >= 1 && B <= 65535, "seg_decode: batch %d outside [1, 65535]", B);
+  if (int e = check_decode("seg_decode", rgb, lut, 0, nullptr, C, B)) return e;
   PSEG_REQUIRE(h >= 1 && w >= 1 && h <= 65535 && w <= 65535, "seg_decode: logit size %dx%d outside [1, 65535]", h, w);
   PSEG_REQUIRE(npix_total >= 1, "seg_decode: npix_total %lld", (long long)npix_total);
   // tile: TW x TH source pixels (+1 halo row / column) whose CP probabilities fit kDecodeLdsFloats; as wide as possible
-  const int CP = C <= 8 ? 8 : (C + 3) / 4 * 4;
+  const int CP = class_pad(C);
   const int per_px = kDecodeLdsFloats / CP;
   int TW = 32;
   while (TW > 1 && per_px / (TW + 1) < TW / 2 + 1) TW /= 2;
@@ -664,19 +671,8 @@ int pseg_seg_decode(const float* logits, int B, int C, int h, int w, const int64
 int pseg_image_preprocess_views(const uint8_t* src, int64_t src_bytes, const int64_t* table, int rows, int flag_mask, int bgr,
                                 float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh,
                                 int ow, void* stream) {
-  PSEG_REQUIRE(src && table && out, "image_preprocess_views: null pointer");
-  PSEG_REQUIRE((flag_mask & ~PSEG_VIEW_MIRROR) == 0, "image_preprocess_views: unknown flag bits 0x%x (known: PSEG_VIEW_MIRROR = 1)",
-               (unsigned)(flag_mask & ~PSEG_VIEW_MIRROR));
-  PSEG_REQUIRE(rows >= 1 && rows <= 65535, "image_preprocess_views: %d table rows outside [1, 65535]", rows);
-  PSEG_REQUIRE(oh >= 1 && oh <= 65535 && ow >= 1 && ow <= 65535, "image_preprocess_views: output size %dx%d outside [1, 65535]", oh,
-               ow);
-  PSEG_REQUIRE(src_bytes >= 3, "image_preprocess_views: src_bytes %lld holds no pixel", (long long)src_bytes);
-  PSEG_REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "image_preprocess_views: std must be non-zero");
-  Norm nm{{mean0, mean1, mean2}, {std0, std1, std2}};
-  hipLaunchKernelGGL(image_preprocess_views_kernel, dim3(cdiv(ow, 256), oh, rows), dim3(256), 0, (hipStream_t)stream, src,
-                     src_bytes, table, flag_mask, bgr ? 1 : 0, nm, out, oh, ow);
-  PSEG_LAUNCH_CHECK();
-  return PSEG_OK;
+  return launch_preprocess<4>("image_preprocess_views", "output", src, src_bytes, table, rows, flag_mask, bgr,
+                              Norm{{mean0, mean1, mean2}, {std0, std1, std2}}, out, oh, ow, stream);
 }
 
 int pseg_softmax_views(const float* logits, int B, int pairs, int C, int h, int w, float* prob, int64_t prob_offset,
@@ -686,7 +682,7 @@ int pseg_softmax_views(const float* logits, int B, int pairs, int C, int h, int 
   PSEG_REQUIRE(C >= 1 && C <= 256, "softmax_views: %d classes; 1 <= C <= 256 supported", C);
   PSEG_REQUIRE(B >= 1 && B <= 65535, "softmax_views: batch %d outside [1, 65535]", B);
   PSEG_REQUIRE(h >= 1 && w >= 1 && h <= 65535 && w <= 65535, "softmax_views: logit size %dx%d outside [1, 65535]", h, w);
-  const int CP = C <= 8 ? 8 : (C + 3) / 4 * 4;
+  const int CP = class_pad(C);
   PSEG_REQUIRE(((uintptr_t)prob & 15) == 0 && prob_offset >= 0 && (prob_offset & 3) == 0,
                "softmax_views: the probability buffer and the map's offset must be 16-byte aligned");
   PSEG_REQUIRE(prob_offset + (int64_t)B * h * w * CP <= prob_floats,
@@ -708,16 +704,9 @@ int pseg_seg_decode_ensemble(const float* prob, int64_t prob_floats, const int64
                              int64_t npix_total, int Hmax, int Wmax, uint8_t* mask, uint8_t* rgb, const uint8_t* lut,
                              void* stream) {
   PSEG_REQUIRE(prob && maps && table && mask, "seg_decode_ensemble: null pointer");
-  PSEG_REQUIRE((rgb == nullptr) == (lut == nullptr), "seg_decode_ensemble: rgb and lut come together");
-  PSEG_REQUIRE(S >= 1 && S <= kEnsMaxMaps, "seg_decode_ensemble: %d maps; 1 <= S <= %d supported", S, kEnsMaxMaps);
-  PSEG_REQUIRE(C >= 1 && C <= 256, "seg_decode_ensemble: %d classes; 1 <= C <= 256 supported (the mask is uint8)", C);
-  PSEG_REQUIRE(B >= 1 && B <= 65535, "seg_decode_ensemble: batch %d outside [1, 65535]", B);
-  PSEG_REQUIRE(Hmax >= 1 && Wmax >= 1 && Hmax <= 65535 && Wmax <= 65535, "seg_decode_ensemble: largest image %dx%d outside [1, 65535]",
-               Hmax, Wmax);
-  PSEG_REQUIRE(((uintptr_t)prob & 15) == 0, "seg_decode_ensemble: the probability buffer must be 16-byte aligned");
-  PSEG_REQUIRE(prob_floats >= 8 && npix_total >= 1, "seg_decode_ensemble: prob_floats %lld, npix_total %lld", (long long)prob_floats,
-               (long long)npix_total);
-  const int CP = C <= 8 ? 8 : (C + 3) / 4 * 4;
+  if (int e = check_decode("seg_decode_ensemble", rgb, lut, S, "maps", C, B)) return e;
+  if (int e = check_packed("seg_decode_ensemble", prob, prob_floats, npix_total, Hmax, Wmax)) return e;
+  const int CP = class_pad(C);
   hipLaunchKernelGGL(seg_decode_ensemble_kernel, dim3(cdiv(Wmax, kEnsTileW), cdiv(Hmax, kEnsTileH), B), dim3(256), 0,
                      (hipStream_t)stream, prob, prob_floats, maps, S, B, C, CP, table, npix_total, Hmax, Wmax, mask, rgb, lut);
   PSEG_LAUNCH_CHECK();
@@ -727,39 +716,20 @@ int pseg_seg_decode_ensemble(const float* prob, int64_t prob_floats, const int64
 int pseg_image_preprocess_windows(const uint8_t* src, int64_t src_bytes, const int64_t* table, int rows, int flag_mask, int bgr,
                                   float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh,
                                   int ow, void* stream) {
-  PSEG_REQUIRE(src && table && out, "image_preprocess_windows: null pointer");
-  PSEG_REQUIRE((flag_mask & ~PSEG_VIEW_MIRROR) == 0,
-               "image_preprocess_windows: unknown flag bits 0x%x (known: PSEG_VIEW_MIRROR = 1)",
-               (unsigned)(flag_mask & ~PSEG_VIEW_MIRROR));
-  PSEG_REQUIRE(rows >= 1 && rows <= 65535, "image_preprocess_windows: %d table rows outside [1, 65535]", rows);
-  PSEG_REQUIRE(oh >= 1 && oh <= 65535 && ow >= 1 && ow <= 65535, "image_preprocess_windows: window size %dx%d outside [1, 65535]",
-               oh, ow);
-  PSEG_REQUIRE(src_bytes >= 3, "image_preprocess_windows: src_bytes %lld holds no pixel", (long long)src_bytes);
-  PSEG_REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, "image_preprocess_windows: std must be non-zero");
-  Norm nm{{mean0, mean1, mean2}, {std0, std1, std2}};
-  hipLaunchKernelGGL(image_preprocess_windows_kernel, dim3(cdiv(ow, 256), oh, rows), dim3(256), 0, (hipStream_t)stream, src,
-                     src_bytes, table, flag_mask, bgr ? 1 : 0, nm, out, oh, ow);
-  PSEG_LAUNCH_CHECK();
-  return PSEG_OK;
+  return launch_preprocess<8>("image_preprocess_windows", "window", src, src_bytes, table, rows, flag_mask, bgr,
+                              Norm{{mean0, mean1, mean2}, {std0, std1, std2}}, out, oh, ow, stream);
 }
 
 int pseg_seg_decode_windows(const float* prob, int64_t prob_floats, const int64_t* groups, int S, int B, int C, int h, int w, int sy,
                             int sx, const int64_t* table, int64_t npix_total, int Hmax, int Wmax, uint8_t* mask, uint8_t* rgb,
                             const uint8_t* lut, void* stream) {
   PSEG_REQUIRE(prob && groups && table && mask, "seg_decode_windows: null pointer");
-  PSEG_REQUIRE((rgb == nullptr) == (lut == nullptr), "seg_decode_windows: rgb and lut come together");
-  PSEG_REQUIRE(S >= 1 && S <= kEnsMaxMaps, "seg_decode_windows: %d scales; 1 <= S <= %d supported", S, kEnsMaxMaps);
-  PSEG_REQUIRE(C >= 1 && C <= 256, "seg_decode_windows: %d classes; 1 <= C <= 256 supported (the mask is uint8)", C);
-  PSEG_REQUIRE(B >= 1 && B <= 65535, "seg_decode_windows: batch %d outside [1, 65535]", B);
+  if (int e = check_decode("seg_decode_windows", rgb, lut, S, "scales", C, B)) return e;
   PSEG_REQUIRE(h >= 1 && w >= 1 && h <= 65535 && w <= 65535, "seg_decode_windows: window size %dx%d outside [1, 65535]", h, w);
   PSEG_REQUIRE(sy >= (h + 1) / 2 && sy <= h && sx >= (w + 1) / 2 && sx <= w,
                "seg_decode_windows: stride %dx%d outside [ceil(h/2), h] x [ceil(w/2), w] of the %dx%d window", sy, sx, h, w);
-  PSEG_REQUIRE(Hmax >= 1 && Wmax >= 1 && Hmax <= 65535 && Wmax <= 65535, "seg_decode_windows: largest image %dx%d outside [1, 65535]",
-               Hmax, Wmax);
-  PSEG_REQUIRE(((uintptr_t)prob & 15) == 0, "seg_decode_windows: the probability buffer must be 16-byte aligned");
-  PSEG_REQUIRE(prob_floats >= 8 && npix_total >= 1, "seg_decode_windows: prob_floats %lld, npix_total %lld", (long long)prob_floats,
-               (long long)npix_total);
-  const int CP = C <= 8 ? 8 : (C + 3) / 4 * 4;
+  if (int e = check_packed("seg_decode_windows", prob, prob_floats, npix_total, Hmax, Wmax)) return e;
+  const int CP = class_pad(C);
   hipLaunchKernelGGL(seg_decode_windows_kernel, dim3(cdiv(Wmax, kEnsTileW), cdiv(Hmax, kEnsTileH), B), dim3(256), 0,
                      (hipStream_t)stream, prob, prob_floats, groups, S, B, C, CP, h, w, FastDiv((uint32_t)sy), FastDiv((uint32_t)sx),
                      table, npix_total, Hmax, Wmax, mask, rgb, lut);

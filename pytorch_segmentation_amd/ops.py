@@ -1210,17 +1210,36 @@ def argmax(logits):
     return mask
 
 
+def _image_preprocess(entry, words, src, table, oh, ow, mean, std, bgr, flag_mask=None):
+    """the three preprocess entry points: table rows of `words` int64; flag_mask None: the entry point takes no flags"""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
+    assert table.device == src.device and table.dtype == torch.int64 and table.is_contiguous() and table.dim() == 2
+    assert table.shape[1] == words and len(mean) == 3 and len(std) == 3
+    R = table.shape[0]
+    out = torch.empty(R, 3, oh, ow, dtype=torch.float32, device=src.device)
+    flags = () if flag_mask is None else (int(flag_mask),)
+    _lib.call(entry, src.data_ptr(), src.numel(), table.data_ptr(), R, *flags, int(bool(bgr)),
+              *[float(m) for m in mean], *[float(v) for v in std], out.data_ptr(), oh, ow, _stream())
+    return out
+
+
+def _decode_out(dev, npix_total, lut, out):
+    """the decode entry points' output: validates (or allocates) out and the lut -> (out, mask, rgb or None)"""
+    nbytes = npix_total * (1 if lut is None else 4)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    assert out.device == dev and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == nbytes
+    mask, rgb = out[:npix_total], None
+    if lut is not None:
+        assert lut.device == dev and lut.dtype == torch.uint8 and lut.is_contiguous() and lut.shape == (256, 3)
+        rgb = out[npix_total:].view(npix_total, 3)
+    return out, mask, rgb
+
+
 def image_preprocess(src, table, oh, ow, mean, std, bgr):
     """Ragged batch of uint8 HWC photos -> fp32 NCHW model input [B,3,oh,ow] (pseg_image_preprocess).  src: flat uint8
     device tensor, photos back to back; table: int64 device tensor [B,3] of {byte offset, H, W} (validated by the caller)."""
-    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
-    assert table.device == src.device and table.dtype == torch.int64 and table.is_contiguous() and table.dim() == 2
-    assert table.shape[1] == 3 and len(mean) == 3 and len(std) == 3
-    B = table.shape[0]
-    out = torch.empty(B, 3, oh, ow, dtype=torch.float32, device=src.device)
-    _lib.call('pseg_image_preprocess', src.data_ptr(), src.numel(), table.data_ptr(), B, int(bool(bgr)),
-              *[float(m) for m in mean], *[float(v) for v in std], out.data_ptr(), oh, ow, _stream())
-    return out
+    return _image_preprocess('pseg_image_preprocess', 3, src, table, oh, ow, mean, std, bgr)
 
 
 def seg_decode(logits, table, npix_total, lut=None, out=None):
@@ -1233,14 +1252,7 @@ def seg_decode(logits, table, npix_total, lut=None, out=None):
     assert table.device == logits.device and table.dtype == torch.int64 and table.is_contiguous()
     assert table.shape == (logits.shape[0], 3)
     B, C, h, w = logits.shape
-    nbytes = npix_total * (1 if lut is None else 4)
-    if out is None:
-        out = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
-    assert out.device == logits.device and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == nbytes
-    mask, rgb = out[:npix_total], None
-    if lut is not None:
-        assert lut.device == logits.device and lut.dtype == torch.uint8 and lut.is_contiguous() and lut.shape == (256, 3)
-        rgb = out[npix_total:].view(npix_total, 3)
+    out, mask, rgb = _decode_out(logits.device, npix_total, lut, out)
     _lib.call('pseg_seg_decode', logits.data_ptr(), B, C, h, w, table.data_ptr(), npix_total, mask.data_ptr(), _ptr(rgb),
               _ptr(lut), _stream())
     return mask, rgb
@@ -1260,14 +1272,7 @@ def image_preprocess_views(src, table, oh, ow, mean, std, bgr, flag_mask=VIEW_MI
     [R,4] of {byte offset, H, W, flags}, several rows may name one photo, -> fp32 [R,3,oh,ow].  A row flagged VIEW_MIRROR
     is the unflagged result flipped along x, bit for bit; a row with flags 0 is image_preprocess's, bit for bit.
     flag_mask: the flag bits the rows use -- unknown bits are refused, rows with bits outside it are skipped."""
-    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
-    assert table.device == src.device and table.dtype == torch.int64 and table.is_contiguous() and table.dim() == 2
-    assert table.shape[1] == 4 and len(mean) == 3 and len(std) == 3
-    R = table.shape[0]
-    out = torch.empty(R, 3, oh, ow, dtype=torch.float32, device=src.device)
-    _lib.call('pseg_image_preprocess_views', src.data_ptr(), src.numel(), table.data_ptr(), R, int(flag_mask), int(bool(bgr)),
-              *[float(m) for m in mean], *[float(v) for v in std], out.data_ptr(), oh, ow, _stream())
-    return out
+    return _image_preprocess('pseg_image_preprocess_views', 4, src, table, oh, ow, mean, std, bgr, flag_mask)
 
 
 def softmax_views(logits, prob, offset, pairs=False):
@@ -1295,14 +1300,7 @@ def seg_decode_ensemble(prob, maps, B, C, table, npix_total, max_hw, lut=None, o
     assert maps.device == prob.device and maps.dtype == torch.int64 and maps.is_contiguous()
     assert maps.dim() == 2 and maps.shape[1] == 3
     assert table.device == prob.device and table.dtype == torch.int64 and table.is_contiguous() and table.shape == (B, 3)
-    nbytes = npix_total * (1 if lut is None else 4)
-    if out is None:
-        out = torch.empty(nbytes, dtype=torch.uint8, device=prob.device)
-    assert out.device == prob.device and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == nbytes
-    mask, rgb = out[:npix_total], None
-    if lut is not None:
-        assert lut.device == prob.device and lut.dtype == torch.uint8 and lut.is_contiguous() and lut.shape == (256, 3)
-        rgb = out[npix_total:].view(npix_total, 3)
+    out, mask, rgb = _decode_out(prob.device, npix_total, lut, out)
     _lib.call('pseg_seg_decode_ensemble', prob.data_ptr(), prob.numel(), maps.data_ptr(), maps.shape[0], B, C, table.data_ptr(),
               npix_total, int(max_hw[0]), int(max_hw[1]), mask.data_ptr(), _ptr(rgb), _ptr(lut), _stream())
     return mask, rgb
@@ -1325,14 +1323,7 @@ def image_preprocess_windows(src, table, oh, ow, mean, std, bgr, flag_mask=VIEW_
     image_preprocess_views' row, bit for bit; a window is the crop of the whole working image, bit for bit.  Rows whose
     photo leaves src, with Hs / Ws outside [1, 65535], an origin outside the working image or flag bits outside flag_mask
     are skipped."""
-    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1
-    assert table.device == src.device and table.dtype == torch.int64 and table.is_contiguous() and table.dim() == 2
-    assert table.shape[1] == 8 and len(mean) == 3 and len(std) == 3
-    R = table.shape[0]
-    out = torch.empty(R, 3, oh, ow, dtype=torch.float32, device=src.device)
-    _lib.call('pseg_image_preprocess_windows', src.data_ptr(), src.numel(), table.data_ptr(), R, int(flag_mask), int(bool(bgr)),
-              *[float(m) for m in mean], *[float(v) for v in std], out.data_ptr(), oh, ow, _stream())
-    return out
+    return _image_preprocess('pseg_image_preprocess_windows', 8, src, table, oh, ow, mean, std, bgr, flag_mask)
 
 
 def seg_decode_windows(prob, groups, B, C, window_hw, stride_hw, table, npix_total, max_hw, lut=None, out=None):
@@ -1346,14 +1337,7 @@ def seg_decode_windows(prob, groups, B, C, window_hw, stride_hw, table, npix_tot
     assert groups.device == prob.device and groups.dtype == torch.int64 and groups.is_contiguous()
     assert groups.dim() == 3 and groups.shape[1:] == (B, 3)
     assert table.device == prob.device and table.dtype == torch.int64 and table.is_contiguous() and table.shape == (B, 3)
-    nbytes = npix_total * (1 if lut is None else 4)
-    if out is None:
-        out = torch.empty(nbytes, dtype=torch.uint8, device=prob.device)
-    assert out.device == prob.device and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == nbytes
-    mask, rgb = out[:npix_total], None
-    if lut is not None:
-        assert lut.device == prob.device and lut.dtype == torch.uint8 and lut.is_contiguous() and lut.shape == (256, 3)
-        rgb = out[npix_total:].view(npix_total, 3)
+    out, mask, rgb = _decode_out(prob.device, npix_total, lut, out)
     _lib.call('pseg_seg_decode_windows', prob.data_ptr(), prob.numel(), groups.data_ptr(), groups.shape[0], B, C,
               int(window_hw[0]), int(window_hw[1]), int(stride_hw[0]), int(stride_hw[1]), table.data_ptr(), npix_total,
               int(max_hw[0]), int(max_hw[1]), mask.data_ptr(), _ptr(rgb), _ptr(lut), _stream())

@@ -171,8 +171,7 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
         slide_scales([], scales)                               # the scales alone: finite, > 0, at most 8
     photos = [_photo(im) for im in imgs]
     if not photos:
-        empty = ([], []) if colors is not None else []
-        return empty if not regions else (empty + ([],) if colors is not None else (empty, []))
+        return _result([], None if colors is None else [], None, post)
     device = next(model.parameters()).device
     if device.type != 'cuda':
         raise RuntimeError('inference() runs on the HIP path: move the model to the GPU first')
@@ -184,50 +183,83 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
         if B * (2 if flip else 1) > 65535:
             raise ValueError('%d photos x %d views exceed 65535 rows per launch' % (B, 2 if flip else 1))
         return _inference_ensemble(model, photos, h, w, sizes, flip, mean, std, bgr, half, colors, device, post)
-    sizes = np.array([(H, W) for _, H, W in photos], dtype=np.int64)
+    lay = photo_layout(photos)
+    tables = np.stack([_table(lay, 3), _table(lay, 1)])           # preprocess: byte offsets; decode: pixel offsets
+    (dtables,), src = _stage(photos, lay, [tables], device)
+    x = ops.image_preprocess(src, dtables[0], h, w, mean, std, bgr)
+    logits = _forward(model, x, half).contiguous()
+    return _finish(lambda lut, out: ops.seg_decode(logits, dtables[1], lay[2], lut, out=out), dtables[1], lay, colors, post,
+                   device)
+
+
+def photo_layout(photos):
+    """[(photo, H, W)] -> (int64 sizes [B,2], pixel offset of each photo in the back-to-back packing, pixels in all)"""
+    sizes = np.array([(H, W) for _, H, W in photos], dtype=np.int64).reshape(-1, 2)
     npix = sizes[:, 0] * sizes[:, 1]
-    pix_off = np.concatenate([[0], np.cumsum(npix)[:-1]])
-    total_pix = int(npix.sum())
-    tables = np.zeros((2, B, 3), dtype=np.int64)
-    tables[0, :, 0], tables[1, :, 0] = 3 * pix_off, pix_off      # preprocess: byte offsets; decode: pixel offsets
-    tables[:, :, 1], tables[:, :, 2] = sizes[:, 0], sizes[:, 1]
-    head = tables.nbytes
+    return sizes, np.concatenate([[0], np.cumsum(npix)[:-1]]).astype(np.int64), int(npix.sum())
 
-    # one pinned buffer = both tables + every host photo; one host-to-device copy
-    staging = torch.empty(head + 3 * total_pix, dtype=torch.uint8, pin_memory=True)
-    sv = staging.numpy()
-    sv[:head] = tables.reshape(-1).view(np.uint8)
-    for (img, _, _), o in zip(photos, pix_off):
-        if isinstance(img, np.ndarray):
-            sv[head + 3 * o:head + 3 * (o + img.shape[0] * img.shape[1])] = np.ascontiguousarray(img).reshape(-1)
+
+def pack_staging(photos, heads, buf=None):
+    """The byte layout of the staging buffer -- the int64 head tables back to back, in order, then the photos back to back
+    (photo i at byte head + 3 * pix_off[i]) -> (head bytes, pix_off, total_pix, sizes).  buf (a uint8 numpy view of head +
+    3 * total_pix bytes, or None for the layout alone) receives the tables and every photo that is a numpy array; photos
+    that live on the device are left for the caller.  numpy only."""
+    sizes, pix_off, total_pix = photo_layout(photos)
+    head = 8 * sum(t.size for t in heads)
+    if buf is not None:
+        buf[:head] = np.concatenate([np.ascontiguousarray(t, dtype=np.int64).reshape(-1) for t in heads]).view(np.uint8)
+        for (img, H, W), o in zip(photos, pix_off):
+            if isinstance(img, np.ndarray):
+                buf[head + 3 * o:head + 3 * (o + H * W)] = np.ascontiguousarray(img).reshape(-1)
+    return head, pix_off, total_pix, sizes
+
+
+def _table(lay, per_px):
+    """int64 [B,3] of {per_px * pixel offset, H, W}: per_px = 3 the preprocess kernels' byte offsets, 1 the decode table"""
+    sizes, pix_off, _ = lay
+    return np.concatenate([per_px * pix_off[:, None], sizes], 1)
+
+
+def _stage(photos, lay, heads, device):
+    """One pinned buffer = the head tables + every host photo, one host-to-device copy; photos already on the device are
+    copied in behind it -> ([each head table as an int64 device view of its own shape], the photo bytes on the device)"""
+    head = pack_staging(photos, heads)[0]
+    staging = torch.empty(head + 3 * lay[2], dtype=torch.uint8, pin_memory=True)
+    pack_staging(photos, heads, staging.numpy())
     dbuf = staging.to(device, non_blocking=True)
-    for (img, _, _), o in zip(photos, pix_off):
+    for (img, H, W), o in zip(photos, lay[1]):
         if isinstance(img, torch.Tensor):
-            dbuf[head + 3 * o:head + 3 * (o + img.shape[0] * img.shape[1])].copy_(img.to(device).reshape(-1))
-    dtables = dbuf[:head].view(torch.int64).view(2, B, 3)
+            dbuf[head + 3 * o:head + 3 * (o + H * W)].copy_(img.to(device).reshape(-1))
+    words, views, at = dbuf[:head].view(torch.int64), [], 0
+    for t in heads:
+        views.append(words[at:at + t.size].view(t.shape))
+        at += t.size
+    return views, dbuf[head:]
 
-    x = ops.image_preprocess(dbuf[head:], dtables[0], h, w, mean, std, bgr)
-    logits = _forward(model, x, half)
+
+def _finish(decode, dtable, lay, colors, post, device):
+    """What follows the forward passes on every route: decode(lut, out) writes the packed masks (and with a lut the
+    colours) of the photos of the device decode table dtable; then the region pass if asked for, the single device-to-host
+    copy and the results in inference()'s shape."""
+    sizes, pix_off, total_pix = lay
     lut = None if colors is None else torch.from_numpy(lut_of(colors)).to(device)
     out = torch.empty(total_pix * (1 if lut is None else 4), dtype=torch.uint8, device=device)
     if post is None:
-        ops.seg_decode(logits.contiguous(), dtables[1], total_pix, lut, out=out)
+        decode(lut, out)
         records = None
     else:                                                       # decode without the palette: mask_clean writes the colours
-        ops.seg_decode(logits.contiguous(), dtables[1], total_pix, None, out=out[:total_pix])
-        records = _postprocess(out, dtables[1], total_pix, sizes, lut, post)
-
-    # one device-to-host copy of masks (and colours)
+        decode(None, out[:total_pix])
+        records = _postprocess(out, dtable, total_pix, sizes, lut, post)
     host = torch.empty(out.numel(), dtype=torch.uint8, pin_memory=True)
     host.copy_(out, non_blocking=True)
     torch.cuda.current_stream(device).synchronize()
     hv = host.numpy()
     masks = [hv[o:o + H * W].reshape(H, W).astype(np.int64) for o, (H, W) in zip(pix_off, sizes)]
-    if colors is None:
-        return _with_regions(masks, records, post, B)
-    rgb = hv[total_pix:]
-    images = [rgb[3 * o:3 * (o + H * W)].reshape(H, W, 3).copy() for o, (H, W) in zip(pix_off, sizes)]
-    return _with_regions((masks, images), records, post, B)
+    images = None
+    if colors is not None:
+        rgb = hv[total_pix:]
+        images = [rgb[3 * o:3 * (o + H * W)].reshape(H, W, 3).copy() for o, (H, W) in zip(pix_off, sizes)]
+    return _result(masks, images, records, post)
 
 
 def _postprocess(out, table, total_pix, sizes, lut, post):
@@ -238,74 +270,39 @@ def _postprocess(out, table, total_pix, sizes, lut, post):
                        largest_only, want_regions)
 
 
-def _with_regions(result, records, post, B):
-    """result as it is, or with the per-photo region lists appended when regions=True asked for them"""
+def _result(masks, images, records, post):
+    """inference()'s four result shapes: masks, or (masks, images) with a palette, each with the per-photo region lists
+    appended when regions=True asked for them"""
+    result = masks if images is None else (masks, images)
     if post is None or not post[3]:
         return result
-    from .regions import region_dicts
-    lists = region_dicts(records, B)
-    return result + (lists,) if isinstance(result, tuple) else (result, lists)
+    lists = []
+    if masks:
+        from .regions import region_dicts
+        lists = region_dicts(records, len(masks))
+    return result + (lists,) if images is not None else (result, lists)
 
 
 def _inference_ensemble(model, photos, h, w, view_sizes, flip, mean, std, bgr, half, colors, device, post=None):
     """inference() with several views: the same single staging buffer (now also carrying the view table and the map
     table) and the same single copy back; per scale one preprocess launch, one forward, one softmax launch."""
     B, S, V = len(photos), len(view_sizes), 2 if flip else 1
-    sizes = np.array([(H, W) for _, H, W in photos], dtype=np.int64)
-    npix = sizes[:, 0] * sizes[:, 1]
-    pix_off = np.concatenate([[0], np.cumsum(npix)[:-1]])
-    total_pix = int(npix.sum())
-    views = np.zeros((V * B, 4), dtype=np.int64)               # rows 0..B-1 plain, rows B..2B-1 mirrored
-    views[:, 0], views[:, 1], views[:, 2] = np.tile(3 * pix_off, V), np.tile(sizes[:, 0], V), np.tile(sizes[:, 1], V)
-    views[B:, 3] = ops.VIEW_MIRROR
-    decode = np.zeros((B, 3), dtype=np.int64)
-    decode[:, 0], decode[:, 1], decode[:, 2] = pix_off, sizes[:, 0], sizes[:, 1]
+    lay = photo_layout(photos)
+    views = np.concatenate([np.tile(_table(lay, 3), (V, 1)), np.zeros((V * B, 1), dtype=np.int64)], 1)
+    views[B:, 3] = ops.VIEW_MIRROR                             # rows 0..B-1 plain, rows B..2B-1 mirrored
     maps = np.zeros((S, 3), dtype=np.int64)                    # pixel offsets: Ensemble scales them by the class padding
     maps[:, 0], maps[:, 1:] = map_offsets(B, view_sizes)[0], np.array(view_sizes, dtype=np.int64)
-    heads = [views.reshape(-1), decode.reshape(-1), maps.reshape(-1)]
-    head = 8 * sum(t.size for t in heads)
-
-    staging = torch.empty(head + 3 * total_pix, dtype=torch.uint8, pin_memory=True)
-    sv = staging.numpy()
-    sv[:head] = np.concatenate(heads).view(np.uint8)
-    for (img, _, _), o in zip(photos, pix_off):
-        if isinstance(img, np.ndarray):
-            sv[head + 3 * o:head + 3 * (o + img.shape[0] * img.shape[1])] = np.ascontiguousarray(img).reshape(-1)
-    dbuf = staging.to(device, non_blocking=True)
-    for (img, _, _), o in zip(photos, pix_off):
-        if isinstance(img, torch.Tensor):
-            dbuf[head + 3 * o:head + 3 * (o + img.shape[0] * img.shape[1])].copy_(img.to(device).reshape(-1))
-    words = dbuf[:head].view(torch.int64)
-    dviews = words[:views.size].view(V * B, 4)
-    ddecode = words[views.size:views.size + decode.size].view(B, 3)
-    dmaps = words[views.size + decode.size:].view(S, 3)
+    (dviews, ddecode, dmaps), src = _stage(photos, lay, [views, _table(lay, 1), maps], device)
 
     ens = Ensemble(B, view_sizes, flip, dmaps)
     for hs, ws in view_sizes:
-        x = ops.image_preprocess_views(dbuf[head:], dviews, hs, ws, mean, std, bgr)
+        x = ops.image_preprocess_views(src, dviews, hs, ws, mean, std, bgr)
         logits = _forward(model, x, half)
         del x
         ens.add(logits)
         del logits                                             # released before the next scale's forward
-    lut = None if colors is None else torch.from_numpy(lut_of(colors)).to(device)
-    out = torch.empty(total_pix * (1 if lut is None else 4), dtype=torch.uint8, device=device)
-    if post is None:
-        ens.decode(ddecode, total_pix, (int(sizes[:, 0].max()), int(sizes[:, 1].max())), lut, out=out)
-        records = None
-    else:
-        ens.decode(ddecode, total_pix, (int(sizes[:, 0].max()), int(sizes[:, 1].max())), None, out=out[:total_pix])
-        records = _postprocess(out, ddecode, total_pix, sizes, lut, post)
-
-    host = torch.empty(out.numel(), dtype=torch.uint8, pin_memory=True)
-    host.copy_(out, non_blocking=True)
-    torch.cuda.current_stream(device).synchronize()
-    hv = host.numpy()
-    masks = [hv[o:o + H * W].reshape(H, W).astype(np.int64) for o, (H, W) in zip(pix_off, sizes)]
-    if colors is None:
-        return _with_regions(masks, records, post, B)
-    rgb = hv[total_pix:]
-    images = [rgb[3 * o:3 * (o + H * W)].reshape(H, W, 3).copy() for o, (H, W) in zip(pix_off, sizes)]
-    return _with_regions((masks, images), records, post, B)
+    max_hw = (int(lay[0][:, 0].max()), int(lay[0][:, 1].max()))
+    return _finish(lambda lut, out: ens.decode(ddecode, lay[2], max_hw, lut, out=out), ddecode, lay, colors, post, device)
 
 
 def work_size(H, W, s):
@@ -366,10 +363,8 @@ def _inference_slide(model, photos, h, w, sy, sx, scales, flip, window_batch, me
     decode.  The window table is staged chunk by chunk -- with flip a chunk is [n plain; n mirrored] -- so every chunk's
     table is a slice of the staged words."""
     B, V = len(photos), 2 if flip else 1
-    sizes = np.array([(H, W) for _, H, W in photos], dtype=np.int64)
-    npix = sizes[:, 0] * sizes[:, 1]
-    pix_off = np.concatenate([[0], np.cumsum(npix)[:-1]])
-    total_pix = int(npix.sum())
+    lay = photo_layout(photos)
+    sizes, pix_off, _ = lay
     work = slide_scales([(int(H), int(W)) for H, W in sizes], scales)
     S = len(work)
     rows, groups = [], np.zeros((S, B, 3), dtype=np.int64)       # groups: window offsets, scaled to floats on the device
@@ -390,30 +385,11 @@ def _inference_slide(model, photos, h, w, sy, sx, scales, flip, window_batch, me
             twin = rows[a:e].copy()
             twin[:, 3] = ops.VIEW_MIRROR
             staged.append(twin)
-    windows = np.concatenate(staged)
-    decode = np.zeros((B, 3), dtype=np.int64)
-    decode[:, 0], decode[:, 1], decode[:, 2] = pix_off, sizes[:, 0], sizes[:, 1]
-    heads = [windows.reshape(-1), decode.reshape(-1), groups.reshape(-1)]
-    head = 8 * sum(t.size for t in heads)
-
-    staging = torch.empty(head + 3 * total_pix, dtype=torch.uint8, pin_memory=True)
-    sv = staging.numpy()
-    sv[:head] = np.concatenate(heads).view(np.uint8)
-    for (img, _, _), o in zip(photos, pix_off):
-        if isinstance(img, np.ndarray):
-            sv[head + 3 * o:head + 3 * (o + img.shape[0] * img.shape[1])] = np.ascontiguousarray(img).reshape(-1)
-    dbuf = staging.to(device, non_blocking=True)
-    for (img, _, _), o in zip(photos, pix_off):
-        if isinstance(img, torch.Tensor):
-            dbuf[head + 3 * o:head + 3 * (o + img.shape[0] * img.shape[1])].copy_(img.to(device).reshape(-1))
-    words = dbuf[:head].view(torch.int64)
-    dwindows = words[:windows.size].view(V * N, 8)
-    ddecode = words[windows.size:windows.size + decode.size].view(B, 3)
-    dgroups = words[windows.size + decode.size:].view(S, B, 3)
+    (dwindows, ddecode, dgroups), src = _stage(photos, lay, [np.concatenate(staged), _table(lay, 1), groups], device)
 
     prob = C = None
     for a, e in chunks:
-        x = ops.image_preprocess_windows(dbuf[head:], dwindows[V * a:V * e], h, w, mean, std, bgr)
+        x = ops.image_preprocess_windows(src, dwindows[V * a:V * e], h, w, mean, std, bgr)
         logits = _forward(model, x, half)
         del x
         if logits.shape[2:] != (h, w):
@@ -425,26 +401,9 @@ def _inference_slide(model, photos, h, w, sy, sx, scales, flip, window_batch, me
             dgroups[:, :, 0] *= CP                             # device arithmetic on S * B numbers: no host round trip
         ops.softmax_views(logits.contiguous(), prob, a * h * w * CP, flip)
         del logits                                             # released before the next chunk's forward
-    lut = None if colors is None else torch.from_numpy(lut_of(colors)).to(device)
-    out = torch.empty(total_pix * (1 if lut is None else 4), dtype=torch.uint8, device=device)
     max_hw = (int(sizes[:, 0].max()), int(sizes[:, 1].max()))
-    if post is None:
-        ops.seg_decode_windows(prob, dgroups, B, C, (h, w), (sy, sx), ddecode, total_pix, max_hw, lut, out=out)
-        records = None
-    else:
-        ops.seg_decode_windows(prob, dgroups, B, C, (h, w), (sy, sx), ddecode, total_pix, max_hw, None, out=out[:total_pix])
-        records = _postprocess(out, ddecode, total_pix, sizes, lut, post)
-
-    host = torch.empty(out.numel(), dtype=torch.uint8, pin_memory=True)
-    host.copy_(out, non_blocking=True)
-    torch.cuda.current_stream(device).synchronize()
-    hv = host.numpy()
-    masks = [hv[o:o + H * W].reshape(H, W).astype(np.int64) for o, (H, W) in zip(pix_off, sizes)]
-    if colors is None:
-        return _with_regions(masks, records, post, B)
-    rgb = hv[total_pix:]
-    images = [rgb[3 * o:3 * (o + H * W)].reshape(H, W, 3).copy() for o, (H, W) in zip(pix_off, sizes)]
-    return _with_regions((masks, images), records, post, B)
+    return _finish(lambda lut, out: ops.seg_decode_windows(prob, dgroups, B, C, (h, w), (sy, sx), ddecode, lay[2], max_hw, lut,
+                                                           out=out), ddecode, lay, colors, post, device)
 
 
 def _forward(model, x, half):

@@ -109,3 +109,32 @@ def test_cli_file_selection_and_names(tmp_path, monkeypatch):
 def torch_module():
     import torch
     return torch.nn.Module
+
+
+@pytest.mark.parametrize('route', ['plain', 'ensemble', 'slide'])
+def test_pack_staging_layout(route):
+    """The staging buffer of every route: the head tables' bytes in order, then the photos back to back at head + 3 *
+    pix_off; offsets and totals against an independent cumulative sum."""
+    from pytorch_segmentation_amd.utils.inference import pack_staging
+    rng = np.random.default_rng(4)
+    shapes = [(5, 7), (1, 1), (4, 3)]
+    imgs = [rng.integers(0, 256, (H, W, 3), dtype=np.uint8) for H, W in shapes]
+    imgs[2] = imgs[2][:, ::-1]                                   # a view that is not contiguous
+    photos = [(im, im.shape[0], im.shape[1]) for im in imgs]
+    B, V, S, N = len(photos), 2, 2, 5
+    dims = {'plain': [(2, B, 3)], 'ensemble': [(V * B, 4), (B, 3), (S, 3)], 'slide': [(N, 8), (B, 3), (S, B, 3)]}[route]
+    heads = [rng.integers(-2 ** 40, 2 ** 40, d, dtype=np.int64) for d in dims]
+    want_off, o = [], 0
+    for H, W in shapes:
+        want_off.append(o)
+        o += H * W
+    want_head = sum(8 * int(np.prod(d)) for d in dims)
+    head, pix_off, total_pix, sizes = pack_staging(photos, heads)        # the layout alone
+    assert head == want_head and list(pix_off) == want_off and total_pix == o == 35 + 1 + 12
+    assert sizes.dtype == np.int64 and sizes.tolist() == [list(s) for s in shapes]
+    buf = np.full(head + 3 * total_pix + 16, 0xAB, dtype=np.uint8)
+    assert pack_staging(photos, heads, buf[:head + 3 * total_pix])[0] == head
+    assert buf[:head].tobytes() == b''.join(t.tobytes() for t in heads)
+    for im, po in zip(imgs, want_off):
+        assert buf[head + 3 * po:head + 3 * po + im.size].tobytes() == np.ascontiguousarray(im).tobytes()
+    assert (buf[head + 3 * total_pix:] == 0xAB).all()

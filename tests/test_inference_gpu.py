@@ -287,3 +287,24 @@ def test_cli_writes_palette_pngs(pkg, tmp_path):
         px = np.asarray(Image.open(str(out_dir / (os.path.splitext(n)[0] + '.png'))).convert('RGB'))
         assert px.shape == im.shape, n
         assert np.array_equal(px, VOC_COLORMAP[:, ::-1][mk]), n
+
+
+def test_infer_bits_match_recorded(pkg, golden_dir):
+    """every entry point of csrc/infer.hip (tests/infer_bits.py: the three preprocess routes at 32 x 48 with bgr and both
+    normalisations, the three decodes at C in {2, 8, 9, 21, 150} with and without mirrored twins, softmax_views) writes the
+    bytes recorded in tests/golden/infer_bits.json from the kernels as they stood before their shared parts were folded"""
+    import json
+
+    import infer_bits
+    from optim_bits import compiler_line
+    from pytorch_segmentation_amd import ops
+    with open(os.path.join(golden_dir, 'infer_bits.json')) as f:
+        rec = json.load(f)
+    got = infer_bits.digests(ops)
+    assert sorted(got) == sorted(rec['digests'])
+    for name, tensors in got.items():
+        assert sorted(tensors) == sorted(rec['digests'][name]), name
+        for k, h in tensors.items():
+            assert h == rec['digests'][name][k], \
+                'case %s, tensor %s: sha256 %s, recorded %s (recorded from %s under "%s", installed "%s")' % (
+                    name, k, h, rec['digests'][name][k], rec['commit'], rec['compiler'], compiler_line())
