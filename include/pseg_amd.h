@@ -483,6 +483,46 @@ int64_t pseg_ce_opts_workspace_bytes(int B, int C, int64_t HW);
 int pseg_ce_opts_fwd_bwd(const float* logits, const int64_t* target, int B, int C, int64_t HW, int64_t ignore_index,
                          const float* class_weight, float label_smoothing, float focal_gamma, float keep_ratio,
                          float* dlogits, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream);
+/* pseg_tversky_fwd_bwd (csrc/tversky.hip): the soft region-overlap loss -- soft Dice, Tversky (Salehi et al.) and
+ *   focal-Tversky (Abraham & Khan) -- over the softmax of the logits, with its gradient.  logits fp32 NCHW [B][C][HW], target
+ *   int64 [B][HW].  A pixel is valid iff target != ignore_index and 0 <= target < C (the predicate of pseg_ce_fwd_bwd);
+ *   other targets that are not ignore_index are counted as out of range and ignored.  p = softmax(logits) in fp32 with the
+ *   max subtracted.  A group is the whole batch (per_image = 0) or one image (per_image = 1).  For a group and a class c,
+ *   over the group's valid pixels:
+ *       n_c = #{t_i = c}      S_c = sum_i p_ic      TP_c = sum_{t_i = c} p_ic
+ *       FP_c = S_c - TP_c     FN_c = n_c - TP_c
+ *       N = TP_c + smooth     D = TP_c + alpha FP_c + beta FN_c + smooth
+ *       TI_c = N / D          (TI_c = 1 when D == 0)
+ *       term_c = (1 - TI_c)^power
+ *   Counted classes of a group: with all_classes = 0 the classes with n_c > 0 ("present"); with all_classes = 1 every
+ *   class of a group that has at least one valid pixel.  The group loss is the mean of term_c over the group's counted
+ *   classes; the loss is the mean of the group losses over the groups with at least one counted class, and 0 with an
+ *   all-zero gradient when there is no such group.  alpha = beta = 0.5, power = 1 is soft Dice; alpha + beta = 1 is
+ *   Tversky; power != 1 is focal-Tversky (Abraham & Khan write the exponent as 1 / gamma).
+ *   Gradient, the group fixed, with K_c = -power (1 - TI_c)^(power - 1) / (n_counted(group) * n_groups_counted) and
+ *   K_c = 0 where 1 - TI_c <= 0 (so power < 1 never produces inf * 0):
+ *       g_ic = K_c * ( t_i == c ?  (beta N + alpha FP_c + beta FN_c) / D^2  :  -alpha N / D^2 )    (0 for classes not counted)
+ *       dlogits_ij = p_ij * (g_ij - sum_k g_ik p_ik)                                               (0 at invalid pixels)
+ *   The target-pixel numerator is D - N (1 - beta) written as a sum of non-negative terms; it is formed that way, never
+ *   by subtraction.  In the same spirit the kernels accumulate FP_c directly (the sum of p_ic over the valid pixels with
+ *   t_i != c; S_c is that plus TP_c) and form 1 - TI_c as (alpha FP_c + beta FN_c) / D.
+ *   out[5] = [loss, n_valid, n_out_of_range, n_terms (counted (group, class) pairs), n_groups_counted] (as floats).
+ *   dlogits ([B][C][HW], nullable, must not alias logits) receives d out[0] / d logits.  class_sums (device memory,
+ *   nullable): [G][C][3] doubles = n_c, S_c, TP_c, G = per_image ? B : 1.  Work: a reduction pass reads the logits and
+ *   the targets once (per-block partials in double, added in a fixed order; no atomics); the coefficients and out[] are
+ *   computed in double on the device; only when dlogits != NULL a gradient pass reads the logits and targets again,
+ *   recomputes p and writes dlogits once.  No host synchronisation.  Deterministic: two calls on the same input give the
+ *   same bits, and the loss is the same bits with and without dlogits.
+ *   Refused with PSEG_ERR_ARG before any launch: null logits / target / out / workspace, non-positive sizes, C > 1024,
+ *   logits or target at or above 2 GiB (B * C * HW * 4 and B * HW * 8 bytes: refused, not chunked), dlogits aliasing
+ *   logits, a workspace below pseg_tversky_workspace_bytes(B, C, HW) (0 for sizes that are refused) or not 16-byte
+ *   aligned, alpha < 0, beta < 0, alpha + beta == 0, smooth < 0, power outside [0.5, 4], a non-finite option.
+ *   The workspace holds 24 bytes per class and block of 1024 pixels of an image, plus 40 bytes per (group, class). */
+int64_t pseg_tversky_workspace_bytes(int B, int C, int64_t HW);
+int pseg_tversky_fwd_bwd(const float* logits, const int64_t* target, int B, int C, int64_t HW, int64_t ignore_index,
+                         float alpha, float beta, float smooth, float power, int per_image, int all_classes,
+                         float* dlogits, float* out, double* class_sums, void* workspace, int64_t workspace_bytes,
+                         void* stream);
 int pseg_scale_inplace(float* x, int64_t n, const float* gscale, void* stream);
 int pseg_argmax(const float* logits, int B, int C, int64_t HW, int64_t* mask, void* stream);
 int pseg_confusion(const int64_t* pred, const int64_t* target, int64_t n, int C, int64_t* counters, void* stream);

@@ -1171,6 +1171,26 @@ def lovasz_softmax_fwd_bwd(logits, target, want_grad=True, ignore_index=-100):
     return out, dl
 
 
+def tversky_fwd_bwd(logits, target, alpha=0.5, beta=0.5, smooth=1.0, power=1.0, per_image=False, all_classes=False,
+                    want_grad=True, ignore_index=-100, want_sums=False):
+    """Soft Dice / Tversky / focal-Tversky loss over the softmax of the logits (pseg_tversky_fwd_bwd).
+    logits: contiguous NCHW fp32 cuda, target: NHW int64.
+    -> (out[5] = [loss, n_valid, n_out_of_range_targets, n_terms, n_groups_counted], dlogits|None), and with want_sums
+    also class_sums: float64 [G, C, 3] = n_c, S_c, TP_c per group (G = B with per_image, else 1)."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.shape == (logits.shape[0],) + logits.shape[2:]
+    B, C, H, W = logits.shape
+    dl = torch.empty_like(logits) if want_grad else None
+    out = torch.empty(5, dtype=torch.float32, device=logits.device)
+    sums = torch.empty(B if per_image else 1, C, 3, dtype=torch.float64, device=logits.device) if want_sums else None
+    nbytes = _lib.query('pseg_tversky_workspace_bytes', B, C, H * W)
+    ws = workspace.get(nbytes, logits.device)
+    _lib.call('pseg_tversky_fwd_bwd', logits.data_ptr(), target.data_ptr(), B, C, H * W, ignore_index, float(alpha),
+              float(beta), float(smooth), float(power), int(bool(per_image)), int(bool(all_classes)), _ptr(dl),
+              out.data_ptr(), _ptr(sums), ws.data_ptr(), nbytes, _stream())
+    return (out, dl, sums) if want_sums else (out, dl)
+
+
 def ce_upsampled_ok_shape(h, w, C, H, W, align_corners):
     return bool(_lib.query('pseg_ce_upsampled_ok', h, w, C, H, W, int(align_corners)))
 

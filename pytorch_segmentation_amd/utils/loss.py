@@ -176,8 +176,60 @@ def weighted_cross_entropy_loss(outputs, targets, class_weight=None, label_smoot
                                      ignore_index)
 
 
-LOSSES = {'ce': compute_loss, 'lovasz': _lovasz_loss_fn, 'ce+lovasz': _ce_lovasz_loss_fn}
+class _TverskyFn(torch.autograd.Function):
+    """Soft Dice / Tversky / focal-Tversky loss over the softmax of the logits (Salehi et al.; Abraham & Khan).  Built like
+    _LovaszSoftmaxFn: forward runs pseg_tversky_fwd_bwd, which leaves the gradient with respect to the logits as well;
+    backward only rescales it by the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, alpha, beta, smooth, power, per_image, all_classes, ignore_index):
+        need = logits.requires_grad
+        out, dl = ops.tversky_fwd_bwd(logits, targets, alpha, beta, smooth, power, per_image, all_classes, want_grad=need,
+                                      ignore_index=ignore_index)
+        if CHECK_LABELS and out[2].item() != 0:     # (host sync: debugging aid, off by default)
+            raise IndexError('%d target values are outside [0, %d) and are not ignore_index'
+                             % (int(out[2].item()), logits.shape[1]))
+        ctx.dl = dl
+        ctx.mark_non_differentiable()
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        dl = ctx.dl
+        ctx.dl = None
+        if dl is None:
+            return (None,) * 9
+        g = g.reshape(1) if g.dtype == torch.float32 else g.float().reshape(1)
+        ops.scale_inplace(dl, g.contiguous())
+        return (dl,) + (None,) * 8
+
+
+def tversky_loss(outputs, targets, alpha=0.5, beta=0.5, smooth=1.0, power=1.0, per_image=False, all_classes=False,
+                 ignore_index=-100):
+    """Soft region-overlap loss of NCHW logits; the softmax is part of the kernel.  Per class, over the valid pixels of a
+    group (the batch, or each image with per_image): TI = (TP + smooth) / (TP + alpha FP + beta FN + smooth) from the soft
+    counts, term = (1 - TI)^power; the mean over the classes present in the group (all_classes: every class), then over the
+    groups.  The defaults are soft Dice; alpha + beta = 1 is Tversky (beta > alpha weighs misses over false alarms);
+    power != 1 is focal-Tversky.  One HIP call (pseg_tversky_fwd_bwd); bit-reproducible."""
+    outputs, targets = _logits_at_target_size(outputs, targets)
+    return _TverskyFn.apply(outputs, targets, float(alpha), float(beta), float(smooth), float(power), bool(per_image),
+                            bool(all_classes), ignore_index)
+
+
+def _tversky_loss_fn(outputs, targets, model=None):
+    return tversky_loss(outputs, targets)
+
+
+def _ce_tversky_loss_fn(outputs, targets, model=None):
+    outputs, targets = _logits_at_target_size(outputs, targets)
+    return _CrossEntropyFn.apply(outputs, targets) + _TverskyFn.apply(outputs, targets, 0.5, 0.5, 1.0, 1.0, False, False, -100)
+
+
+LOSSES = {'ce': compute_loss, 'lovasz': _lovasz_loss_fn, 'ce+lovasz': _ce_lovasz_loss_fn, 'tversky': _tversky_loss_fn,
+          'ce+tversky': _ce_tversky_loss_fn}
 CE_OPTIONS = {'class_weight': None, 'label_smoothing': 0.0, 'focal_gamma': 0.0, 'keep_ratio': 1.0}
+TVERSKY_OPTIONS = {'tversky_alpha': 0.5, 'tversky_beta': 0.5, 'tversky_smooth': 1.0, 'tversky_power': 1.0,
+                   'tversky_per_image': False, 'tversky_all_classes': False, 'tversky_weight': 1.0}
 
 
 def _configured_ce(name, opts):
@@ -201,23 +253,63 @@ def _configured_ce(name, opts):
     return _ce_opts_loss_fn if name == 'ce' else _ce_opts_lovasz_loss_fn
 
 
-def make_loss(name, **ce_options):
-    """'ce' | 'lovasz' | 'ce+lovasz' -> loss_fn(outputs, targets, model) for Trainer(loss_fn=...).  'ce' without options is
-    compute_loss itself (the Trainer's fused fast path keys on that object); everything else goes through the Trainer's
-    autograd route.  ce_options (class_weight=, label_smoothing=, focal_gamma=, keep_ratio=) configure the cross-entropy of
-    'ce' and 'ce+lovasz' (weighted_cross_entropy_loss); an option left at its default (None, 0, 0, 1) is not an option."""
+def _configured_tversky(name, opts, ce_set, tv):
+    """loss_fn(outputs, targets, model) of 'tversky' / 'ce+tversky' with the Tversky term configured by `tv` and, for
+    'ce+tversky' with ce_set, the cross-entropy by `opts`"""
+    args = (float(tv['tversky_alpha']), float(tv['tversky_beta']), float(tv['tversky_smooth']), float(tv['tversky_power']),
+            bool(tv['tversky_per_image']), bool(tv['tversky_all_classes']))
+    weight = float(tv['tversky_weight'])
+    state = {'w': opts['class_weight'], 'device': None}
+    ls, fg, kr = float(opts['label_smoothing']), float(opts['focal_gamma']), float(opts['keep_ratio'])
+
+    def weight_on(device):      # moved to the logits' device once
+        if state['w'] is not None and state['device'] != device:
+            state['w'], state['device'] = _class_weight_on(state['w'], device), device
+        return state['w']
+
+    def _tversky_opts_loss_fn(outputs, targets, model=None):
+        loss = tversky_loss(outputs, targets, *args)
+        return loss if weight == 1.0 else weight * loss
+
+    def _ce_tversky_opts_loss_fn(outputs, targets, model=None):
+        outputs, targets = _logits_at_target_size(outputs, targets)
+        if ce_set:
+            ce = weighted_cross_entropy_loss(outputs, targets, weight_on(outputs.device), ls, fg, kr)
+        else:
+            ce = _CrossEntropyFn.apply(outputs, targets)
+        tvl = _TverskyFn.apply(outputs, targets, *args, -100)
+        return ce + (tvl if weight == 1.0 else weight * tvl)
+
+    return _tversky_opts_loss_fn if name == 'tversky' else _ce_tversky_opts_loss_fn
+
+
+def make_loss(name, **options):
+    """'ce' | 'lovasz' | 'ce+lovasz' | 'tversky' | 'ce+tversky' -> loss_fn(outputs, targets, model) for Trainer(loss_fn=...).
+    'ce' without options is compute_loss itself (the Trainer's fused fast path keys on that object); everything else goes
+    through the Trainer's autograd route.  The cross-entropy options (class_weight=, label_smoothing=, focal_gamma=,
+    keep_ratio=) configure the cross-entropy of 'ce', 'ce+lovasz' and 'ce+tversky' (weighted_cross_entropy_loss); the
+    Tversky options (tversky_alpha=, tversky_beta=, tversky_smooth=, tversky_power=, tversky_per_image=,
+    tversky_all_classes=, and tversky_weight= for ce + weight * tversky) configure the Tversky term of 'tversky' and
+    'ce+tversky' (tversky_loss).  An option left at its default is not an option."""
     if name not in LOSSES:
         raise ValueError('unknown loss %r (choose from %s)' % (name, ', '.join(sorted(LOSSES))))
-    unknown = sorted(set(ce_options) - set(CE_OPTIONS))
+    unknown = sorted(set(options) - set(CE_OPTIONS) - set(TVERSKY_OPTIONS))
     if unknown:
-        raise TypeError('unknown cross-entropy option(s) %s (choose from %s)' % (', '.join(unknown), ', '.join(sorted(CE_OPTIONS))))
-    opts = dict(CE_OPTIONS, **ce_options)
+        raise TypeError('unknown cross-entropy option(s) %s (choose from %s; Tversky options: %s)'
+                        % (', '.join(unknown), ', '.join(sorted(CE_OPTIONS)), ', '.join(sorted(TVERSKY_OPTIONS))))
+    opts = dict(CE_OPTIONS, **{k: v for k, v in options.items() if k in CE_OPTIONS})
+    tv = dict(TVERSKY_OPTIONS, **{k: v for k, v in options.items() if k in TVERSKY_OPTIONS})
     is_set = opts['class_weight'] is not None or any(float(opts[k]) != CE_OPTIONS[k] for k in
                                                       ('label_smoothing', 'focal_gamma', 'keep_ratio'))
-    if not is_set:
+    tv_set = any(float(tv[k]) != float(TVERSKY_OPTIONS[k]) for k in TVERSKY_OPTIONS)
+    if tv_set and 'tversky' not in name:
+        raise ValueError("the Tversky options do not apply to %r (use 'tversky' or 'ce+tversky')" % name)
+    if not is_set and not tv_set:
         return LOSSES[name]
-    if name == 'lovasz':
-        raise ValueError("the cross-entropy options do not apply to 'lovasz' (use 'ce' or 'ce+lovasz')")
+    if is_set and name in ('lovasz', 'tversky'):
+        raise ValueError("the cross-entropy options do not apply to %r (use 'ce', 'ce+lovasz' or 'ce+tversky')" % name)
+    if 'tversky' in name:
+        return _configured_tversky(name, opts, is_set, tv)
     return _configured_ce(name, opts)
 
 

@@ -4,7 +4,9 @@ on the MI355X HIP path.
 
     python3 train.py data/<custom> [--epochs N] [-s W H] [-bs N] [-a ACC] [--lr LR] [--adam] [--resume]
                      [--weights F] [--notest] [--nosave] [--model unet|deeplabv3plus] [--augment | --augment-full | --augment-warps]
-                     [--loss ce|lovasz|ce+lovasz] [--class-weights W0 W1 ...] [--label-smoothing E] [--focal-gamma G] [--ohem-keep R]
+                     [--loss ce|lovasz|ce+lovasz|tversky|ce+tversky] [--class-weights W0 W1 ...] [--label-smoothing E] [--focal-gamma G] [--ohem-keep R]
+                     [--tversky-alpha A] [--tversky-beta B] [--tversky-smooth S] [--tversky-power P] [--tversky-per-image]
+                     [--tversky-all-classes] [--tversky-weight W]
                      [--weight-decay WD] [--momentum M] [--adamw] [--no-decay-norm-bias] [--backbone-lr-mult F]
                      [--clip-grad N] [--ema-decay D] [--schedule poly|cosine] [--warmup-steps N] [--min-lr LR]
     python3 -m torch.distributed.run --nproc-per-node <n> train.py data/<custom>        # RCCL data parallel
@@ -124,9 +126,10 @@ def build_parser():
     ap.add_argument('--augment-warps', action='store_true',
                     help='--augment-full plus elastic, piecewise-affine and perspective warps of images and labels: '
                          'DeviceAugment.warps()')
-    ap.add_argument('--loss', choices=['ce', 'lovasz', 'ce+lovasz'], default='ce',
+    ap.add_argument('--loss', choices=['ce', 'lovasz', 'ce+lovasz', 'tversky', 'ce+tversky'], default='ce',
                     help='training objective: per-pixel cross-entropy, the Lovasz-softmax surrogate of the mean IoU '
-                         '(classes present in the batch), or their sum')
+                         '(classes present in the batch), or their sum; the soft Dice / Tversky / focal-Tversky '
+                         'region-overlap loss, or cross-entropy plus --tversky-weight times it')
     ap.add_argument('--class-weights', type=float, nargs='+', default=None, metavar='W',
                     help='per-class weights of the cross-entropy, one value per class (ce and ce+lovasz)')
     ap.add_argument('--label-smoothing', type=float, default=0.0, metavar='E', help='label smoothing of the cross-entropy, in [0, 1)')
@@ -135,6 +138,17 @@ def build_parser():
     ap.add_argument('--ohem-keep', type=float, default=1.0, metavar='R',
                     help='online hard-example mining: average the cross-entropy over the share R in (0, 1] of the valid '
                          'pixels of a batch with the largest loss')
+    ap.add_argument('--tversky-alpha', type=float, default=0.5, metavar='A',
+                    help='weight of the soft false positives in the Tversky index (0.5 with --tversky-beta 0.5: soft Dice)')
+    ap.add_argument('--tversky-beta', type=float, default=0.5, metavar='B',
+                    help='weight of the soft false negatives (above --tversky-alpha: misses cost more than false alarms)')
+    ap.add_argument('--tversky-smooth', type=float, default=1.0, metavar='S', help='added to numerator and denominator, >= 0')
+    ap.add_argument('--tversky-power', type=float, default=1.0, metavar='P',
+                    help='focal-Tversky exponent on 1 - index, in [0.5, 4] (Abraham & Khan: 1 / gamma = 0.75)')
+    ap.add_argument('--tversky-per-image', action='store_true', help='one index per image and class, not per batch and class')
+    ap.add_argument('--tversky-all-classes', action='store_true',
+                    help='average over every class, not only over the classes present in the batch (image)')
+    ap.add_argument('--tversky-weight', type=float, default=1.0, metavar='W', help='ce+tversky: ce + W * tversky')
     ap.add_argument('--weight-decay', type=float, default=None, metavar='WD', help='weight decay (default 0)')
     ap.add_argument('--momentum', type=float, default=None, metavar='M', help='SGD momentum (default 0.9)')
     ap.add_argument('--adamw', action='store_true', help='decoupled weight decay (AdamW with --adam, SGDW without)')
@@ -181,9 +195,12 @@ def optim_from_options(opt):
 
 def loss_from_options(opt):
     """(loss_fn, class weights or None) of the parsed --loss / --class-weights / --label-smoothing / --focal-gamma /
-    --ohem-keep; with none of the four given this is make_loss(opt.loss), as before"""
+    --ohem-keep / --tversky-*; with none of them given this is make_loss(opt.loss), as before"""
     return make_loss(opt.loss, class_weight=opt.class_weights, label_smoothing=opt.label_smoothing,
-                     focal_gamma=opt.focal_gamma, keep_ratio=opt.ohem_keep), opt.class_weights
+                     focal_gamma=opt.focal_gamma, keep_ratio=opt.ohem_keep, tversky_alpha=opt.tversky_alpha,
+                     tversky_beta=opt.tversky_beta, tversky_smooth=opt.tversky_smooth, tversky_power=opt.tversky_power,
+                     tversky_per_image=opt.tversky_per_image, tversky_all_classes=opt.tversky_all_classes,
+                     tversky_weight=opt.tversky_weight), opt.class_weights
 
 
 def main():
