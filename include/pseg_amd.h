@@ -62,7 +62,8 @@ extern "C" {
  * Entry points added since 14 (pseg_image_preprocess_views, pseg_softmax_views, pseg_seg_decode_ensemble, the
  * connected-region calls pseg_regions_workspace_bytes, pseg_mask_label, pseg_mask_regions, pseg_mask_clean, and the
  * sliding-window calls pseg_image_preprocess_windows, pseg_seg_decode_windows, and the grouped optimiser calls
- * pseg_grad_sumsq_workspace_bytes, pseg_grad_sumsq, pseg_opt_step_sgd, pseg_opt_step_adam) are purely
+ * pseg_grad_sumsq_workspace_bytes, pseg_grad_sumsq, pseg_opt_step_sgd, pseg_opt_step_adam, and the contour-measure calls
+ * pseg_label_depth, pseg_boundary_counts_workspace_bytes, pseg_boundary_counts) are purely
  * additive and do not bump it: the loader checks every declared prototype against the library's exports by name. */
 #define PSEG_ABI_VERSION 14
 int pseg_abi_version(void);
@@ -688,6 +689,49 @@ int pseg_mask_regions(const uint8_t* mask, const int* labels, const int64_t* tab
 int pseg_mask_clean(const uint8_t* mask, const int* labels, const int64_t* table, int B, int64_t npix_total, int Hmax, int Wmax,
                     int64_t min_area, int largest_only, uint8_t* mask_out, uint8_t* rgb, const uint8_t* lut, void* ws,
                     int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------ contour measures of the evaluation (csrc/boundary.hip)
+ * Boundary IoU (Cheng et al., CVPR 2021) and the trimap IoU of the DeepLabV3+ paper both come from one quantity per pixel
+ * that does not depend on the class count.  These entry points are additive: PSEG_ABI_VERSION does not move.
+ *
+ * Label depth.  L is a label map of H x W (int64), C the class count, d the width, 1 <= d <= 254.  A label outside [0, C) is
+ * VOID.  Two pixels carry a DIFFERENT LABEL when their values differ -- void included: void values are compared by value
+ * like any other, so two different void values next to each other are a label change.
+ *   depth(p)      = the smallest k >= 1 such that a pixel q INSIDE the image with max(|dx|, |dy|) = k has L(q) != L(p),
+ *                   clipped to d + 1 when there is none within d;
+ *   depth_edge(p) = min(depth(p), x + 1, W - x, y + 1, H - y): the outside of the image counts as a different label, the
+ *                   nearest outside pixel of column 0 being at distance 1.
+ * Pixels of another image of the batch never count.  For every class c, with M = (L == c), M & (depth_edge <= d) equals
+ * M & ~erode^d(M), erode being the 3 x 3 erosion of the zero-padded mask: the boundary region of the published Boundary IoU
+ * code (cv2.copyMakeBorder(..., 0), cv2.erode(ones(3, 3), iterations = d), crop, subtract).  One depth map serves all classes.
+ * The depth is separable: with c(q) the distance along q's column to the nearest different label, clipped to d + 1,
+ *   depth(p) = min(c(p), min over the pixels q of p's row at offset k, 1 <= |k| <= d, of (L(q) != L(p) ? |k| : max(|k|, c(q)))),
+ * which is how the kernels compute it: O(d) work per pixel, no pass per class.
+ *
+ * pseg_label_depth: labels int64 [B][H][W] -> depth uint8 [B][H][W], the clipped depth (1 .. d + 1) of every pixel, void
+ *   pixels included; edge != 0: depth_edge instead.  No workspace: the column distances are staged in `depth` itself.
+ *
+ * Counters.  counters is int64 [6][C], ACCUMULATED into like pseg_confusion's.  T is the target; P' is the prediction with
+ * every pixel whose target is void set to the void value -1 (a pixel nobody labelled can be neither right nor wrong, and must
+ * not create a contour in the prediction either).  Depths of T and of P' are taken separately.
+ *   row 0      inter[c] = #{T = c, P' = c, depth_edge_T <= d, depth_edge_P' <= d}
+ *   row 1      gband[c] = #{T = c, depth_edge_T <= d}
+ *   row 2      pband[c] = #{P' = c, depth_edge_P' <= d}
+ *   row 3/4/5  trimap tp / fn / fp = pseg_confusion's three counts (same rules, prediction values outside [0, C) included)
+ *              over the pixels with a valid target and depth_T <= d -- WITHOUT the edge term: the image border is not an
+ *              object contour.
+ * Boundary IoU of class c = inter / (gband + pband - inter), trimap IoU = tp / (tp + fn + fp); a denominator <= 0 is
+ * replaced by 1 (utils.compute_boundary_metrics, as compute_metrics does).
+ * pseg_boundary_counts_workspace_bytes(B, H, W, d): bytes of the workspace (one byte per pixel and map, each plane rounded up
+ *   to 16 bytes; nothing depends on C); -1 for arguments out of range.
+ * pseg_boundary_counts: pred, target int64 [B][H][W].  Two launches, integer atomics only, no host synchronisation.
+ *
+ * Both calls: B, H, W >= 1, H, W <= 2^30, B * H * W <= 2^40, 1 <= C <= 1024 (pseg_confusion's bound), 1 <= d <= 254;
+ * otherwise PSEG_ERR_ARG with a message that names the argument, before anything is launched. */
+int pseg_label_depth(const int64_t* labels, int B, int H, int W, int C, int d, int edge, uint8_t* depth, void* stream);
+int64_t pseg_boundary_counts_workspace_bytes(int B, int H, int W, int d);
+int pseg_boundary_counts(const int64_t* pred, const int64_t* target, int B, int H, int W, int C, int d, int64_t* counters,
+                         void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ training augmentation (csrc/augment.hip)
  * The geometric and colour-affine part of the reference's online augmentation (utils/datasets.py:26-125, imgaug on the

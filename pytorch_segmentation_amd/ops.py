@@ -1511,6 +1511,52 @@ def confusion(pred, target, counters):
               counters.data_ptr(), _stream())
 
 
+BOUNDARY_MAX_WIDTH = 254     # the clipped depth d + 1 fits a byte
+BOUNDARY_ROWS = 6            # inter, gband, pband, trimap tp / fn / fp (layout: include/pseg_amd.h)
+
+# the boundary counters' scratch (one byte per pixel and map): its own buffer, like the regions calls'
+boundary_workspace = _Workspace()
+
+
+def _label_map(name, t):
+    if not t.is_cuda:
+        raise RuntimeError('%s runs on the HIP path only (got %s)' % (name, t.device))
+    assert t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 3, \
+        '%s takes contiguous int64 [B, H, W] label maps (got %s %s)' % (name, t.dtype, tuple(t.shape))
+    assert t.numel() > 0, '%s: empty label map %s' % (name, tuple(t.shape))
+
+
+def label_depth(labels, num_classes, d, edge=False):
+    """Clipped Chebyshev distance of every pixel to the nearest pixel of its own image that carries a different label
+    (pseg_label_depth): labels int64 [B, H, W] -> uint8 [B, H, W] with values 1 .. d + 1, d + 1 standing for "none within
+    d".  Labels outside [0, num_classes) are void and compare by value.  edge: the outside of the image counts as a
+    different label (depth_edge)."""
+    _label_map('label_depth', labels)
+    B, H, W = labels.shape
+    out = torch.empty(B, H, W, dtype=torch.uint8, device=labels.device)
+    _lib.call('pseg_label_depth', labels.data_ptr(), B, H, W, int(num_classes), int(d), int(bool(edge)), out.data_ptr(), _stream())
+    return out
+
+
+def boundary_counts(pred, target, counters, d):
+    """counters: int64 [6][C] (Boundary IoU's inter / gband / pband of width d, then the trimap's tp / fn / fp), accumulated
+    in place (pseg_boundary_counts).  pred, target: int64 [B, H, W]; a prediction pixel counts as void where its target is."""
+    _label_map('boundary_counts', pred)
+    _label_map('boundary_counts', target)
+    assert pred.shape == target.shape and pred.device == target.device, 'boundary_counts: pred %s / target %s' % (
+        tuple(pred.shape), tuple(target.shape))
+    assert counters.device == pred.device and counters.dtype == torch.int64 and counters.is_contiguous()
+    assert counters.dim() == 2 and counters.shape[0] == BOUNDARY_ROWS, 'boundary_counts: counters are int64 [6][C]'
+    B, H, W = pred.shape
+    nbytes = _lib.query('pseg_boundary_counts_workspace_bytes', B, H, W, int(d))
+    if nbytes < 0:
+        raise ValueError('boundary_counts: shape %s or width d = %d out of range (1 <= d <= %d)'
+                         % (tuple(pred.shape), d, BOUNDARY_MAX_WIDTH))
+    ws = boundary_workspace.get(nbytes, pred.device)
+    _lib.call('pseg_boundary_counts', pred.data_ptr(), target.data_ptr(), B, H, W, counters.shape[1], int(d),
+              counters.data_ptr(), ws.data_ptr(), nbytes, _stream())
+
+
 # ---------------------------------------------------------------------------------------------- optimiser
 def sgd_step(param, grad, mbuf, lr, momentum, weight_decay, nesterov, grad_scale, first_step):
     _lib.call('pseg_sgd_step', param.data_ptr(), grad.data_ptr(), _ptr(mbuf), param.numel(), float(lr), float(momentum),

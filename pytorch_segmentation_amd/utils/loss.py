@@ -419,3 +419,43 @@ def compute_metrics(tp, fn, fp):
     R = tp / guarded(tp + fn)
     F1 = 2 * tp / guarded(2 * tp + fp + fn)
     return T, P, R, miou, F1
+
+
+def boundary_width(hw, ratio=0.02):
+    """Width in pixels of the contour band of an (H, W) label map: max(1, int(ratio * sqrt(H^2 + W^2) + 0.5)), the image
+    diagonal times `ratio` rounded half up (0.02 is the Boundary IoU paper's value)."""
+    h, w = int(hw[0]), int(hw[1])
+    if h < 1 or w < 1:
+        raise ValueError('boundary_width: size %r' % (tuple(hw),))
+    if not 0.0 < float(ratio) <= 0.5:
+        raise ValueError('boundary_width: ratio must be in (0, 0.5]; got %r' % (ratio,))
+    d = max(1, int(float(ratio) * (h * h + w * w) ** 0.5 + 0.5))
+    if d > ops.BOUNDARY_MAX_WIDTH:
+        raise ValueError('boundary width %d of a %d x %d map at ratio %g exceeds %d pixels: give a smaller ratio or a fixed '
+                         'width' % (d, h, w, ratio, ops.BOUNDARY_MAX_WIDTH))
+    return d
+
+
+def update_boundary_counts(counters, predicted, targets, width):
+    """Accumulate the Boundary IoU and trimap counts of a batch into the int64 device tensor counters[6][C] (rows: inter,
+    gband, pband, trimap tp / fn / fp; include/pseg_amd.h) with two launches, whatever the class count.  predicted,
+    targets: [B, H, W]; width: the band's width in pixels (boundary_width)."""
+    width = int(width)
+    if not 1 <= width <= ops.BOUNDARY_MAX_WIDTH:
+        raise ValueError('boundary width must be in [1, %d]; got %d' % (ops.BOUNDARY_MAX_WIDTH, width))
+    ops.boundary_counts(predicted.to(torch.int64).contiguous(), targets.to(device=predicted.device, dtype=torch.int64).contiguous(),
+                        counters, width)
+    return counters
+
+
+def compute_boundary_metrics(counters):
+    """counters[6][C] -> (Boundary IoU [C], trimap IoU [C]) as fp32 host tensors; a denominator <= 0 is replaced by 1, as in
+    compute_metrics."""
+    inter, gband, pband, tp, fn, fp = (c.float() for c in counters.detach().cpu())
+
+    def guarded(den):
+        den = den.clone()
+        den[den <= 0] = 1
+        return den
+
+    return inter / guarded(gband + pband - inter), tp / guarded(tp + fn + fp)

@@ -3,7 +3,7 @@
 
     python3 test.py data/<custom>/val.json --weights weights/best.pt [-s W H] [-bs N] [--model deeplabv3plus|unet]
                     [--scales S [S ...]] [--flip] [--min-area N] [--connectivity {4,8}] [--largest-only]
-                    [--window W H [--stride SW SH]] [--ema]
+                    [--window W H [--stride SW SH]] [--ema] [--boundary [RATIO] | --boundary-width D]
 
 `test(model, fetcher)` keeps the reference's contract: evaluates in eval mode without gradients, prints per-class
 (or the five worst classes') targets / precision / recall / IoU / F1 and returns the mean IoU.  The per-class
@@ -15,6 +15,10 @@ cleaned mask (utils/regions.py: small connected regions dropped) of either route
 can be read off; the loss again stays as it is.  With --window W H the counted prediction is the sliding-window one
 (utils.predict_mask_windows: W x H windows at --stride over the images -s delivers, the probabilities of the windows covering
 a pixel averaged; --scales then scale the image, --flip adds every window's mirrored twin).
+With --boundary [RATIO] or --boundary-width D the counted prediction -- whichever route made it -- is also scored near the
+contours: Boundary IoU (Cheng et al. 2021) and the trimap IoU of the DeepLabV3+ paper, in a band of RATIO times the target's
+diagonal (default 0.02) or of D pixels (utils.update_boundary_counts: two launches per batch, any class count).  One more
+summary line and two more columns per class row are printed; everything else, the returned mean IoU included, stays.
 """
 import argparse
 
@@ -22,16 +26,30 @@ import torch
 from torch.utils.data import DataLoader
 
 from pytorch_segmentation_amd.models import DeepLabV3Plus, HRNet, UNet
-from pytorch_segmentation_amd.utils import (Fetcher, all_reduce_counters, broadcast_buffers, compute_loss, compute_metrics,
-                                            predict_mask, predict_mask_ensemble, predict_mask_windows, update_class_counts)
+from pytorch_segmentation_amd.utils import (Fetcher, all_reduce_counters, broadcast_buffers,
+                                            compute_boundary_metrics, compute_loss, compute_metrics, predict_mask,
+                                            predict_mask_ensemble, predict_mask_windows, update_boundary_counts,
+                                            update_class_counts)
+from pytorch_segmentation_amd.utils import boundary_width as band_width      # (test() has an argument of that name)
 from pytorch_segmentation_amd.utils.datasets import CocoDataset
 
 MODELS = {'deeplabv3plus': DeepLabV3Plus, 'unet': UNet, 'hrnet': HRNet}
 
 
 @torch.no_grad()
-def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, largest_only=False, window=None, stride=None):
+def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, largest_only=False, window=None, stride=None,
+         boundary=None, boundary_width=None, results=None):
+    """boundary (a ratio of the target's diagonal) or boundary_width (pixels): also count Boundary IoU and trimap IoU on the
+    prediction that is scored.  results: a dict that receives 'boundary_iou' and 'trimap_iou' ([C] tensors),
+    'boundary_counters' (int64 [6][C], summed over the ranks) and 'boundary_widths' (the sorted widths used)."""
     model.eval()
+    if boundary is not None and boundary_width is not None:
+        raise ValueError('boundary= (a ratio) and boundary_width= (pixels) exclude each other')
+    if boundary is not None and not 0.0 < boundary <= 0.5:
+        raise ValueError('boundary must be in (0, 0.5]; got %r' % (boundary,))
+    if boundary_width is not None and not 1 <= boundary_width <= 254:
+        raise ValueError('boundary_width must be in [1, 254]; got %r' % (boundary_width,))
+    contours = boundary is not None or boundary_width is not None
     if window is None and stride is not None:
         raise ValueError('stride belongs to window=')
     if min_area < 0:
@@ -49,6 +67,7 @@ def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, la
     if clean and nc > 256:
         raise ValueError('mask cleanup handles at most 256 classes; the dataset has %d' % nc)
     counters = None
+    bcounters, widths = None, set()
     loss_sum, batches = None, 0
     for inputs, targets in fetcher:
         if window is not None:                                 # sliding windows of (w, h) over the delivered batch
@@ -76,6 +95,13 @@ def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, la
             from pytorch_segmentation_amd.utils.regions import clean_predictions
             predicted = clean_predictions(predicted, min_area, connectivity, largest_only)
         update_class_counts(counters, predicted, targets)
+        if contours:
+            if bcounters is None:
+                bcounters = torch.zeros(6, nc, dtype=torch.int64, device=outputs.device)
+            # the width follows the target size of the batch (--rect delivers more than one)
+            width = band_width(targets.shape[1:], boundary) if boundary_width is None else boundary_width
+            widths.add(width)
+            update_boundary_counts(bcounters, predicted, targets, width)
     if counters is None:
         return 0.0
     all_reduce_counters(counters)
@@ -83,13 +109,20 @@ def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, la
     T, P, R, miou, F1 = compute_metrics(tp, fn, fp)
     print('loss: %8g, mAP: %8g, F1: %8g, miou: %8g' % (loss_sum.item() / batches, P.mean(), F1.mean(), miou.mean()))
     row = 'cls: %8s, targets: %8d, pre: %8g, rec: %8g, iou: %8g, F1: %8g'
+    if contours:
+        all_reduce_counters(bcounters)
+        biou, tiou = compute_boundary_metrics(bcounters)
+        print('boundary iou: %8g, trimap iou: %8g, width: %s' % (biou.mean(), tiou.mean(), ' '.join(map(str, sorted(widths)))))
+        if results is not None:
+            results.update(boundary_iou=biou, trimap_iou=tiou, boundary_counters=bcounters.cpu(), boundary_widths=sorted(widths))
     if nc < 10:
         order = range(nc)
     else:
         print('top error 5')
         order = torch.argsort(miou)[:5].tolist()
     for c in order:
-        print(row % (classes[c], T[c], P[c], R[c], miou[c], F1[c]))
+        line = row % (classes[c], T[c], P[c], R[c], miou[c], F1[c])
+        print(line + ', biou: %8g, trimap: %8g' % (biou[c], tiou[c]) if contours else line)
     return miou.mean().item()
 
 
@@ -124,7 +157,17 @@ def parse_args(argv=None):
     ap.add_argument('--stride', type=int, nargs=2, default=None, metavar=('SW', 'SH'),
                     help='with --window: the window stride, between half the window and the window (default: 2/3 of it)')
     ap.add_argument('--ema', action='store_true', help="evaluate the averaged weights ('model_ema') of the checkpoint")
+    contour = ap.add_mutually_exclusive_group()
+    contour.add_argument('--boundary', type=float, nargs='?', const=0.02, default=None, metavar='RATIO',
+                         help='also report Boundary IoU and trimap IoU in a band of RATIO (default 0.02, in (0, 0.5]) times '
+                              "the target's diagonal")
+    contour.add_argument('--boundary-width', type=int, default=None, metavar='D',
+                         help='the same with a band of D pixels (1 .. 254)')
     opt = ap.parse_args(argv)
+    if opt.boundary is not None and not 0.0 < opt.boundary <= 0.5:
+        ap.error('--boundary must be in (0, 0.5]')
+    if opt.boundary_width is not None and not 1 <= opt.boundary_width <= 254:
+        ap.error('--boundary-width must be in [1, 254]')
     if opt.min_area < 0:
         ap.error('--min-area must be >= 0')
     if opt.stride is not None and opt.window is None:
@@ -143,7 +186,7 @@ def main(argv=None):
     elif opt.ema:
         raise ValueError('--ema needs --weights')
     metrics = test(model.cuda(), fetcher, opt.scales, opt.flip, opt.min_area, opt.connectivity,
-                   opt.largest_only, opt.window, opt.stride)
+                   opt.largest_only, opt.window, opt.stride, opt.boundary, opt.boundary_width)
     print('metrics: %8g' % metrics)
     return metrics
 
