@@ -484,6 +484,26 @@ int64_t pseg_ce_opts_workspace_bytes(int B, int C, int64_t HW);
 int pseg_ce_opts_fwd_bwd(const float* logits, const int64_t* target, int B, int C, int64_t HW, int64_t ignore_index,
                          const float* class_weight, float label_smoothing, float focal_gamma, float keep_ratio,
                          float* dlogits, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream);
+/* pseg_ce_opts_binned_fwd_bwd (csrc/ce_opts.hip): pseg_ce_opts_fwd_bwd with a per-pixel weight taken from a table by a byte
+ *   per pixel -- the boundary-weighted cross-entropy when the byte is pseg_label_depth's depth.  pixel_bin uint8 [B][HW]
+ *   (device; no alignment beyond one byte is needed), bin_weight 256 fp32 values (device).  PRECONDITION: the 256 values are
+ *   finite and non-negative; the call cannot read device memory on the host, so the caller checks them before upload.
+ *   The pixel weight is u_i = bin_weight[pixel_bin[i]].  Everything else is pseg_ce_opts_fwd_bwd's contract with, f_i as
+ *   defined there, the per-pixel quantity g_i = u_i f_i in f_i's place:
+ *       the selection (keep_ratio < 1) parks and ranks g_i; tau = the k-th largest g; kept = valid pixels with g_i >= tau,
+ *         ties at tau all kept;
+ *       loss = sum_kept g_i / sum_kept (u_i w_{t_i});      dlogits_i = u_i (df_i/dz) / divisor on kept pixels, 0 elsewhere.
+ *   A pixel with u_i = 0 is still valid: it is counted in n_valid, may be kept, and contributes 0 to both sums and a zero
+ *   gradient.  loss_out[6] has the same layout, [5] = sum_kept u_i w_{t_i}; a zero divisor gives a NaN loss and an all-zero
+ *   gradient.  The same arguments are refused, and null pixel_bin / bin_weight; the messages start with
+ *   "pseg_ce_opts_binned_fwd_bwd:" and come before any launch.  workspace: pseg_ce_opts_workspace_bytes(B, C, HW), unchanged.
+ *   Deterministic under the same rules.  With bin_weight all ones the loss, tau, the counts and every gradient element equal
+ *   pseg_ce_opts_fwd_bwd's bit for bit (1.0f * x is exact).  One byte per pixel is read beside the target in every pass
+ *   that reads the target; the table lives in LDS; no fp32 weight map exists. */
+int pseg_ce_opts_binned_fwd_bwd(const float* logits, const int64_t* target, const uint8_t* pixel_bin,
+                                const float* bin_weight, int B, int C, int64_t HW, int64_t ignore_index,
+                                const float* class_weight, float label_smoothing, float focal_gamma, float keep_ratio,
+                                float* dlogits, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream);
 /* pseg_tversky_fwd_bwd (csrc/tversky.hip): the soft region-overlap loss -- soft Dice, Tversky (Salehi et al.) and
  *   focal-Tversky (Abraham & Khan) -- over the softmax of the logits, with its gradient.  logits fp32 NCHW [B][C][HW], target
  *   int64 [B][HW].  A pixel is valid iff target != ignore_index and 0 <= target < C (the predicate of pseg_ce_fwd_bwd);

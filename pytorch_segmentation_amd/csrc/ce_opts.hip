@@ -15,6 +15,10 @@
 // The kept set, tau and the loss all come from the parked values, so they are consistent by construction; ties at tau are
 // all kept.  Floating-point sums go through per-block partials added in a fixed order, in double; atomics add integers
 // only (counts, histograms), so two calls give identical bits.
+// pseg_ce_opts_binned_fwd_bwd is the same pipeline with a per-pixel weight u = bin_weight[pixel_bin]: the
+// BINNED instantiations of the kernels that see pixels read one byte beside the target and look u up in a 256-entry table
+// staged in LDS; u scales the per-pixel value BEFORE it is summed or parked (g = u f), the divisor's terms (u w_t) and the
+// gradient.  1.0f * x is exact, so a table of ones gives the unbinned call's bits.
 #include "common.h"
 
 #include <math.h>
@@ -46,9 +50,33 @@ struct CoArgs {
   long long HW, groups, ignore_index;
   float eps, gamma;
   int gint;              // gamma when it is an integer, else -1
+  const uint8_t* bins;   // BINNED only: [B][HW], any alignment
+  const float* btab;     // BINNED only: 256 pixel weights
+  int bins_aligned;      // bins is 4-byte aligned: a lane's VEC bytes are one load
 };
 
 __device__ __forceinline__ float co_wgt(const float* __restrict__ w, long long c) { return w ? w[c] : 1.f; }
+
+// The table of pixel weights in LDS, one entry per lane of the 256-lane block (the caller's next barrier publishes it).
+// Lookups are ds_read_b32 at a per-lane address: equal bins broadcast, and neighbouring pixels mostly share a depth.
+__device__ __forceinline__ void co_stage_table(float* ltab, const float* __restrict__ btab) { ltab[threadIdx.x] = btab[threadIdx.x]; }
+
+// the VEC consecutive bin bytes of a lane: one 32-bit (16-bit) load when the plane is aligned, else byte loads
+template <int VEC>
+__device__ __forceinline__ void co_load_bins(const uint8_t* __restrict__ bp, bool aligned, unsigned (&bin)[VEC]) {
+  if (VEC == 4 && aligned) {
+    const unsigned wd = *reinterpret_cast<const unsigned*>(bp);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) bin[e] = (wd >> (8 * e)) & 0xFFu;
+  } else if (VEC == 2 && aligned) {
+    const unsigned wd = *reinterpret_cast<const unsigned short*>(bp);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) bin[e] = (wd >> (8 * e)) & 0xFFu;
+  } else {
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) bin[e] = bp[e];
+  }
+}
 
 // order-preserving map float -> unsigned (and back); valid pixels never get key 0
 __device__ __forceinline__ unsigned co_key(float f) {
@@ -121,12 +149,19 @@ __device__ __forceinline__ CoTerm co_term(float s, float so, float et, float zt,
   return r;
 }
 
-// targets only (keep_ratio == 1): label counts and the partials of the divisor sum_valid w_t
+// targets only (keep_ratio == 1): label counts and the partials of the divisor sum_valid w_t (BINNED: u w_t)
+template <bool BINNED>
 __global__ __launch_bounds__(256) void co_count_kernel(const int64_t* __restrict__ target, long long n, long long ignore_index,
                                                        int C, const float* __restrict__ w, CoHeader* __restrict__ hdr,
-                                                       double* __restrict__ pw) {
+                                                       double* __restrict__ pw, const uint8_t* __restrict__ bins,
+                                                       const float* __restrict__ btab) {
   __shared__ double shd[4];
   __shared__ int shc[2][4];
+  __shared__ float ltab[BINNED ? 256 : 1];
+  if (BINNED) {
+    co_stage_table(ltab, btab);
+    __syncthreads();
+  }
   int cnt = 0, bad = 0;
   double sw = 0.0;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
@@ -134,7 +169,7 @@ __global__ __launch_bounds__(256) void co_count_kernel(const int64_t* __restrict
     const bool v = ce_valid(t, ignore_index, C);
     cnt += v ? 1 : 0;
     bad += (!v && t != ignore_index) ? 1 : 0;
-    if (v) sw += (double)co_wgt(w, t);
+    if (v) sw += BINNED ? (double)(ltab[bins[i]] * co_wgt(w, t)) : (double)co_wgt(w, t);
   }
   co_block_count(cnt, bad, &hdr->n_valid, &hdr->n_bad, shc);
   const double tot = co_block_sum_d(sw, shd);
@@ -144,20 +179,20 @@ __global__ __launch_bounds__(256) void co_count_kernel(const int64_t* __restrict
 // MODE 0: loss partials + gradient, every valid pixel kept.  MODE 1: park the keys, count the labels, histogram of the
 // keys' top byte.  MODE 2: gradient, kept = parked key >= key of tau.
 // CMAX: compile-time bound on the class count (values live in registers); VEC consecutive pixels per lane.
-template <int CMAX, int VEC, int MODE>
+template <int CMAX, int VEC, int MODE, bool BINNED>
 __global__ __launch_bounds__(256) void co_pixel_kernel(const CoArgs a) {
   typedef float vecf __attribute__((ext_vector_type(VEC)));
   typedef unsigned vecu __attribute__((ext_vector_type(VEC)));
   __shared__ double shd[4];
   __shared__ int shc[2][4];
   __shared__ unsigned lh[256];
+  __shared__ float ltab[BINNED ? 256 : 1];
   const int C = a.C;
   const long long HW = a.HW;
   const float* __restrict__ w = a.w;
-  if (MODE == 1) {
-    lh[threadIdx.x] = 0;
-    __syncthreads();
-  }
+  if (MODE == 1) lh[threadIdx.x] = 0;
+  if (BINNED) co_stage_table(ltab, a.btab);
+  if (MODE == 1 || BINNED) __syncthreads();
   float W = 0.f;
   for (int c = 0; c < C; ++c) W += co_wgt(w, c);
   const float epsC = a.eps / (float)C;
@@ -193,6 +228,13 @@ __global__ __launch_bounds__(256) void co_pixel_kernel(const CoArgs a) {
       valid[e] = ce_valid(t[e], a.ignore_index, C);
       wt[e] = valid[e] ? co_wgt(w, t[e]) : 0.f;
     }
+    vecf u = 1.f;
+    if (BINNED) {
+      unsigned bin[VEC];
+      co_load_bins<VEC>(a.bins + b * HW + p, a.bins_aligned != 0, bin);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) u[e] = ltab[bin[e]];
+    }
     // one exponential per logit: v[c] becomes exp(v[c] - m) (__expf / __logf: the hardware exp2 / log2 paths)
     vecf s = 0.f, so = 0.f, et = 0.f, zt = 0.f, wz = 0.f;
 #pragma unroll
@@ -216,16 +258,17 @@ __global__ __launch_bounds__(256) void co_pixel_kernel(const CoArgs a) {
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
       const CoTerm r = co_term(s[e], so[e], et[e], zt[e], wz[e], wt[e], W, a.eps, epsC, a.gamma, a.gint, __logf(s[e]));
+      const float gf = BINNED ? u[e] * r.f : r.f;      // (u >= 0, f >= +0: never -0)
       bool kept = valid[e];
-      if (MODE == 0 && valid[e]) lsum += (double)r.f;
+      if (MODE == 0 && valid[e]) lsum += (double)gf;
       if (MODE == 1) {
-        key[e] = valid[e] ? co_key(r.f) : 0u;
+        key[e] = valid[e] ? co_key(gf) : 0u;
         if (valid[e]) atomicAdd(&lh[key[e] >> 24], 1u);
         cnt += valid[e] ? 1 : 0;
         bad += (!valid[e] && t[e] != a.ignore_index) ? 1 : 0;
       }
       if (MODE == 2) kept = valid[e] && key[e] >= tau_key;
-      const float sc = kept ? inv_den : 0.f;
+      const float sc = kept ? (BINNED ? u[e] * inv_den : inv_den) : 0.f;
       P[e] = r.P * sc;
       Q[e] = r.Q * sc;
       T[e] = r.T * sc;
@@ -254,18 +297,18 @@ __global__ __launch_bounds__(256) void co_pixel_kernel(const CoArgs a) {
 }
 
 // any class count: one pixel per lane, sweeps over the class planes (the re-reads hit L2)
-template <int MODE>
+template <int MODE, bool BINNED>
 __global__ __launch_bounds__(256) void co_generic_kernel(const CoArgs a) {
   __shared__ double shd[4];
   __shared__ int shc[2][4];
   __shared__ unsigned lh[256];
+  __shared__ float ltab[BINNED ? 256 : 1];
   const int C = a.C;
   const long long HW = a.HW;
   const float* __restrict__ w = a.w;
-  if (MODE == 1) {
-    lh[threadIdx.x] = 0;
-    __syncthreads();
-  }
+  if (MODE == 1) lh[threadIdx.x] = 0;
+  if (BINNED) co_stage_table(ltab, a.btab);
+  if (MODE == 1 || BINNED) __syncthreads();
   float W = 0.f;
   for (int c = 0; c < C; ++c) W += co_wgt(w, c);
   const float epsC = a.eps / (float)C;
@@ -294,10 +337,12 @@ __global__ __launch_bounds__(256) void co_generic_kernel(const CoArgs a) {
       wz += co_wgt(w, c) * d;
     }
     const CoTerm r = co_term(s, so, et, zt, wz, wt, W, a.eps, epsC, a.gamma, a.gint, logf(s));
+    const float u = BINNED ? ltab[a.bins[g]] : 1.f;
+    const float gf = BINNED ? u * r.f : r.f;
     bool kept = valid;
-    if (MODE == 0 && valid) lsum += (double)r.f;
+    if (MODE == 0 && valid) lsum += (double)gf;
     if (MODE == 1) {
-      const unsigned key = valid ? co_key(r.f) : 0u;
+      const unsigned key = valid ? co_key(gf) : 0u;
       a.keys[g] = key;
       if (valid) atomicAdd(&lh[key >> 24], 1u);
       cnt += valid ? 1 : 0;
@@ -305,7 +350,7 @@ __global__ __launch_bounds__(256) void co_generic_kernel(const CoArgs a) {
     }
     if (MODE == 2) kept = valid && a.keys[g] >= tau_key;
     if (MODE != 1 && a.dlogits) {
-      const float sc = kept ? inv_den : 0.f;
+      const float sc = kept ? (BINNED ? u * inv_den : inv_den) : 0.f;
       const float P = r.P * sc, Q = r.Q * sc, T = r.T * sc;
       float* dp = a.dlogits + b * C * HW + p;
       for (int c = 0; c < C; ++c) {
@@ -365,13 +410,21 @@ __global__ __launch_bounds__(256) void co_select_kernel(CoHeader* __restrict__ h
   }
 }
 
-// keys + targets: partials of sum f and sum w_t over the kept pixels, and their number
+// keys + targets: partials of sum f and sum w_t over the kept pixels, and their number (BINNED: the parked values are
+// u f already; the divisor's terms are u w_t)
+template <bool BINNED>
 __global__ __launch_bounds__(256) void co_kept_kernel(const unsigned* __restrict__ keys, const int64_t* __restrict__ target,
                                                       long long n, long long ignore_index, int C,
                                                       const float* __restrict__ w, CoHeader* __restrict__ hdr,
-                                                      double* __restrict__ pf, double* __restrict__ pw) {
+                                                      double* __restrict__ pf, double* __restrict__ pw,
+                                                      const uint8_t* __restrict__ bins, const float* __restrict__ btab) {
   __shared__ double shd[4];
   __shared__ int shc[2][4];
+  __shared__ float ltab[BINNED ? 256 : 1];
+  if (BINNED) {
+    co_stage_table(ltab, btab);
+    __syncthreads();
+  }
   const unsigned tau_key = hdr->prefix;
   int cnt = 0;
   double sf = 0.0, sw = 0.0;
@@ -380,7 +433,7 @@ __global__ __launch_bounds__(256) void co_kept_kernel(const unsigned* __restrict
     const long long t = target[i];
     if (ce_valid(t, ignore_index, C) && k >= tau_key) {
       sf += (double)co_unkey(k);
-      sw += (double)co_wgt(w, t);
+      sw += BINNED ? (double)(ltab[bins[i]] * co_wgt(w, t)) : (double)co_wgt(w, t);
       ++cnt;
     }
   }
@@ -460,14 +513,14 @@ static bool co_sizes_ok(int B, int C, int64_t HW) {
 }
 
 // launch the per-pixel kernel of one MODE: the register form for C <= 32 (vector loads when the planes allow), else generic
-template <int MODE>
+template <int MODE, bool BINNED>
 static int co_launch_pixels(CoArgs a, long long npix, bool vec4, hipStream_t st) {
   int blocks;
 #define CO_LAUNCH(CMAX, VEC)                                                                              \
   do {                                                                                                    \
     a.groups = npix / VEC;                                                                                \
     blocks = co_blocks(a.groups, kCoMaxBlocks);                                                           \
-    hipLaunchKernelGGL((co_pixel_kernel<CMAX, VEC, MODE>), dim3(blocks), dim3(256), 0, st, a);            \
+    hipLaunchKernelGGL((co_pixel_kernel<CMAX, VEC, MODE, BINNED>), dim3(blocks), dim3(256), 0, st, a);            \
   } while (0)
   const int C = a.C;
   if (C <= 4 && vec4) CO_LAUNCH(4, 4);
@@ -481,41 +534,34 @@ static int co_launch_pixels(CoArgs a, long long npix, bool vec4, hipStream_t st)
   else {
     a.groups = npix;
     blocks = co_blocks(npix, kCoMaxBlocks);
-    hipLaunchKernelGGL((co_generic_kernel<MODE>), dim3(blocks), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((co_generic_kernel<MODE, BINNED>), dim3(blocks), dim3(256), 0, st, a);
   }
 #undef CO_LAUNCH
   return blocks;
 }
 
-}  // namespace pseg
-
-using namespace pseg;
-
-extern "C" {
-
-int64_t pseg_ce_opts_workspace_bytes(int B, int C, int64_t HW) {
-  if (!co_sizes_ok(B, C, HW)) return 0;
-  return co_plan((int64_t)B * HW).bytes;
-}
-
-int pseg_ce_opts_fwd_bwd(const float* logits, const int64_t* target, int B, int C, int64_t HW, int64_t ignore_index,
-                         const float* class_weight, float label_smoothing, float focal_gamma, float keep_ratio,
-                         float* dlogits, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream) {
-  PSEG_REQUIRE(logits && target && loss_out && workspace, "ce_opts: null pointer");
-  PSEG_REQUIRE(B > 0 && C > 0 && HW > 0, "ce_opts: bad sizes");
-  PSEG_REQUIRE(co_sizes_ok(B, C, HW), "ce_opts: more than 2^31 - 1 pixels are not supported (B=%d HW=%lld); split the batch", B,
+// both entry points: `fn` heads the refusal messages; BINNED takes pixel_bin / bin_weight
+template <bool BINNED>
+static int co_run(const char* fn, const float* logits, const int64_t* target, const uint8_t* pixel_bin, const float* bin_weight,
+                  int B, int C, int64_t HW, int64_t ignore_index, const float* class_weight, float label_smoothing,
+                  float focal_gamma, float keep_ratio, float* dlogits, float* loss_out, void* workspace,
+                  int64_t workspace_bytes, void* stream) {
+  PSEG_REQUIRE(logits && target && loss_out && workspace, "%s: null pointer", fn);
+  PSEG_REQUIRE(!BINNED || (pixel_bin && bin_weight), "%s: null pixel_bin or bin_weight", fn);
+  PSEG_REQUIRE(B > 0 && C > 0 && HW > 0, "%s: bad sizes", fn);
+  PSEG_REQUIRE(co_sizes_ok(B, C, HW), "%s: more than 2^31 - 1 pixels are not supported (B=%d HW=%lld); split the batch", fn, B,
                (long long)HW);
   const long long npix = (long long)B * HW;
   const CoPlan pl = co_plan(npix);
-  PSEG_REQUIRE(workspace_bytes >= pl.bytes, "ce_opts: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+  PSEG_REQUIRE(workspace_bytes >= pl.bytes, "%s: workspace too small (%lld < %lld bytes)", fn, (long long)workspace_bytes,
                (long long)pl.bytes);
-  PSEG_REQUIRE(((uintptr_t)workspace & 15) == 0, "ce_opts: workspace must be 16-byte aligned");
-  PSEG_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "ce_opts: label_smoothing must be in [0, 1) (got %g)",
+  PSEG_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", fn);
+  PSEG_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "%s: label_smoothing must be in [0, 1) (got %g)", fn,
                (double)label_smoothing);
-  PSEG_REQUIRE(keep_ratio > 0.f && keep_ratio <= 1.f, "ce_opts: keep_ratio must be in (0, 1] (got %g)", (double)keep_ratio);
+  PSEG_REQUIRE(keep_ratio > 0.f && keep_ratio <= 1.f, "%s: keep_ratio must be in (0, 1] (got %g)", fn, (double)keep_ratio);
   // 0 < gamma < 1: with smoothing the derivative of (1 - p_t)^gamma is unbounded as p_t -> 1
   PSEG_REQUIRE(focal_gamma == 0.f || (focal_gamma >= 1.f && focal_gamma <= 8.f),
-               "ce_opts: focal_gamma must be 0 or in [1, 8] (got %g)", (double)focal_gamma);
+               "%s: focal_gamma must be 0 or in [1, 8] (got %g)", fn, (double)focal_gamma);
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
   CoHeader* hdr = (CoHeader*)ws;
@@ -523,7 +569,7 @@ int pseg_ce_opts_fwd_bwd(const float* logits, const int64_t* target, int B, int 
   double* pw = (double*)(ws + pl.pw);
   unsigned* keys = (unsigned*)(ws + pl.keys);
   if (hipMemsetAsync(hdr, 0, sizeof(CoHeader), st) != hipSuccess) {
-    set_error("ce_opts: hipMemsetAsync failed");
+    set_error("%s: hipMemsetAsync failed", fn);
     return PSEG_ERR_HIP;
   }
   CoArgs a;
@@ -541,22 +587,26 @@ int pseg_ce_opts_fwd_bwd(const float* logits, const int64_t* target, int B, int 
   a.eps = label_smoothing;
   a.gamma = focal_gamma;
   a.gint = (focal_gamma == floorf(focal_gamma)) ? (int)focal_gamma : -1;
+  a.bins = pixel_bin;
+  a.btab = bin_weight;
+  a.bins_aligned = (((uintptr_t)pixel_bin & 3) == 0) ? 1 : 0;      // (vector paths have HW % 4 == 0: every lane's bytes are then aligned)
   const bool vec4 = (HW % 4 == 0) && (((uintptr_t)logits & 15) == 0) && (!dlogits || ((uintptr_t)dlogits & 15) == 0);
   const long long ign = (long long)ignore_index;
   if (keep_ratio == 1.f) {
     const int nb = co_blocks(npix, 2048);
-    hipLaunchKernelGGL(co_count_kernel, dim3(nb), dim3(256), 0, st, target, npix, ign, C, class_weight, hdr, pw);
+    hipLaunchKernelGGL(co_count_kernel<BINNED>, dim3(nb), dim3(256), 0, st, target, npix, ign, C, class_weight, hdr, pw, pixel_bin,
+                       bin_weight);
     PSEG_LAUNCH_CHECK();
     hipLaunchKernelGGL(co_den_kernel, dim3(1), dim3(256), 0, st, (const double*)pw, nb, hdr);
     PSEG_LAUNCH_CHECK();
-    const int blocks = co_launch_pixels<0>(a, npix, vec4, st);
+    const int blocks = co_launch_pixels<0, BINNED>(a, npix, vec4, st);
     PSEG_LAUNCH_CHECK();
     hipLaunchKernelGGL(co_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)pf, blocks, 0, (const CoHeader*)hdr,
                        loss_out);
     PSEG_LAUNCH_CHECK();
     return PSEG_OK;
   }
-  co_launch_pixels<1>(a, npix, vec4, st);
+  co_launch_pixels<1, BINNED>(a, npix, vec4, st);
   PSEG_LAUNCH_CHECK();
   const int nb = co_blocks(npix, 2048);
   for (int round = 0; round < 4; ++round) {
@@ -567,18 +617,45 @@ int pseg_ce_opts_fwd_bwd(const float* logits, const int64_t* target, int B, int 
     hipLaunchKernelGGL(co_select_kernel, dim3(1), dim3(256), 0, st, hdr, round, keep_ratio);
     PSEG_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(co_kept_kernel, dim3(nb), dim3(256), 0, st, (const unsigned*)keys, target, npix, ign, C, class_weight, hdr,
-                     pf, pw);
+  hipLaunchKernelGGL(co_kept_kernel<BINNED>, dim3(nb), dim3(256), 0, st, (const unsigned*)keys, target, npix, ign, C, class_weight,
+                     hdr, pf, pw, pixel_bin, bin_weight);
   PSEG_LAUNCH_CHECK();
   hipLaunchKernelGGL(co_den_kernel, dim3(1), dim3(256), 0, st, (const double*)pw, nb, hdr);
   PSEG_LAUNCH_CHECK();
   hipLaunchKernelGGL(co_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)pf, nb, 1, (const CoHeader*)hdr, loss_out);
   PSEG_LAUNCH_CHECK();
   if (dlogits) {
-    co_launch_pixels<2>(a, npix, vec4, st);
+    co_launch_pixels<2, BINNED>(a, npix, vec4, st);
     PSEG_LAUNCH_CHECK();
   }
   return PSEG_OK;
+}
+
+}  // namespace pseg
+
+using namespace pseg;
+
+extern "C" {
+
+int64_t pseg_ce_opts_workspace_bytes(int B, int C, int64_t HW) {
+  if (!co_sizes_ok(B, C, HW)) return 0;
+  return co_plan((int64_t)B * HW).bytes;
+}
+
+int pseg_ce_opts_fwd_bwd(const float* logits, const int64_t* target, int B, int C, int64_t HW, int64_t ignore_index,
+                         const float* class_weight, float label_smoothing, float focal_gamma, float keep_ratio,
+                         float* dlogits, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream) {
+  return co_run<false>("ce_opts", logits, target, nullptr, nullptr, B, C, HW, ignore_index, class_weight, label_smoothing,
+                       focal_gamma, keep_ratio, dlogits, loss_out, workspace, workspace_bytes, stream);
+}
+
+int pseg_ce_opts_binned_fwd_bwd(const float* logits, const int64_t* target, const uint8_t* pixel_bin,
+                                const float* bin_weight, int B, int C, int64_t HW, int64_t ignore_index,
+                                const float* class_weight, float label_smoothing, float focal_gamma, float keep_ratio,
+                                float* dlogits, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream) {
+  return co_run<true>("pseg_ce_opts_binned_fwd_bwd", logits, target, pixel_bin, bin_weight, B, C, HW, ignore_index,
+                      class_weight, label_smoothing, focal_gamma, keep_ratio, dlogits, loss_out, workspace, workspace_bytes,
+                      stream);
 }
 
 }  // extern "C"

@@ -1150,6 +1150,47 @@ def ce_opts_fwd_bwd(logits, target, class_weight=None, label_smoothing=0.0, foca
     return out, dl
 
 
+def bin_weight_table(values, device):
+    """256 pixel weights -> the contiguous fp32 [256] tensor on `device` that ce_opts_binned_fwd_bwd takes.  The values are
+    checked HERE, on the host before the upload (finite and non-negative: pseg_ce_opts_binned_fwd_bwd's precondition, which
+    the C call cannot check without reading device memory)."""
+    t = torch.as_tensor(values, dtype=torch.float32).detach().cpu().contiguous()
+    if t.shape != (256,):
+        raise ValueError('bin_weight: 256 values, one per byte value (got shape %s)' % (tuple(t.shape),))
+    if not bool(torch.isfinite(t).all()) or bool((t < 0).any()):
+        raise ValueError('bin_weight: the 256 values must be finite and non-negative')
+    return t.to(device)
+
+
+def ce_opts_binned_fwd_bwd(logits, target, pixel_bin, bin_weight, class_weight=None, label_smoothing=0.0, focal_gamma=0.0,
+                           keep_ratio=1.0, want_grad=True, ignore_index=-100):
+    """ce_opts_fwd_bwd with the per-pixel weight bin_weight[pixel_bin] (pseg_ce_opts_binned_fwd_bwd): the per-pixel value,
+    the divisor's terms and the gradient are scaled by it, and the selection ranks the scaled values.  pixel_bin: uint8
+    [B, H, W] on the logits' device, contiguous itself but at any byte offset of its storage; bin_weight: fp32 [256] on that
+    device, finite and non-negative (bin_weight_table checks and uploads).  Both are required: the call without them is
+    ce_opts_fwd_bwd.  -> (out[6] = [loss, n_valid, n_out_of_range_targets, n_kept, tau, sum of the kept pixels' u * w], dlogits|None)."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.shape == (logits.shape[0],) + logits.shape[2:]
+    if pixel_bin is None or bin_weight is None:
+        raise ValueError('ce_opts_binned_fwd_bwd: pixel_bin and bin_weight come together (without them: ce_opts_fwd_bwd)')
+    B, C, H, W = logits.shape
+    assert pixel_bin.device == logits.device and pixel_bin.dtype == torch.uint8 and pixel_bin.is_contiguous() and \
+        pixel_bin.shape == (B, H, W), 'pixel_bin: contiguous uint8 %s on %s' % ((B, H, W), logits.device)
+    assert bin_weight.device == logits.device and bin_weight.dtype == torch.float32 and bin_weight.is_contiguous() and \
+        bin_weight.shape == (256,), 'bin_weight: 256 fp32 values on %s' % (logits.device,)
+    if class_weight is not None:
+        assert class_weight.device == logits.device and class_weight.dtype == torch.float32 and \
+            class_weight.is_contiguous() and class_weight.shape == (C,), 'class_weight: %d fp32 values on %s' % (C, logits.device)
+    dl = torch.empty_like(logits) if want_grad else None
+    out = torch.empty(6, dtype=torch.float32, device=logits.device)
+    nbytes = _lib.query('pseg_ce_opts_workspace_bytes', B, C, H * W)
+    ws = workspace.get(nbytes, logits.device)
+    _lib.call('pseg_ce_opts_binned_fwd_bwd', logits.data_ptr(), target.data_ptr(), pixel_bin.data_ptr(), bin_weight.data_ptr(),
+              B, C, H * W, ignore_index, _ptr(class_weight), float(label_smoothing), float(focal_gamma), float(keep_ratio),
+              _ptr(dl), out.data_ptr(), ws.data_ptr(), nbytes, _stream())
+    return out, dl
+
+
 # the Lovasz loss's sort buffers (hundreds of MiB at training sizes) get a cache of their own: allocated once per stream,
 # and the small scratch every conv shares stays small
 lovasz_workspace = _Workspace()

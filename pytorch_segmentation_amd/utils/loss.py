@@ -176,6 +176,100 @@ def weighted_cross_entropy_loss(outputs, targets, class_weight=None, label_smoot
                                      ignore_index)
 
 
+class _CrossEntropyBinnedFn(torch.autograd.Function):
+    """_CrossEntropyOptsFn with a per-pixel weight bin_weight[pixel_bin] (pseg_ce_opts_binned_fwd_bwd).  Built the same way:
+    forward leaves the gradient with respect to the logits, backward only rescales it by the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, pixel_bin, bin_weight, class_weight, label_smoothing, focal_gamma, keep_ratio,
+                ignore_index):
+        need = logits.requires_grad
+        out, dl = ops.ce_opts_binned_fwd_bwd(logits, targets, pixel_bin, bin_weight, class_weight, label_smoothing,
+                                             focal_gamma, keep_ratio, want_grad=need, ignore_index=ignore_index)
+        if CHECK_LABELS and out[2].item() != 0:     # (host sync: debugging aid, off by default)
+            raise IndexError('%d target values are outside [0, %d) and are not ignore_index'
+                             % (int(out[2].item()), logits.shape[1]))
+        ctx.dl = dl
+        ctx.mark_non_differentiable()
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        dl = ctx.dl
+        ctx.dl = None
+        if dl is None:
+            return (None,) * 9
+        g = g.reshape(1) if g.dtype == torch.float32 else g.float().reshape(1)
+        ops.scale_inplace(dl, g.contiguous())
+        return (dl,) + (None,) * 8
+
+
+BOUNDARY_FALLOFFS = ('flat', 'linear', 'gaussian')
+
+
+def boundary_weight_table(width, boost, falloff='gaussian', sigma=None):
+    """The 256 pixel weights of the boundary-weighted cross-entropy, indexed by ops.label_depth's byte: fp32 [256] on the CPU.
+    For a depth k in 1 .. width (k = 1: the pixel touches a different label) the weight is 1 + boost (falloff 'flat'),
+    1 + boost (width + 1 - k) / width ('linear') or 1 + boost exp(-(k - 1)^2 / (2 sigma^2)) ('gaussian', sigma defaulting
+    to width / 3: the UNet paper's w0 exp(-d^2 / 2 sigma^2) with the Chebyshev depth for d).  Depth width + 1 ("no contour
+    within width") and the bytes the depth map cannot hold (0 and above width + 1) weigh 1."""
+    import math
+    if int(width) != width or not 1 <= int(width) <= ops.BOUNDARY_MAX_WIDTH:
+        raise ValueError('boundary_weight_table: width must be an integer in [1, %d]; got %r' % (ops.BOUNDARY_MAX_WIDTH, width))
+    width, boost = int(width), float(boost)
+    if not (math.isfinite(boost) and boost >= 0.0):
+        raise ValueError('boundary_weight_table: boost must be finite and >= 0; got %r' % (boost,))
+    if falloff not in BOUNDARY_FALLOFFS:
+        raise ValueError('boundary_weight_table: unknown falloff %r (choose from %s)' % (falloff, ', '.join(BOUNDARY_FALLOFFS)))
+    if sigma is None:
+        sigma = width / 3.0
+    sigma = float(sigma)
+    if not (math.isfinite(sigma) and sigma > 0.0):
+        raise ValueError('boundary_weight_table: sigma must be finite and > 0; got %r' % (sigma,))
+    table = torch.ones(256, dtype=torch.float64)
+    k = torch.arange(1, width + 1, dtype=torch.float64)
+    if falloff == 'flat':
+        shape = torch.ones_like(k)
+    elif falloff == 'linear':
+        shape = (width + 1 - k) / width
+    else:
+        shape = torch.exp(-(k - 1) ** 2 / (2.0 * sigma * sigma))
+    table[1:width + 1] = 1.0 + boost * shape
+    return table.float()
+
+
+_BOUNDARY_TABLES = {}      # (width, boost, falloff, sigma, device) -> the uploaded table
+
+
+def _boundary_table_on(width, boost, falloff, sigma, device):
+    key = (int(width), float(boost), falloff, None if sigma is None else float(sigma), str(device))
+    if key not in _BOUNDARY_TABLES:
+        _BOUNDARY_TABLES[key] = ops.bin_weight_table(boundary_weight_table(width, boost, falloff, sigma), device)
+    return _BOUNDARY_TABLES[key]
+
+
+def boundary_weighted_cross_entropy_loss(outputs, targets, boundary_boost, boundary_width=None, boundary_ratio=0.02,
+                                         boundary_falloff='gaussian', boundary_sigma=None, class_weight=None,
+                                         label_smoothing=0.0, focal_gamma=0.0, keep_ratio=1.0, ignore_index=-100):
+    """weighted_cross_entropy_loss with every pixel weighted by its distance to the nearest label change of the target:
+    u = boundary_weight_table(d, boundary_boost, boundary_falloff, boundary_sigma)[depth], depth = ops.label_depth(targets,
+    C, d, edge=False), d = boundary_width or boundary_width(target size, boundary_ratio) -- the evaluation's rule, so the band
+    follows multi-scale and --rect.  loss = sum_kept u f / sum_kept u w_t; with keep_ratio < 1 the hardest pixels are chosen
+    by u f.  The image border is not a contour (edge=False).  Void labels compare by value in the depth map: a pixel beside
+    an ignore band (VOC's 255 outline) counts as near a contour and is boosted, while the void pixels themselves stay out of
+    the loss.  Two depth launches plus one HIP call (pseg_ce_opts_binned_fwd_bwd), which reads the depth byte beside the
+    target; no fp32 weight map is written.  Bit-reproducible."""
+    outputs, targets = _logits_at_target_size(outputs, targets)
+    w = _class_weight_on(class_weight, outputs.device)
+    if w is not None and w.numel() != outputs.shape[1]:
+        raise ValueError('class_weight has %d values for %d classes' % (w.numel(), outputs.shape[1]))
+    d = int(boundary_width) if boundary_width else _width_from_ratio(targets.shape[1:], boundary_ratio)
+    table = _boundary_table_on(d, boundary_boost, boundary_falloff, boundary_sigma, outputs.device)
+    depth = ops.label_depth(targets, outputs.shape[1], d, edge=False)
+    return _CrossEntropyBinnedFn.apply(outputs, targets, depth, table, w, float(label_smoothing), float(focal_gamma),
+                                       float(keep_ratio), ignore_index)
+
+
 class _TverskyFn(torch.autograd.Function):
     """Soft Dice / Tversky / focal-Tversky loss over the softmax of the logits (Salehi et al.; Abraham & Khan).  Built like
     _LovaszSoftmaxFn: forward runs pseg_tversky_fwd_bwd, which leaves the gradient with respect to the logits as well;
@@ -230,10 +324,14 @@ LOSSES = {'ce': compute_loss, 'lovasz': _lovasz_loss_fn, 'ce+lovasz': _ce_lovasz
 CE_OPTIONS = {'class_weight': None, 'label_smoothing': 0.0, 'focal_gamma': 0.0, 'keep_ratio': 1.0}
 TVERSKY_OPTIONS = {'tversky_alpha': 0.5, 'tversky_beta': 0.5, 'tversky_smooth': 1.0, 'tversky_power': 1.0,
                    'tversky_per_image': False, 'tversky_all_classes': False, 'tversky_weight': 1.0}
+# boundary_width 0: from boundary_ratio; boundary_sigma 0: width / 3.  On iff boundary_boost > 0.
+BOUNDARY_OPTIONS = {'boundary_boost': 0.0, 'boundary_width': 0, 'boundary_ratio': 0.02, 'boundary_falloff': 'gaussian',
+                    'boundary_sigma': 0.0}
 
 
-def _configured_ce(name, opts):
-    """loss_fn(outputs, targets, model) of 'ce' / 'ce+lovasz' with the cross-entropy configured by `opts`"""
+def _configured_ce_term(opts, bd):
+    """ce(outputs, targets) on logits already at the targets' size: the cross-entropy configured by `opts`, weighted by
+    the distance to the target's contours when `bd` (the boundary options, boost > 0) is given"""
     state = {'w': opts['class_weight'], 'device': None}
     ls, fg, kr = float(opts['label_smoothing']), float(opts['focal_gamma']), float(opts['keep_ratio'])
 
@@ -242,30 +340,37 @@ def _configured_ce(name, opts):
             state['w'], state['device'] = _class_weight_on(state['w'], device), device
         return state['w']
 
+    if bd is None:
+        return lambda outputs, targets: weighted_cross_entropy_loss(outputs, targets, weight_on(outputs.device), ls, fg, kr)
+    boost, falloff = float(bd['boundary_boost']), bd['boundary_falloff']
+    width, ratio = int(bd['boundary_width']) or None, float(bd['boundary_ratio'])
+    sigma = float(bd['boundary_sigma']) or None
+    boundary_weight_table(width or 1, boost, falloff, sigma)      # bad options are refused here, not at the first batch
+    return lambda outputs, targets: boundary_weighted_cross_entropy_loss(outputs, targets, boost, width, ratio, falloff, sigma,
+                                                                         weight_on(outputs.device), ls, fg, kr)
+
+
+def _configured_ce(name, opts, bd=None):
+    """loss_fn(outputs, targets, model) of 'ce' / 'ce+lovasz' with the cross-entropy configured by `opts` (and `bd`)"""
+    ce = _configured_ce_term(opts, bd)
+
     def _ce_opts_loss_fn(outputs, targets, model=None):
-        return weighted_cross_entropy_loss(outputs, targets, weight_on(outputs.device), ls, fg, kr)
+        return ce(outputs, targets)
 
     def _ce_opts_lovasz_loss_fn(outputs, targets, model=None):
         outputs, targets = _logits_at_target_size(outputs, targets)
-        return (weighted_cross_entropy_loss(outputs, targets, weight_on(outputs.device), ls, fg, kr)
-                + _LovaszSoftmaxFn.apply(outputs, targets, -100))
+        return ce(outputs, targets) + _LovaszSoftmaxFn.apply(outputs, targets, -100)
 
     return _ce_opts_loss_fn if name == 'ce' else _ce_opts_lovasz_loss_fn
 
 
-def _configured_tversky(name, opts, ce_set, tv):
+def _configured_tversky(name, opts, ce_set, tv, bd=None):
     """loss_fn(outputs, targets, model) of 'tversky' / 'ce+tversky' with the Tversky term configured by `tv` and, for
-    'ce+tversky' with ce_set, the cross-entropy by `opts`"""
+    'ce+tversky' with ce_set or `bd`, the cross-entropy by `opts` and `bd`"""
     args = (float(tv['tversky_alpha']), float(tv['tversky_beta']), float(tv['tversky_smooth']), float(tv['tversky_power']),
             bool(tv['tversky_per_image']), bool(tv['tversky_all_classes']))
     weight = float(tv['tversky_weight'])
-    state = {'w': opts['class_weight'], 'device': None}
-    ls, fg, kr = float(opts['label_smoothing']), float(opts['focal_gamma']), float(opts['keep_ratio'])
-
-    def weight_on(device):      # moved to the logits' device once
-        if state['w'] is not None and state['device'] != device:
-            state['w'], state['device'] = _class_weight_on(state['w'], device), device
-        return state['w']
+    ce = _configured_ce_term(opts, bd) if (ce_set or bd is not None) else _CrossEntropyFn.apply
 
     def _tversky_opts_loss_fn(outputs, targets, model=None):
         loss = tversky_loss(outputs, targets, *args)
@@ -273,12 +378,8 @@ def _configured_tversky(name, opts, ce_set, tv):
 
     def _ce_tversky_opts_loss_fn(outputs, targets, model=None):
         outputs, targets = _logits_at_target_size(outputs, targets)
-        if ce_set:
-            ce = weighted_cross_entropy_loss(outputs, targets, weight_on(outputs.device), ls, fg, kr)
-        else:
-            ce = _CrossEntropyFn.apply(outputs, targets)
         tvl = _TverskyFn.apply(outputs, targets, *args, -100)
-        return ce + (tvl if weight == 1.0 else weight * tvl)
+        return ce(outputs, targets) + (tvl if weight == 1.0 else weight * tvl)
 
     return _tversky_opts_loss_fn if name == 'tversky' else _ce_tversky_opts_loss_fn
 
@@ -290,27 +391,43 @@ def make_loss(name, **options):
     keep_ratio=) configure the cross-entropy of 'ce', 'ce+lovasz' and 'ce+tversky' (weighted_cross_entropy_loss); the
     Tversky options (tversky_alpha=, tversky_beta=, tversky_smooth=, tversky_power=, tversky_per_image=,
     tversky_all_classes=, and tversky_weight= for ce + weight * tversky) configure the Tversky term of 'tversky' and
-    'ce+tversky' (tversky_loss).  An option left at its default is not an option."""
+    'ce+tversky' (tversky_loss); the boundary options (boundary_boost= > 0 turns them on; boundary_width= in pixels or
+    boundary_ratio= of the diagonal, boundary_falloff=, boundary_sigma=) weight that same cross-entropy term by the distance
+    to the target's contours (boundary_weighted_cross_entropy_loss) and compose with the cross-entropy options.  An option
+    left at its default is not an option."""
     if name not in LOSSES:
         raise ValueError('unknown loss %r (choose from %s)' % (name, ', '.join(sorted(LOSSES))))
-    unknown = sorted(set(options) - set(CE_OPTIONS) - set(TVERSKY_OPTIONS))
+    unknown = sorted(set(options) - set(CE_OPTIONS) - set(TVERSKY_OPTIONS) - set(BOUNDARY_OPTIONS))
     if unknown:
-        raise TypeError('unknown cross-entropy option(s) %s (choose from %s; Tversky options: %s)'
-                        % (', '.join(unknown), ', '.join(sorted(CE_OPTIONS)), ', '.join(sorted(TVERSKY_OPTIONS))))
+        raise TypeError('unknown cross-entropy option(s) %s (choose from %s; Tversky options: %s; boundary options: %s)'
+                        % (', '.join(unknown), ', '.join(sorted(CE_OPTIONS)), ', '.join(sorted(TVERSKY_OPTIONS)),
+                           ', '.join(sorted(BOUNDARY_OPTIONS))))
     opts = dict(CE_OPTIONS, **{k: v for k, v in options.items() if k in CE_OPTIONS})
     tv = dict(TVERSKY_OPTIONS, **{k: v for k, v in options.items() if k in TVERSKY_OPTIONS})
+    bd = dict(BOUNDARY_OPTIONS, **{k: v for k, v in options.items() if k in BOUNDARY_OPTIONS and v is not None})
     is_set = opts['class_weight'] is not None or any(float(opts[k]) != CE_OPTIONS[k] for k in
                                                       ('label_smoothing', 'focal_gamma', 'keep_ratio'))
     tv_set = any(float(tv[k]) != float(TVERSKY_OPTIONS[k]) for k in TVERSKY_OPTIONS)
+    bd_changed = sorted(k for k in BOUNDARY_OPTIONS if bd[k] != BOUNDARY_OPTIONS[k])
+    bd_set = float(bd['boundary_boost']) > 0.0
+    if float(bd['boundary_boost']) < 0.0:
+        raise ValueError('boundary_boost must be >= 0; got %r' % (bd['boundary_boost'],))
+    if bd_changed and not bd_set:
+        raise ValueError('the boundary options (%s) need boundary_boost > 0' % ', '.join(bd_changed))
+    if bd_set and 'boundary_width' in bd_changed and 'boundary_ratio' in bd_changed:
+        raise ValueError('the boundary options boundary_width and boundary_ratio exclude each other')
     if tv_set and 'tversky' not in name:
         raise ValueError("the Tversky options do not apply to %r (use 'tversky' or 'ce+tversky')" % name)
-    if not is_set and not tv_set:
+    if not is_set and not tv_set and not bd_set:
         return LOSSES[name]
     if is_set and name in ('lovasz', 'tversky'):
         raise ValueError("the cross-entropy options do not apply to %r (use 'ce', 'ce+lovasz' or 'ce+tversky')" % name)
+    if bd_set and name in ('lovasz', 'tversky'):
+        raise ValueError("the boundary options do not apply to %r: they weight a cross-entropy term, and 'lovasz' and 'tversky' "
+                         "have none (use 'ce', 'ce+lovasz' or 'ce+tversky')" % name)
     if 'tversky' in name:
-        return _configured_tversky(name, opts, is_set, tv)
-    return _configured_ce(name, opts)
+        return _configured_tversky(name, opts, is_set, tv, bd if bd_set else None)
+    return _configured_ce(name, opts, bd if bd_set else None)
 
 
 def predict_mask(outputs):
@@ -434,6 +551,9 @@ def boundary_width(hw, ratio=0.02):
         raise ValueError('boundary width %d of a %d x %d map at ratio %g exceeds %d pixels: give a smaller ratio or a fixed '
                          'width' % (d, h, w, ratio, ops.BOUNDARY_MAX_WIDTH))
     return d
+
+
+_width_from_ratio = boundary_width      # (boundary_weighted_cross_entropy_loss has a keyword of that name)
 
 
 def update_boundary_counts(counters, predicted, targets, width):

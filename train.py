@@ -7,6 +7,8 @@ on the MI355X HIP path.
                      [--loss ce|lovasz|ce+lovasz|tversky|ce+tversky] [--class-weights W0 W1 ...] [--label-smoothing E] [--focal-gamma G] [--ohem-keep R]
                      [--tversky-alpha A] [--tversky-beta B] [--tversky-smooth S] [--tversky-power P] [--tversky-per-image]
                      [--tversky-all-classes] [--tversky-weight W]
+                     [--boundary-boost A] [--boundary-loss-ratio R | --boundary-loss-width D] [--boundary-falloff flat|linear|gaussian]
+                     [--boundary-sigma S]
                      [--weight-decay WD] [--momentum M] [--adamw] [--no-decay-norm-bias] [--backbone-lr-mult F]
                      [--clip-grad N] [--ema-decay D] [--schedule poly|cosine] [--warmup-steps N] [--min-lr LR]
     python3 -m torch.distributed.run --nproc-per-node <n> train.py data/<custom>        # RCCL data parallel
@@ -149,6 +151,17 @@ def build_parser():
     ap.add_argument('--tversky-all-classes', action='store_true',
                     help='average over every class, not only over the classes present in the batch (image)')
     ap.add_argument('--tversky-weight', type=float, default=1.0, metavar='W', help='ce+tversky: ce + W * tversky')
+    ap.add_argument('--boundary-boost', type=float, default=0.0, metavar='A',
+                    help='weight the cross-entropy of ce, ce+lovasz and ce+tversky by 1 + A * falloff(distance to the nearest '
+                         "label change of the target) inside a band along the target's contours (0: off)")
+    band = ap.add_mutually_exclusive_group()
+    band.add_argument('--boundary-loss-ratio', type=float, default=None, metavar='R',
+                      help="width of that band as a share of the target's diagonal (default 0.02, the evaluation's rule)")
+    band.add_argument('--boundary-loss-width', type=int, default=None, metavar='D', help='width of that band in pixels')
+    ap.add_argument('--boundary-falloff', choices=['flat', 'linear', 'gaussian'], default='gaussian',
+                    help='how the extra weight decays from the contour to the edge of the band')
+    ap.add_argument('--boundary-sigma', type=float, default=None, metavar='S',
+                    help='sigma of the gaussian falloff in pixels (default: a third of the width)')
     ap.add_argument('--weight-decay', type=float, default=None, metavar='WD', help='weight decay (default 0)')
     ap.add_argument('--momentum', type=float, default=None, metavar='M', help='SGD momentum (default 0.9)')
     ap.add_argument('--adamw', action='store_true', help='decoupled weight decay (AdamW with --adam, SGDW without)')
@@ -195,12 +208,23 @@ def optim_from_options(opt):
 
 def loss_from_options(opt):
     """(loss_fn, class weights or None) of the parsed --loss / --class-weights / --label-smoothing / --focal-gamma /
-    --ohem-keep / --tversky-*; with none of them given this is make_loss(opt.loss), as before"""
+    --ohem-keep / --tversky-* / --boundary-*; with none of them given this is make_loss(opt.loss), as before"""
+    boundary = {'boundary_boost': opt.boundary_boost, 'boundary_falloff': opt.boundary_falloff}
+    if opt.boundary_loss_ratio is not None:
+        boundary['boundary_ratio'] = opt.boundary_loss_ratio
+    if opt.boundary_loss_width is not None:
+        if not 1 <= opt.boundary_loss_width <= 254:
+            raise ValueError('--boundary-loss-width must be in [1, 254]; got %d' % opt.boundary_loss_width)
+        boundary['boundary_width'] = opt.boundary_loss_width
+    if opt.boundary_sigma is not None:
+        if not opt.boundary_sigma > 0:
+            raise ValueError('--boundary-sigma must be > 0; got %g' % opt.boundary_sigma)
+        boundary['boundary_sigma'] = opt.boundary_sigma
     return make_loss(opt.loss, class_weight=opt.class_weights, label_smoothing=opt.label_smoothing,
                      focal_gamma=opt.focal_gamma, keep_ratio=opt.ohem_keep, tversky_alpha=opt.tversky_alpha,
                      tversky_beta=opt.tversky_beta, tversky_smooth=opt.tversky_smooth, tversky_power=opt.tversky_power,
                      tversky_per_image=opt.tversky_per_image, tversky_all_classes=opt.tversky_all_classes,
-                     tversky_weight=opt.tversky_weight), opt.class_weights
+                     tversky_weight=opt.tversky_weight, **boundary), opt.class_weights
 
 
 def main():
