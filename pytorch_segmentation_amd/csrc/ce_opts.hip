@@ -19,7 +19,7 @@
 // BINNED instantiations of the kernels that see pixels read one byte beside the target and look u up in a 256-entry table
 // staged in LDS; u scales the per-pixel value BEFORE it is summed or parked (g = u f), the divisor's terms (u w_t) and the
 // gradient.  1.0f * x is exact, so a table of ones gives the unbinned call's bits.
-#include "common.h"
+#include "loss_common.h"
 
 #include <math.h>
 
@@ -88,33 +88,6 @@ __device__ __forceinline__ float co_unkey(unsigned k) {
   return __builtin_bit_cast(float, k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
 }
 
-__device__ __forceinline__ double co_block_sum_d(double v, double* sh) {
-  v = wave_sum_d(v);
-  __syncthreads();       // (sh may still be read from an earlier call)
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// integer counts of a block into the header: order-independent, so the atomics are bit-reproducible
-__device__ __forceinline__ void co_block_count(int a, int b, int* pa, int* pb, int (*sh)[4]) {
-  for (int o = 32; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o, 64);
-    b += __shfl_xor(b, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    sh[0][threadIdx.x >> 6] = a;
-    sh[1][threadIdx.x >> 6] = b;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int ta = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
-    const int tb = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
-    if (ta) atomicAdd(pa, ta);
-    if (tb && pb) atomicAdd(pb, tb);
-  }
-}
-
 // What one pixel contributes, from the pieces of its softmax: s = sum_c e_c, so = sum_{c != t} e_c, et = e_t with
 // e_c = exp(z_c - max), zt = z_t - max, wz = sum_c w_c (z_c - max), wt = w_t.
 struct CoTerm {
@@ -171,8 +144,8 @@ __global__ __launch_bounds__(256) void co_count_kernel(const int64_t* __restrict
     bad += (!v && t != ignore_index) ? 1 : 0;
     if (v) sw += BINNED ? (double)(ltab[bins[i]] * co_wgt(w, t)) : (double)co_wgt(w, t);
   }
-  co_block_count(cnt, bad, &hdr->n_valid, &hdr->n_bad, shc);
-  const double tot = co_block_sum_d(sw, shd);
+  block_count(cnt, bad, &hdr->n_valid, &hdr->n_bad, shc);
+  const double tot = block_sum_d_again(sw, shd);
   if (threadIdx.x == 0) pw[blockIdx.x] = tot;
 }
 
@@ -287,11 +260,11 @@ __global__ __launch_bounds__(256) void co_pixel_kernel(const CoArgs a) {
     }
   }
   if (MODE == 0) {
-    const double tot = co_block_sum_d(lsum, shd);
+    const double tot = block_sum_d_again(lsum, shd);
     if (threadIdx.x == 0) a.pf[blockIdx.x] = tot;
   }
   if (MODE == 1) {
-    co_block_count(cnt, bad, &a.hdr->n_valid, &a.hdr->n_bad, shc);      // (barrier inside: lh is complete after it)
+    block_count(cnt, bad, &a.hdr->n_valid, &a.hdr->n_bad, shc);      // (barrier inside: lh is complete after it)
     if (lh[threadIdx.x]) atomicAdd(&a.hdr->hist[0][threadIdx.x], lh[threadIdx.x]);
   }
 }
@@ -360,11 +333,11 @@ __global__ __launch_bounds__(256) void co_generic_kernel(const CoArgs a) {
     }
   }
   if (MODE == 0) {
-    const double tot = co_block_sum_d(lsum, shd);
+    const double tot = block_sum_d_again(lsum, shd);
     if (threadIdx.x == 0) a.pf[blockIdx.x] = tot;
   }
   if (MODE == 1) {
-    co_block_count(cnt, bad, &a.hdr->n_valid, &a.hdr->n_bad, shc);
+    block_count(cnt, bad, &a.hdr->n_valid, &a.hdr->n_bad, shc);
     if (lh[threadIdx.x]) atomicAdd(&a.hdr->hist[0][threadIdx.x], lh[threadIdx.x]);
   }
 }
@@ -437,9 +410,9 @@ __global__ __launch_bounds__(256) void co_kept_kernel(const unsigned* __restrict
       ++cnt;
     }
   }
-  co_block_count(cnt, 0, &hdr->n_kept, (int*)nullptr, shc);
-  const double tf = co_block_sum_d(sf, shd);
-  const double tw = co_block_sum_d(sw, shd);
+  block_count(cnt, 0, &hdr->n_kept, (int*)nullptr, shc);
+  const double tf = block_sum_d_again(sf, shd);
+  const double tw = block_sum_d_again(sw, shd);
   if (threadIdx.x == 0) {
     pf[blockIdx.x] = tf;
     pw[blockIdx.x] = tw;
@@ -448,17 +421,7 @@ __global__ __launch_bounds__(256) void co_kept_kernel(const unsigned* __restrict
 
 // one block, fixed order (ce_finish_kernel's): lane t adds partials t, t + 256, ..., then waves, then lanes
 __device__ __forceinline__ double co_sum_partials(const double* __restrict__ partial, int nblocks, double* sh) {
-  double s = 0.0;
-  int i = threadIdx.x;
-  for (; i + 7 * 256 < nblocks; i += 8 * 256) {
-    double t[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) t[k] = partial[i + k * 256];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += t[k];
-  }
-  for (; i < nblocks; i += 256) s += partial[i];
-  return co_block_sum_d(s, sh);
+  return block_sum_d_again(thread_sum_partials(partial, nblocks), sh);
 }
 
 __global__ __launch_bounds__(256) void co_den_kernel(const double* __restrict__ pw, int nblocks, CoHeader* __restrict__ hdr) {
@@ -485,25 +448,16 @@ __global__ __launch_bounds__(256) void co_finish_kernel(const double* __restrict
   }
 }
 
-static int co_blocks(long long work_items, int cap) {
-  long long b = (work_items + 255) / 256;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-static int64_t co_align(int64_t v) { return (v + 255) / 256 * 256; }
-
 struct CoPlan {
   int64_t pf, pw, keys, bytes;      // byte offsets into the workspace
 };
 
 static CoPlan co_plan(int64_t npix) {
   CoPlan p;
-  int64_t o = co_align(sizeof(CoHeader));
-  p.pf = o;   o = co_align(o + (int64_t)kCoMaxBlocks * 8);
-  p.pw = o;   o = co_align(o + (int64_t)kCoMaxBlocks * 8);
-  p.keys = o; o = co_align(o + (npix + 3) / 4 * 16);      // the parked values: 4 bytes per pixel
+  int64_t o = align256(sizeof(CoHeader));
+  p.pf = o;   o = align256(o + (int64_t)kCoMaxBlocks * 8);
+  p.pw = o;   o = align256(o + (int64_t)kCoMaxBlocks * 8);
+  p.keys = o; o = align256(o + (npix + 3) / 4 * 16);      // the parked values: 4 bytes per pixel
   p.bytes = o;
   return p;
 }
@@ -519,7 +473,7 @@ static int co_launch_pixels(CoArgs a, long long npix, bool vec4, hipStream_t st)
 #define CO_LAUNCH(CMAX, VEC)                                                                              \
   do {                                                                                                    \
     a.groups = npix / VEC;                                                                                \
-    blocks = co_blocks(a.groups, kCoMaxBlocks);                                                           \
+    blocks = capped_blocks(a.groups, kCoMaxBlocks);                                                       \
     hipLaunchKernelGGL((co_pixel_kernel<CMAX, VEC, MODE, BINNED>), dim3(blocks), dim3(256), 0, st, a);            \
   } while (0)
   const int C = a.C;
@@ -533,7 +487,7 @@ static int co_launch_pixels(CoArgs a, long long npix, bool vec4, hipStream_t st)
   else if (C <= 32) CO_LAUNCH(32, 1);
   else {
     a.groups = npix;
-    blocks = co_blocks(npix, kCoMaxBlocks);
+    blocks = capped_blocks(npix, kCoMaxBlocks);
     hipLaunchKernelGGL((co_generic_kernel<MODE, BINNED>), dim3(blocks), dim3(256), 0, st, a);
   }
 #undef CO_LAUNCH
@@ -593,7 +547,7 @@ static int co_run(const char* fn, const float* logits, const int64_t* target, co
   const bool vec4 = (HW % 4 == 0) && (((uintptr_t)logits & 15) == 0) && (!dlogits || ((uintptr_t)dlogits & 15) == 0);
   const long long ign = (long long)ignore_index;
   if (keep_ratio == 1.f) {
-    const int nb = co_blocks(npix, 2048);
+    const int nb = capped_blocks(npix, 2048);
     hipLaunchKernelGGL(co_count_kernel<BINNED>, dim3(nb), dim3(256), 0, st, target, npix, ign, C, class_weight, hdr, pw, pixel_bin,
                        bin_weight);
     PSEG_LAUNCH_CHECK();
@@ -608,7 +562,7 @@ static int co_run(const char* fn, const float* logits, const int64_t* target, co
   }
   co_launch_pixels<1, BINNED>(a, npix, vec4, st);
   PSEG_LAUNCH_CHECK();
-  const int nb = co_blocks(npix, 2048);
+  const int nb = capped_blocks(npix, 2048);
   for (int round = 0; round < 4; ++round) {
     if (round > 0) {
       hipLaunchKernelGGL(co_hist_kernel, dim3(nb), dim3(256), 0, st, (const unsigned*)keys, npix, round, hdr);

@@ -6,7 +6,7 @@
 //  - argmax: outputs.max(1)[1] (reference test.py:31), first index wins ties.
 //  - confusion: per-class tp / fn / fp (reference test.py:34-46) without the 3*C host syncs per batch.
 // Lanes walk consecutive pixels of one class plane, so every load is a coalesced 256-B / 1-KiB segment.
-#include "common.h"
+#include "loss_common.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -31,30 +31,8 @@ __global__ __launch_bounds__(256) void ce_count_kernel(const int64_t* __restrict
     cnt += v ? 1 : 0;
     bad += (!v && t != ignore_index) ? 1 : 0;
   }
-  // integer reduction: order-independent, so an atomic is still bit-reproducible
-  for (int o = 32; o > 0; o >>= 1) {
-    cnt += __shfl_xor(cnt, o, 64);
-    bad += __shfl_xor(bad, o, 64);
-  }
   __shared__ int sh[2][4];
-  if ((threadIdx.x & 63) == 0) {
-    sh[0][threadIdx.x >> 6] = cnt;
-    sh[1][threadIdx.x >> 6] = bad;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int t = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
-    const int b = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
-    if (t) atomicAdd(&hdr->n_valid, t);
-    if (b) atomicAdd(&hdr->n_bad, b);
-  }
-}
-
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  v = wave_sum_d(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
+  block_count(cnt, bad, &hdr->n_valid, &hdr->n_bad, sh);
 }
 
 // CMAX: compile-time bound on the class count (values live in registers); VEC consecutive pixels per lane.
@@ -158,20 +136,9 @@ __global__ __launch_bounds__(256) void ce_generic_kernel(const float* __restrict
 
 __global__ __launch_bounds__(256) void ce_finish_kernel(const double* __restrict__ partial, int nblocks,
                                                         const CeHeader* __restrict__ hdr, float* __restrict__ loss_out) {
-  // one block, fixed order: lane t adds partials t, t + 256, ... (eight loads in flight -- the up-sampled loss leaves 16384
-  // partials, one dependent round trip each was 64 us between the forward and the backward pass), then waves, then lanes
+  // one block, fixed order: lane t adds partials t, t + 256, ..., then waves, then lanes
   __shared__ double sh[4];
-  double s = 0.0;
-  int i = threadIdx.x;
-  for (; i + 7 * 256 < nblocks; i += 8 * 256) {
-    double t[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) t[k] = partial[i + k * 256];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += t[k];
-  }
-  for (; i < nblocks; i += 256) s += partial[i];
-  s = block_sum_d(s, sh);
+  const double s = block_sum_d(thread_sum_partials(partial, nblocks), sh);
   if (threadIdx.x == 0) {
     const int nv = hdr->n_valid;
     loss_out[0] = nv > 0 ? (float)(s / (double)nv) : NAN;  // torch: mean over zero elements is NaN
@@ -814,13 +781,6 @@ __global__ __launch_bounds__(256) void confusion_kernel(const int64_t* __restric
   __syncthreads();
   for (int i = threadIdx.x; i < 3 * C; i += 256)
     if (h[i]) atomicAdd(&counters[i], (unsigned long long)h[i]);
-}
-
-static int capped_blocks(long long work_items, int cap) {
-  long long b = (work_items + 255) / 256;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
 }
 
 constexpr int kCeMaxBlocks = 4096;

@@ -23,7 +23,7 @@
 // Absent classes cost an early exit per block: every kernel of stages 1-3 reads the device histogram.
 // Sums of floats are taken in a fixed order (per thread, xor-shuffle tree, waves in order, tiles in order); atomics add
 // integers only, so two calls give identical bits.
-#include "common.h"
+#include "loss_common.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -41,6 +41,7 @@ constexpr unsigned kLvFg = 0x80000000u;             // foreground flag of a key 
 constexpr int kLvPasses = 4;                        // 8-bit digits over key bits 0..29
 constexpr int64_t kLvSortBudget = 512ll << 20;      // bytes of sort buffers one class group may take
 constexpr int kLvMaxBlocks = 4096;
+static_assert(kLvThreads == 256, "capped_blocks (loss_common.h) counts blocks of 256 threads");
 
 struct LvHeader {
   int n_valid, n_bad, n_present, pad;
@@ -84,22 +85,7 @@ __global__ __launch_bounds__(kLvThreads) void lovasz_hist_kernel(const int64_t* 
       ++bad;
     }
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    cnt += __shfl_xor(cnt, o, 64);
-    bad += __shfl_xor(bad, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    sh[0][threadIdx.x >> 6] = cnt;
-    sh[1][threadIdx.x >> 6] = bad;
-  }
-  __syncthreads();
-  // integer sums: order-independent, so the atomics are bit-reproducible
-  if (threadIdx.x == 0) {
-    const int v = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
-    const int b = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
-    if (v) atomicAdd(&hdr->n_valid, v);
-    if (b) atomicAdd(&hdr->n_bad, b);
-  }
+  block_count(cnt, bad, &hdr->n_valid, &hdr->n_bad, sh);
   for (int i = threadIdx.x; i < C; i += kLvThreads)
     if (bins[i]) atomicAdd(&hdr->hist[i], bins[i]);
 }
@@ -358,10 +344,8 @@ __global__ __launch_bounds__(kLvThreads) void lovasz_grad_kernel(const unsigned*
       }
     }
   }
-  acc = wave_sum_d(acc);
-  if (lane == 0) shd[w] = acc;
-  __syncthreads();
-  if (t == 0) partial[(size_t)c * nb + blockIdx.x] = shd[0] + shd[1] + shd[2] + shd[3];
+  acc = block_sum_d(acc, shd);
+  if (t == 0) partial[(size_t)c * nb + blockIdx.x] = acc;
 }
 
 __global__ __launch_bounds__(kLvThreads) void lovasz_finish_kernel(const double* __restrict__ partial, int C, unsigned nb,
@@ -372,12 +356,10 @@ __global__ __launch_bounds__(kLvThreads) void lovasz_finish_kernel(const double*
     if (hdr->hist[c] == 0) continue;
     for (unsigned i = threadIdx.x; i < nb; i += kLvThreads) s += partial[(size_t)c * nb + i];
   }
-  s = wave_sum_d(s);
-  if ((threadIdx.x & 63) == 0) shd[threadIdx.x >> 6] = s;
-  __syncthreads();
+  s = block_sum_d(s, shd);
   if (threadIdx.x == 0) {
     const int np = hdr->n_present;
-    out[0] = np > 0 ? (float)((shd[0] + shd[1] + shd[2] + shd[3]) / (double)np) : 0.f;
+    out[0] = np > 0 ? (float)(s / (double)np) : 0.f;
     out[1] = (float)hdr->n_valid;
     out[2] = (float)hdr->n_bad;
     out[3] = (float)np;
@@ -421,8 +403,6 @@ struct LvPlan {
   int64_t totals, blockhist, tilecnt, partial, keys[2], idx[2], bytes;   // byte offsets into the workspace
 };
 
-static int64_t lv_align(int64_t v) { return (v + 255) / 256 * 256; }
-
 static LvPlan lv_plan(int64_t npix, int C) {
   LvPlan p;
   p.nb = (unsigned)((npix + kLvTile - 1) / kLvTile);
@@ -430,14 +410,14 @@ static LvPlan lv_plan(int64_t npix, int C) {
   const int64_t gmax = kLvSortBudget / (16 * (int64_t)p.S) > 0 ? kLvSortBudget / (16 * (int64_t)p.S) : 1;
   const int64_t ngroups = (C + gmax - 1) / gmax;
   p.G = (int)((C + ngroups - 1) / ngroups);
-  int64_t o = lv_align(sizeof(LvHeader));
-  p.totals = o;    o = lv_align(o + (int64_t)p.G * 256 * 4);
-  p.blockhist = o; o = lv_align(o + (int64_t)p.G * 256 * p.nb * 4);
-  p.tilecnt = o;   o = lv_align(o + (int64_t)p.G * p.nb * 4);
-  p.partial = o;   o = lv_align(o + (int64_t)C * p.nb * 8);
+  int64_t o = align256(sizeof(LvHeader));
+  p.totals = o;    o = align256(o + (int64_t)p.G * 256 * 4);
+  p.blockhist = o; o = align256(o + (int64_t)p.G * 256 * p.nb * 4);
+  p.tilecnt = o;   o = align256(o + (int64_t)p.G * p.nb * 4);
+  p.partial = o;   o = align256(o + (int64_t)C * p.nb * 8);
   for (int i = 0; i < 2; ++i) {
-    p.keys[i] = o; o = lv_align(o + (int64_t)p.G * p.S * 4);
-    p.idx[i] = o;  o = lv_align(o + (int64_t)p.G * p.S * 4);
+    p.keys[i] = o; o = align256(o + (int64_t)p.G * p.S * 4);
+    p.idx[i] = o;  o = align256(o + (int64_t)p.G * p.S * 4);
   }
   p.bytes = o;
   return p;
@@ -455,11 +435,6 @@ static int lv_group_override(int G) {
   const char* e = getenv("PSEG_LOVASZ_GROUP");
   const int v = e ? atoi(e) : 0;
   return (v > 0 && v < G) ? v : G;
-}
-
-static int lv_blocks(long long items) {
-  long long b = (items + kLvThreads - 1) / kLvThreads;
-  return (int)(b > kLvMaxBlocks ? kLvMaxBlocks : (b < 1 ? 1 : b));
 }
 
 }  // namespace pseg
@@ -505,7 +480,7 @@ int pseg_lovasz_softmax_fwd_bwd(const float* logits, const int64_t* target, int 
     set_error("lovasz: hipMemsetAsync failed");
     return PSEG_ERR_HIP;
   }
-  hipLaunchKernelGGL(lovasz_hist_kernel, dim3(lv_blocks(npix64) > 2048 ? 2048 : lv_blocks(npix64)), dim3(kLvThreads), 0, st,
+  hipLaunchKernelGGL(lovasz_hist_kernel, dim3(capped_blocks(npix64, 2048)), dim3(kLvThreads), 0, st,
                      target, npix, ign, C, hdr);
   PSEG_LAUNCH_CHECK();
   hipLaunchKernelGGL(lovasz_present_kernel, dim3(1), dim3(kLvThreads), 0, st, C, hdr);
@@ -513,8 +488,8 @@ int pseg_lovasz_softmax_fwd_bwd(const float* logits, const int64_t* target, int 
   for (int c0 = 0; c0 < C; c0 += G) {
     const int g = C - c0 < G ? C - c0 : G;
     const dim3 tiles(nb, g);
-    hipLaunchKernelGGL(lovasz_errors_kernel, dim3(lv_blocks(npix64)), dim3(kLvThreads), 0, st, logits, target, C, hw, npix,
-                       ign, (const LvHeader*)hdr, c0, g, S, keys[0]);
+    hipLaunchKernelGGL(lovasz_errors_kernel, dim3(capped_blocks(npix64, kLvMaxBlocks)), dim3(kLvThreads), 0, st, logits, target,
+                       C, hw, npix, ign, (const LvHeader*)hdr, c0, g, S, keys[0]);
     PSEG_LAUNCH_CHECK();
     for (int pass = 0; pass < kLvPasses; ++pass) {      // keys[0] -> [1] -> [0] -> [1] -> [0]
       const int a = pass & 1, b = a ^ 1, shift = 8 * pass;
@@ -548,8 +523,8 @@ int pseg_lovasz_softmax_fwd_bwd(const float* logits, const int64_t* target, int 
                      (const LvHeader*)hdr, out);
   PSEG_LAUNCH_CHECK();
   if (dlogits) {
-    hipLaunchKernelGGL(lovasz_softmax_bwd_kernel, dim3(lv_blocks(npix64)), dim3(kLvThreads), 0, st, logits, target, C, hw,
-                       npix, ign, (const LvHeader*)hdr, dlogits);
+    hipLaunchKernelGGL(lovasz_softmax_bwd_kernel, dim3(capped_blocks(npix64, kLvMaxBlocks)), dim3(kLvThreads), 0, st, logits,
+                       target, C, hw, npix, ign, (const LvHeader*)hdr, dlogits);
     PSEG_LAUNCH_CHECK();
   }
   return PSEG_OK;

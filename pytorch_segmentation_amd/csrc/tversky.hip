@@ -18,7 +18,7 @@
 //      sweep writes p_ij (g_ij - dot) once.  p is never parked anywhere.
 // No per-thread state grows with C (1024 classes cost registers for four pixels, like 2), and every floating-point sum
 // has a fixed order, so two calls give identical bits.
-#include "common.h"
+#include "loss_common.h"
 
 #include <math.h>
 
@@ -271,16 +271,6 @@ __device__ __forceinline__ TvClass tv_class(const double* __restrict__ s, const 
   return k;
 }
 
-// the same value in every thread of the block (sh: 4 doubles)
-__device__ __forceinline__ double tv_block_sum(double v, double* sh) {
-  v = wave_sum_d(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double r = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-  __syncthreads();
-  return r;
-}
-
 // one block: the loss and out[], then coef[g][c] = {ct, cn}: g_ic at a pixel of label c / of another label
 __global__ __launch_bounds__(kTvThreads) void tversky_coef_kernel(const double* __restrict__ sums, const int* __restrict__ pbad,
                                                                   int C, int G, size_t nblk, TvOpts o, float* __restrict__ coef,
@@ -292,7 +282,7 @@ __global__ __launch_bounds__(kTvThreads) void tversky_coef_kernel(const double* 
     const double* sg = sums + (size_t)g * C * 4;
     double nv = 0.0;
     for (int c = tid; c < C; c += kTvThreads) nv += sg[(size_t)c * 4];
-    nv = tv_block_sum(nv, sh);
+    nv = block_sum_d_again(nv, sh);
     double ts = 0.0, cnt = 0.0;
     if (nv > 0.0) {
       for (int c = tid; c < C; c += kTvThreads) {
@@ -301,8 +291,8 @@ __global__ __launch_bounds__(kTvThreads) void tversky_coef_kernel(const double* 
         cnt += 1.0;
       }
     }
-    ts = tv_block_sum(ts, sh);
-    cnt = tv_block_sum(cnt, sh);
+    ts = block_sum_d_again(ts, sh);
+    cnt = block_sum_d_again(cnt, sh);
     if (tid == 0) gcnt[g] = (int)cnt;
     if (cnt > 0.0) {
       loss_sum += ts / cnt;
@@ -313,7 +303,7 @@ __global__ __launch_bounds__(kTvThreads) void tversky_coef_kernel(const double* 
   }
   double n_bad = 0.0;
   for (size_t i = tid; i < nblk; i += kTvThreads) n_bad += (double)pbad[i];
-  n_bad = tv_block_sum(n_bad, sh);      // (its barriers also order gcnt[] before the reads below)
+  n_bad = block_sum_d_again(n_bad, sh);      // (its barriers also order gcnt[] before the reads below)
   for (int g = 0; g < G; ++g) {
     const double* sg = sums + (size_t)g * C * 4;
     const double cnt = (double)gcnt[g];
@@ -406,8 +396,6 @@ struct TvPlan {
   int64_t pq, ptp, pn, pbad, sums, coef, gcnt, bytes;      // byte offsets into the workspace
 };
 
-static int64_t tv_align(int64_t v) { return (v + 255) / 256 * 256; }
-
 static bool tv_sizes_ok(int B, int C, int64_t HW) {
   if (B <= 0 || C <= 0 || HW <= 0 || C > kTvMaxClasses) return false;
   if (HW > (1ll << 31) / 8 / B) return false;                            // targets: B * HW * 8 bytes
@@ -420,13 +408,13 @@ static TvPlan tv_plan(int B, int C, int64_t HW, int per_image) {
   p.nblk = (int64_t)B * p.tiles;
   p.G = per_image ? B : 1;
   int64_t o = 0;
-  p.pq = o;   o = tv_align(o + (int64_t)C * p.nblk * 8);
-  p.ptp = o;  o = tv_align(o + (int64_t)C * p.nblk * 8);
-  p.pn = o;   o = tv_align(o + (int64_t)C * p.nblk * 8);
-  p.pbad = o; o = tv_align(o + p.nblk * 4);
-  p.sums = o; o = tv_align(o + (int64_t)p.G * C * 32);
-  p.coef = o; o = tv_align(o + (int64_t)p.G * C * 8);
-  p.gcnt = o; o = tv_align(o + (int64_t)p.G * 4);
+  p.pq = o;   o = align256(o + (int64_t)C * p.nblk * 8);
+  p.ptp = o;  o = align256(o + (int64_t)C * p.nblk * 8);
+  p.pn = o;   o = align256(o + (int64_t)C * p.nblk * 8);
+  p.pbad = o; o = align256(o + p.nblk * 4);
+  p.sums = o; o = align256(o + (int64_t)p.G * C * 32);
+  p.coef = o; o = align256(o + (int64_t)p.G * C * 8);
+  p.gcnt = o; o = align256(o + (int64_t)p.G * 4);
   p.bytes = o;
   return p;
 }

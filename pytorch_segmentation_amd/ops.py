@@ -1114,19 +1114,38 @@ def maxpool_bwd(dy, arg, dx, k, stride, pad, accumulate=False):
 
 
 # ---------------------------------------------------------------------------------------------- loss / masks
+def _loss_operands(logits, target):
+    """the loss entry points' shared operand check -> (B, C, H, W)"""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.shape == (logits.shape[0],) + logits.shape[2:]
+    return logits.shape
+
+
+def _loss_class_weight(class_weight, logits):
+    if class_weight is not None:
+        C = logits.shape[1]
+        assert class_weight.device == logits.device and class_weight.dtype == torch.float32 and \
+            class_weight.is_contiguous() and class_weight.shape == (C,), 'class_weight: %d fp32 values on %s' % (C, logits.device)
+
+
+def _loss_call(entry, head, logits, want_grad, n_out, ws_query, cache, tail=()):
+    """the loss entry points' shared call shape, entry(*head, dlogits, out, *tail, workspace, workspace bytes, stream): a
+    fresh gradient (want_grad) and out[n_out]; the workspace sized by the query ws_query = (name, *integers) and taken from
+    `cache` -> (out, dlogits | None)"""
+    dl = torch.empty_like(logits) if want_grad else None
+    out = torch.empty(n_out, dtype=torch.float32, device=logits.device)
+    nbytes = _lib.query(*ws_query)
+    ws = cache.get(nbytes, logits.device)
+    _lib.call(entry, *head, _ptr(dl), out.data_ptr(), *tail, ws.data_ptr(), nbytes, _stream())
+    return out, dl
+
+
 def ce_fwd_bwd(logits, target, want_grad=True, ignore_index=-100):
     """logits: contiguous NCHW fp32 cuda, target: NHW int64.
     -> (loss_out[3] = [mean loss, n_valid, n_out_of_range_targets], dlogits|None)."""
-    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
-    assert target.dtype == torch.int64 and target.is_contiguous() and target.shape == (logits.shape[0],) + logits.shape[2:]
-    B, C, H, W = logits.shape
-    dl = torch.empty_like(logits) if want_grad else None
-    out = torch.empty(3, dtype=torch.float32, device=logits.device)
-    nbytes = _lib.query('pseg_ce_workspace_bytes', B * H * W)
-    ws = workspace.get(nbytes, logits.device)
-    _lib.call('pseg_ce_fwd_bwd', logits.data_ptr(), target.data_ptr(), B, C, H * W, ignore_index, _ptr(dl),
-              out.data_ptr(), ws.data_ptr(), nbytes, _stream())
-    return out, dl
+    B, C, H, W = _loss_operands(logits, target)
+    return _loss_call('pseg_ce_fwd_bwd', (logits.data_ptr(), target.data_ptr(), B, C, H * W, ignore_index), logits, want_grad,
+                      3, ('pseg_ce_workspace_bytes', B * H * W), workspace)
 
 
 def ce_opts_fwd_bwd(logits, target, class_weight=None, label_smoothing=0.0, focal_gamma=0.0, keep_ratio=1.0, want_grad=True,
@@ -1134,20 +1153,11 @@ def ce_opts_fwd_bwd(logits, target, class_weight=None, label_smoothing=0.0, foca
     """Cross-entropy with class weights, label smoothing, the focal factor and hard-pixel selection (pseg_ce_opts_fwd_bwd).
     logits: contiguous NCHW fp32 cuda, target: NHW int64, class_weight: [C] fp32 on the logits' device or None.
     -> (out[6] = [loss, n_valid, n_out_of_range_targets, n_kept, tau, sum of the kept pixels' weights], dlogits|None)."""
-    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
-    assert target.dtype == torch.int64 and target.is_contiguous() and target.shape == (logits.shape[0],) + logits.shape[2:]
-    B, C, H, W = logits.shape
-    if class_weight is not None:
-        assert class_weight.device == logits.device and class_weight.dtype == torch.float32 and \
-            class_weight.is_contiguous() and class_weight.shape == (C,), 'class_weight: %d fp32 values on %s' % (C, logits.device)
-    dl = torch.empty_like(logits) if want_grad else None
-    out = torch.empty(6, dtype=torch.float32, device=logits.device)
-    nbytes = _lib.query('pseg_ce_opts_workspace_bytes', B, C, H * W)
-    ws = workspace.get(nbytes, logits.device)
-    _lib.call('pseg_ce_opts_fwd_bwd', logits.data_ptr(), target.data_ptr(), B, C, H * W, ignore_index, _ptr(class_weight),
-              float(label_smoothing), float(focal_gamma), float(keep_ratio), _ptr(dl), out.data_ptr(), ws.data_ptr(), nbytes,
-              _stream())
-    return out, dl
+    B, C, H, W = _loss_operands(logits, target)
+    _loss_class_weight(class_weight, logits)
+    head = (logits.data_ptr(), target.data_ptr(), B, C, H * W, ignore_index, _ptr(class_weight), float(label_smoothing),
+            float(focal_gamma), float(keep_ratio))
+    return _loss_call('pseg_ce_opts_fwd_bwd', head, logits, want_grad, 6, ('pseg_ce_opts_workspace_bytes', B, C, H * W), workspace)
 
 
 def bin_weight_table(values, device):
@@ -1169,26 +1179,18 @@ def ce_opts_binned_fwd_bwd(logits, target, pixel_bin, bin_weight, class_weight=N
     [B, H, W] on the logits' device, contiguous itself but at any byte offset of its storage; bin_weight: fp32 [256] on that
     device, finite and non-negative (bin_weight_table checks and uploads).  Both are required: the call without them is
     ce_opts_fwd_bwd.  -> (out[6] = [loss, n_valid, n_out_of_range_targets, n_kept, tau, sum of the kept pixels' u * w], dlogits|None)."""
-    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
-    assert target.dtype == torch.int64 and target.is_contiguous() and target.shape == (logits.shape[0],) + logits.shape[2:]
+    B, C, H, W = _loss_operands(logits, target)
     if pixel_bin is None or bin_weight is None:
         raise ValueError('ce_opts_binned_fwd_bwd: pixel_bin and bin_weight come together (without them: ce_opts_fwd_bwd)')
-    B, C, H, W = logits.shape
     assert pixel_bin.device == logits.device and pixel_bin.dtype == torch.uint8 and pixel_bin.is_contiguous() and \
         pixel_bin.shape == (B, H, W), 'pixel_bin: contiguous uint8 %s on %s' % ((B, H, W), logits.device)
     assert bin_weight.device == logits.device and bin_weight.dtype == torch.float32 and bin_weight.is_contiguous() and \
         bin_weight.shape == (256,), 'bin_weight: 256 fp32 values on %s' % (logits.device,)
-    if class_weight is not None:
-        assert class_weight.device == logits.device and class_weight.dtype == torch.float32 and \
-            class_weight.is_contiguous() and class_weight.shape == (C,), 'class_weight: %d fp32 values on %s' % (C, logits.device)
-    dl = torch.empty_like(logits) if want_grad else None
-    out = torch.empty(6, dtype=torch.float32, device=logits.device)
-    nbytes = _lib.query('pseg_ce_opts_workspace_bytes', B, C, H * W)
-    ws = workspace.get(nbytes, logits.device)
-    _lib.call('pseg_ce_opts_binned_fwd_bwd', logits.data_ptr(), target.data_ptr(), pixel_bin.data_ptr(), bin_weight.data_ptr(),
-              B, C, H * W, ignore_index, _ptr(class_weight), float(label_smoothing), float(focal_gamma), float(keep_ratio),
-              _ptr(dl), out.data_ptr(), ws.data_ptr(), nbytes, _stream())
-    return out, dl
+    _loss_class_weight(class_weight, logits)
+    head = (logits.data_ptr(), target.data_ptr(), pixel_bin.data_ptr(), bin_weight.data_ptr(), B, C, H * W, ignore_index,
+            _ptr(class_weight), float(label_smoothing), float(focal_gamma), float(keep_ratio))
+    return _loss_call('pseg_ce_opts_binned_fwd_bwd', head, logits, want_grad, 6, ('pseg_ce_opts_workspace_bytes', B, C, H * W),
+                      workspace)
 
 
 # the Lovasz loss's sort buffers (hundreds of MiB at training sizes) get a cache of their own: allocated once per stream,
@@ -1200,16 +1202,9 @@ def lovasz_softmax_fwd_bwd(logits, target, want_grad=True, ignore_index=-100):
     """Lovasz-softmax loss over the present classes of the whole batch (pseg_lovasz_softmax_fwd_bwd).
     logits: contiguous NCHW fp32 cuda, target: NHW int64.
     -> (out[4] = [loss, n_valid, n_out_of_range_targets, n_present], dlogits|None)."""
-    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
-    assert target.dtype == torch.int64 and target.is_contiguous() and target.shape == (logits.shape[0],) + logits.shape[2:]
-    B, C, H, W = logits.shape
-    dl = torch.empty_like(logits) if want_grad else None
-    out = torch.empty(4, dtype=torch.float32, device=logits.device)
-    nbytes = _lib.query('pseg_lovasz_workspace_bytes', B, C, H * W)
-    ws = lovasz_workspace.get(nbytes, logits.device)
-    _lib.call('pseg_lovasz_softmax_fwd_bwd', logits.data_ptr(), target.data_ptr(), B, C, H * W, ignore_index, _ptr(dl),
-              out.data_ptr(), ws.data_ptr(), nbytes, _stream())
-    return out, dl
+    B, C, H, W = _loss_operands(logits, target)
+    return _loss_call('pseg_lovasz_softmax_fwd_bwd', (logits.data_ptr(), target.data_ptr(), B, C, H * W, ignore_index), logits,
+                      want_grad, 4, ('pseg_lovasz_workspace_bytes', B, C, H * W), lovasz_workspace)
 
 
 def tversky_fwd_bwd(logits, target, alpha=0.5, beta=0.5, smooth=1.0, power=1.0, per_image=False, all_classes=False,
@@ -1218,17 +1213,12 @@ def tversky_fwd_bwd(logits, target, alpha=0.5, beta=0.5, smooth=1.0, power=1.0, 
     logits: contiguous NCHW fp32 cuda, target: NHW int64.
     -> (out[5] = [loss, n_valid, n_out_of_range_targets, n_terms, n_groups_counted], dlogits|None), and with want_sums
     also class_sums: float64 [G, C, 3] = n_c, S_c, TP_c per group (G = B with per_image, else 1)."""
-    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
-    assert target.dtype == torch.int64 and target.is_contiguous() and target.shape == (logits.shape[0],) + logits.shape[2:]
-    B, C, H, W = logits.shape
-    dl = torch.empty_like(logits) if want_grad else None
-    out = torch.empty(5, dtype=torch.float32, device=logits.device)
+    B, C, H, W = _loss_operands(logits, target)
     sums = torch.empty(B if per_image else 1, C, 3, dtype=torch.float64, device=logits.device) if want_sums else None
-    nbytes = _lib.query('pseg_tversky_workspace_bytes', B, C, H * W)
-    ws = workspace.get(nbytes, logits.device)
-    _lib.call('pseg_tversky_fwd_bwd', logits.data_ptr(), target.data_ptr(), B, C, H * W, ignore_index, float(alpha),
-              float(beta), float(smooth), float(power), int(bool(per_image)), int(bool(all_classes)), _ptr(dl),
-              out.data_ptr(), _ptr(sums), ws.data_ptr(), nbytes, _stream())
+    head = (logits.data_ptr(), target.data_ptr(), B, C, H * W, ignore_index, float(alpha), float(beta), float(smooth),
+            float(power), int(bool(per_image)), int(bool(all_classes)))
+    out, dl = _loss_call('pseg_tversky_fwd_bwd', head, logits, want_grad, 5, ('pseg_tversky_workspace_bytes', B, C, H * W),
+                         workspace, tail=(_ptr(sums),))
     return (out, dl, sums) if want_sums else (out, dl)
 
 

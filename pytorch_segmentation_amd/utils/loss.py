@@ -13,30 +13,38 @@ from ..ops import Act
 CHECK_LABELS = os.environ.get('PSEG_CHECK_LABELS', '0') == '1'
 
 
-class _CrossEntropyFn(torch.autograd.Function):
-    """nn.CrossEntropyLoss() defaults; forward and backward arithmetic happen in ONE pass over the logits
-    (pseg_ce_fwd_bwd); backward only rescales by the incoming scalar (a device-side no-op when it is 1)."""
+BAD_LABELS = '%d target values are outside [0, %d) and are not ignore_index'
+
+
+class _FusedLossFn(torch.autograd.Function):
+    """A loss whose forward and backward arithmetic happen in ONE call: run(want_grad) -> (out, dlogits | None) is one of
+    the ops.*_fwd_bwd calls on `logits` (out[0] the loss, out[2] the number of out-of-range targets); everything that is
+    not differentiated -- targets, weights, depth bytes, options -- reaches the kernel inside `run`.  backward only
+    rescales the kept gradient by the incoming scalar (a device-side no-op when it is 1)."""
 
     @staticmethod
-    def forward(ctx, logits, targets):
-        need = logits.requires_grad
-        out, dl = ops.ce_fwd_bwd(logits, targets, want_grad=need)
+    def forward(ctx, logits, run, bad_labels):
+        out, dl = run(logits.requires_grad)
         if CHECK_LABELS and out[2].item() != 0:     # (host sync: debugging aid, off by default)
-            raise IndexError('%d target values are outside [0, %d) and are not ignore_index (torch raises "Target ... is '
-                             'out of bounds" here)' % (int(out[2].item()), logits.shape[1]))
+            raise IndexError(bad_labels % (int(out[2].item()), logits.shape[1]))
         ctx.dl = dl
-        ctx.mark_non_differentiable()
         return out[0]
 
     @staticmethod
     def backward(ctx, g):
         dl = ctx.dl
         ctx.dl = None
-        if dl is None:
-            return None, None
-        g = g.reshape(1) if g.dtype == torch.float32 else g.float().reshape(1)
-        ops.scale_inplace(dl, g.contiguous())
-        return dl, None
+        if dl is not None:
+            g = g.reshape(1) if g.dtype == torch.float32 else g.float().reshape(1)
+            ops.scale_inplace(dl, g.contiguous())
+        return dl, None, None
+
+
+def _ce_term(logits, targets):
+    """nn.CrossEntropyLoss() defaults (pseg_ce_fwd_bwd).  Like every term below: (contiguous fp32 logits at the targets'
+    size, int64 targets on their device) -> the scalar."""
+    return _FusedLossFn.apply(logits, lambda want_grad: ops.ce_fwd_bwd(logits, targets, want_grad=want_grad),
+                              BAD_LABELS + ' (torch raises "Target ... is out of bounds" here)')
 
 
 class _ResizeFn(torch.autograd.Function):
@@ -67,34 +75,7 @@ def compute_loss(outputs, targets, model=None):
     if (outputs.size(2), outputs.size(3)) != (th, tw):
         outputs = _ResizeFn.apply(outputs, th, tw)
     # equal sizes: bilinear align_corners=True is the exact identity, so nothing is launched
-    return _CrossEntropyFn.apply(outputs.contiguous(), targets)
-
-
-class _LovaszSoftmaxFn(torch.autograd.Function):
-    """Lovasz-softmax over the classes present in the batch (Berman et al.; the loss the reference names in
-    utils/criterions.py).  Built like _CrossEntropyFn: forward runs pseg_lovasz_softmax_fwd_bwd, which leaves the gradient
-    with respect to the logits as well; backward only rescales it by the incoming scalar."""
-
-    @staticmethod
-    def forward(ctx, logits, targets, ignore_index):
-        need = logits.requires_grad
-        out, dl = ops.lovasz_softmax_fwd_bwd(logits, targets, want_grad=need, ignore_index=ignore_index)
-        if CHECK_LABELS and out[2].item() != 0:     # (host sync: debugging aid, off by default)
-            raise IndexError('%d target values are outside [0, %d) and are not ignore_index'
-                             % (int(out[2].item()), logits.shape[1]))
-        ctx.dl = dl
-        ctx.mark_non_differentiable()
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        dl = ctx.dl
-        ctx.dl = None
-        if dl is None:
-            return None, None, None
-        g = g.reshape(1) if g.dtype == torch.float32 else g.float().reshape(1)
-        ops.scale_inplace(dl, g.contiguous())
-        return dl, None, None
+    return _ce_term(outputs.contiguous(), targets)
 
 
 def _logits_at_target_size(outputs, targets):
@@ -115,44 +96,16 @@ def lovasz_softmax_loss(outputs, targets, ignore_index=-100):
     lovasz_softmax(probas, labels, ignore=...) describes it); the softmax is part of the kernel.  A direct surrogate of the
     mean IoU the trainer selects checkpoints by."""
     outputs, targets = _logits_at_target_size(outputs, targets)
-    return _LovaszSoftmaxFn.apply(outputs, targets, ignore_index)
+    return _lovasz_term(ignore_index)(outputs, targets)
 
 
-def _lovasz_loss_fn(outputs, targets, model=None):
-    return lovasz_softmax_loss(outputs, targets)
-
-
-def _ce_lovasz_loss_fn(outputs, targets, model=None):
-    outputs, targets = _logits_at_target_size(outputs, targets)
-    return _CrossEntropyFn.apply(outputs, targets) + _LovaszSoftmaxFn.apply(outputs, targets, -100)
-
-
-class _CrossEntropyOptsFn(torch.autograd.Function):
-    """Cross-entropy with class weights, label smoothing, the focal factor and hard-pixel selection.  Built like
-    _CrossEntropyFn: forward runs pseg_ce_opts_fwd_bwd, which leaves the gradient with respect to the logits as well (the
-    kept set held fixed); backward only rescales it by the incoming scalar."""
-
-    @staticmethod
-    def forward(ctx, logits, targets, class_weight, label_smoothing, focal_gamma, keep_ratio, ignore_index):
-        need = logits.requires_grad
-        out, dl = ops.ce_opts_fwd_bwd(logits, targets, class_weight, label_smoothing, focal_gamma, keep_ratio, want_grad=need,
-                                      ignore_index=ignore_index)
-        if CHECK_LABELS and out[2].item() != 0:     # (host sync: debugging aid, off by default)
-            raise IndexError('%d target values are outside [0, %d) and are not ignore_index'
-                             % (int(out[2].item()), logits.shape[1]))
-        ctx.dl = dl
-        ctx.mark_non_differentiable()
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        dl = ctx.dl
-        ctx.dl = None
-        if dl is None:
-            return (None,) * 7
-        g = g.reshape(1) if g.dtype == torch.float32 else g.float().reshape(1)
-        ops.scale_inplace(dl, g.contiguous())
-        return (dl,) + (None,) * 6
+def _lovasz_term(ignore_index=-100):
+    """The Lovasz-softmax term over the classes present in the batch (Berman et al.; the loss the reference names in
+    utils/criterions.py): pseg_lovasz_softmax_fwd_bwd."""
+    def term(logits, targets):
+        return _FusedLossFn.apply(logits, lambda want_grad: ops.lovasz_softmax_fwd_bwd(
+            logits, targets, want_grad=want_grad, ignore_index=ignore_index), BAD_LABELS)
+    return term
 
 
 def _class_weight_on(class_weight, device):
@@ -162,6 +115,33 @@ def _class_weight_on(class_weight, device):
     return torch.as_tensor(class_weight, dtype=torch.float32).to(device).contiguous()
 
 
+def _ce_opts_term(class_weight, label_smoothing, focal_gamma, keep_ratio, ignore_index=-100, boundary=None):
+    """The cross-entropy term with class weights (None, a sequence or a tensor: moved to the logits' device once), label
+    smoothing, the focal factor and hard-pixel selection (pseg_ce_opts_fwd_bwd; the kept set is held fixed in the
+    gradient).  boundary = (boost, width in pixels or None, ratio, falloff, sigma or None): every pixel is also weighted
+    by its ops.label_depth bin (pseg_ce_opts_binned_fwd_bwd)."""
+    state = {'w': class_weight, 'device': None}
+    ls, fg, kr = float(label_smoothing), float(focal_gamma), float(keep_ratio)
+
+    def term(logits, targets):
+        C = logits.shape[1]
+        if state['w'] is not None and state['device'] != logits.device:
+            state['w'], state['device'] = _class_weight_on(state['w'], logits.device), logits.device
+        w = state['w']
+        if w is not None and w.numel() != C:
+            raise ValueError('class_weight has %d values for %d classes' % (w.numel(), C))
+        if boundary is None:
+            return _FusedLossFn.apply(logits, lambda want_grad: ops.ce_opts_fwd_bwd(
+                logits, targets, w, ls, fg, kr, want_grad=want_grad, ignore_index=ignore_index), BAD_LABELS)
+        boost, width, ratio, falloff, sigma = boundary
+        d = int(width) if width else boundary_width(targets.shape[1:], ratio)
+        table = _boundary_table_on(d, boost, falloff, sigma, logits.device)
+        depth = ops.label_depth(targets, C, d, edge=False)
+        return _FusedLossFn.apply(logits, lambda want_grad: ops.ce_opts_binned_fwd_bwd(
+            logits, targets, depth, table, w, ls, fg, kr, want_grad=want_grad, ignore_index=ignore_index), BAD_LABELS)
+    return term
+
+
 def weighted_cross_entropy_loss(outputs, targets, class_weight=None, label_smoothing=0.0, focal_gamma=0.0, keep_ratio=1.0,
                                 ignore_index=-100):
     """Cross-entropy of NCHW logits with per-class weights and label smoothing (F.cross_entropy(weight=, label_smoothing=)
@@ -169,39 +149,7 @@ def weighted_cross_entropy_loss(outputs, targets, class_weight=None, label_smoot
     keep_ratio hardest valid pixels of the batch -- all of them at keep_ratio = 1.  One HIP call (pseg_ce_opts_fwd_bwd);
     bit-reproducible."""
     outputs, targets = _logits_at_target_size(outputs, targets)
-    w = _class_weight_on(class_weight, outputs.device)
-    if w is not None and w.numel() != outputs.shape[1]:
-        raise ValueError('class_weight has %d values for %d classes' % (w.numel(), outputs.shape[1]))
-    return _CrossEntropyOptsFn.apply(outputs, targets, w, float(label_smoothing), float(focal_gamma), float(keep_ratio),
-                                     ignore_index)
-
-
-class _CrossEntropyBinnedFn(torch.autograd.Function):
-    """_CrossEntropyOptsFn with a per-pixel weight bin_weight[pixel_bin] (pseg_ce_opts_binned_fwd_bwd).  Built the same way:
-    forward leaves the gradient with respect to the logits, backward only rescales it by the incoming scalar."""
-
-    @staticmethod
-    def forward(ctx, logits, targets, pixel_bin, bin_weight, class_weight, label_smoothing, focal_gamma, keep_ratio,
-                ignore_index):
-        need = logits.requires_grad
-        out, dl = ops.ce_opts_binned_fwd_bwd(logits, targets, pixel_bin, bin_weight, class_weight, label_smoothing,
-                                             focal_gamma, keep_ratio, want_grad=need, ignore_index=ignore_index)
-        if CHECK_LABELS and out[2].item() != 0:     # (host sync: debugging aid, off by default)
-            raise IndexError('%d target values are outside [0, %d) and are not ignore_index'
-                             % (int(out[2].item()), logits.shape[1]))
-        ctx.dl = dl
-        ctx.mark_non_differentiable()
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        dl = ctx.dl
-        ctx.dl = None
-        if dl is None:
-            return (None,) * 9
-        g = g.reshape(1) if g.dtype == torch.float32 else g.float().reshape(1)
-        ops.scale_inplace(dl, g.contiguous())
-        return (dl,) + (None,) * 8
+    return _ce_opts_term(class_weight, label_smoothing, focal_gamma, keep_ratio, ignore_index)(outputs, targets)
 
 
 BOUNDARY_FALLOFFS = ('flat', 'linear', 'gaussian')
@@ -260,42 +208,21 @@ def boundary_weighted_cross_entropy_loss(outputs, targets, boundary_boost, bound
     the loss.  Two depth launches plus one HIP call (pseg_ce_opts_binned_fwd_bwd), which reads the depth byte beside the
     target; no fp32 weight map is written.  Bit-reproducible."""
     outputs, targets = _logits_at_target_size(outputs, targets)
-    w = _class_weight_on(class_weight, outputs.device)
-    if w is not None and w.numel() != outputs.shape[1]:
-        raise ValueError('class_weight has %d values for %d classes' % (w.numel(), outputs.shape[1]))
-    d = int(boundary_width) if boundary_width else _width_from_ratio(targets.shape[1:], boundary_ratio)
-    table = _boundary_table_on(d, boundary_boost, boundary_falloff, boundary_sigma, outputs.device)
-    depth = ops.label_depth(targets, outputs.shape[1], d, edge=False)
-    return _CrossEntropyBinnedFn.apply(outputs, targets, depth, table, w, float(label_smoothing), float(focal_gamma),
-                                       float(keep_ratio), ignore_index)
+    boundary = (boundary_boost, boundary_width, boundary_ratio, boundary_falloff, boundary_sigma)
+    return _ce_opts_term(class_weight, label_smoothing, focal_gamma, keep_ratio, ignore_index, boundary)(outputs, targets)
 
 
-class _TverskyFn(torch.autograd.Function):
-    """Soft Dice / Tversky / focal-Tversky loss over the softmax of the logits (Salehi et al.; Abraham & Khan).  Built like
-    _LovaszSoftmaxFn: forward runs pseg_tversky_fwd_bwd, which leaves the gradient with respect to the logits as well;
-    backward only rescales it by the incoming scalar."""
+def _tversky_term(alpha=0.5, beta=0.5, smooth=1.0, power=1.0, per_image=False, all_classes=False, ignore_index=-100, weight=1.0):
+    """weight x the soft Dice / Tversky / focal-Tversky term over the softmax of the logits (Salehi et al.; Abraham & Khan):
+    pseg_tversky_fwd_bwd.  A weight of 1 is no multiply."""
+    args = (float(alpha), float(beta), float(smooth), float(power), bool(per_image), bool(all_classes))
+    weight = float(weight)
 
-    @staticmethod
-    def forward(ctx, logits, targets, alpha, beta, smooth, power, per_image, all_classes, ignore_index):
-        need = logits.requires_grad
-        out, dl = ops.tversky_fwd_bwd(logits, targets, alpha, beta, smooth, power, per_image, all_classes, want_grad=need,
-                                      ignore_index=ignore_index)
-        if CHECK_LABELS and out[2].item() != 0:     # (host sync: debugging aid, off by default)
-            raise IndexError('%d target values are outside [0, %d) and are not ignore_index'
-                             % (int(out[2].item()), logits.shape[1]))
-        ctx.dl = dl
-        ctx.mark_non_differentiable()
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        dl = ctx.dl
-        ctx.dl = None
-        if dl is None:
-            return (None,) * 9
-        g = g.reshape(1) if g.dtype == torch.float32 else g.float().reshape(1)
-        ops.scale_inplace(dl, g.contiguous())
-        return (dl,) + (None,) * 8
+    def term(logits, targets):
+        loss = _FusedLossFn.apply(logits, lambda want_grad: ops.tversky_fwd_bwd(
+            logits, targets, *args, want_grad=want_grad, ignore_index=ignore_index), BAD_LABELS)
+        return loss if weight == 1.0 else weight * loss
+    return term
 
 
 def tversky_loss(outputs, targets, alpha=0.5, beta=0.5, smooth=1.0, power=1.0, per_image=False, all_classes=False,
@@ -306,82 +233,40 @@ def tversky_loss(outputs, targets, alpha=0.5, beta=0.5, smooth=1.0, power=1.0, p
     groups.  The defaults are soft Dice; alpha + beta = 1 is Tversky (beta > alpha weighs misses over false alarms);
     power != 1 is focal-Tversky.  One HIP call (pseg_tversky_fwd_bwd); bit-reproducible."""
     outputs, targets = _logits_at_target_size(outputs, targets)
-    return _TverskyFn.apply(outputs, targets, float(alpha), float(beta), float(smooth), float(power), bool(per_image),
-                            bool(all_classes), ignore_index)
+    return _tversky_term(alpha, beta, smooth, power, per_image, all_classes, ignore_index)(outputs, targets)
 
 
-def _tversky_loss_fn(outputs, targets, model=None):
-    return tversky_loss(outputs, targets)
+# the one table behind every named loss: name -> its kinds of term, in the order they are added
+TERMS = {'ce': ('ce',), 'lovasz': ('lovasz',), 'ce+lovasz': ('ce', 'lovasz'), 'tversky': ('tversky',),
+         'ce+tversky': ('ce', 'tversky')}
 
 
-def _ce_tversky_loss_fn(outputs, targets, model=None):
-    outputs, targets = _logits_at_target_size(outputs, targets)
-    return _CrossEntropyFn.apply(outputs, targets) + _TverskyFn.apply(outputs, targets, 0.5, 0.5, 1.0, 1.0, False, False, -100)
+def _compose(name, term_of, launch_last_first=False):
+    """loss_fn(outputs, targets, model) of the loss `name`: the logits brought to the targets' size once, then the sum of
+    TERMS[name] in table order, term_of[kind] giving each.  launch_last_first: the terms' kernels are launched in reverse
+    (only the order on the stream: the sum is the same expression)."""
+    terms = [term_of[kind] for kind in TERMS[name]]
+
+    def loss_fn(outputs, targets, model=None):
+        outputs, targets = _logits_at_target_size(outputs, targets)
+        order = reversed(range(len(terms))) if launch_last_first else range(len(terms))
+        values = {i: terms[i](outputs, targets) for i in order}
+        loss = values[0]
+        for i in range(1, len(terms)):
+            loss = loss + values[i]
+        return loss
+    return loss_fn
 
 
-LOSSES = {'ce': compute_loss, 'lovasz': _lovasz_loss_fn, 'ce+lovasz': _ce_lovasz_loss_fn, 'tversky': _tversky_loss_fn,
-          'ce+tversky': _ce_tversky_loss_fn}
+_DEFAULT_TERMS = {'ce': _ce_term, 'lovasz': _lovasz_term(), 'tversky': _tversky_term()}
+LOSSES = {name: compute_loss if name == 'ce' else _compose(name, _DEFAULT_TERMS) for name in TERMS}
+_lovasz_loss_fn, _ce_lovasz_loss_fn = LOSSES['lovasz'], LOSSES['ce+lovasz']
 CE_OPTIONS = {'class_weight': None, 'label_smoothing': 0.0, 'focal_gamma': 0.0, 'keep_ratio': 1.0}
 TVERSKY_OPTIONS = {'tversky_alpha': 0.5, 'tversky_beta': 0.5, 'tversky_smooth': 1.0, 'tversky_power': 1.0,
                    'tversky_per_image': False, 'tversky_all_classes': False, 'tversky_weight': 1.0}
 # boundary_width 0: from boundary_ratio; boundary_sigma 0: width / 3.  On iff boundary_boost > 0.
 BOUNDARY_OPTIONS = {'boundary_boost': 0.0, 'boundary_width': 0, 'boundary_ratio': 0.02, 'boundary_falloff': 'gaussian',
                     'boundary_sigma': 0.0}
-
-
-def _configured_ce_term(opts, bd):
-    """ce(outputs, targets) on logits already at the targets' size: the cross-entropy configured by `opts`, weighted by
-    the distance to the target's contours when `bd` (the boundary options, boost > 0) is given"""
-    state = {'w': opts['class_weight'], 'device': None}
-    ls, fg, kr = float(opts['label_smoothing']), float(opts['focal_gamma']), float(opts['keep_ratio'])
-
-    def weight_on(device):      # moved to the logits' device once
-        if state['w'] is not None and state['device'] != device:
-            state['w'], state['device'] = _class_weight_on(state['w'], device), device
-        return state['w']
-
-    if bd is None:
-        return lambda outputs, targets: weighted_cross_entropy_loss(outputs, targets, weight_on(outputs.device), ls, fg, kr)
-    boost, falloff = float(bd['boundary_boost']), bd['boundary_falloff']
-    width, ratio = int(bd['boundary_width']) or None, float(bd['boundary_ratio'])
-    sigma = float(bd['boundary_sigma']) or None
-    boundary_weight_table(width or 1, boost, falloff, sigma)      # bad options are refused here, not at the first batch
-    return lambda outputs, targets: boundary_weighted_cross_entropy_loss(outputs, targets, boost, width, ratio, falloff, sigma,
-                                                                         weight_on(outputs.device), ls, fg, kr)
-
-
-def _configured_ce(name, opts, bd=None):
-    """loss_fn(outputs, targets, model) of 'ce' / 'ce+lovasz' with the cross-entropy configured by `opts` (and `bd`)"""
-    ce = _configured_ce_term(opts, bd)
-
-    def _ce_opts_loss_fn(outputs, targets, model=None):
-        return ce(outputs, targets)
-
-    def _ce_opts_lovasz_loss_fn(outputs, targets, model=None):
-        outputs, targets = _logits_at_target_size(outputs, targets)
-        return ce(outputs, targets) + _LovaszSoftmaxFn.apply(outputs, targets, -100)
-
-    return _ce_opts_loss_fn if name == 'ce' else _ce_opts_lovasz_loss_fn
-
-
-def _configured_tversky(name, opts, ce_set, tv, bd=None):
-    """loss_fn(outputs, targets, model) of 'tversky' / 'ce+tversky' with the Tversky term configured by `tv` and, for
-    'ce+tversky' with ce_set or `bd`, the cross-entropy by `opts` and `bd`"""
-    args = (float(tv['tversky_alpha']), float(tv['tversky_beta']), float(tv['tversky_smooth']), float(tv['tversky_power']),
-            bool(tv['tversky_per_image']), bool(tv['tversky_all_classes']))
-    weight = float(tv['tversky_weight'])
-    ce = _configured_ce_term(opts, bd) if (ce_set or bd is not None) else _CrossEntropyFn.apply
-
-    def _tversky_opts_loss_fn(outputs, targets, model=None):
-        loss = tversky_loss(outputs, targets, *args)
-        return loss if weight == 1.0 else weight * loss
-
-    def _ce_tversky_opts_loss_fn(outputs, targets, model=None):
-        outputs, targets = _logits_at_target_size(outputs, targets)
-        tvl = _TverskyFn.apply(outputs, targets, *args, -100)
-        return ce(outputs, targets) + (tvl if weight == 1.0 else weight * tvl)
-
-    return _tversky_opts_loss_fn if name == 'tversky' else _ce_tversky_opts_loss_fn
 
 
 def make_loss(name, **options):
@@ -425,9 +310,20 @@ def make_loss(name, **options):
     if bd_set and name in ('lovasz', 'tversky'):
         raise ValueError("the boundary options do not apply to %r: they weight a cross-entropy term, and 'lovasz' and 'tversky' "
                          "have none (use 'ce', 'ce+lovasz' or 'ce+tversky')" % name)
+    term_of = dict(_DEFAULT_TERMS)
     if 'tversky' in name:
-        return _configured_tversky(name, opts, is_set, tv, bd if bd_set else None)
-    return _configured_ce(name, opts, bd if bd_set else None)
+        term_of['tversky'] = _tversky_term(**{k[len('tversky_'):]: v for k, v in tv.items()})
+    if is_set or bd_set:
+        boundary = None
+        if bd_set:
+            boundary = (float(bd['boundary_boost']), int(bd['boundary_width']) or None, float(bd['boundary_ratio']),
+                        bd['boundary_falloff'], float(bd['boundary_sigma']) or None)
+            # bad options are refused here, not at the first batch
+            boundary_weight_table(boundary[1] or 1, boundary[0], boundary[3], boundary[4])
+        term_of['ce'] = _ce_opts_term(opts['class_weight'], opts['label_smoothing'], opts['focal_gamma'], opts['keep_ratio'],
+                                      boundary=boundary)
+    # (a configured 'ce+tversky' has always launched its Tversky kernels before its cross-entropy's)
+    return _compose(name, term_of, launch_last_first=name == 'ce+tversky')
 
 
 def predict_mask(outputs):
@@ -521,20 +417,22 @@ def update_class_counts(counters, predicted, targets):
     return counters
 
 
+def _guarded(den):
+    """a denominator with every entry <= 0 replaced by 1"""
+    den = den.clone()
+    den[den <= 0] = 1
+    return den
+
+
 def compute_metrics(tp, fn, fp):
     """reference utils/utils.py:51-65 -- host-side, [num_classes]-sized tensors (not on the hot path)."""
     tp, fn, fp = tp.clone().float(), fn.clone().float(), fp.clone().float()
 
-    def guarded(den):
-        den = den.clone()
-        den[den <= 0] = 1
-        return den
-
-    miou = tp / guarded(tp + fp + fn)
+    miou = tp / _guarded(tp + fp + fn)
     T = tp + fn
-    P = tp / guarded(tp + fp)
-    R = tp / guarded(tp + fn)
-    F1 = 2 * tp / guarded(2 * tp + fp + fn)
+    P = tp / _guarded(tp + fp)
+    R = tp / _guarded(tp + fn)
+    F1 = 2 * tp / _guarded(2 * tp + fp + fn)
     return T, P, R, miou, F1
 
 
@@ -551,9 +449,6 @@ def boundary_width(hw, ratio=0.02):
         raise ValueError('boundary width %d of a %d x %d map at ratio %g exceeds %d pixels: give a smaller ratio or a fixed '
                          'width' % (d, h, w, ratio, ops.BOUNDARY_MAX_WIDTH))
     return d
-
-
-_width_from_ratio = boundary_width      # (boundary_weighted_cross_entropy_loss has a keyword of that name)
 
 
 def update_boundary_counts(counters, predicted, targets, width):
@@ -573,9 +468,4 @@ def compute_boundary_metrics(counters):
     compute_metrics."""
     inter, gband, pband, tp, fn, fp = (c.float() for c in counters.detach().cpu())
 
-    def guarded(den):
-        den = den.clone()
-        den[den <= 0] = 1
-        return den
-
-    return inter / guarded(gband + pband - inter), tp / guarded(tp + fn + fp)
+    return inter / _guarded(gband + pband - inter), tp / _guarded(tp + fn + fp)

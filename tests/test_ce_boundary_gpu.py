@@ -248,3 +248,26 @@ def test_trainer_step_with_a_boundary_weighted_loss(tmp_path):
     assert np.isfinite(loss) and loss > 0, loss
     moved = [not torch.equal(a, b.detach()) for a, b in zip(before, tr.model.parameters())]
     assert all(moved), '%d of %d parameters did not move' % (moved.count(False), len(moved))
+
+
+# ------------------------------------------------------------------ the loss family's recorded bits
+def test_loss_bits_match_recorded(golden_dir):
+    """every make_loss configuration of tests/loss_bits.py at its five shapes, the resize and fp16 cases and the five direct
+    ops.*_fwd_bwd calls give the loss bytes, the gradient bytes and the sequence of C entry points recorded in
+    tests/golden/loss_bits.json from the code as it stood before the loss Functions, closures and kernel helpers were folded"""
+    import json
+    import os
+
+    import loss_bits
+    from optim_bits import compiler_line
+    from pytorch_segmentation_amd import ops
+    with open(os.path.join(golden_dir, 'loss_bits.json')) as f:
+        rec = json.load(f)
+    got = loss_bits.digests(ops)
+    assert sorted(got) == sorted(rec['digests'])
+    for name, fields in got.items():
+        assert sorted(fields) == sorted(rec['digests'][name]), name
+        for k, v in fields.items():
+            assert v == rec['digests'][name][k], \
+                'case %s, %s: %s, recorded %s (recorded from %s under "%s", installed "%s")' % (
+                    name, k, v, rec['digests'][name][k], rec['commit'], rec['compiler'], compiler_line())

@@ -91,8 +91,10 @@ def test_compiled_sets_restate_the_source():
     assert 'capped_blocks(n4?n4:1,%d)' % lc.kScaleMaxBlocks in flat and 'capped_blocks(n,%d)' % lc.kConfusionMaxBlocks in flat
     assert 'capped_blocks(npix/4,%d)' % lc.kArgmaxMaxBlocks in flat and 'capped_blocks(npix,%d)' % lc.kArgmaxMaxBlocks in flat
     assert 'capped_blocks(total,%d)' % lc.kCombineMaxBlocks in flat
-    # the unrolled loops of the finish kernels
-    assert 'for(;i+7*256<nblocks;i+=8*256)' in flat and 'for(;i+3*256<nblocks;i+=4*256)' in flat
+    # the unrolled loops of the finish kernels (ce_finish_kernel's is the loss family's shared one, in loss_common.h)
+    shared = re.sub(r'\s+', '', open(os.path.join(os.path.dirname(HERE), 'pytorch_segmentation_amd', 'csrc', 'loss_common.h')).read())
+    assert 'for(;i+7*256<nblocks;i+=8*256)' in flat + shared and 'for(;i+3*256<nblocks;i+=4*256)' in flat
+    assert 'block_sum_d(thread_sum_partials(partial,nblocks),sh)' in flat
     assert 'returnbest+(a.align?0:2);' in flat
     header = open(os.path.join(os.path.dirname(HERE), 'include', 'pseg_amd.h')).read()
     assert re.search(r'int\s+pseg_debug_last_loss\(\s*int\s*\*\s*out8\s*\)\s*;', header)
