@@ -63,7 +63,8 @@ extern "C" {
  * connected-region calls pseg_regions_workspace_bytes, pseg_mask_label, pseg_mask_regions, pseg_mask_clean, and the
  * sliding-window calls pseg_image_preprocess_windows, pseg_seg_decode_windows, and the grouped optimiser calls
  * pseg_grad_sumsq_workspace_bytes, pseg_grad_sumsq, pseg_opt_step_sgd, pseg_opt_step_adam, and the contour-measure calls
- * pseg_label_depth, pseg_boundary_counts_workspace_bytes, pseg_boundary_counts) are purely
+ * pseg_label_depth, pseg_boundary_counts_workspace_bytes, pseg_boundary_counts, and the outline calls
+ * pseg_mask_rings_workspace_bytes, pseg_mask_rings) are purely
  * additive and do not bump it: the loader checks every declared prototype against the library's exports by name. */
 #define PSEG_ABI_VERSION 14
 int pseg_abi_version(void);
@@ -708,6 +709,58 @@ int pseg_mask_regions(const uint8_t* mask, const int* labels, const int64_t* tab
                       int64_t max_regions, int64_t* records, int64_t* count, void* ws, int64_t ws_bytes, void* stream);
 int pseg_mask_clean(const uint8_t* mask, const int* labels, const int64_t* table, int B, int64_t npix_total, int Hmax, int Wmax,
                     int64_t min_area, int largest_only, uint8_t* mask_out, uint8_t* rgb, const uint8_t* lut, void* ws,
+                    int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------ outlines of the regions (csrc/polygons.hip)
+ * The boundary of every connected region as closed rings of lattice vertices.  mask, labels, table, npix_total, Hmax, Wmax
+ * are the regions section's; labels must be pseg_mask_label's result for mask with the SAME connectivity.  Integer
+ * arithmetic only, so results are exact and bit-reproducible.  These entry points are additive: PSEG_ABI_VERSION does not move.
+ *
+ * Lattice.  Pixel (x, y) of a photo is the unit square [x, x+1] x [y, y+1]; vertices are the integer points 0..W x 0..H.
+ *   (The records' pixel-centre coordinates are these minus 0.5.)
+ * Cracks.  Side s of pixel p is a directed unit edge with the pixel on its right hand:
+ *     s = 0  N  east   (x, y)     -> (x+1, y)          s = 2  S  west   (x+1, y+1) -> (x, y+1)
+ *     s = 1  E  south  (x+1, y)   -> (x+1, y+1)        s = 3  W  north  (x, y+1)   -> (x, y)
+ *   The edge exists iff the pixel across that side lies outside the photo or has another LABEL.  Edge id = 4 * (pixel
+ *   index) + s: photo-relative (pixel index y*W + x) in the records, packed-buffer-relative (offset + y*W + x) for ordering.
+ * Successor.  At the head of edge (p, s) let a be the pixel ahead of p in the travel direction, b the pixel ahead-left
+ *   (diagonal to p), and in(q) mean: q is inside the photo and labels[q] == labels[p].  Then the successor is
+ *     in(a) and in(b):   turn left,  (b, (s+3)%4)
+ *     in(a), not in(b):  straight,   (a, s)
+ *     neither:           turn right, (p, (s+1)%4)
+ *     in(b), not in(a) -- a saddle:  connectivity 8 turns left, (b, (s+3)%4); connectivity 4 turns right, (p, (s+1)%4).
+ *   Every edge has exactly one successor and one predecessor, so the edges fall into closed RINGS.  With connectivity 8 a
+ *   component has one outer ring, which may pass a vertex twice, and its holes are the 4-connected pieces of its
+ *   complement; with connectivity 4 all rings are simple and the holes are the 8-connected pieces of the complement.
+ * Corner edge: an edge whose predecessor has a different s.  A ring's VERTICES are the tails of its corner edges, in ring
+ *   order, beginning at the corner edge of smallest id, the ring's START EDGE.  A ring has at least 4 vertices, an even
+ *   count, and horizontal and vertical segments alternate.
+ * Outer ring and holes.  The outer ring of a component is the one whose start edge is 4 * label + 0; every other ring of
+ *   that label is a hole.  With y down the shoelace sum sum(x_i * y_{i+1} - x_{i+1} * y_i) is positive for outer rings and
+ *   negative for holes, and the signed areas of a component's rings add up to its pixel area exactly.
+ * Output order: rings ascend by the packed id of their start edge -- photo first (table offsets ascending), then raster.
+ *
+ * pseg_mask_rings_workspace_bytes(npix_total, max_edges): bytes of the 16-byte aligned workspace (5 bytes per pixel and 37
+ *   per edge of capacity, plus the scans' block sums); -1 for arguments out of range.
+ * pseg_mask_rings: npix_total < 2^29 (edge ids and indices are int32), 0 <= max_edges <= 4 * npix_total, connectivity 4 or
+ *   8; otherwise PSEG_ERR_ARG.  rings: max_edges / 4 records of PSEG_RING_WORDS int64: [0] photo * 256 + class, [1] label,
+ *   [2] start edge id (photo-relative), [3] offset of the first vertex, [4] vertex count, [5] 1 for a hole, 0 for an outer
+ *   ring.  vertices: max_edges (x, y) int32 pairs; each ring's vertices are contiguous, in ring order.  counts[0..2]
+ *   (int64): the full numbers of edges, rings and vertices.  If counts[0] > max_edges the call sets counts[1] = counts[2] =
+ *   -1 and writes nothing into rings or vertices (both may be null with max_edges 0): repeat it with max_edges = counts[0].
+ *   Words of rings and vertices past the counts are left as they are.  Skipped table records (regions section) are
+ *   skipped here too: nothing is read or written for them.  No host synchronisation; the number of launches, 11 + 2 R with
+ *   R = ceil(log2(min(max_edges, 4 * Hmax * Wmax))), depends on max_edges, Hmax and Wmax only: cracks per pixel, an
+ *   exclusive scan, the compact edge list with successors, R rounds of pointer doubling (minimum over corner-edge ids,
+ *   between two buffers) for the start edges, R rounds of list ranking of the rings opened at their start edges, a scan
+ *   of ring flags and vertex counts, the scatter.  No thread walks along a ring.
+ * Not here: polygon simplification, a device-side convex hull or minimum-area rectangle (utils/regions.py does the
+ * rectangle on the host from the ring's vertices), run-length export.
+ */
+#define PSEG_RING_WORDS 6
+int64_t pseg_mask_rings_workspace_bytes(int64_t npix_total, int64_t max_edges);
+int pseg_mask_rings(const uint8_t* mask, const int* labels, const int64_t* table, int B, int64_t npix_total, int Hmax, int Wmax,
+                    int connectivity, int64_t max_edges, int64_t* rings, int32_t* vertices, int64_t* counts, void* ws,
                     int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ contour measures of the evaluation (csrc/boundary.hip)

@@ -4,6 +4,7 @@
     python3 inference.py data/samples outputs --weights weights.pth [-s W H] [-nc N] [-bs N] [--model ...] [-mp]
                          [--norm dataset|reference] [--scales S [S ...]] [--flip]
                          [--min-area N] [--connectivity {4,8}] [--largest-only] [--regions FILE.json]
+                         [--polygons] [--coco FILE.json]
                          [--slide [--stride SW SH] [--window-batch N]] [--ema]
 
 Every file of img_dir whose extension is in IMG_EXT (case-sensitive, as the reference) is segmented, in name order, and
@@ -17,6 +18,10 @@ multiples of 32), and with --flip of the left-right mirrored photo as well, are 
 --largest-only keeps the largest region of every class but background, --connectivity chooses 4- or 8-neighbour regions
 (utils/regions.py); the PNGs show the cleaned masks.  --regions FILE.json writes {file name: [region, ...]} for the whole
 folder: class, area, bbox, centroid, angle, sides and label of every region of the (cleaned) mask.
+--polygons adds every region's outline to that file: polygon (flat [x0, y0, x1, y1, ...] rings on the pixel lattice, the
+outer ring first, then the holes), perimeter and min_rect (the minimum-area enclosing rectangle).  --coco FILE.json writes
+the regions of every class but background as COCO annotations in the layout utils/datasets.py reads; a COCO polygon
+cannot express holes, so only the outer ring goes there (--regions keeps them).
 --slide does not squeeze a photo into -s W H: the model runs on overlapping W x H windows (multiples of 32) laid over the
 photo at its own size -- with --scales over the photo scaled by each factor -- at --stride SW SH (default 2/3 of the
 window), the class probabilities of the windows covering a pixel are averaged and the argmax is taken; --window-batch N
@@ -51,13 +56,16 @@ def load_image(path):
 
 def run(img_dir, output_dir, img_size, num_classes, weights, show=False, model_name='deeplabv3plus', batch_size=1,
         half=False, norm='dataset', scales=None, flip=False, min_area=0, connectivity=8, largest_only=False, regions=None,
-        slide=False, stride=None, window_batch=None, ema=False):
+        slide=False, stride=None, window_batch=None, ema=False, polygons=False, coco=None):
     if not slide and (stride is not None or window_batch is not None):
         raise ValueError('--stride and --window-batch need --slide')
     if min_area < 0:
         raise ValueError('--min-area must be >= 0; got %d' % min_area)
     if connectivity not in (4, 8):
         raise ValueError('--connectivity must be 4 or 8; got %r' % (connectivity,))
+    if polygons and not (regions or coco):
+        raise ValueError('--polygons needs --regions or --coco')
+    polygons = bool(polygons or coco)
     if show:
         _warn_ignored('--show', 'the reference accepts it and never displays anything either')
     os.makedirs(output_dir, exist_ok=True)
@@ -72,22 +80,29 @@ def run(img_dir, output_dir, img_size, num_classes, weights, show=False, model_n
     tta = {} if scales is None and not flip else {'scales': scales, 'flip': bool(flip)}
     if slide:
         tta.update(slide=True, stride=None if stride is None else tuple(stride), window_batch=window_batch)
-    if min_area > 1 or largest_only or regions:
-        tta.update(min_area=min_area, connectivity=connectivity, largest_only=bool(largest_only), regions=bool(regions))
-    found = {}
+    if min_area > 1 or largest_only or regions or coco:
+        tta.update(min_area=min_area, connectivity=connectivity, largest_only=bool(largest_only), regions=bool(regions or coco))
+    if polygons:
+        tta.update(polygons=True)
+    found, sizes = {}, {}
     for i in range(0, len(names), max(1, batch_size)):
         batch = names[i:i + max(1, batch_size)]
         imgs = [load_image(osp.join(img_dir, n)) for n in batch]
         result = inference(model, imgs, tuple(img_size), norm=norm, bgr=False, half=half, colors=PALETTE_RGB, **tta)
         colored = result[1]
-        if regions:
+        if regions or coco:
             found.update(zip(batch, result[2]))
+            sizes.update((n, im.shape[:2]) for n, im in zip(batch, imgs))
         for name, seg in zip(batch, colored):
             Image.fromarray(seg).save(osp.join(output_dir, osp.splitext(name)[0] + '.png'))
         print('%d/%d' % (min(i + batch_size, len(names)), len(names)), flush=True)
     if regions:
         with open(regions, 'w') as f:
             json.dump(found, f)
+    if coco:
+        from pytorch_segmentation_amd.utils.regions import coco_annotations
+        with open(coco, 'w') as f:
+            json.dump(coco_annotations(found, sizes, num_classes), f)
     return names
 
 
@@ -113,6 +128,10 @@ def main(argv=None):
     parser.add_argument('--largest-only', action='store_true', help='keep only the largest region of every class >= 1')
     parser.add_argument('--regions', type=str, default=None, metavar='FILE.json',
                         help='write {file name: [region, ...]} (class, area, bbox, centroid, angle, sides, label)')
+    parser.add_argument('--polygons', action='store_true',
+                        help='with --regions or --coco: add polygon, perimeter and min_rect to every region')
+    parser.add_argument('--coco', type=str, default=None, metavar='FILE.json',
+                        help='write the regions of every class >= 1 as COCO polygon annotations (outer rings; holes are dropped)')
     parser.add_argument('--slide', action='store_true',
                         help='sliding-window inference: -s W H is the window (multiples of 32) laid over the photo at its own '
                              'size; --scales then scale the photo')
@@ -128,10 +147,12 @@ def main(argv=None):
         parser.error('--stride and --window-batch need --slide')
     if opt.window_batch is not None and opt.window_batch < 1:
         parser.error('--window-batch must be >= 1')
+    if opt.polygons and not (opt.regions or opt.coco):
+        parser.error('--polygons needs --regions or --coco')
     print(opt)
     run(opt.img_dir, opt.output_dir, opt.img_size, opt.num_classes, opt.weights, opt.show, opt.model, opt.batch_size,
         opt.mix_precision, opt.norm, opt.scales, opt.flip, opt.min_area, opt.connectivity, opt.largest_only, opt.regions,
-        opt.slide, opt.stride, opt.window_batch, opt.ema)
+        opt.slide, opt.stride, opt.window_batch, opt.ema, opt.polygons, opt.coco)
 
 
 if __name__ == '__main__':

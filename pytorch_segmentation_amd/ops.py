@@ -1471,7 +1471,46 @@ def mask_clean(mask, labels, table, npix_total, max_hw, min_area=0, largest_only
     return mask_out, rgb
 
 
-AUGMENT_ROW = 24        # PSEG_AUGMENT_ROW: floats per sample of augment_batch's parameter table (layout: include/pseg_amd.h)
+RING_WORDS = 6          # PSEG_RING_WORDS: int64 per record of mask_rings (layout: include/pseg_amd.h)
+
+# the rings call's scratch (5 bytes per mask pixel, 37 per edge of capacity): its own buffer, like the regions calls'
+rings_workspace = _Workspace()
+
+
+def mask_rings(mask, labels, table, npix_total, max_hw, connectivity, max_edges, rings=None, vertices=None, counts=None):
+    """The outlines of the components of a labelled packed mask as closed rings of lattice vertices (pseg_mask_rings;
+    definitions and record layout in include/pseg_amd.h).  labels: mask_label's result for the same connectivity.
+    -> (rings int64 [max_edges // 4, RING_WORDS], vertices int32 [max_edges, 2], counts int64 [3] = edges, rings,
+    vertices).  If counts[0] > max_edges nothing is written and counts[1] = counts[2] = -1: repeat with max_edges =
+    counts[0].  No host synchronisation: read counts yourself."""
+    assert mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.dim() == 1
+    assert mask.numel() == npix_total
+    assert table.device == mask.device and table.dtype == torch.int64 and table.is_contiguous()
+    assert table.dim() == 2 and table.shape[1] == 3
+    assert labels.device == mask.device and labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == npix_total
+    Hmax, Wmax = int(max_hw[0]), int(max_hw[1])
+    max_edges = int(max_edges)
+    nbytes = _lib.query('pseg_mask_rings_workspace_bytes', int(npix_total), max_edges)
+    assert nbytes >= 0, 'npix_total %d or max_edges %d out of range' % (npix_total, max_edges)
+    ws = rings_workspace.get(nbytes, mask.device)
+    if rings is None:
+        rings = torch.empty(max_edges // 4, RING_WORDS, dtype=torch.int64, device=mask.device)
+    if vertices is None:
+        vertices = torch.empty(max_edges, 2, dtype=torch.int32, device=mask.device)
+    if counts is None:
+        counts = torch.empty(3, dtype=torch.int64, device=mask.device)
+    assert rings.device == mask.device and rings.dtype == torch.int64 and rings.is_contiguous()
+    assert rings.numel() >= max_edges // 4 * RING_WORDS
+    assert vertices.device == mask.device and vertices.dtype == torch.int32 and vertices.is_contiguous()
+    assert vertices.numel() >= 2 * max_edges
+    assert counts.device == mask.device and counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() >= 3
+    _lib.call('pseg_mask_rings', mask.data_ptr(), labels.data_ptr(), table.data_ptr(), table.shape[0], npix_total, Hmax, Wmax,
+              int(connectivity), max_edges, rings.data_ptr() if max_edges else 0, vertices.data_ptr() if max_edges else 0,
+              counts.data_ptr(), ws.data_ptr(), nbytes, _stream())
+    return rings, vertices, counts
+
+
+AUGMENT_ROW = 24       # PSEG_AUGMENT_ROW: floats per sample of augment_batch's parameter table (layout: include/pseg_amd.h)
 
 
 def augment_batch(imgs, segs, params, oh, ow, mean, std, out=None, target=None):

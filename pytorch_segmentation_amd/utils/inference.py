@@ -116,7 +116,8 @@ class Ensemble:
 
 @torch.no_grad()
 def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=False, colors=None, scales=None, flip=False,
-              min_area=0, connectivity=8, largest_only=False, regions=False, slide=False, stride=None, window_batch=None):
+              min_area=0, connectivity=8, largest_only=False, regions=False, slide=False, stride=None, window_batch=None,
+              polygons=False):
     """The reference's contract: ``imgs`` is a list of uint8 H x W x 3 photos (numpy arrays, or CPU or device tensors),
     ``img_size`` = (w, h) of the model input as cv2.resize takes it; returns one int64 numpy H x W mask per photo, at
     that photo's own size.  ``bgr=True``: the photos are cv2.imread output (B, G, R).  ``half=True``: the forward runs
@@ -134,6 +135,9 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
     class of the region above their first pixel (``connectivity`` 4 or 8); the colours are those of the cleaned mask.
     ``regions=True`` appends one more result: per photo, a list of dicts {class, area, bbox, centroid, angle, sides, label}
     of the regions of the cleaned mask (utils.regions.region_dicts).  With all four at their defaults none of this runs.
+    ``polygons=True`` (with ``regions=True``) traces every region's outline on the cleaned device mask before the copy
+    back (utils.regions.mask_polygons) and adds {polygon, perimeter, min_rect} to each region's dict; without it nothing
+    of that is launched or allocated.
 
     ``slide=True`` turns on sliding-window inference for photos larger than the model input: ``img_size`` is then the
     WINDOW (both sides multiples of 32), laid over the photo at ``stride`` = (sw, sh) in ``img_size``'s order (between
@@ -153,7 +157,10 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
         raise ValueError('min_area must be >= 0; got %d' % min_area)
     if connectivity not in (4, 8):
         raise ValueError('connectivity must be 4 or 8; got %r' % (connectivity,))
-    post = (min_area, int(connectivity), bool(largest_only), bool(regions)) if min_area > 1 or largest_only or regions else None
+    if polygons and not regions:
+        raise ValueError('polygons=True adds to the region dicts: it needs regions=True')
+    post = (min_area, int(connectivity), bool(largest_only), bool(regions), bool(polygons)) \
+        if min_area > 1 or largest_only or regions else None
     if norm not in NORMS:
         raise ValueError('norm must be one of %s' % sorted(NORMS))
     mean, std = NORMS[norm]
@@ -265,21 +272,21 @@ def _finish(decode, dtable, lay, colors, post, device):
 def _postprocess(out, table, total_pix, sizes, lut, post):
     """the connected-region pass on the decoded device mask (imported here: the default route never loads it)"""
     from .regions import postprocess
-    min_area, connectivity, largest_only, want_regions = post
+    min_area, connectivity, largest_only, want_regions, want_polygons = post
     return postprocess(out, table, total_pix, (int(sizes[:, 0].max()), int(sizes[:, 1].max())), lut, min_area, connectivity,
-                       largest_only, want_regions)
+                       largest_only, want_regions, want_polygons)
 
 
 def _result(masks, images, records, post):
     """inference()'s four result shapes: masks, or (masks, images) with a palette, each with the per-photo region lists
-    appended when regions=True asked for them"""
+    appended when regions=True asked for them (records: postprocess's result, with polygons=True the pair it returns)"""
     result = masks if images is None else (masks, images)
     if post is None or not post[3]:
         return result
     lists = []
     if masks:
         from .regions import region_dicts
-        lists = region_dicts(records, len(masks))
+        lists = region_dicts(records[0], len(masks), records[1]) if post[4] else region_dicts(records, len(masks))
     return result + (lists,) if images is not None else (result, lists)
 
 
