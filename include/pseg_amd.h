@@ -64,7 +64,7 @@ extern "C" {
  * sliding-window calls pseg_image_preprocess_windows, pseg_seg_decode_windows, and the grouped optimiser calls
  * pseg_grad_sumsq_workspace_bytes, pseg_grad_sumsq, pseg_opt_step_sgd, pseg_opt_step_adam, and the contour-measure calls
  * pseg_label_depth, pseg_boundary_counts_workspace_bytes, pseg_boundary_counts, and the outline calls
- * pseg_mask_rings_workspace_bytes, pseg_mask_rings) are purely
+ * pseg_mask_rings_workspace_bytes, pseg_mask_rings, and the dense-CRF calls pseg_crf_workspace_bytes, pseg_crf_refine) are purely
  * additive and do not bump it: the loader checks every declared prototype against the library's exports by name. */
 #define PSEG_ABI_VERSION 14
 int pseg_abi_version(void);
@@ -762,6 +762,51 @@ int64_t pseg_mask_rings_workspace_bytes(int64_t npix_total, int64_t max_edges);
 int pseg_mask_rings(const uint8_t* mask, const int* labels, const int64_t* table, int B, int64_t npix_total, int Hmax, int Wmax,
                     int connectivity, int64_t max_edges, int64_t* rings, int32_t* vertices, int64_t* counts, void* ws,
                     int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------ local dense-CRF refinement of logits (csrc/crf.hip)
+ * Mean-field inference of the locally connected dense CRF of Teichmann & Cipolla, "Convolutional CRFs for Semantic
+ * Segmentation" (2018): the Kraehenbuehl-Koltun appearance and smoothness kernels truncated to a dilated (2R+1) x (2R+1)
+ * window.  Logits in, logits out, on the model-input grid; the guide is the model input.  These entry points are additive:
+ * PSEG_ABI_VERSION does not move.
+ *
+ * Given logits U fp32 NCHW [B,C,h,w], a guide G fp32 NCHW [B,3,h,w], guide scales g_c (the preprocess call's std_c: then
+ * (G_c(p) - G_c(q)) * g_c is the colour difference in 8-bit units whatever the normalisation), radius R in 1..5, dilation
+ * D in 1..4, iterations T in 1..10, theta_alpha, theta_beta, theta_gamma > 0 and weights w_a, w_s >= 0.
+ * Neighbours.  N(p) = the pixels q = p + D * (dy, dx) with |dy|, |dx| <= R, q != p, inside the image.
+ * Kernels.    k_a(p,q) = exp(-|p-q|^2 / (2 theta_alpha^2) - sum_c ((G_c(p) - G_c(q)) g_c)^2 / (2 theta_beta^2))
+ *             k_s(p,q) = exp(-|p-q|^2 / (2 theta_gamma^2))
+ * Iteration.  Q^0 = softmax_c(U); for t = 1..T
+ *             m_c(p)   = w_a * (sum_{q in N(p)} k_a Q^{t-1}_c(q)) / (sum_{q in N(p)} k_a)
+ *                      + w_s * (sum_{q in N(p)} k_s Q^{t-1}_c(q)) / (sum_{q in N(p)} k_s)
+ *             L^t_c(p) = U_c(p) + m_c(p)       (Potts compatibility; the class-independent term drops out of the softmax)
+ *             Q^t      = softmax_c(L^t)
+ * Result.     out = L^T, fp32 NCHW [B,C,h,w]: its softmax is the refined distribution, so every consumer of logits works
+ *             on it as it stands.
+ * Each kernel's message is normalised by its own weight sum over the in-image neighbours: a border pixel is not starved,
+ * and w_a, w_s are in logit units independent of R and D.  Only the RATIOS k / sum k enter, so the implementation takes
+ * each kernel's weights relative to the pixel's largest one, exp(e(q) - max_q e(q)): the same ratios, and a pixel whose
+ * every neighbour is far in colour (exp underflows in fp32) still gets a finite message.  A pixel with no in-image
+ * neighbour at all (possible only where D reaches the image's size, e.g. 2 x 2 at D = 2) gets no message: L = U there.
+ * With w_a = w_s = 0 the output equals U bit for bit (a copy; nothing is launched).  All arithmetic is fp32, there are no
+ * atomics, and two calls on the same input give the same bits.  The order of the sum over the window is row-major, so the
+ * result of a mirrored input is the mirrored result up to rounding, not bit for bit.
+ *
+ * pseg_crf_workspace_bytes(B, C, h, w): bytes of the 16-byte aligned workspace -- two ping-pong buffers of Q, pixel-major
+ *   [B,h,w,CP] in pseg_softmax_views' layout (CP = 8 for C <= 8, else C rounded up to 4), and nothing else; -1 for sizes
+ *   outside the ranges below.
+ * pseg_crf_refine: B, h, w in [1, 65535], h * w > 1, C in [1, 256], R, D, T in their ranges, thetas finite and > 0 with
+ *   1 / (2 theta^2) finite, weights and guide scales finite and >= 0, every operand (logits, guide, one Q buffer) below
+ *   2 GiB -- refused, not chunked --, workspace 16-byte aligned and at least the query's size; otherwise PSEG_ERR_ARG before
+ *   any launch.  out may be logits itself; it must not overlap the workspace and must not be the guide.  Launches: one
+ *   forms Q^0 (pseg_softmax_views' kernel), then one per iteration; the last iteration writes NCHW L^T itself.  The pair
+ *   weights never reach global memory: an iteration recomputes them from a guide tile with its R * D halo in LDS and reads
+ *   the neighbours' class vectors from an LDS tile of Q with the same halo, a class chunk at a time.
+ * Not here: a learned compatibility matrix, the full-image (permutohedral) CRF, a backward pass, fp16 Q.
+ */
+int64_t pseg_crf_workspace_bytes(int B, int C, int h, int w);
+int pseg_crf_refine(const float* logits, const float* guide, int B, int C, int h, int w, float g0, float g1, float g2, int R, int D,
+                    int T, float theta_alpha, float theta_beta, float theta_gamma, float w_a, float w_s, float* out, void* workspace,
+                    int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ contour measures of the evaluation (csrc/boundary.hip)
  * Boundary IoU (Cheng et al., CVPR 2021) and the trimap IoU of the DeepLabV3+ paper both come from one quantity per pixel

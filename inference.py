@@ -6,6 +6,7 @@
                          [--min-area N] [--connectivity {4,8}] [--largest-only] [--regions FILE.json]
                          [--polygons] [--coco FILE.json]
                          [--slide [--stride SW SH] [--window-batch N]] [--ema]
+                         [--crf [--crf-radius R] [--crf-dilation D] [--crf-iters T] [--crf-theta A B G] [--crf-weights WA WS]]
 
 Every file of img_dir whose extension is in IMG_EXT (case-sensitive, as the reference) is segmented, in name order, and
 written to output_dir as <name>.png in VOC colours.  Photos are decoded with PIL (RGB); resizing, normalisation, softmax,
@@ -26,6 +27,12 @@ cannot express holes, so only the outer ring goes there (--regions keeps them).
 photo at its own size -- with --scales over the photo scaled by each factor -- at --stride SW SH (default 2/3 of the
 window), the class probabilities of the windows covering a pixel are averaged and the argmax is taken; --window-batch N
 windows go through the model at a time (default: the photos of a batch).
+--crf refines the logits of every forward -- on any of the routes above -- by a local dense CRF guided by the model input
+(utils/crf.py, csrc/crf.hip) before the softmax and the decode: label changes snap to colour edges, specks go.  --crf-radius
+R (1 .. 5, default 3) and --crf-dilation D (1 .. 4, default 2) set the window, (2R+1) x (2R+1) taps D pixels apart at the
+model input's resolution; --crf-iters T (1 .. 10, default 5) the mean-field iterations; --crf-theta A B G (default 8 13 3) the
+appearance kernel's spatial and colour widths and the smoothness kernel's spatial width; --crf-weights WA WS (default 4 3)
+the two kernels' weights in logit units.
 """
 import argparse
 import json
@@ -56,7 +63,7 @@ def load_image(path):
 
 def run(img_dir, output_dir, img_size, num_classes, weights, show=False, model_name='deeplabv3plus', batch_size=1,
         half=False, norm='dataset', scales=None, flip=False, min_area=0, connectivity=8, largest_only=False, regions=None,
-        slide=False, stride=None, window_batch=None, ema=False, polygons=False, coco=None):
+        slide=False, stride=None, window_batch=None, ema=False, polygons=False, coco=None, crf=None):
     if not slide and (stride is not None or window_batch is not None):
         raise ValueError('--stride and --window-batch need --slide')
     if min_area < 0:
@@ -66,6 +73,9 @@ def run(img_dir, output_dir, img_size, num_classes, weights, show=False, model_n
     if polygons and not (regions or coco):
         raise ValueError('--polygons needs --regions or --coco')
     polygons = bool(polygons or coco)
+    if crf is not None and crf is not False:
+        from pytorch_segmentation_amd.utils.crf import CRF
+        crf = CRF.of(crf)                                      # bad options are refused before the weights are read
     if show:
         _warn_ignored('--show', 'the reference accepts it and never displays anything either')
     os.makedirs(output_dir, exist_ok=True)
@@ -84,6 +94,8 @@ def run(img_dir, output_dir, img_size, num_classes, weights, show=False, model_n
         tta.update(min_area=min_area, connectivity=connectivity, largest_only=bool(largest_only), regions=bool(regions or coco))
     if polygons:
         tta.update(polygons=True)
+    if crf:
+        tta.update(crf=crf)
     found, sizes = {}, {}
     for i in range(0, len(names), max(1, batch_size)):
         batch = names[i:i + max(1, batch_size)]
@@ -140,6 +152,19 @@ def main(argv=None):
     parser.add_argument('--window-batch', type=int, default=None, metavar='N',
                         help='with --slide: windows per forward (default: -bs)')
     parser.add_argument('--ema', action='store_true', help="use the averaged weights ('model_ema') of the checkpoint")
+    # (argparse.SUPPRESS: without the flags the options printed below are what they were)
+    parser.add_argument('--crf', action='store_true', default=argparse.SUPPRESS,
+                        help='refine the logits of every forward by the local dense CRF (utils/crf.py) before the decode')
+    parser.add_argument('--crf-radius', type=int, default=argparse.SUPPRESS, metavar='R',
+                        help='with --crf: window radius in taps, 1 .. 5 (default 3)')
+    parser.add_argument('--crf-dilation', type=int, default=argparse.SUPPRESS, metavar='D',
+                        help='with --crf: pixels between taps, 1 .. 4 (default 2)')
+    parser.add_argument('--crf-iters', type=int, default=argparse.SUPPRESS, metavar='T',
+                        help='with --crf: mean-field iterations, 1 .. 10 (default 5)')
+    parser.add_argument('--crf-theta', type=float, nargs=3, default=argparse.SUPPRESS, metavar=('A', 'B', 'G'),
+                        help='with --crf: theta_alpha, theta_beta, theta_gamma (default 8 13 3)')
+    parser.add_argument('--crf-weights', type=float, nargs=2, default=argparse.SUPPRESS, metavar=('WA', 'WS'),
+                        help='with --crf: appearance and smoothness weights in logit units (default 4 3)')
     opt = parser.parse_args(argv)
     if opt.min_area < 0:
         parser.error('--min-area must be >= 0')
@@ -149,10 +174,18 @@ def main(argv=None):
         parser.error('--window-batch must be >= 1')
     if opt.polygons and not (opt.regions or opt.coco):
         parser.error('--polygons needs --regions or --coco')
+    crf = None
+    crf_flags = [getattr(opt, 'crf_' + k, None) for k in ('radius', 'dilation', 'iters', 'theta', 'weights')]
+    if getattr(opt, 'crf', False) or any(v is not None for v in crf_flags):
+        from pytorch_segmentation_amd.utils.crf import from_flags
+        try:
+            crf = from_flags(getattr(opt, 'crf', False), *crf_flags)
+        except ValueError as e:
+            parser.error(str(e))
     print(opt)
     run(opt.img_dir, opt.output_dir, opt.img_size, opt.num_classes, opt.weights, opt.show, opt.model, opt.batch_size,
         opt.mix_precision, opt.norm, opt.scales, opt.flip, opt.min_area, opt.connectivity, opt.largest_only, opt.regions,
-        opt.slide, opt.stride, opt.window_batch, opt.ema, opt.polygons, opt.coco)
+        opt.slide, opt.stride, opt.window_batch, opt.ema, opt.polygons, opt.coco, crf)
 
 
 if __name__ == '__main__':

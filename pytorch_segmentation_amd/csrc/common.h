@@ -34,6 +34,10 @@ int launch_col_reduce(const float* part, int rows, int C, float* out, int accumu
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// Floats per pixel of a pixel-major probability map (infer.hip, crf.hip): a multiple of 4 (a class chunk is a run of
+// 16-byte vectors), at least 8
+static inline int class_pad(int C) { return C <= 8 ? 8 : (C + 3) / 4 * 4; }
+
 // Exact n / d for 0 <= n < 2^31, 1 <= d < 2^31 by one 32x32->64 multiply and a shift
 // (mul = ceil(2^(31+s)/d), s = ceil(log2 d); error term e = mul*d - 2^(31+s) < 2^s, so n*e < 2^(31+s)).
 struct FastDiv {

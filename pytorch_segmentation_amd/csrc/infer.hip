@@ -160,9 +160,6 @@ __global__ __launch_bounds__(256) void image_preprocess_kernel(const uint8_t* __
 // ------------------------------------------------------------------ decode
 constexpr int kDecodeLdsFloats = 12288;   // 48 KiB of probabilities per block
 
-// Floats per pixel of a probability map: a multiple of 4 (a class chunk is a run of 16-byte vectors), at least 8
-static inline int class_pad(int C) { return C <= 8 ? 8 : (C + 3) / 4 * 4; }
-
 // The running argmax over classes c .. c + 3 of v; classes >= C are padding
 __device__ __forceinline__ void scan_classes(const f32x4& v, int c, int C, float& best, int& bi) {
 #pragma unroll

@@ -1510,6 +1510,34 @@ def mask_rings(mask, labels, table, npix_total, max_hw, connectivity, max_edges,
     return rings, vertices, counts
 
 
+# the CRF's two ping-pong buffers of Q (pixel-major [B,h,w,class_pad(C)]): its own buffer, kept per stream while the
+# shape does not grow
+crf_workspace = _Workspace()
+
+
+def crf_refine(logits, guide, guide_scale, radius, dilation, iters, theta_alpha, theta_beta, theta_gamma, w_appearance, w_smooth,
+               out=None):
+    """Local dense-CRF refinement of logits (pseg_crf_refine; definition in include/pseg_amd.h): fp32 NCHW logits
+    [B,C,h,w] and guide [B,3,h,w] (the model input; guide_scale = the std of its normalisation) -> fp32 NCHW L^T, whose
+    softmax is the refined distribution.  out (optional) may be logits itself.  Every range is checked by the library
+    before any launch (PsegError)."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
+    assert guide.device == logits.device and guide.dtype == torch.float32 and guide.is_contiguous()
+    B, C, h, w = logits.shape
+    assert guide.shape == (B, 3, h, w), 'crf_refine: guide %s for logits %s' % (tuple(guide.shape), tuple(logits.shape))
+    assert len(guide_scale) == 3
+    if out is None:
+        out = torch.empty_like(logits)
+    assert out.device == logits.device and out.dtype == torch.float32 and out.is_contiguous() and out.shape == logits.shape
+    nbytes = _lib.query('pseg_crf_workspace_bytes', B, C, h, w)
+    # (a shape the query refuses goes to the call with an empty workspace: the call names the argument that is wrong)
+    ws = crf_workspace.get(max(nbytes, 0), logits.device)
+    _lib.call('pseg_crf_refine', logits.data_ptr(), guide.data_ptr(), B, C, h, w, *[float(g) for g in guide_scale], int(radius),
+              int(dilation), int(iters), float(theta_alpha), float(theta_beta), float(theta_gamma), float(w_appearance),
+              float(w_smooth), out.data_ptr(), ws.data_ptr(), max(nbytes, 0), _stream())
+    return out
+
+
 AUGMENT_ROW = 24       # PSEG_AUGMENT_ROW: floats per sample of augment_batch's parameter table (layout: include/pseg_amd.h)
 
 

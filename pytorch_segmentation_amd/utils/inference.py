@@ -117,7 +117,7 @@ class Ensemble:
 @torch.no_grad()
 def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=False, colors=None, scales=None, flip=False,
               min_area=0, connectivity=8, largest_only=False, regions=False, slide=False, stride=None, window_batch=None,
-              polygons=False):
+              polygons=False, crf=None):
     """The reference's contract: ``imgs`` is a list of uint8 H x W x 3 photos (numpy arrays, or CPU or device tensors),
     ``img_size`` = (w, h) of the model input as cv2.resize takes it; returns one int64 numpy H x W mask per photo, at
     that photo's own size.  ``bgr=True``: the photos are cv2.imread output (B, G, R).  ``half=True``: the forward runs
@@ -146,7 +146,12 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
     (align_corners=False) working probability, which is the unweighted mean of the softmaxes (with ``flip``: softmax plus
     un-mirrored softmax of the mirrored window) of the windows covering a working-image pixel.  Windows go through the
     model at most ``window_batch`` at a time (default: the number of photos).  ``colors``, ``half`` and the region
-    options compose as on the other routes.  Without ``slide`` neither ``stride`` nor ``window_batch`` may be given."""
+    options compose as on the other routes.  Without ``slide`` neither ``stride`` nor ``window_batch`` may be given.
+
+    ``crf`` (None, True for the defaults, a ``utils.crf.CRF`` or a dict of its options) refines the logits of every forward
+    -- the single one, each scale's (mirrored rows with their mirrored inputs), each chunk of windows -- by the local dense
+    CRF of ops.crf_refine, guided by that forward's own input, before the softmax and decode of the route; in fp32 also
+    under ``half``.  With None nothing of it is imported, launched or allocated."""
     slide = bool(slide)
     if not slide and (stride is not None or window_batch is not None):
         raise ValueError('stride and window_batch belong to slide=True')
@@ -164,6 +169,7 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
     if norm not in NORMS:
         raise ValueError('norm must be one of %s' % sorted(NORMS))
     mean, std = NORMS[norm]
+    refine = _refiner(crf, std)
     w, h = int(img_size[0]), int(img_size[1])
     flip = bool(flip)
     if scales is not None:
@@ -185,16 +191,18 @@ def inference(model, imgs, img_size=(64, 64), norm='dataset', bgr=True, half=Fal
     B = len(photos)
     if slide:
         return _inference_slide(model, photos, h, w, sy, sx, scales, flip, window_batch, mean, std, bgr, half, colors, device,
-                                post)
+                                post, refine)
     if tta:
         if B * (2 if flip else 1) > 65535:
             raise ValueError('%d photos x %d views exceed 65535 rows per launch' % (B, 2 if flip else 1))
-        return _inference_ensemble(model, photos, h, w, sizes, flip, mean, std, bgr, half, colors, device, post)
+        return _inference_ensemble(model, photos, h, w, sizes, flip, mean, std, bgr, half, colors, device, post, refine)
     lay = photo_layout(photos)
     tables = np.stack([_table(lay, 3), _table(lay, 1)])           # preprocess: byte offsets; decode: pixel offsets
     (dtables,), src = _stage(photos, lay, [tables], device)
     x = ops.image_preprocess(src, dtables[0], h, w, mean, std, bgr)
     logits = _forward(model, x, half).contiguous()
+    if refine is not None:
+        logits = refine(logits, x)
     return _finish(lambda lut, out: ops.seg_decode(logits, dtables[1], lay[2], lut, out=out), dtables[1], lay, colors, post,
                    device)
 
@@ -290,7 +298,16 @@ def _result(masks, images, records, post):
     return result + (lists,) if images is not None else (result, lists)
 
 
-def _inference_ensemble(model, photos, h, w, view_sizes, flip, mean, std, bgr, half, colors, device, post=None):
+def _refiner(crf, std):
+    """inference()'s ``crf=`` -> None, or the call (logits, model input) -> refined logits (utils/crf.py is imported only here)"""
+    if crf is None or crf is False:
+        return None
+    from .crf import CRF
+    opts = CRF.of(crf)
+    return lambda logits, x: opts.refine(logits, x, std)
+
+
+def _inference_ensemble(model, photos, h, w, view_sizes, flip, mean, std, bgr, half, colors, device, post=None, refine=None):
     """inference() with several views: the same single staging buffer (now also carrying the view table and the map
     table) and the same single copy back; per scale one preprocess launch, one forward, one softmax launch."""
     B, S, V = len(photos), len(view_sizes), 2 if flip else 1
@@ -305,6 +322,8 @@ def _inference_ensemble(model, photos, h, w, view_sizes, flip, mean, std, bgr, h
     for hs, ws in view_sizes:
         x = ops.image_preprocess_views(src, dviews, hs, ws, mean, std, bgr)
         logits = _forward(model, x, half)
+        if refine is not None:
+            logits = refine(logits, x)
         del x
         ens.add(logits)
         del logits                                             # released before the next scale's forward
@@ -364,7 +383,8 @@ def slide_scales(photo_sizes, scales):
     return kept
 
 
-def _inference_slide(model, photos, h, w, sy, sx, scales, flip, window_batch, mean, std, bgr, half, colors, device, post=None):
+def _inference_slide(model, photos, h, w, sy, sx, scales, flip, window_batch, mean, std, bgr, half, colors, device, post=None,
+                     refine=None):
     """inference(slide=True): the same single staging buffer (now also carrying the window table and the group table) and
     the same single copy back; per chunk of windows one preprocess launch, one forward, one softmax launch, then ONE
     decode.  The window table is staged chunk by chunk -- with flip a chunk is [n plain; n mirrored] -- so every chunk's
@@ -398,9 +418,11 @@ def _inference_slide(model, photos, h, w, sy, sx, scales, flip, window_batch, me
     for a, e in chunks:
         x = ops.image_preprocess_windows(src, dwindows[V * a:V * e], h, w, mean, std, bgr)
         logits = _forward(model, x, half)
-        del x
         if logits.shape[2:] != (h, w):
             raise RuntimeError('the model returns %dx%d logits for a %dx%d window' % (tuple(logits.shape[2:]) + (h, w)))
+        if refine is not None:
+            logits = refine(logits, x)
+        del x
         if prob is None:
             C = logits.shape[1]
             CP = ops.class_pad(C)

@@ -332,13 +332,14 @@ def predict_mask(outputs):
 
 
 @torch.no_grad()
-def predict_mask_ensemble(model, inputs, out_hw, scales=(1.0,), flip=False, view_logits=None):
+def predict_mask_ensemble(model, inputs, out_hw, scales=(1.0,), flip=False, view_logits=None, refine=None):
     """Test-time-ensembled prediction for an already normalised device batch [B,3,H,W]: int64 [B,out_h,out_w] =
     argmax_c of the unweighted sum, over the views, of the un-mirrored softmax resized bilinearly (align_corners=False) to
     out_hw; first index on ties.  Views: ``inputs`` resized (F.interpolate bilinear, align_corners=False; the identity at
     its own size) to every size of ``tta_sizes(H, W, scales)``, each also flipped along x with ``flip``.  The softmaxes
     and the resize-sum-argmax are ops.softmax_views / ops.seg_decode_ensemble.  view_logits (optional): a dict that
-    receives {(h_s, w_s): that scale's logits}."""
+    receives {(h_s, w_s): that scale's logits}.  refine (optional): a call (logits, view) -> logits applied to every view's
+    logits before its softmax (utils/crf.py); view_logits keeps the logits as the model gave them."""
     import torch.nn.functional as F
     from .inference import Ensemble, tta_sizes
     if not inputs.is_cuda:
@@ -356,6 +357,8 @@ def predict_mask_ensemble(model, inputs, out_hw, scales=(1.0,), flip=False, view
         logits = model(x.contiguous()).float()
         if view_logits is not None:
             view_logits[(hs, ws)] = logits
+        if refine is not None:
+            logits = refine(logits, x)
         ens.add(logits)
         del logits, x
     table = torch.tensor([[b * oh * ow, oh, ow] for b in range(B)], dtype=torch.int64).to(inputs.device)
@@ -364,7 +367,7 @@ def predict_mask_ensemble(model, inputs, out_hw, scales=(1.0,), flip=False, view
 
 
 @torch.no_grad()
-def predict_mask_windows(model, inputs, out_hw, window_hw, stride_hw=None, scales=(1.0,), flip=False):
+def predict_mask_windows(model, inputs, out_hw, window_hw, stride_hw=None, scales=(1.0,), flip=False, refine=None):
     """Sliding-window prediction for an already normalised device batch [B,3,H,W]: int64 [B,out_h,out_w] = argmax_c of the
     sum, over the scales, of the bilinearly resized (align_corners=False) working probability -- the unweighted mean of the
     softmaxes (with ``flip``: plus the un-mirrored softmax of the mirrored window) of the windows covering a pixel of the
@@ -372,7 +375,8 @@ def predict_mask_windows(model, inputs, out_hw, window_hw, stride_hw=None, scale
     align_corners=False; the identity at 1.0) to ``work_size(H, W, s)``; the windows of ``window_hw`` = (h, w) at
     ``stride_hw`` = (sy, sx) (default: 2/3 of the window, ``window_grid``) are slices of it, zero-padded where it is
     smaller than the window; one forward per scale and image.  The softmaxes and the decode are ops.softmax_views /
-    ops.seg_decode_windows."""
+    ops.seg_decode_windows.  refine (optional): a call (logits, windows) -> logits applied to every forward's logits before
+    their softmax (utils/crf.py)."""
     import torch.nn.functional as F
     from .inference import slide_scales, slide_strides, window_grid
     if not inputs.is_cuda:
@@ -395,7 +399,10 @@ def predict_mask_windows(model, inputs, out_hw, window_hw, stride_hw=None, scale
             wins = torch.stack([x[b, :, y0:y0 + h, x0:x0 + w] for y0, x0 in grid])
             if flip:
                 wins = torch.cat([wins, torch.flip(wins, [3])], 0)
-            logits = model(wins.contiguous()).float()
+            wins = wins.contiguous()
+            logits = model(wins).float()
+            if refine is not None:
+                logits = refine(logits, wins)
             if prob is None:
                 CP = ops.class_pad(logits.shape[1])
                 prob = torch.empty(sum(len(g) for g in grids) * B * h * w * CP, dtype=torch.float32, device=inputs.device)

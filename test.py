@@ -4,6 +4,7 @@
     python3 test.py data/<custom>/val.json --weights weights/best.pt [-s W H] [-bs N] [--model deeplabv3plus|unet]
                     [--scales S [S ...]] [--flip] [--min-area N] [--connectivity {4,8}] [--largest-only]
                     [--window W H [--stride SW SH]] [--ema] [--boundary [RATIO] | --boundary-width D]
+                    [--crf [--crf-radius R] [--crf-dilation D] [--crf-iters T] [--crf-theta A B G] [--crf-weights WA WS]]
 
 `test(model, fetcher)` keeps the reference's contract: evaluates in eval mode without gradients, prints per-class
 (or the five worst classes') targets / precision / recall / IoU / F1 and returns the mean IoU.  The per-class
@@ -19,6 +20,9 @@ With --boundary [RATIO] or --boundary-width D the counted prediction -- whicheve
 contours: Boundary IoU (Cheng et al. 2021) and the trimap IoU of the DeepLabV3+ paper, in a band of RATIO times the target's
 diagonal (default 0.02) or of D pixels (utils.update_boundary_counts: two launches per batch, any class count).  One more
 summary line and two more columns per class row are printed; everything else, the returned mean IoU included, stays.
+With --crf the logits of every forward of the route in use -- plain, --scales / --flip, --window -- are refined by the local
+dense CRF (utils/crf.py, csrc/crf.hip), guided by that forward's inputs, before the prediction is made; --boundary shows what
+it does to the contours.  The printed loss stays that of the unrefined plain forward.
 """
 import argparse
 
@@ -38,10 +42,18 @@ MODELS = {'deeplabv3plus': DeepLabV3Plus, 'unet': UNet, 'hrnet': HRNet}
 
 @torch.no_grad()
 def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, largest_only=False, window=None, stride=None,
-         boundary=None, boundary_width=None, results=None):
+         boundary=None, boundary_width=None, results=None, crf=None):
     """boundary (a ratio of the target's diagonal) or boundary_width (pixels): also count Boundary IoU and trimap IoU on the
     prediction that is scored.  results: a dict that receives 'boundary_iou' and 'trimap_iou' ([C] tensors),
-    'boundary_counters' (int64 [6][C], summed over the ranks) and 'boundary_widths' (the sorted widths used)."""
+    'boundary_counters' (int64 [6][C], summed over the ranks) and 'boundary_widths' (the sorted widths used).
+    crf (None, True, a utils.crf.CRF or a dict of its options): the counted prediction of every route is made from logits
+    refined by the local dense CRF, guided by the inputs of the forward that gave them; the loss stays the plain forward's."""
+    refine = None
+    if crf is not None and crf is not False:
+        from pytorch_segmentation_amd.utils.crf import CRF
+        from pytorch_segmentation_amd.utils.datasets import STD
+        crf = CRF.of(crf)
+        refine = lambda logits, x: crf.refine(logits, x, STD)   # the loader normalises with MEAN / STD
     model.eval()
     if boundary is not None and boundary_width is not None:
         raise ValueError('boundary= (a ratio) and boundary_width= (pixels) exclude each other')
@@ -72,11 +84,11 @@ def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, la
     for inputs, targets in fetcher:
         if window is not None:                                 # sliding windows of (w, h) over the delivered batch
             predicted = predict_mask_windows(model, inputs, targets.shape[1:], (window[1], window[0]),
-                                             None if stride is None else (stride[1], stride[0]), scales, flip)
+                                             None if stride is None else (stride[1], stride[0]), scales, flip, refine)
             outputs = model(inputs)                            # the loss stays that of the plain forward
         elif tta:
             view_logits = {}
-            predicted = predict_mask_ensemble(model, inputs, targets.shape[1:], scales, flip, view_logits)
+            predicted = predict_mask_ensemble(model, inputs, targets.shape[1:], scales, flip, view_logits, refine)
             # the loss of the plain forward: the scale-1.0 unmirrored view, or one extra forward without scale 1.0
             outputs = view_logits.get(tuple(inputs.shape[2:]))
             del view_logits
@@ -90,7 +102,7 @@ def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, la
         if counters is None:
             counters = torch.zeros(3, nc, dtype=torch.int64, device=outputs.device)
         if predicted is None:
-            predicted = predict_mask(outputs)
+            predicted = predict_mask(outputs if refine is None else refine(outputs, inputs))
         if clean:
             from pytorch_segmentation_amd.utils.regions import clean_predictions
             predicted = clean_predictions(predicted, min_area, connectivity, largest_only)
@@ -163,7 +175,26 @@ def parse_args(argv=None):
                               "the target's diagonal")
     contour.add_argument('--boundary-width', type=int, default=None, metavar='D',
                          help='the same with a band of D pixels (1 .. 254)')
+    ap.add_argument('--crf', action='store_true',
+                    help='refine the logits of every forward by the local dense CRF (utils/crf.py) before the prediction is made')
+    ap.add_argument('--crf-radius', type=int, default=None, metavar='R', help='with --crf: window radius in taps, 1 .. 5 (default 3)')
+    ap.add_argument('--crf-dilation', type=int, default=None, metavar='D', help='with --crf: pixels between taps, 1 .. 4 (default 2)')
+    ap.add_argument('--crf-iters', type=int, default=None, metavar='T', help='with --crf: mean-field iterations, 1 .. 10 (default 5)')
+    ap.add_argument('--crf-theta', type=float, nargs=3, default=None, metavar=('A', 'B', 'G'),
+                    help='with --crf: theta_alpha, theta_beta, theta_gamma (default 8 13 3)')
+    ap.add_argument('--crf-weights', type=float, nargs=2, default=None, metavar=('WA', 'WS'),
+                    help='with --crf: appearance and smoothness weights in logit units (default 4 3)')
     opt = ap.parse_args(argv)
+    crf_flags = (opt.crf_radius, opt.crf_dilation, opt.crf_iters, opt.crf_theta, opt.crf_weights)
+    if not opt.crf and any(v is not None for v in crf_flags):
+        ap.error('--crf-radius, --crf-dilation, --crf-iters, --crf-theta and --crf-weights need --crf')
+    opt.crf_options = None
+    if opt.crf:
+        from pytorch_segmentation_amd.utils.crf import from_flags
+        try:
+            opt.crf_options = from_flags(True, *crf_flags)
+        except ValueError as e:
+            ap.error(str(e))
     if opt.boundary is not None and not 0.0 < opt.boundary <= 0.5:
         ap.error('--boundary must be in (0, 0.5]')
     if opt.boundary_width is not None and not 1 <= opt.boundary_width <= 254:
@@ -186,7 +217,7 @@ def main(argv=None):
     elif opt.ema:
         raise ValueError('--ema needs --weights')
     metrics = test(model.cuda(), fetcher, opt.scales, opt.flip, opt.min_area, opt.connectivity,
-                   opt.largest_only, opt.window, opt.stride, opt.boundary, opt.boundary_width)
+                   opt.largest_only, opt.window, opt.stride, opt.boundary, opt.boundary_width, crf=opt.crf_options)
     print('metrics: %8g' % metrics)
     return metrics
 
