@@ -64,7 +64,8 @@ extern "C" {
  * sliding-window calls pseg_image_preprocess_windows, pseg_seg_decode_windows, and the grouped optimiser calls
  * pseg_grad_sumsq_workspace_bytes, pseg_grad_sumsq, pseg_opt_step_sgd, pseg_opt_step_adam, and the contour-measure calls
  * pseg_label_depth, pseg_boundary_counts_workspace_bytes, pseg_boundary_counts, and the outline calls
- * pseg_mask_rings_workspace_bytes, pseg_mask_rings, and the dense-CRF calls pseg_crf_workspace_bytes, pseg_crf_refine) are purely
+ * pseg_mask_rings_workspace_bytes, pseg_mask_rings, and the dense-CRF calls pseg_crf_workspace_bytes, pseg_crf_refine, and
+ * the surface-loss calls pseg_class_sdist_workspace_bytes, pseg_class_sdist, pseg_surface_workspace_bytes, pseg_surface_fwd_bwd) are purely
  * additive and do not bump it: the loader checks every declared prototype against the library's exports by name. */
 #define PSEG_ABI_VERSION 14
 int pseg_abi_version(void);
@@ -850,6 +851,56 @@ int pseg_label_depth(const int64_t* labels, int B, int H, int W, int C, int d, i
 int64_t pseg_boundary_counts_workspace_bytes(int B, int H, int W, int d);
 int pseg_boundary_counts(const int64_t* pred, const int64_t* target, int B, int H, int W, int C, int d, int64_t* counters,
                          void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ surface (boundary-distance) loss (csrc/surface.hip)
+ * Kervadec et al., "Boundary loss for highly unbalanced segmentation" (MIDL 2019): the softmax weighted by a signed distance
+ * to the target's contour, per class.  The distance map is an exact Euclidean distance transform and a public call of its
+ * own.  These entry points are additive: PSEG_ABI_VERSION does not move.
+ *
+ * pseg_class_sdist: labels int64 [B][H][W] -> sdist int32 [B][C][H][W], the signed SQUARED Euclidean distance to the contour
+ *   of every class.  For image b and class c in [0, C) let M = {q in image b : L(q) == c}.  A label outside [0, C)
+ *   (ignore_index, 255, anything else) belongs to no class: it is outside M for every c (void labels compare by value, as
+ *   in the label depth).  Pixels of another image never count, and the image border is not a contour.
+ *       M empty or M the whole image:   sdist = 0 everywhere (the class has no contour in this image)
+ *       p not in M:                     sdist(p) = +min over q in M     of |p - q|^2      (>= 1)
+ *       p in M:                         sdist(p) = -min over q not in M of |p - q|^2      (<= -1)
+ *   Integers, exact; 0 is the "no term" sentinel and occurs in no other way.  Two calls on the same input give the same bits.
+ *   The distance is separable: with s(x, y) the signed distance along column x to the nearest pixel of the other kind
+ *   (negative in M; "none" when the column has no such pixel),
+ *       |sdist(x, y)| = min over x' of (x - x')^2 + f(x'),    f(x') = 0 where (x', y) is of the other kind, else s(x', y)^2,
+ *   which is how the kernels compute it: a memset and a pass that packs the labels to 16 bits and counts every class per
+ *   image (integer atomics: order-independent), a column sweep that stages s in sdist itself, and a row pass with the row
+ *   of s in LDS that searches outwards from x and stops once (x - x')^2 reaches the best value so far.  Integer arithmetic
+ *   only; no host synchronisation.
+ *   Refused with PSEG_ERR_ARG before any launch: null labels / sdist / workspace, B, H or W below 1, H or W above 16384 (so
+ *   H^2 + W^2 <= 2^29 fits), C outside [1, 1024], B * C * H * W * 4 at or above 2 GiB (refused, not chunked), a workspace
+ *   below pseg_class_sdist_workspace_bytes(B, C, H, W) (0 for sizes that are refused) or not 16-byte aligned.
+ *   The workspace holds 4 bytes per (image, class) and 2 bytes per pixel.
+ *
+ * pseg_surface_fwd_bwd: logits fp32 NCHW [B][C][HW], target int64 [B][HW], sdist int32 [B][C][HW] (pseg_class_sdist of the
+ *   target).  phi = sqrt(sdist) where sdist > 0, -(sqrt(-sdist) - 1) where sdist < 0, 0 where sdist == 0 (Kervadec's
+ *   one_hot2dist: edt(neg) neg - (edt(pos) - 1) pos, and a zero map for a class without a contour); with clip > 0, phi is
+ *   limited to [-clip, clip]; clip == 0: no limit.  A pixel is valid iff target != ignore_index and 0 <= target < C; other
+ *   targets that are not ignore_index are counted as out of range and ignored.  p = softmax(logits), max subtracted.
+ *       loss       = (1 / n_valid) sum over valid i, over c of phi_ic p_ic          (0 with a zero gradient when n_valid == 0)
+ *       dlogits_ij = p_ij (phi_ij - sum_k phi_ik p_ik) / n_valid                     (0 at invalid pixels)
+ *       out[3]     = [loss, n_valid, n_out_of_range] (as floats)
+ *   The sum runs over ALL classes and the divisor is the number of valid pixels only.  dlogits ([B][C][HW], nullable) must
+ *   alias neither logits nor sdist.  Work: a reduction pass reads logits, sdist and targets once (per-block partials in
+ *   double, added in a fixed order; no atomics); one block forms out[]; only when dlogits != NULL a gradient pass reads
+ *   logits and sdist twice more and writes dlogits once.  No host synchronisation.  Deterministic: two calls give the same
+ *   bits, and the loss is the same bits with and without dlogits.
+ *   Refused with PSEG_ERR_ARG before any launch: null logits / target / sdist / out / workspace, non-positive sizes,
+ *   C > 1024, logits or target at or above 2 GiB, a negative or non-finite clip, an aliasing dlogits, a workspace below
+ *   pseg_surface_workspace_bytes(B, C, HW) (0 for sizes that are refused) or not 16-byte aligned.
+ *   The workspace holds 24 bytes per block of 1024 pixels of an image. */
+int64_t pseg_class_sdist_workspace_bytes(int B, int C, int H, int W);
+int pseg_class_sdist(const int64_t* labels, int B, int H, int W, int C, int32_t* sdist, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+int64_t pseg_surface_workspace_bytes(int B, int C, int64_t HW);
+int pseg_surface_fwd_bwd(const float* logits, const int64_t* target, const int32_t* sdist, int B, int C, int64_t HW,
+                         int64_t ignore_index, float clip, float* dlogits, float* out, void* workspace,
+                         int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ training augmentation (csrc/augment.hip)
  * The geometric and colour-affine part of the reference's online augmentation (utils/datasets.py:26-125, imgaug on the

@@ -1222,6 +1222,18 @@ def tversky_fwd_bwd(logits, target, alpha=0.5, beta=0.5, smooth=1.0, power=1.0, 
     return (out, dl, sums) if want_sums else (out, dl)
 
 
+def surface_fwd_bwd(logits, target, sdist, clip=0.0, want_grad=True, ignore_index=-100):
+    """Kervadec's surface loss over the softmax of the logits (pseg_surface_fwd_bwd): the mean over the valid pixels of
+    sum_c phi_c p_c, phi the signed distance sqrt(sdist) / -(sqrt(-sdist) - 1) / 0 limited to [-clip, clip] when clip > 0.
+    logits: contiguous NCHW fp32 cuda, target: NHW int64, sdist: int32 NCHW = class_sdist(target, C).
+    -> (out[3] = [loss, n_valid, n_out_of_range_targets], dlogits|None)."""
+    B, C, H, W = _loss_operands(logits, target)
+    assert sdist.device == logits.device and sdist.dtype == torch.int32 and sdist.is_contiguous() and \
+        sdist.shape == logits.shape, 'sdist: contiguous int32 %s on %s' % (tuple(logits.shape), logits.device)
+    head = (logits.data_ptr(), target.data_ptr(), sdist.data_ptr(), B, C, H * W, ignore_index, float(clip))
+    return _loss_call('pseg_surface_fwd_bwd', head, logits, want_grad, 3, ('pseg_surface_workspace_bytes', B, C, H * W), workspace)
+
+
 def ce_upsampled_ok_shape(h, w, C, H, W, align_corners):
     return bool(_lib.query('pseg_ce_upsampled_ok', h, w, C, H, W, int(align_corners)))
 
@@ -1653,6 +1665,30 @@ def boundary_counts(pred, target, counters, d):
     ws = boundary_workspace.get(nbytes, pred.device)
     _lib.call('pseg_boundary_counts', pred.data_ptr(), target.data_ptr(), B, H, W, counters.shape[1], int(d),
               counters.data_ptr(), ws.data_ptr(), nbytes, _stream())
+
+
+SDIST_MAX_SIDE = 16384       # H^2 + W^2 of class_sdist fits 2^29
+
+# the distance transform's packed labels (two bytes per pixel): a buffer of its own, like the boundary counters'
+sdist_workspace = _Workspace()
+
+
+def class_sdist(labels, num_classes):
+    """Exact signed squared Euclidean distance of every pixel to the contour of every class (pseg_class_sdist): labels int64
+    [B, H, W] -> int32 [B, num_classes, H, W], +|p - q|^2 to the nearest pixel q of the class outside it, -|p - q|^2 to the
+    nearest pixel of another label (void included) inside it, and a plane of zeros for a class that is absent from its image
+    or fills it.  The image border is not a contour."""
+    _label_map('class_sdist', labels)
+    B, H, W = labels.shape
+    C = int(num_classes)
+    nbytes = _lib.query('pseg_class_sdist_workspace_bytes', B, C, H, W)
+    if nbytes <= 0:
+        raise ValueError('class_sdist: shape %s x %d classes out of range (H, W <= %d, 1 <= C <= 1024, the int32 result below '
+                         '2 GiB)' % (tuple(labels.shape), C, SDIST_MAX_SIDE))
+    out = torch.empty(B, C, H, W, dtype=torch.int32, device=labels.device)
+    ws = sdist_workspace.get(nbytes, labels.device)
+    _lib.call('pseg_class_sdist', labels.data_ptr(), B, H, W, C, out.data_ptr(), ws.data_ptr(), nbytes, _stream())
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- optimiser

@@ -236,9 +236,63 @@ def tversky_loss(outputs, targets, alpha=0.5, beta=0.5, smooth=1.0, power=1.0, p
     return _tversky_term(alpha, beta, smooth, power, per_image, all_classes, ignore_index)(outputs, targets)
 
 
+def _surface_options(weight, clip):
+    """the checked (weight: a float or a zero-argument callable, clip: a float) of a surface term"""
+    import math
+    if not callable(weight):
+        weight = float(weight)
+        if not (math.isfinite(weight) and weight >= 0.0):
+            raise ValueError('surface_weight must be finite and >= 0 (or a zero-argument callable); got %r' % (weight,))
+    clip = float(clip)
+    if not (math.isfinite(clip) and clip >= 0.0):
+        raise ValueError('surface_clip must be finite and >= 0 (pixels; 0: no limit); got %r' % (clip,))
+    return weight, clip
+
+
+def _surface_term(weight=1.0, clip=0.0, ignore_index=-100):
+    """weight x Kervadec's surface term (Kervadec et al., MIDL 2019): the mean over the valid pixels of sum_c phi_c p_c, phi
+    the signed Euclidean distance to the contour of class c in the target (ops.class_sdist, computed here from the targets)
+    limited to [-clip, clip] when clip > 0: pseg_surface_fwd_bwd.  weight: a float, or a zero-argument callable that is
+    read at every call (a schedule needs no rebuild).  A weight of 1 is no multiply."""
+    weight, clip = _surface_options(weight, clip)
+
+    def term(logits, targets):
+        sdist = ops.class_sdist(targets, logits.shape[1])
+        loss = _FusedLossFn.apply(logits, lambda want_grad: ops.surface_fwd_bwd(
+            logits, targets, sdist, clip, want_grad=want_grad, ignore_index=ignore_index), BAD_LABELS)
+        w = float(weight()) if callable(weight) else weight
+        return loss if w == 1.0 else w * loss
+    return term
+
+
+def surface_loss(outputs, targets, clip=0.0, ignore_index=-100):
+    """Kervadec's surface (boundary) loss of NCHW logits; the softmax is part of the kernel.  With phi_c the signed distance
+    in pixels of a pixel to the contour of class c in the target -- positive outside the class, -(distance - 1) inside, 0 for
+    a class that is absent from the image or fills it (Kervadec's one_hot2dist), limited to [-clip, clip] when clip > 0 --
+    the loss is the mean over the valid pixels of sum_c phi_c p_c, over ALL classes (Kervadec's code averages over the
+    selected classes too, usually the foreground only: a constant factor the weight absorbs).  The distance map is an exact
+    Euclidean transform on the device (three launches and a memset), the loss one HIP call (pseg_surface_fwd_bwd);
+    bit-reproducible.  Unbounded below in practice: a companion of a region loss (make_loss's '...+surface'), not an
+    objective of its own."""
+    outputs, targets = _logits_at_target_size(outputs, targets)
+    return _surface_term(1.0, clip, ignore_index)(outputs, targets)
+
+
+def signed_distance(targets, num_classes, clip=0.0):
+    """phi of surface_loss as fp32 [B, num_classes, H, W] on the targets' device, from ops.class_sdist with torch ops (for
+    inspection and logging; the loss reads the integer map itself)."""
+    if not targets.is_cuda:
+        raise RuntimeError('signed_distance runs on the HIP path only (got %s)' % targets.device)
+    _, clip = _surface_options(1.0, clip)
+    sd = ops.class_sdist(targets.to(torch.int64).contiguous(), num_classes).float()
+    phi = torch.where(sd > 0, sd.abs().sqrt(), torch.where(sd < 0, 1.0 - sd.abs().sqrt(), torch.zeros_like(sd)))
+    return phi.clamp_(-clip, clip) if clip > 0 else phi
+
+
 # the one table behind every named loss: name -> its kinds of term, in the order they are added
 TERMS = {'ce': ('ce',), 'lovasz': ('lovasz',), 'ce+lovasz': ('ce', 'lovasz'), 'tversky': ('tversky',),
-         'ce+tversky': ('ce', 'tversky')}
+         'ce+tversky': ('ce', 'tversky'), 'ce+surface': ('ce', 'surface'), 'tversky+surface': ('tversky', 'surface'),
+         'ce+tversky+surface': ('ce', 'tversky', 'surface')}
 
 
 def _compose(name, term_of, launch_last_first=False):
@@ -258,8 +312,12 @@ def _compose(name, term_of, launch_last_first=False):
     return loss_fn
 
 
-_DEFAULT_TERMS = {'ce': _ce_term, 'lovasz': _lovasz_term(), 'tversky': _tversky_term()}
-LOSSES = {name: compute_loss if name == 'ce' else _compose(name, _DEFAULT_TERMS) for name in TERMS}
+# surface_weight: Kervadec's starting alpha (a term measured in pixels must not swamp a term of order 1); a float or a
+# zero-argument callable.  surface_clip 0: the distance is not limited.
+SURFACE_OPTIONS = {'surface_weight': 0.01, 'surface_clip': 0.0}
+_DEFAULT_TERMS = {'ce': _ce_term, 'lovasz': _lovasz_term(), 'tversky': _tversky_term(),
+                  'surface': _surface_term(SURFACE_OPTIONS['surface_weight'], SURFACE_OPTIONS['surface_clip'])}
+LOSSES ={name: compute_loss if name == 'ce' else _compose(name, _DEFAULT_TERMS) for name in TERMS}
 _lovasz_loss_fn, _ce_lovasz_loss_fn = LOSSES['lovasz'], LOSSES['ce+lovasz']
 CE_OPTIONS = {'class_weight': None, 'label_smoothing': 0.0, 'focal_gamma': 0.0, 'keep_ratio': 1.0}
 TVERSKY_OPTIONS = {'tversky_alpha': 0.5, 'tversky_beta': 0.5, 'tversky_smooth': 1.0, 'tversky_power': 1.0,
@@ -270,7 +328,8 @@ BOUNDARY_OPTIONS = {'boundary_boost': 0.0, 'boundary_width': 0, 'boundary_ratio'
 
 
 def make_loss(name, **options):
-    """'ce' | 'lovasz' | 'ce+lovasz' | 'tversky' | 'ce+tversky' -> loss_fn(outputs, targets, model) for Trainer(loss_fn=...).
+    """'ce' | 'lovasz' | 'ce+lovasz' | 'tversky' | 'ce+tversky' | 'ce+surface' | 'tversky+surface' | 'ce+tversky+surface' ->
+    loss_fn(outputs, targets, model) for Trainer(loss_fn=...).
     'ce' without options is compute_loss itself (the Trainer's fused fast path keys on that object); everything else goes
     through the Trainer's autograd route.  The cross-entropy options (class_weight=, label_smoothing=, focal_gamma=,
     keep_ratio=) configure the cross-entropy of 'ce', 'ce+lovasz' and 'ce+tversky' (weighted_cross_entropy_loss); the
@@ -278,21 +337,29 @@ def make_loss(name, **options):
     tversky_all_classes=, and tversky_weight= for ce + weight * tversky) configure the Tversky term of 'tversky' and
     'ce+tversky' (tversky_loss); the boundary options (boundary_boost= > 0 turns them on; boundary_width= in pixels or
     boundary_ratio= of the diagonal, boundary_falloff=, boundary_sigma=) weight that same cross-entropy term by the distance
-    to the target's contours (boundary_weighted_cross_entropy_loss) and compose with the cross-entropy options.  An option
-    left at its default is not an option."""
+    to the target's contours (boundary_weighted_cross_entropy_loss) and compose with the cross-entropy options; the surface
+    options (surface_weight=, a float or a zero-argument callable read at every call, and surface_clip= in pixels)
+    configure the surface term that the '...+surface' names add last (surface_loss; there is no bare 'surface': the term
+    alone is unbounded below).  Every kind of option applies wherever TERMS[name] has its kind of term: the cross-entropy and
+    boundary options need a 'ce', the Tversky options a 'tversky', the surface options a 'surface'.  An option left at its
+    default is not an option."""
     if name not in LOSSES:
         raise ValueError('unknown loss %r (choose from %s)' % (name, ', '.join(sorted(LOSSES))))
-    unknown = sorted(set(options) - set(CE_OPTIONS) - set(TVERSKY_OPTIONS) - set(BOUNDARY_OPTIONS))
+    unknown = sorted(set(options) - set(CE_OPTIONS) - set(TVERSKY_OPTIONS) - set(BOUNDARY_OPTIONS) - set(SURFACE_OPTIONS))
     if unknown:
-        raise TypeError('unknown cross-entropy option(s) %s (choose from %s; Tversky options: %s; boundary options: %s)'
+        raise TypeError('unknown cross-entropy option(s) %s (choose from %s; Tversky options: %s; boundary options: %s; '
+                        'surface options: %s)'
                         % (', '.join(unknown), ', '.join(sorted(CE_OPTIONS)), ', '.join(sorted(TVERSKY_OPTIONS)),
-                           ', '.join(sorted(BOUNDARY_OPTIONS))))
+                           ', '.join(sorted(BOUNDARY_OPTIONS)), ', '.join(sorted(SURFACE_OPTIONS))))
+    kinds = TERMS[name]
     opts = dict(CE_OPTIONS, **{k: v for k, v in options.items() if k in CE_OPTIONS})
     tv = dict(TVERSKY_OPTIONS, **{k: v for k, v in options.items() if k in TVERSKY_OPTIONS})
     bd = dict(BOUNDARY_OPTIONS, **{k: v for k, v in options.items() if k in BOUNDARY_OPTIONS and v is not None})
+    sf = dict(SURFACE_OPTIONS, **{k: v for k, v in options.items() if k in SURFACE_OPTIONS and v is not None})
     is_set = opts['class_weight'] is not None or any(float(opts[k]) != CE_OPTIONS[k] for k in
                                                       ('label_smoothing', 'focal_gamma', 'keep_ratio'))
     tv_set = any(float(tv[k]) != float(TVERSKY_OPTIONS[k]) for k in TVERSKY_OPTIONS)
+    sf_set = callable(sf['surface_weight']) or any(float(sf[k]) != SURFACE_OPTIONS[k] for k in SURFACE_OPTIONS)
     bd_changed = sorted(k for k in BOUNDARY_OPTIONS if bd[k] != BOUNDARY_OPTIONS[k])
     bd_set = float(bd['boundary_boost']) > 0.0
     if float(bd['boundary_boost']) < 0.0:
@@ -301,18 +368,23 @@ def make_loss(name, **options):
         raise ValueError('the boundary options (%s) need boundary_boost > 0' % ', '.join(bd_changed))
     if bd_set and 'boundary_width' in bd_changed and 'boundary_ratio' in bd_changed:
         raise ValueError('the boundary options boundary_width and boundary_ratio exclude each other')
-    if tv_set and 'tversky' not in name:
+    if tv_set and 'tversky' not in kinds:
         raise ValueError("the Tversky options do not apply to %r (use 'tversky' or 'ce+tversky')" % name)
-    if not is_set and not tv_set and not bd_set:
+    if sf_set and 'surface' not in kinds:
+        raise ValueError("the surface options do not apply to %r (use 'ce+surface', 'tversky+surface' or 'ce+tversky+surface')"
+                         % name)
+    if not is_set and not tv_set and not bd_set and not sf_set:
         return LOSSES[name]
-    if is_set and name in ('lovasz', 'tversky'):
+    if is_set and 'ce' not in kinds:
         raise ValueError("the cross-entropy options do not apply to %r (use 'ce', 'ce+lovasz' or 'ce+tversky')" % name)
-    if bd_set and name in ('lovasz', 'tversky'):
+    if bd_set and 'ce' not in kinds:
         raise ValueError("the boundary options do not apply to %r: they weight a cross-entropy term, and 'lovasz' and 'tversky' "
                          "have none (use 'ce', 'ce+lovasz' or 'ce+tversky')" % name)
     term_of = dict(_DEFAULT_TERMS)
-    if 'tversky' in name:
+    if 'tversky' in kinds:
         term_of['tversky'] = _tversky_term(**{k[len('tversky_'):]: v for k, v in tv.items()})
+    if sf_set:
+        term_of['surface'] = _surface_term(sf['surface_weight'], sf['surface_clip'])
     if is_set or bd_set:
         boundary = None
         if bd_set:

@@ -4,11 +4,13 @@ on the MI355X HIP path.
 
     python3 train.py data/<custom> [--epochs N] [-s W H] [-bs N] [-a ACC] [--lr LR] [--adam] [--resume]
                      [--weights F] [--notest] [--nosave] [--model unet|deeplabv3plus] [--augment | --augment-full | --augment-warps]
-                     [--loss ce|lovasz|ce+lovasz|tversky|ce+tversky] [--class-weights W0 W1 ...] [--label-smoothing E] [--focal-gamma G] [--ohem-keep R]
+                     [--loss ce|lovasz|ce+lovasz|tversky|ce+tversky|ce+surface|tversky+surface|ce+tversky+surface]
+                     [--class-weights W0 W1 ...] [--label-smoothing E] [--focal-gamma G] [--ohem-keep R]
                      [--tversky-alpha A] [--tversky-beta B] [--tversky-smooth S] [--tversky-power P] [--tversky-per-image]
                      [--tversky-all-classes] [--tversky-weight W]
                      [--boundary-boost A] [--boundary-loss-ratio R | --boundary-loss-width D] [--boundary-falloff flat|linear|gaussian]
                      [--boundary-sigma S]
+                     [--surface-weight W] [--surface-clip D] [--surface-ramp-epochs E]
                      [--weight-decay WD] [--momentum M] [--adamw] [--no-decay-norm-bias] [--backbone-lr-mult F]
                      [--clip-grad N] [--ema-decay D] [--schedule poly|cosine] [--warmup-steps N] [--min-lr LR]
     python3 -m torch.distributed.run --nproc-per-node <n> train.py data/<custom>        # RCCL data parallel
@@ -40,11 +42,26 @@ MODELS = {'deeplabv3plus': DeepLabV3Plus, 'unet': UNet, 'hrnet': HRNet}
 # what train() minimises: main() sets it from --loss (train()'s keyword surface is the reference's and stays as it is);
 # the validation loss test.py reports is cross-entropy whatever is chosen here
 LOSS_FN = compute_loss
+# --surface-ramp-epochs: the schedule behind the surface term's weight (SurfaceRamp), or None; train() hands it the Trainer
+SURFACE_RAMP = None
 # --class-weights as given, or None: train() checks their number against the data set's classes
 CLASS_WEIGHTS = None
 # optimiser recipe: Trainer keywords main() fills from --weight-decay ... --min-lr (optim_from_options); empty = the
 # Trainer's defaults, as before.  'total_steps' is worked out in train() once the loader's length is known.
 OPTIM = {}
+
+
+class SurfaceRamp:
+    """The surface term's weight as a zero-argument callable: W * min(1, (epoch + 1) / E) during the 0-based epoch of
+    `trainer` (Kervadec's rebalancing in its simplest form), W before a trainer is attached."""
+
+    def __init__(self, weight, epochs):
+        self.weight, self.epochs, self.trainer = float(weight), int(epochs), None
+
+    def __call__(self):
+        if self.trainer is None:
+            return self.weight
+        return self.weight * min(1.0, (self.trainer.epoch + 1) / self.epochs)
 
 
 def _loader(dataset, batch_size, num_workers, train=True):
@@ -79,6 +96,8 @@ def train(data_dir, epochs=100, img_size=(320, 320), batch_size=32, accumulate=2
         optim['total_steps'] = epochs * (len(train_fetcher) // max(1, accumulate))
     trainer = Trainer(model, train_fetcher, loss_fn=LOSS_FN, workdir='weights', accumulate=accumulate, adam=adam,
                       lr=lr, weights=weights, resume=resume, mixed_precision=mixed_precision, **optim)
+    if SURFACE_RAMP is not None:
+        SURFACE_RAMP.trainer = trainer
     use_ema = optim.get('ema_decay', 0.0) > 0
     last_loss = None
     while trainer.epoch < epochs:
@@ -128,10 +147,12 @@ def build_parser():
     ap.add_argument('--augment-warps', action='store_true',
                     help='--augment-full plus elastic, piecewise-affine and perspective warps of images and labels: '
                          'DeviceAugment.warps()')
-    ap.add_argument('--loss', choices=['ce', 'lovasz', 'ce+lovasz', 'tversky', 'ce+tversky'], default='ce',
+    ap.add_argument('--loss', choices=['ce', 'lovasz', 'ce+lovasz', 'tversky', 'ce+tversky', 'ce+surface', 'tversky+surface',
+                                       'ce+tversky+surface'], default='ce',
                     help='training objective: per-pixel cross-entropy, the Lovasz-softmax surrogate of the mean IoU '
                          '(classes present in the batch), or their sum; the soft Dice / Tversky / focal-Tversky '
-                         'region-overlap loss, or cross-entropy plus --tversky-weight times it')
+                         'region-overlap loss, or cross-entropy plus --tversky-weight times it; ...+surface adds '
+                         "--surface-weight times Kervadec's surface (boundary-distance) loss to any of these")
     ap.add_argument('--class-weights', type=float, nargs='+', default=None, metavar='W',
                     help='per-class weights of the cross-entropy, one value per class (ce and ce+lovasz)')
     ap.add_argument('--label-smoothing', type=float, default=0.0, metavar='E', help='label smoothing of the cross-entropy, in [0, 1)')
@@ -162,6 +183,12 @@ def build_parser():
                     help='how the extra weight decays from the contour to the edge of the band')
     ap.add_argument('--boundary-sigma', type=float, default=None, metavar='S',
                     help='sigma of the gaussian falloff in pixels (default: a third of the width)')
+    ap.add_argument('--surface-weight', type=float, default=None, metavar='W',
+                    help='...+surface: weight of the surface term, >= 0 (default 0.01)')
+    ap.add_argument('--surface-clip', type=float, default=None, metavar='D',
+                    help='limit the signed distance of the surface term to [-D, D] pixels (default 0: no limit)')
+    ap.add_argument('--surface-ramp-epochs', type=int, default=None, metavar='E',
+                    help='raise the surface weight linearly to W over the first E epochs: W * min(1, (epoch + 1) / E) (default 0: off)')
     ap.add_argument('--weight-decay', type=float, default=None, metavar='WD', help='weight decay (default 0)')
     ap.add_argument('--momentum', type=float, default=None, metavar='M', help='SGD momentum (default 0.9)')
     ap.add_argument('--adamw', action='store_true', help='decoupled weight decay (AdamW with --adam, SGDW without)')
@@ -208,7 +235,30 @@ def optim_from_options(opt):
 
 def loss_from_options(opt):
     """(loss_fn, class weights or None) of the parsed --loss / --class-weights / --label-smoothing / --focal-gamma /
-    --ohem-keep / --tversky-* / --boundary-*; with none of them given this is make_loss(opt.loss), as before"""
+    --ohem-keep / --tversky-* / --boundary-* / --surface-*; with none of them given this is make_loss(opt.loss), as before.
+    With --surface-ramp-epochs the surface weight is a SurfaceRamp, kept in SURFACE_RAMP for train() to attach the Trainer."""
+    global SURFACE_RAMP
+    SURFACE_RAMP = None
+    surface = {}
+    given = [flag for flag, v in (('--surface-weight', opt.surface_weight), ('--surface-clip', opt.surface_clip),
+                                  ('--surface-ramp-epochs', opt.surface_ramp_epochs)) if v is not None]
+    if given and 'surface' not in opt.loss:
+        raise ValueError("%s: the surface options do not apply to --loss %s (use 'ce+surface', 'tversky+surface' or "
+                         "'ce+tversky+surface')" % (', '.join(given), opt.loss))
+    if opt.surface_weight is not None:
+        if not opt.surface_weight >= 0:
+            raise ValueError('--surface-weight must be >= 0; got %g' % opt.surface_weight)
+        surface['surface_weight'] = opt.surface_weight
+    if opt.surface_clip is not None:
+        if not opt.surface_clip >= 0:
+            raise ValueError('--surface-clip must be >= 0; got %g' % opt.surface_clip)
+        surface['surface_clip'] = opt.surface_clip
+    if opt.surface_ramp_epochs is not None:
+        if opt.surface_ramp_epochs < 0:
+            raise ValueError('--surface-ramp-epochs must be >= 0; got %d' % opt.surface_ramp_epochs)
+        if opt.surface_ramp_epochs > 0:
+            SURFACE_RAMP = SurfaceRamp(surface.get('surface_weight', 0.01), opt.surface_ramp_epochs)
+            surface['surface_weight'] = SURFACE_RAMP
     boundary = {'boundary_boost': opt.boundary_boost, 'boundary_falloff': opt.boundary_falloff}
     if opt.boundary_loss_ratio is not None:
         boundary['boundary_ratio'] = opt.boundary_loss_ratio
@@ -224,7 +274,7 @@ def loss_from_options(opt):
                      focal_gamma=opt.focal_gamma, keep_ratio=opt.ohem_keep, tversky_alpha=opt.tversky_alpha,
                      tversky_beta=opt.tversky_beta, tversky_smooth=opt.tversky_smooth, tversky_power=opt.tversky_power,
                      tversky_per_image=opt.tversky_per_image, tversky_all_classes=opt.tversky_all_classes,
-                     tversky_weight=opt.tversky_weight, **boundary), opt.class_weights
+                     tversky_weight=opt.tversky_weight, **boundary, **surface), opt.class_weights
 
 
 def main():
