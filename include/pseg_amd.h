@@ -65,7 +65,8 @@ extern "C" {
  * pseg_grad_sumsq_workspace_bytes, pseg_grad_sumsq, pseg_opt_step_sgd, pseg_opt_step_adam, and the contour-measure calls
  * pseg_label_depth, pseg_boundary_counts_workspace_bytes, pseg_boundary_counts, and the outline calls
  * pseg_mask_rings_workspace_bytes, pseg_mask_rings, and the dense-CRF calls pseg_crf_workspace_bytes, pseg_crf_refine, and
- * the surface-loss calls pseg_class_sdist_workspace_bytes, pseg_class_sdist, pseg_surface_workspace_bytes, pseg_surface_fwd_bwd) are purely
+ * the surface-loss calls pseg_class_sdist_workspace_bytes, pseg_class_sdist, pseg_surface_workspace_bytes, pseg_surface_fwd_bwd,
+ * and the surface-distance calls pseg_hausdorff_workspace_bytes, pseg_hausdorff_stats) are purely
  * additive and do not bump it: the loader checks every declared prototype against the library's exports by name. */
 #define PSEG_ABI_VERSION 14
 int pseg_abi_version(void);
@@ -901,6 +902,51 @@ int64_t pseg_surface_workspace_bytes(int B, int C, int64_t HW);
 int pseg_surface_fwd_bwd(const float* logits, const int64_t* target, const int32_t* sdist, int B, int C, int64_t HW,
                          int64_t ignore_index, float clip, float* dlogits, float* out, void* workspace,
                          int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ surface-distance evaluation (csrc/hausdorff.hip)
+ * The record behind the Hausdorff distance (HD), its percentile (HD95), the average symmetric surface distance (ASSD) and the
+ * surface Dice at a tolerance (NSD), per image and class, from two label maps.  These entry points are additive:
+ * PSEG_ABI_VERSION does not move.
+ *
+ * pred, target: int64 [B][H][W]; C classes.
+ * Void.  A pixel whose target is outside [0, C) is void, and its prediction counts as void too (the rule of
+ *   pseg_boundary_counts); a prediction outside [0, C) is void.  A void pixel is in no class mask.
+ * Masks and border.  For image b and class c, P = (pred == c, not void) and G = (target == c).  The border dM of a mask M is the
+ *   set of its pixels with at least one of the four edge neighbours not in M; a neighbour outside the image counts as not in M
+ *   (M & ~binary_erosion(M, cross) with a zero border: the edge rule of medpy and MONAI; unlike pseg_class_sdist, the image
+ *   border is a contour).
+ * Directed distance sets.  D(P->G) holds, for every p in dP, min over q in dG of |p - q|^2: an exact integer, in pixels
+ *   squared, no spacing.  D(G->P) is the same the other way round.
+ * Record.  stats int64 [B][C][8], sums double [B][C][2]:
+ *   stats[0], [1]   n_p = |dP|, n_g = |dG|
+ *   stats[2], [3]   the maximum of D(P->G), of D(G->P)
+ *   stats[4], [5]   the nearest-rank quantile of each: its k-th smallest element, k = (n * permille + 999) / 1000 in integer
+ *                   division (permille = 1000: the maximum)
+ *   stats[6], [7]   the number of elements <= tol * tol in each
+ *   sums[0], [1]    the sum of sqrt(d2) over each multiset, in double
+ *   If n_p == 0 or n_g == 0 the distances are undefined: stats[2..5] = -1, stats[6], [7] = 0 and both sums are 0.
+ *   permille: an int in [1, 1000]; tol: an int in [0, 255] pixels.
+ *   From the record (utils.compute_surface_metrics): HD = sqrt(max(stats[2], stats[3])), HD95 = sqrt(max(stats[4], stats[5])),
+ *   ASSD = (sums[0] / n_p + sums[1] / n_g) / 2 where n_p > 0 and n_g > 0; NSD = (stats[6] + stats[7]) / (n_p + n_g) where
+ *   n_p + n_g > 0.
+ * The integer fields are exact.  The sums are added from per-block double partials in a fixed order, without floating-point
+ * atomics (integer atomics only): two calls on the same input give the same bits.  No host synchronisation.
+ * How: the border pixels of both maps are marked and counted per (image, class); only a class with a border in both maps of an
+ * image gets any further work.  For those, a column sweep leaves the distance along the column to the nearest border pixel, and
+ * a row pass (Meijster's lower-envelope scan: work bounded by the row's length whatever the distances are, a lane per row, the
+ * stack inside the row's own LDS words) gives the squared distance, kept only at the other map's border pixels.  The quantile is
+ * a four-round segmented radix select over all (image, class, direction) segments at once.
+ *
+ * pseg_hausdorff_workspace_bytes(B, C, H, W): bytes of the workspace; 0 for sizes that are refused.  It holds 4 C bytes per pixel
+ *   (an int16 plane per class and map), 12 bytes per pixel, about 2 KiB per (image, class) and 8 bytes per block of the row pass.
+ * pseg_hausdorff_stats: refused with PSEG_ERR_ARG before any launch, with a message that starts "pseg_hausdorff_stats:": B, H
+ *   or W below 1, H or W above 16384 (so H^2 + W^2 <= 2^29 fits), C outside [1, 1024], a workspace buffer at or above 2 GiB
+ *   (B * C * H * W * 4 or B * C * 2048 at or above 2 GiB: refused, not chunked), permille outside [1, 1000], tol outside [0, 255],
+ *   null pred / target / stats / sums / workspace, a workspace below pseg_hausdorff_workspace_bytes(B, C, H, W) or not 16-byte
+ *   aligned.  Nothing outside the buffers named by the arguments is touched. */
+int64_t pseg_hausdorff_workspace_bytes(int B, int C, int H, int W);
+int pseg_hausdorff_stats(const int64_t* pred, const int64_t* target, int B, int H, int W, int C, int permille, int tol,
+                         int64_t* stats, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ training augmentation (csrc/augment.hip)
  * The geometric and colour-affine part of the reference's online augmentation (utils/datasets.py:26-125, imgaug on the

@@ -13,7 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 LIB = os.path.join(PKG, 'libpseg_amd.so')
-SOURCES = ['conv_gather.hip', 'conv_wgrad.hip', 'core.hip', 'conv_half_gather.hip', 'conv_half_wgrad.hip', 'norm_act.hip', 'pool_resize.hip', 'loss.hip', 'optim.hip', 'dwconv.hip', 'lanes.hip', 'comm.hip', 'diag.hip', 'infer.hip', 'augment.hip', 'lovasz.hip', 'ce_opts.hip', 'regions.hip', 'tversky.hip', 'boundary.hip', 'polygons.hip', 'crf.hip', 'surface.hip']
+SOURCES = ['conv_gather.hip', 'conv_wgrad.hip', 'core.hip', 'conv_half_gather.hip', 'conv_half_wgrad.hip', 'norm_act.hip', 'pool_resize.hip', 'loss.hip', 'optim.hip', 'dwconv.hip', 'lanes.hip', 'comm.hip', 'diag.hip', 'infer.hip', 'augment.hip', 'lovasz.hip', 'ce_opts.hip', 'regions.hip', 'tversky.hip', 'boundary.hip', 'polygons.hip', 'crf.hip', 'surface.hip', 'hausdorff.hip']
 HEADERS = ['common.h', 'conv_common.h', 'conv_limb.h', 'conv_half.h', 'half_io.h', 'loss_common.h', os.path.join('..', '..', 'include', 'pseg_amd.h')]
 ARCH = 'gfx950'
 

@@ -1691,6 +1691,44 @@ def class_sdist(labels, num_classes):
     return out
 
 
+# the surface-distance records' planes, border maps and histograms: a buffer of its own, like the distance transform's
+hausdorff_workspace = _Workspace()
+HAUSDORFF_MAX_IMAGES = None  # images per call of hausdorff_stats; None: as many as the workspace query accepts (tests force chunks)
+
+
+def hausdorff_stats(pred, target, num_classes, permille=950, tol=2):
+    """The surface-distance record of every image and class (pseg_hausdorff_stats): pred, target int64 [B, H, W] ->
+    (stats int64 [B, C, 8], sums float64 [B, C, 2]): the sizes of the two borders, the maximum, the nearest-rank permille
+    quantile and the number within tol pixels of the squared border-to-border distances in either direction, and the sums of
+    the distances (layout: include/pseg_amd.h).  Records are per image, so a batch that the workspace query refuses is walked
+    in chunks of images; only a single image that is refused raises."""
+    _label_map('hausdorff_stats', pred)
+    _label_map('hausdorff_stats', target)
+    assert pred.shape == target.shape and pred.device == target.device, 'hausdorff_stats: pred %s / target %s' % (
+        tuple(pred.shape), tuple(target.shape))
+    B, H, W = pred.shape
+    C, permille, tol = int(num_classes), int(permille), int(tol)
+    if not 1 <= permille <= 1000:
+        raise ValueError('hausdorff_stats: permille must be in [1, 1000]; got %d' % permille)
+    if not 0 <= tol <= 255:
+        raise ValueError('hausdorff_stats: tol must be in [0, 255]; got %d' % tol)
+    n = B if HAUSDORFF_MAX_IMAGES is None else max(1, min(B, int(HAUSDORFF_MAX_IMAGES)))
+    while n > 1 and _lib.query('pseg_hausdorff_workspace_bytes', n, C, H, W) <= 0:
+        n = (n + 1) // 2
+    if _lib.query('pseg_hausdorff_workspace_bytes', n, C, H, W) <= 0:
+        raise ValueError('hausdorff_stats: an image of %d x %d with %d classes is out of range (H, W <= %d, 1 <= C <= 1024, '
+                         'the planes of one image below 2 GiB)' % (H, W, C, SDIST_MAX_SIDE))
+    stats = torch.empty(B, C, 8, dtype=torch.int64, device=pred.device)
+    sums = torch.empty(B, C, 2, dtype=torch.float64, device=pred.device)
+    for b0 in range(0, B, n):
+        nb = min(n, B - b0)
+        nbytes = _lib.query('pseg_hausdorff_workspace_bytes', nb, C, H, W)
+        ws = hausdorff_workspace.get(nbytes, pred.device)
+        _lib.call('pseg_hausdorff_stats', pred[b0:b0 + nb].data_ptr(), target[b0:b0 + nb].data_ptr(), nb, H, W, C, permille, tol,
+                  stats[b0:b0 + nb].data_ptr(), sums[b0:b0 + nb].data_ptr(), ws.data_ptr(), nbytes, _stream())
+    return stats, sums
+
+
 # ---------------------------------------------------------------------------------------------- optimiser
 def sgd_step(param, grad, mbuf, lr, momentum, weight_decay, nesterov, grad_scale, first_step):
     _lib.call('pseg_sgd_step', param.data_ptr(), grad.data_ptr(), _ptr(mbuf), param.numel(), float(lr), float(momentum),

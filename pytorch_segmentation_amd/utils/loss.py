@@ -548,3 +548,43 @@ def compute_boundary_metrics(counters):
     inter, gband, pband, tp, fn, fp = (c.float() for c in counters.detach().cpu())
 
     return inter / _guarded(gband + pband - inter), tp / _guarded(tp + fn + fp)
+
+
+SURFACE_ROWS = 7             # images defined, sum of HD, of HD95, of ASSD, images with an NSD, sum of NSD, misses
+
+
+def update_surface_stats(acc, predicted, targets, permille=950, tol=2):
+    """Accumulate the surface-distance metrics of a batch into the float64 device tensor acc[7][C] (rows: images where the
+    class has a border in both maps, the sums of their HD, HD95 and ASSD, images where it has one in either map, the sum of
+    their NSD, and the misses: images where it has one in exactly one map).  predicted, targets: [B, H, W]; permille: the
+    quantile of HD95 in thousandths; tol: the NSD tolerance in pixels.  One call of ops.hausdorff_stats and torch ops on its
+    [B, C] records: no host synchronisation."""
+    assert acc.dtype == torch.float64 and acc.dim() == 2 and acc.shape[0] == SURFACE_ROWS, \
+        'update_surface_stats: the accumulator is float64 [7][C]'
+    stats, sums = ops.hausdorff_stats(predicted.to(torch.int64).contiguous(),
+                                      targets.to(device=predicted.device, dtype=torch.int64).contiguous(), acc.shape[1],
+                                      permille, tol)
+    s = stats.double()
+    n_p, n_g = s[..., 0], s[..., 1]
+    defined = (n_p > 0) & (n_g > 0)
+    has_nsd = (n_p + n_g) > 0
+    one, zero = torch.ones_like(n_p), torch.zeros_like(n_p)
+    hd = torch.where(defined, torch.maximum(s[..., 2], s[..., 3]).clamp(min=0).sqrt(), zero)
+    hd95 = torch.where(defined, torch.maximum(s[..., 4], s[..., 5]).clamp(min=0).sqrt(), zero)
+    assd = torch.where(defined, (sums[..., 0] / torch.where(defined, n_p, one) + sums[..., 1] / torch.where(defined, n_g, one)) / 2,
+                       zero)
+    nsd = torch.where(has_nsd, (s[..., 6] + s[..., 7]) / torch.where(has_nsd, n_p + n_g, one), zero)
+    acc += torch.stack([defined.double().sum(0), hd.sum(0), hd95.sum(0), assd.sum(0), has_nsd.double().sum(0), nsd.sum(0),
+                        (has_nsd & ~defined).double().sum(0)])
+    return acc
+
+
+def compute_surface_metrics(acc):
+    """acc[7][C] -> (hd, hd95, assd, nsd, misses) as float64 [C] host tensors: every class's mean over the images that define
+    the value (an image where only one map has the class is a miss: it enters nsd as 0 and none of the distances), NaN where
+    no image does; misses is the count."""
+    acc = acc.detach().cpu().double()
+    nan = torch.full_like(acc[0], float('nan'))
+    hd, hd95, assd = (torch.where(acc[0] > 0, acc[i] / acc[0].clamp(min=1), nan) for i in (1, 2, 3))
+    nsd = torch.where(acc[4] > 0, acc[5] / acc[4].clamp(min=1), nan)
+    return hd, hd95, assd, nsd, acc[6].clone()

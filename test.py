@@ -5,6 +5,7 @@
                     [--scales S [S ...]] [--flip] [--min-area N] [--connectivity {4,8}] [--largest-only]
                     [--window W H [--stride SW SH]] [--ema] [--boundary [RATIO] | --boundary-width D]
                     [--crf [--crf-radius R] [--crf-dilation D] [--crf-iters T] [--crf-theta A B G] [--crf-weights WA WS]]
+                    [--surface-distance [--hd-percentile P] [--surface-tolerance T]]
 
 `test(model, fetcher)` keeps the reference's contract: evaluates in eval mode without gradients, prints per-class
 (or the five worst classes') targets / precision / recall / IoU / F1 and returns the mean IoU.  The per-class
@@ -23,6 +24,11 @@ summary line and two more columns per class row are printed; everything else, th
 With --crf the logits of every forward of the route in use -- plain, --scales / --flip, --window -- are refined by the local
 dense CRF (utils/crf.py, csrc/crf.hip), guided by that forward's inputs, before the prediction is made; --boundary shows what
 it does to the contours.  The printed loss stays that of the unrefined plain forward.
+With --surface-distance the counted prediction -- whichever route made it -- is also scored by the distances between its
+contours and the target's, per image and class (utils.update_surface_stats, csrc/hausdorff.hip): the Hausdorff distance, its
+--hd-percentile (default 95), the average symmetric surface distance and the surface Dice within --surface-tolerance pixels
+(default 2), each class's value the mean over the images that define it.  One more summary line and four more columns per
+class row are printed; it composes with --boundary, and everything else, the returned mean IoU included, stays.
 """
 import argparse
 
@@ -42,12 +48,22 @@ MODELS = {'deeplabv3plus': DeepLabV3Plus, 'unet': UNet, 'hrnet': HRNet}
 
 @torch.no_grad()
 def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, largest_only=False, window=None, stride=None,
-         boundary=None, boundary_width=None, results=None, crf=None):
+         boundary=None, boundary_width=None, results=None, crf=None, surface_distance=False, hd_percentile=95.0,
+         surface_tolerance=2):
     """boundary (a ratio of the target's diagonal) or boundary_width (pixels): also count Boundary IoU and trimap IoU on the
     prediction that is scored.  results: a dict that receives 'boundary_iou' and 'trimap_iou' ([C] tensors),
     'boundary_counters' (int64 [6][C], summed over the ranks) and 'boundary_widths' (the sorted widths used).
     crf (None, True, a utils.crf.CRF or a dict of its options): the counted prediction of every route is made from logits
-    refined by the local dense CRF, guided by the inputs of the forward that gave them; the loss stays the plain forward's."""
+    refined by the local dense CRF, guided by the inputs of the forward that gave them; the loss stays the plain forward's.
+    surface_distance: also score the counted prediction by HD, HD at hd_percentile (percent, one decimal at most), ASSD and
+    the surface Dice within surface_tolerance pixels; results receives 'hd', 'hd95', 'assd', 'nsd', 'surface_misses' (float64
+    [C], NaN where no image defines the value) and 'surface_stats' (the float64 [7][C] accumulator, summed over the ranks)."""
+    permille = None
+    if surface_distance:
+        from pytorch_segmentation_amd.utils import compute_surface_metrics, update_surface_stats
+        permille = hd_permille(hd_percentile)
+        if not 0 <= surface_tolerance <= 255 or int(surface_tolerance) != surface_tolerance:
+            raise ValueError('surface_tolerance must be an integer in [0, 255]; got %r' % (surface_tolerance,))
     refine = None
     if crf is not None and crf is not False:
         from pytorch_segmentation_amd.utils.crf import CRF
@@ -80,6 +96,7 @@ def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, la
         raise ValueError('mask cleanup handles at most 256 classes; the dataset has %d' % nc)
     counters = None
     bcounters, widths = None, set()
+    sacc = None
     loss_sum, batches = None, 0
     for inputs, targets in fetcher:
         if window is not None:                                 # sliding windows of (w, h) over the delivered batch
@@ -114,6 +131,10 @@ def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, la
             width = band_width(targets.shape[1:], boundary) if boundary_width is None else boundary_width
             widths.add(width)
             update_boundary_counts(bcounters, predicted, targets, width)
+        if surface_distance:
+            if sacc is None:
+                sacc = torch.zeros(7, nc, dtype=torch.float64, device=outputs.device)
+            update_surface_stats(sacc, predicted, targets, permille, int(surface_tolerance))
     if counters is None:
         return 0.0
     all_reduce_counters(counters)
@@ -127,6 +148,13 @@ def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, la
         print('boundary iou: %8g, trimap iou: %8g, width: %s' % (biou.mean(), tiou.mean(), ' '.join(map(str, sorted(widths)))))
         if results is not None:
             results.update(boundary_iou=biou, trimap_iou=tiou, boundary_counters=bcounters.cpu(), boundary_widths=sorted(widths))
+    if surface_distance:
+        all_reduce_counters(sacc)
+        hd, hd95, assd, nsd, misses = compute_surface_metrics(sacc)
+        print('hd: %8g, hd%g: %8g, assd: %8g, nsd@%d: %8g, misses: %d'
+              % (nanmean(hd), permille / 10, nanmean(hd95), nanmean(assd), surface_tolerance, nanmean(nsd), misses.sum()))
+        if results is not None:
+            results.update(hd=hd, hd95=hd95, assd=assd, nsd=nsd, surface_misses=misses, surface_stats=sacc.cpu())
     if nc < 10:
         order = range(nc)
     else:
@@ -134,8 +162,24 @@ def test(model, fetcher, scales=None, flip=False, min_area=0, connectivity=8, la
         order = torch.argsort(miou)[:5].tolist()
     for c in order:
         line = row % (classes[c], T[c], P[c], R[c], miou[c], F1[c])
-        print(line + ', biou: %8g, trimap: %8g' % (biou[c], tiou[c]) if contours else line)
+        line = line + ', biou: %8g, trimap: %8g' % (biou[c], tiou[c]) if contours else line
+        print(line + ', hd: %8g, hd%g: %8g, assd: %8g, nsd: %8g' % (hd[c], permille / 10, hd95[c], assd[c], nsd[c])
+              if surface_distance else line)
     return miou.mean().item()
+
+
+def hd_permille(percent):
+    """--hd-percentile in percent, one decimal at most -> thousandths in [1, 1000]"""
+    permille = int(round(float(percent) * 10))
+    if abs(float(percent) * 10 - permille) > 1e-6 or not 1 <= permille <= 1000:
+        raise ValueError('hd_percentile must be in [0.1, 100] with at most one decimal; got %r' % (percent,))
+    return permille
+
+
+def nanmean(v):
+    """the mean over the classes that have a value; NaN when none has"""
+    have = ~torch.isnan(v)
+    return (v[have].mean() if have.any() else torch.tensor(float('nan'))).item()
 
 
 def checkpoint_weights(checkpoint, ema=False, path='the checkpoint'):
@@ -184,7 +228,25 @@ def parse_args(argv=None):
                     help='with --crf: theta_alpha, theta_beta, theta_gamma (default 8 13 3)')
     ap.add_argument('--crf-weights', type=float, nargs=2, default=None, metavar=('WA', 'WS'),
                     help='with --crf: appearance and smoothness weights in logit units (default 4 3)')
+    ap.add_argument('--surface-distance', action='store_true',
+                    help='also report the Hausdorff distance, its percentile, the average symmetric surface distance and the '
+                         'surface Dice of the counted prediction, per image and class')
+    ap.add_argument('--hd-percentile', type=float, default=None, metavar='P',
+                    help='with --surface-distance: the percentile of the Hausdorff distance, in (0, 100] with one decimal at '
+                         'most (default 95)')
+    ap.add_argument('--surface-tolerance', type=int, default=None, metavar='T',
+                    help='with --surface-distance: the surface Dice tolerance in pixels, 0 .. 255 (default 2)')
     opt = ap.parse_args(argv)
+    if not opt.surface_distance and (opt.hd_percentile is not None or opt.surface_tolerance is not None):
+        ap.error('--hd-percentile and --surface-tolerance need --surface-distance')
+    opt.hd_percentile = 95.0 if opt.hd_percentile is None else opt.hd_percentile
+    opt.surface_tolerance = 2 if opt.surface_tolerance is None else opt.surface_tolerance
+    try:
+        hd_permille(opt.hd_percentile)
+    except ValueError:
+        ap.error('--hd-percentile must be in [0.1, 100] with at most one decimal')
+    if not 0 <= opt.surface_tolerance <= 255:
+        ap.error('--surface-tolerance must be in [0, 255]')
     crf_flags = (opt.crf_radius, opt.crf_dilation, opt.crf_iters, opt.crf_theta, opt.crf_weights)
     if not opt.crf and any(v is not None for v in crf_flags):
         ap.error('--crf-radius, --crf-dilation, --crf-iters, --crf-theta and --crf-weights need --crf')
@@ -217,7 +279,9 @@ def main(argv=None):
     elif opt.ema:
         raise ValueError('--ema needs --weights')
     metrics = test(model.cuda(), fetcher, opt.scales, opt.flip, opt.min_area, opt.connectivity,
-                   opt.largest_only, opt.window, opt.stride, opt.boundary, opt.boundary_width, crf=opt.crf_options)
+                   opt.largest_only, opt.window, opt.stride, opt.boundary, opt.boundary_width, crf=opt.crf_options,
+                   surface_distance=opt.surface_distance, hd_percentile=opt.hd_percentile,
+                   surface_tolerance=opt.surface_tolerance)
     print('metrics: %8g' % metrics)
     return metrics
 
