@@ -1052,6 +1052,67 @@ int pseg_augment_batch_warp(const uint8_t* img, const uint8_t* seg, const float*
                             float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh, int ow,
                             int64_t* target, void* stream);
 
+/* pseg_augment_batch_blend: pseg_augment_batch_warp with a median window, a second filter blended in by a mask, a second
+ * colour matrix blended in by a mask, and a hue / saturation shift (the reference's MedianBlur, BlendAlphaSimplexNoise over
+ * EdgeDetect / DirectedEdgeDetect, BlendAlphaFrequencyNoise over Multiply / LinearContrast, AddToHueAndSaturation).
+ * Arguments are pseg_augment_batch_warp's, except shape_host: HOST int [B][5] = {K, mh, mw, kmed, K2} of each row, which the
+ * entry point validates and sizes LDS from; they must equal the rows'.  The kernel clamps what it reads from the row so that
+ * a table that disagrees still touches nothing but img, seg, its row and its own LDS.  params: fp32 [B][PSEG_AUGMENT_BLEND_ROW]:
+ *   [0..251]    pseg_augment_batch_warp's row, verbatim
+ *   [252]       kmed, the median window: 0 = none, otherwise odd, 3 .. PSEG_AUGMENT_BLEND_KMEDMAX
+ *   [253]       K2, the size of the second filter G: 0 = no edge blend, otherwise odd, 3 .. PSEG_AUGMENT_BLEND_K2MAX
+ *   [254]       != 0: the colour blend is on
+ *   [255] [256] dh, the hue shift in sixths of the colour circle, and ds, the saturation shift as a fraction; the stage is
+ *               skipped when either is NaN / infinite or both are 0
+ *   [257..259]  reserved, ignored
+ *   [260..271]  the second colour matrix Mb, 3 x 4 row-major, as [6..17]
+ *   [272..496]  K2 x K2 weights of G, row-major with row length K2
+ *   [497..499]  reserved, ignored
+ *   [500..755]  mask table T1 (edge blend), 16 x 16 row-major        [756..1011] mask table T2 (colour blend), likewise
+ * Image, per sample on the H x W working grid, each stage rounded to 8 bits half up and saturated (round_u8):
+ *   1. the warp, exactly pseg_augment_batch_warp's;
+ *   2. median (kmed >= 3), per plane: element (kmed^2 - 1) / 2 of the sorted values of the kmed x kmed window of stage-1 values;
+ *      window indices reflect as the filter's (-1 -> 1, H -> H - 2, repeatedly when the window is wider than the grid).  Like
+ *      the warp it is a function of the working-grid pixel: stage 3 reads it beyond the grid at the REFLECTED pixel's index;
+ *   3. filter and edge blend over stage-2 values (stage-1 values when kmed = 0): y = round_u8(F), pseg_augment_batch_nbhd's
+ *      correlation with the K x K weights at [40..] (K <= 1: y is the input); with K2 >= 3, e = round_u8(G) by the same
+ *      correlation and reflection with the weights at [272..], and the result is round_u8(fmaf(m1, e - y, y)), m1 = the sample
+ *      of T1 at this pixel;
+ *   4. colour: qa = round_u8(M v) as pseg_augment_batch; with [254] != 0, qb = round_u8(Mb v) and the result is
+ *      round_u8(fmaf(m2, qa - qb, qb)), m2 = the sample of T2;
+ *   5. hue and saturation, on the stage-4 integers r, g, b in fp32 with correctly rounded divisions: mx = max, mn = min,
+ *      d = mx - mn; s = mx > 0 ? d / mx : 0; the hue h in [0, 6): 0 when d == 0, else (g - b) / d (+ 6 if negative) when
+ *      mx == r, else 2 + (b - r) / d when mx == g, else 4 + (r - g) / d; h' = h + dh, h' -= 6 floorf(h' / 6), taken as 0 when
+ *      it lands on 6 (or, under an absurd dh, anywhere outside [0, 6)); s' = clamp(s + ds, 0, 1); i = min((int)h', 5),
+ *      f = h' - i; p = mx (1 - s'), q = mx (1 - s' f), t = mx (1 - s' (1 - f)); (r, g, b) = (mx, t, p), (q, mx, p), (p, mx, t),
+ *      (p, q, mx), (t, p, mx), (mx, p, q) for i = 0..5; each rounded with round_u8;
+ *   6. noise, dropout, (q - mean_c) / std_c and the multi-scale index, exactly pseg_augment_batch_warp's.
+ * Mask sample of table T at working-grid pixel (x, y): gx = clamp(fmaf((float)x + 0.5f, 16.f / (float)W, -0.5f), 0, 15),
+ * i0 = min((int)gx, 14), fu = gx - i0; gy, j0, fv likewise with H; t = fmaf(fu, T[j0][i0+1] - T[j0][i0], T[j0][i0]), b the same
+ * on row j0 + 1, m = fmaf(fv, b - t, t), clamped to [0, 1], a NaN counting as 0.  The clamp of gx comes before the float -> int
+ * conversion: no index leaves the table.
+ * Labels are pseg_augment_batch_warp's: stages 2 to 5 never touch them.  A row with kmed = 0, K2 = 0, [254] = 0 and
+ * dh = ds = 0 gives pseg_augment_batch_warp's output bit for bit; T1 all 0 gives the bits of the same row with K2 = 0, T1 all 1
+ * those of a row whose F is G with no blend; T2 all 1 gives the bits of the row with M alone, T2 all 0 those of a row with Mb
+ * in M's place.  Dynamic LDS, 4 bytes per pixel: the span of a 32 x 8 output tile plus a halo of kmed/2 + max(K/2, K2/2) (at
+ * most 12) for stage 1 and, with a median, a second tile with a halo of max(K/2, K2/2) for stage 2, for the sample of the
+ * launch that needs most; refused above 64 KiB. */
+#define PSEG_AUGMENT_BLEND_ROW 1012
+#define PSEG_AUGMENT_BLEND_KMEDMAX 11
+#define PSEG_AUGMENT_BLEND_K2MAX 15
+#define PSEG_AUGMENT_BLEND_KMED 252
+#define PSEG_AUGMENT_BLEND_K2 253
+#define PSEG_AUGMENT_BLEND_COLOUR_ON 254
+#define PSEG_AUGMENT_BLEND_HUE 255
+#define PSEG_AUGMENT_BLEND_MB 260
+#define PSEG_AUGMENT_BLEND_WEIGHTS2 272
+#define PSEG_AUGMENT_BLEND_T1 500
+#define PSEG_AUGMENT_BLEND_T2 756
+#define PSEG_AUGMENT_BLEND_TABLE 16
+int pseg_augment_batch_blend(const uint8_t* img, const uint8_t* seg, const float* params, const int* shape_host, int B, int H, int W,
+                             float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh, int ow,
+                             int64_t* target, void* stream);
+
 /* ------------------------------------------------------------------ optimiser (flat parameter arena)
  * One launch over the whole arena; grad_scale folds the 1/world_size of the data-parallel mean
  * (README.md:42-44, train.py:112-117) and the 1/accumulate of gradient accumulation (train.py:65).

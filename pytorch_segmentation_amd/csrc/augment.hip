@@ -235,9 +235,94 @@ __device__ __forceinline__ void aug_warp(const uint8_t* __restrict__ p, const fl
   }
 }
 
-// one kernel for pseg_augment_batch_nbhd (kWarp = false) and pseg_augment_batch_warp (true): they differ in the row length and
-// in aug_coord, which the halo fill evaluates at the REFLECTED pixel's index and the label blocks on [H, W]
-template <bool kWarp>
+// pseg_augment_batch_blend's stages (kBlend; contract: include/pseg_amd.h).  The sample of a 16 x 16 mask table at working-grid
+// pixel (x, y): the clamp comes before the float -> int conversion, so the four loads stay inside the table
+__device__ __forceinline__ float aug_mask(const float* __restrict__ T, int x, int y, int H, int W) {
+  const float gx = fminf(fmaxf(fmaf((float)x + 0.5f, 16.f / (float)W, -0.5f), 0.f), 15.f);
+  const float gy = fminf(fmaxf(fmaf((float)y + 0.5f, 16.f / (float)H, -0.5f), 0.f), 15.f);
+  const int i0 = clampi((int)gx, 14), j0 = clampi((int)gy, 14);
+  const float fu = gx - (float)i0, fv = gy - (float)j0;
+  const float* __restrict__ n = T + PSEG_AUGMENT_BLEND_TABLE * j0 + i0;
+  const float t = fmaf(fu, n[1] - n[0], n[0]);
+  const float b = fmaf(fu, n[PSEG_AUGMENT_BLEND_TABLE + 1] - n[PSEG_AUGMENT_BLEND_TABLE], n[PSEG_AUGMENT_BLEND_TABLE]);
+  const float m = fmaf(fv, b - t, t);
+  return m > 0.f ? (m < 1.f ? m : 1.f) : 0.f;             // NaN -> 0
+}
+
+// K x K correlation over a packed tile, the accumulation order of pseg_augment_batch_nbhd; win: the window's top-left tap
+__device__ __forceinline__ void aug_correlate(const uint32_t* __restrict__ win, int stride, int K, const float* __restrict__ wt, float v[3]) {
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+  for (int j = 0; j < K; ++j) {
+    for (int i = 0; i < K; ++i) {
+      const float wji = wt[j * K + i];
+      const uint32_t px = win[j * stride + i];
+      a0 = fmaf(wji, (float)(px & 0xffu), a0);
+      a1 = fmaf(wji, (float)((px >> 8) & 0xffu), a1);
+      a2 = fmaf(wji, (float)((px >> 16) & 0xffu), a2);
+    }
+  }
+  v[0] = round_u8(a0), v[1] = round_u8(a1), v[2] = round_u8(a2);
+}
+
+// the median of the k x k window of packed pixels, three planes at once: bisection on the 8-bit value, eight rounds of
+// counting the taps <= mid per plane (no per-thread array, no scratch); rank = (k * k - 1) / 2
+__device__ __forceinline__ uint32_t aug_median(const uint32_t* __restrict__ win, int stride, int k) {
+  const int need = (k * k - 1) / 2 + 1;
+  int lo0 = 0, lo1 = 0, lo2 = 0, hi0 = 255, hi1 = 255, hi2 = 255;
+#pragma unroll 1
+  for (int round = 0; round < 8; ++round) {
+    const int m0 = (lo0 + hi0) >> 1, m1 = (lo1 + hi1) >> 1, m2 = (lo2 + hi2) >> 1;
+    int c0 = 0, c1 = 0, c2 = 0;
+    for (int j = 0; j < k; ++j) {
+      for (int i = 0; i < k; ++i) {
+        const uint32_t px = win[j * stride + i];
+        c0 += (int)(px & 0xffu) <= m0;
+        c1 += (int)((px >> 8) & 0xffu) <= m1;
+        c2 += (int)((px >> 16) & 0xffu) <= m2;
+      }
+    }
+    if (c0 >= need) hi0 = m0; else lo0 = m0 + 1;
+    if (c1 >= need) hi1 = m1; else lo1 = m1 + 1;
+    if (c2 >= need) hi2 = m2; else lo2 = m2 + 1;
+  }
+  return (uint32_t)lo0 | ((uint32_t)lo1 << 8) | ((uint32_t)lo2 << 16);
+}
+
+// stage 5 of pseg_augment_batch_blend on the 8-bit values q[3]
+__device__ __forceinline__ void aug_hue_sat(float q[3], float dh, float ds) {
+  const float r = q[0], g = q[1], b = q[2];
+  const float mx = fmaxf(r, fmaxf(g, b)), mn = fminf(r, fminf(g, b)), d = mx - mn;
+  const float s = mx > 0.f ? d / mx : 0.f;
+  float h = 0.f;
+  if (d != 0.f) {
+    if (mx == r) {
+      h = (g - b) / d;
+      h = h < 0.f ? h + 6.f : h;
+    } else if (mx == g) {
+      h = 2.f + (b - r) / d;
+    } else {
+      h = 4.f + (r - g) / d;
+    }
+  }
+  float hp = h + dh;
+  hp -= 6.f * floorf(hp / 6.f);
+  if (!(hp >= 0.f && hp < 6.f)) hp = 0.f;                  // lands on 6; or a dh so large that the wrap is all rounding error
+  const float sp = fminf(fmaxf(s + ds, 0.f), 1.f);
+  const int i = min((int)hp, 5);
+  const float f = hp - (float)i;
+  const float p = mx * (1.f - sp), qq = mx * (1.f - sp * f), t = mx * (1.f - sp * (1.f - f));
+  const float nr = i == 0 || i == 5 ? mx : (i == 1 ? qq : (i == 4 ? t : p));
+  const float ng = i == 1 || i == 2 ? mx : (i == 0 ? t : (i == 3 ? qq : p));
+  const float nb = i == 3 || i == 4 ? mx : (i == 2 ? t : (i == 5 ? qq : p));
+  q[0] = round_u8(nr), q[1] = round_u8(ng), q[2] = round_u8(nb);
+}
+
+// one kernel for pseg_augment_batch_nbhd (kWarp = false), pseg_augment_batch_warp (true) and pseg_augment_batch_blend (true,
+// kBlend): the first two differ in the row length and in aug_coord, which the halo fill evaluates at the REFLECTED pixel's
+// index and the label blocks on [H, W]; kBlend is the warp kernel's body plus the median, the second filter, the second
+// colour matrix and the hue / saturation shift, all sample- and hence block-uniform branches.  Its LDS holds the stage-1 tile
+// with a halo of kmed/2 + max(K/2, K2/2) and, behind it, with a median, the stage-2 tile with a halo of max(K/2, K2/2)
+template <bool kWarp, bool kBlend>
 __global__ __launch_bounds__(256) void augment_batch_nbhd_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ seg,
                                                                  const float* __restrict__ params, AugNorm nm, float* __restrict__ out,
                                                                  int64_t* __restrict__ target, int H, int W, int oh, int ow,
@@ -250,7 +335,7 @@ __global__ __launch_bounds__(256) void augment_batch_nbhd_kernel(const uint8_t* 
   const uint32_t per = is_img ? img_tiles : lab_tiles, per_x = is_img ? img_tiles_x : lab_tiles_x;
   const uint32_t b = blk / per, t = blk - b * per;
   const uint32_t tyi = t / per_x, txi = t - tyi * per_x;
-  const float* __restrict__ row = params + (int64_t)b * (kWarp ? PSEG_AUGMENT_WARP_ROW : PSEG_AUGMENT_NBHD_ROW);
+  const float* __restrict__ row = params + (int64_t)b * (kBlend ? PSEG_AUGMENT_BLEND_ROW : kWarp ? PSEG_AUGMENT_WARP_ROW : PSEG_AUGMENT_NBHD_ROW);
   const int64_t plane = (int64_t)H * W;
 
   if (!is_img) {                                           // ---- labels: [H, W], nearest, 0 outside
@@ -282,7 +367,59 @@ __global__ __launch_bounds__(256) void augment_batch_nbhd_kernel(const uint8_t* 
   if ((uint64_t)sw * (uint64_t)sh > lds_elems) k2 = 0;              // cannot happen with the host's sizing; never write past LDS
 
   float v[3];
-  if (k2 == 0) {
+  if constexpr (kBlend) {
+    // the median's halo hm and the second filter's g2, clamped like K; the two tiles must fit what the host sized
+    const float kmf = row[PSEG_AUGMENT_BLEND_KMED], k2f = row[PSEG_AUGMENT_BLEND_K2];
+    int hm = (kmf >= 3.f && kmf <= (float)PSEG_AUGMENT_BLEND_KMEDMAX) ? (int)kmf / 2 : 0;
+    int g2 = (k2f >= 3.f && k2f <= (float)PSEG_AUGMENT_BLEND_K2MAX) ? (int)k2f / 2 : 0;
+    const int span_w = gx1 - gx0 + 1, span_h = gy1 - gy0 + 1;
+    {
+      const uint64_t hf = (uint64_t)max(k2, g2), ht = (uint64_t)hm + hf;
+      const uint64_t need = (span_w + 2 * ht) * (span_h + 2 * ht) + (hm ? (span_w + 2 * hf) * (span_h + 2 * hf) : 0);
+      if (need > lds_elems) hm = 0, g2 = 0, k2 = 0;                     // cannot happen with the host's sizing; never write past LDS
+    }
+    const int hf = max(k2, g2), ht = hm + hf;
+    if (ht == 0) {
+      aug_warp<kWarp>(p, row, ix, iy, H, W, plane, v);
+      v[0] = round_u8(v[0]), v[1] = round_u8(v[1]), v[2] = round_u8(v[2]);
+    } else {
+      // stage 1 at working-grid pixels [g0 - ht, g1 + ht]
+      const int sw1 = span_w + 2 * ht, sh1 = span_h + 2 * ht;
+      for (int i = threadIdx.x; i < sw1 * sh1; i += 256) {
+        const int ly = i / sw1, lx = i - ly * sw1;
+        float w[3];
+        aug_warp<kWarp>(p, row, reflect101(gx0 - ht + lx, W), reflect101(gy0 - ht + ly, H), H, W, plane, w);
+        aug_tile[i] = (uint32_t)round_u8(w[0]) | ((uint32_t)round_u8(w[1]) << 8) | ((uint32_t)round_u8(w[2]) << 16);
+      }
+      __syncthreads();
+      const uint32_t* __restrict__ src = aug_tile;
+      int stride = sw1;
+      if (hm) {
+        // stage 2 at [g0 - hf, g1 + hf], behind the first tile.  The window of a pixel beyond the grid, taken from the first
+        // tile, is the mirror image of the window of the reflected pixel (the reflection is even about 0 and about n - 1 and
+        // has the period 2 n - 2), and a median does not see the order of its taps: the value IS the reflected pixel's
+        uint32_t* __restrict__ med = aug_tile + sw1 * sh1;
+        const int sw2 = span_w + 2 * hf, sh2 = span_h + 2 * hf;
+        for (int i = threadIdx.x; i < sw2 * sh2; i += 256) {
+          const int ly = i / sw2, lx = i - ly * sw2;
+          med[i] = aug_median(aug_tile + ly * sw1 + lx, sw1, 2 * hm + 1);
+        }
+        __syncthreads();
+        src = med, stride = sw2;
+      }
+      if (!live) return;
+      const uint32_t* __restrict__ centre = src + (iy - gy0 + hf) * stride + (ix - gx0 + hf);
+      const uint32_t px = *centre;
+      v[0] = (float)(px & 0xffu), v[1] = (float)((px >> 8) & 0xffu), v[2] = (float)((px >> 16) & 0xffu);
+      if (k2) aug_correlate(centre - k2 * stride - k2, stride, 2 * k2 + 1, row + PSEG_AUGMENT_NBHD_WEIGHTS, v);
+      if (g2) {
+        float e[3];
+        aug_correlate(centre - g2 * stride - g2, stride, 2 * g2 + 1, row + PSEG_AUGMENT_BLEND_WEIGHTS2, e);
+        const float m1 = aug_mask(row + PSEG_AUGMENT_BLEND_T1, ix, iy, H, W);
+        v[0] = round_u8(fmaf(m1, e[0] - v[0], v[0])), v[1] = round_u8(fmaf(m1, e[1] - v[1], v[1])), v[2] = round_u8(fmaf(m1, e[2] - v[2], v[2]));
+      }
+    }
+  } else if (k2 == 0) {
     aug_warp<kWarp>(p, row, ix, iy, H, W, plane, v);
     v[0] = round_u8(v[0]), v[1] = round_u8(v[1]), v[2] = round_u8(v[2]);
   } else {
@@ -326,10 +463,29 @@ __global__ __launch_bounds__(256) void augment_batch_nbhd_kernel(const uint8_t* 
   float* o = out + (int64_t)b * 3 * oplane + (int64_t)oy * ow + ox;
   float n_shared = 0.f;
   bool keep_shared = true;
+  float qc[3];
+  if constexpr (kBlend) {                                  // stages 4 and 5: the two colour matrices, hue and saturation
+    const bool blend = row[PSEG_AUGMENT_BLEND_COLOUR_ON] != 0.f;
+    const float m2 = blend ? aug_mask(row + PSEG_AUGMENT_BLEND_T2, ix, iy, H, W) : 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float* m = row + 6 + 4 * k;
+      qc[k] = round_u8(fmaf(m[0], v[0], fmaf(m[1], v[1], fmaf(m[2], v[2], m[3]))));
+      if (blend) {
+        const float* mb = row + PSEG_AUGMENT_BLEND_MB + 4 * k;
+        const float qb = round_u8(fmaf(mb[0], v[0], fmaf(mb[1], v[1], fmaf(mb[2], v[2], mb[3]))));
+        qc[k] = round_u8(fmaf(m2, qc[k] - qb, qb));
+      }
+    }
+    const float dh = row[PSEG_AUGMENT_BLEND_HUE], ds = row[PSEG_AUGMENT_BLEND_HUE + 1];
+    if (fabsf(dh) <= 3.0e38f && fabsf(ds) <= 3.0e38f && (dh != 0.f || ds != 0.f)) aug_hue_sat(qc, dh, ds);
+  }
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const float* m = row + 6 + 4 * k;
-    float q = round_u8(fmaf(m[0], v[0], fmaf(m[1], v[1], fmaf(m[2], v[2], m[3]))));
+    float q;
+    if constexpr (kBlend) q = qc[k];
+    else q = round_u8(fmaf(m[0], v[0], fmaf(m[1], v[1], fmaf(m[2], v[2], m[3]))));
     if (noisy) {
       if (k == 0 || noise_pc) {
         const Philox4 r = philox4x32_10(pix, kStreamNoise + (uint32_t)k, seed_lo, seed_hi);
@@ -353,24 +509,36 @@ __global__ __launch_bounds__(256) void augment_batch_nbhd_kernel(const uint8_t* 
 
 using namespace pseg;
 
-// pseg_augment_batch_nbhd and pseg_augment_batch_warp: the same arguments, checks, launch geometry and LDS sizing
-static int augment_nbhd_launch(const char* what, bool warp, const uint8_t* img, const uint8_t* seg, const float* params,
+// pseg_augment_batch_nbhd, pseg_augment_batch_warp and pseg_augment_batch_blend: the same arguments, checks, launch geometry
+// and LDS sizing; cols = the columns of shape_host: 3 = {K, mh, mw}, or 5 with {kmed, K2} behind them (the blend kernel)
+static int augment_nbhd_launch(const char* what, bool warp, int cols, const uint8_t* img, const uint8_t* seg, const float* params,
                                const int* shape_host, int B, int H, int W, const AugNorm& nm, float* out, int oh, int ow,
                                int64_t* target, void* stream) {
+  const bool blend = cols == 5;
   PSEG_REQUIRE(img && seg && params && shape_host && out && target, "%s: null pointer", what);
   PSEG_REQUIRE(B >= 1 && B <= 65535, "%s: batch %d outside [1, 65535]", what, B);
   PSEG_REQUIRE(H >= 1 && H <= 65535 && W >= 1 && W <= 65535, "%s: input size %dx%d outside [1, 65535]", what, H, W);
   PSEG_REQUIRE(oh >= 1 && oh <= 65535 && ow >= 1 && ow <= 65535, "%s: output size %dx%d outside [1, 65535]", what, oh, ow);
   PSEG_REQUIRE(nm.std[0] != 0.f && nm.std[1] != 0.f && nm.std[2] != 0.f, "%s: std must be non-zero", what);
   int kmax = 0;
+  bool any_halo = false;
   for (int b = 0; b < B; ++b) {
-    const int K = shape_host[3 * b], mh = shape_host[3 * b + 1], mw = shape_host[3 * b + 2];
+    const int K = shape_host[cols * b], mh = shape_host[cols * b + 1], mw = shape_host[cols * b + 2];
     PSEG_REQUIRE(K >= 0 && K <= PSEG_AUGMENT_NBHD_KMAX && (K <= 1 || (K & 1)),
                  "%s: sample %d: filter size %d is not 0, 1 or an odd number up to %d", what, b, K, PSEG_AUGMENT_NBHD_KMAX);
     PSEG_REQUIRE(mh >= 0 && mw >= 0 && mh <= 65535 && mw <= 65535 && (mh == 0) == (mw == 0),
                  "%s: sample %d: dropout mask %dx%d (0x0 = per pixel, otherwise 1..65535 each way)", what, b, mh, mw);
     kmax = K > kmax ? K : kmax;
+    if (blend) {
+      const int kmed = shape_host[cols * b + 3], K2 = shape_host[cols * b + 4];
+      PSEG_REQUIRE(kmed == 0 || (kmed >= 3 && kmed <= PSEG_AUGMENT_BLEND_KMEDMAX && (kmed & 1)),
+                   "%s: sample %d: median window %d is not 0 or an odd number from 3 to %d", what, b, kmed, PSEG_AUGMENT_BLEND_KMEDMAX);
+      PSEG_REQUIRE(K2 == 0 || (K2 >= 3 && K2 <= PSEG_AUGMENT_BLEND_K2MAX && (K2 & 1)),
+                   "%s: sample %d: second filter size %d is not 0 or an odd number from 3 to %d", what, b, K2, PSEG_AUGMENT_BLEND_K2MAX);
+      any_halo = any_halo || kmed || K2;
+    }
   }
+  any_halo = any_halo || kmax > 1;
   const int halo = kmax / 2;
   const int64_t img_tiles_x = cdiv(ow, kNbTileW), img_tiles_y = cdiv(oh, kNbTileH), img_tiles = img_tiles_x * img_tiles_y;
   const int64_t lab_tiles_x = cdiv(W, kAugTileW), lab_tiles = lab_tiles_x * cdiv(H, kAugTileH);
@@ -379,7 +547,7 @@ static int augment_nbhd_launch(const char* what, bool warp, const uint8_t* img, 
                (long long)(n_img + n_lab), B, H, W, oh, ow);
   // LDS: the widest and the tallest working-grid span of an output tile (the kernel's own index function), plus the halo
   int64_t lds_elems = 0;
-  if (halo > 0) {
+  if (any_halo) {
     int span_w = 1, span_h = 1;
     for (int64_t t = 0; t < img_tiles_x; ++t) {
       const int o0 = (int)t * kNbTileW, o1 = (o0 + kNbTileW < ow ? o0 + kNbTileW : ow) - 1;
@@ -391,11 +559,24 @@ static int augment_nbhd_launch(const char* what, bool warp, const uint8_t* img, 
       const int s = aug_ms_index(o1, H, oh) - aug_ms_index(o0, H, oh) + 1;
       span_h = s > span_h ? s : span_h;
     }
-    lds_elems = (int64_t)(span_w + 2 * halo) * (span_h + 2 * halo);
-    PSEG_REQUIRE(lds_elems * 4 <= 65536, "%s: a %dx%d output tile of %dx%d -> %dx%d with K = %d needs %lld bytes of LDS (limit 65536)", what,
-                 kNbTileW, kNbTileH, H, W, oh, ow, kmax, (long long)(lds_elems * 4));
+    if (!blend) {
+      lds_elems = (int64_t)(span_w + 2 * halo) * (span_h + 2 * halo);
+      PSEG_REQUIRE(lds_elems * 4 <= 65536, "%s: a %dx%d output tile of %dx%d -> %dx%d with K = %d needs %lld bytes of LDS (limit 65536)", what,
+                   kNbTileW, kNbTileH, H, W, oh, ow, kmax, (long long)(lds_elems * 4));
+    } else {
+      // two tiles (the kernel's own arithmetic): stage 1 with the whole halo, and with a median stage 2 with the filters'
+      for (int b = 0; b < B; ++b) {
+        const int K = shape_host[cols * b], kmed = shape_host[cols * b + 3], K2 = shape_host[cols * b + 4];
+        const int hm = kmed / 2, hf = (K > K2 ? K : K2) / 2, ht = hm + hf;
+        if (ht == 0) continue;
+        const int64_t need = (int64_t)(span_w + 2 * ht) * (span_h + 2 * ht) + (hm ? (int64_t)(span_w + 2 * hf) * (span_h + 2 * hf) : 0);
+        PSEG_REQUIRE(need * 4 <= 65536, "%s: sample %d: a %dx%d output tile of %dx%d -> %dx%d with kmed = %d, K = %d, K2 = %d needs %lld bytes of LDS (limit 65536)",
+                     what, b, kNbTileW, kNbTileH, H, W, oh, ow, kmed, K, K2, (long long)(need * 4));
+        lds_elems = need > lds_elems ? need : lds_elems;
+      }
+    }
   }
-  const auto kernel = warp ? augment_batch_nbhd_kernel<true> : augment_batch_nbhd_kernel<false>;
+  const auto kernel = blend ? augment_batch_nbhd_kernel<true, true> : warp ? augment_batch_nbhd_kernel<true, false> : augment_batch_nbhd_kernel<false, false>;
   hipLaunchKernelGGL(kernel, dim3((uint32_t)(n_img + n_lab)), dim3(256), (size_t)lds_elems * 4, (hipStream_t)stream, img, seg, params, nm,
                      out, target, H, W, oh, ow, (uint32_t)n_img, (uint32_t)img_tiles_x, (uint32_t)img_tiles,
                      (uint32_t)lab_tiles_x, (uint32_t)lab_tiles, halo, (uint32_t)lds_elems);
@@ -430,14 +611,21 @@ int pseg_augment_batch(const uint8_t* img, const uint8_t* seg, const float* para
 int pseg_augment_batch_nbhd(const uint8_t* img, const uint8_t* seg, const float* params, const int* shape_host, int B, int H, int W,
                             float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh, int ow,
                             int64_t* target, void* stream) {
-  return augment_nbhd_launch("augment_batch_nbhd", false, img, seg, params, shape_host, B, H, W, AugNorm{{mean0, mean1, mean2}, {std0, std1, std2}},
+  return augment_nbhd_launch("augment_batch_nbhd", false, 3, img, seg, params, shape_host, B, H, W, AugNorm{{mean0, mean1, mean2}, {std0, std1, std2}},
                              out, oh, ow, target, stream);
 }
 
 int pseg_augment_batch_warp(const uint8_t* img, const uint8_t* seg, const float* params, const int* shape_host, int B, int H, int W,
                             float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh, int ow,
                             int64_t* target, void* stream) {
-  return augment_nbhd_launch("augment_batch_warp", true, img, seg, params, shape_host, B, H, W, AugNorm{{mean0, mean1, mean2}, {std0, std1, std2}},
+  return augment_nbhd_launch("augment_batch_warp", true, 3, img, seg, params, shape_host, B, H, W, AugNorm{{mean0, mean1, mean2}, {std0, std1, std2}},
+                             out, oh, ow, target, stream);
+}
+
+int pseg_augment_batch_blend(const uint8_t* img, const uint8_t* seg, const float* params, const int* shape_host, int B, int H, int W,
+                             float mean0, float mean1, float mean2, float std0, float std1, float std2, float* out, int oh, int ow,
+                             int64_t* target, void* stream) {
+  return augment_nbhd_launch("augment_batch_blend", true, 5, img, seg, params, shape_host, B, H, W, AugNorm{{mean0, mean1, mean2}, {std0, std1, std2}},
                              out, oh, ow, target, stream);
 }
 

@@ -1578,13 +1578,13 @@ AUGMENT_NBHD_ROW = 212  # PSEG_AUGMENT_NBHD_ROW: floats per sample of augment_ba
 AUGMENT_NBHD_KMAX = 13  # PSEG_AUGMENT_NBHD_KMAX
 
 
-def _augment_batch_wide(entry, row, imgs, segs, params, shapes, oh, ow, mean, std, out, target):
+def _augment_batch_wide(entry, row, imgs, segs, params, shapes, oh, ow, mean, std, out, target, cols=3):
     assert imgs.is_cuda and imgs.dtype == torch.uint8 and imgs.is_contiguous() and imgs.dim() == 4 and imgs.shape[1] == 3
     B, _, H, W = imgs.shape
     assert segs.device == imgs.device and segs.dtype == torch.uint8 and segs.is_contiguous() and segs.shape == (B, H, W)
     assert params.device == imgs.device and params.dtype == torch.float32 and params.is_contiguous()
     assert params.shape == (B, row) and len(mean) == 3 and len(std) == 3
-    assert not shapes.is_cuda and shapes.dtype == torch.int32 and shapes.is_contiguous() and shapes.shape == (B, 3)
+    assert not shapes.is_cuda and shapes.dtype == torch.int32 and shapes.is_contiguous() and shapes.shape == (B, cols)
     if out is None:
         out = torch.empty(B, 3, oh, ow, dtype=torch.float32, device=imgs.device)
     if target is None:
@@ -1611,6 +1611,20 @@ def augment_batch_warp(imgs, segs, params, shapes, oh, ow, mean, std, out=None, 
     map of images and labels, in one launch (pseg_augment_batch_warp).  params: fp32 device table [B, AUGMENT_WARP_ROW];
     everything else as augment_batch_nbhd."""
     return _augment_batch_wide('pseg_augment_batch_warp', AUGMENT_WARP_ROW, imgs, segs, params, shapes, oh, ow, mean, std, out, target)
+
+
+AUGMENT_BLEND_ROW = 1012  # PSEG_AUGMENT_BLEND_ROW: floats per sample of augment_batch_blend's table (layout: include/pseg_amd.h)
+AUGMENT_BLEND_KMEDMAX = 11  # PSEG_AUGMENT_BLEND_KMEDMAX
+AUGMENT_BLEND_K2MAX = 15    # PSEG_AUGMENT_BLEND_K2MAX
+
+
+def augment_batch_blend(imgs, segs, params, shapes, oh, ow, mean, std, out=None, target=None):
+    """augment_batch_warp with a per-sample median window, a second filter and a second colour matrix blended in by two
+    16 x 16 mask tables, and a hue / saturation shift, in one launch (pseg_augment_batch_blend).  params: fp32 device table
+    [B, AUGMENT_BLEND_ROW]; shapes: HOST int32 tensor [B, 5] of each row's {K, mh, mw, kmed, K2}; everything else as
+    augment_batch_warp."""
+    return _augment_batch_wide('pseg_augment_batch_blend', AUGMENT_BLEND_ROW, imgs, segs, params, shapes, oh, ow, mean, std, out, target,
+                               cols=5)
 
 
 def confusion(pred, target, counters):

@@ -11,7 +11,10 @@ drew a filter, noise or dropout gets the wider rows of ``pseg_augment_batch_nbhd
 same 24, then K, the noise and dropout parameters, the sample's 64-bit seed bit-cast into two floats, and the K x K
 weights) and goes through that kernel; a batch in which some sample drew an elastic, piecewise-affine or perspective warp
 gets the still wider rows of ``pseg_augment_batch_warp`` (``PSEG_AUGMENT_WARP_ROW`` floats: the same 212, then the third row
-of an inverse homography, the elastic alpha and a 4 x 4 displacement grid); every other batch goes through
+of an inverse homography, the elastic alpha and a 4 x 4 displacement grid); a batch in which some sample drew a median blur,
+an edge-detect blend, a hue / saturation shift or a frequency-noise colour blend gets the widest rows, those of
+``pseg_augment_batch_blend`` (``PSEG_AUGMENT_BLEND_ROW`` floats: the same 252, then the median window, a second filter, a
+second colour matrix, the hue and saturation shifts and two 16 x 16 mask tables); every other batch goes through
 ``pseg_augment_batch`` as before.
 
 Built (defaults of ``DeviceAugment.reference()`` = the reference's values):
@@ -31,6 +34,9 @@ Built (defaults of ``DeviceAugment.reference()`` = the reference's values):
   * only with ``DeviceAugment.warps()`` (= ``full()`` plus these, all off by default): the three slots that move pixels by
     something other than one matrix, ``ElasticTransformation``, ``PiecewiseAffine`` and ``PerspectiveTransform`` -- see
     "Local warps" below.  With them 13 of the 16 slots are live.
+  * only with ``DeviceAugment.blends()`` (= ``warps()`` plus these, all off by default): ``AddToHueAndSaturation``, the
+    edge-detect blend, the median blur and the frequency-noise blend -- see "Median, blends, hue and saturation" below.
+    With them 15 of the 16 slots are live and every ``OneOf`` is complete.
 Labels are warped with the same coordinate map, nearest sample, background 0, as imgaug warps segmentation maps.
 
 Filters, noise and dropout (``full()``).  These formulas are THIS MODULE'S CONTRACT.  They were written down from imgaug's
@@ -39,7 +45,7 @@ either.  Each takes one slot of the ``SomeOf`` block (slots 5..9):
   * blur ``OneOf``: one third of the time ``GaussianBlur``: sigma ~ U(0, 3), no blur if sigma < 0.001,
     ``k = int(max(3.3 sigma, 5))`` (sigma < 3) made odd by + 1, weights ``exp(-d^2 / 2 sigma^2)`` normalised, the separable
     outer product; one third ``AverageBlur``: integer k ~ U{2..7}, window ``[x - k//2, x - k//2 + k - 1]``, weights 1/k^2,
-    embedded in the next odd K; one third ``MedianBlur``, which is out of scope: nothing happens;
+    embedded in the next odd K; one third ``MedianBlur``: nothing happens here, ``blends()`` builds it (below);
   * ``Sharpen``: alpha ~ U(0, 1), lightness l ~ U(0.75, 1.5): ``(1 - alpha) delta + alpha [[-1,-1,-1],[-1,8+l,-1],[-1,-1,-1]]``;
   * ``Emboss``: alpha ~ U(0, 1), strength s ~ U(0, 2): ``(1 - alpha) delta + alpha [[-1-s,-s,0],[-s,1,s],[0,s,1+s]]``;
   * ``AdditiveGaussianNoise``: scale ~ U(0, 12.75), per channel with probability 0.5;
@@ -69,10 +75,38 @@ the source: elastic jitter -> displacement grid -> inverse homography (include/p
     draws at s = 0.1, the upper end, none was dropped).  For a convex quad the inverse's denominator is positive on the whole
     grid, which ``rows()`` checks: it raises ``ValueError`` for a hand-made recipe that fails it.
 
-OUT OF SCOPE -- the remaining three slots of the block: the edge-detect blend (BlendAlphaSimplexNoise), Superpixels and
-AddToHueAndSaturation; and the frequency-noise blend (BlendAlphaFrequencyNoise), the median blur and the frequency-noise
-branch inside two ``OneOf``s; and imgaug's border modes other than constant and edge (``ia.ALL`` also draws reflect,
-symmetric and wrap).
+Median, blends, hue and saturation (``blends()``).  Like the filters' and the warps', these draws and formulas are THIS
+MODULE'S CONTRACT, written down from imgaug's documentation and NOT checked against imgaug or cv2 (include/pseg_amd.h has
+the kernel's arithmetic, stage by stage):
+  * ``MedianBlur``, the blur ``OneOf``'s third branch: integer k ~ U{3..11}, made odd by + 1 when even, capped at 11; per
+    channel the median of the k x k window, border reflected as the filters'.  As in the ``OneOf`` that draw holds no Gaussian
+    or average blur; a picked sharpen / emboss still composes into F, which runs after the median;
+  * the edge-detect blend (slot 13, ``BlendAlphaSimplexNoise(OneOf([EdgeDetect, DirectedEdgeDetect]))``): alpha ~ U(0.5, 1);
+    half of the time ``EdgeDetect``, ``(1 - alpha) delta + alpha [[0,1,0],[1,-4,1],[0,1,0]]``, otherwise
+    ``DirectedEdgeDetect`` with direction ~ U(0, 1) of a turn: a 3 x 3 kernel with centre 1 whose eight neighbours are weighted
+    by the squared clipped cosine between their direction and the drawn one and normalised to sum to -1, blended with delta
+    the same way.  The picked linear filters compose to F and the edge filter E is linear too, so the blend
+    ``m E(F x) + (1 - m) F x`` is two filters over the same pixels, F and G = E * F (full 2-D convolution in fp64, E itself
+    without a filter; K2 <= 15 follows from K <= 13), blended per pixel by the mask m = T1.  T1 is a blobby 16 x 16 table that
+    the kernel samples bilinearly over the image: the sum of 1..3 octaves, each a random g x g grid, g ~ U{2..16}, resized to
+    16 x 16 with the sample's draw of nearest or linear, normalised to [0, 1] and, half of the time, passed through the
+    sigmoid ``1 / (1 + exp(-10 (m - 0.5)))``.  That is VALUE noise: there is no gradient-noise library here, and it is not
+    simplex noise;
+  * ``AddToHueAndSaturation((-20, 20))`` (slot 14): one integer v ~ U{-20..20} serves both, dh = 6 v / 255 sixths of the colour
+    circle and ds = v / 255: imgaug's one value applied to cv2's 8-bit HSV, whose hue covers the half-circle in 180 steps.
+    The kernel converts the 8-bit RGB to hue / saturation / value in fp32, shifts, wraps the hue, clamps the saturation and
+    converts back;
+  * the frequency-noise blend, the other half of the Multiply ``OneOf``
+    (``BlendAlphaFrequencyNoise(foreground=Multiply, background=LinearContrast)``): Ma is Multiply per channel, U(0.5, 1.5)
+    each, Mb is LinearContrast, U(0.5, 2); both are affine, so each is composed with the sample's other colour operations on
+    either side, in the order drawn, into one pair (M, Mb), and the kernel blends ``m (M v) + (1 - m) (Mb v)`` per pixel by
+    the mask m = T2: a 16 x 16 random-phase spectrum weighted by ``|f|^exponent``, exponent ~ U(-4, 0), through
+    ``numpy.fft.irfft2``, normalised to [0, 1], with the same sigmoid coin.
+Both tables are fp32, finite and in [0, 1]; ``rows()`` checks them, the median window and K2, and raises ``ValueError`` for a
+hand-made recipe outside the ranges.
+
+OUT OF SCOPE -- the last slot of the block, Superpixels (it needs a segmentation pass); and imgaug's border modes other
+than constant and edge (``ia.ALL`` also draws reflect, symmetric and wrap).
 
 Simplifications, all on the host side: the geometric augmenters run in the fixed order flips, crop-and-pad, affine,
 perspective, piecewise-affine, elastic (the reference shuffles the top-level list and the block), and the chain is ONE warp (imgaug resamples once per augmenter); one (order, cval,
@@ -80,8 +114,10 @@ mode) triple serves a sample -- crop-and-pad alone is bilinear, the affine's own
 operations are composed into one matrix, so the 8-bit rounding and saturation that imgaug applies between two of them
 happens once, after the last; the picked filters of a sample (blur, sharpen, emboss) are composed, in fp64, into ONE K x K
 filter by full 2-D convolution (K <= 13: 9 + 2 + 2), which likewise gives up the 8-bit rounding between them (and the
-border handling of each on its own); and the stages of a sample run in the fixed order warp, filter, colour matrix,
-noise, dropout, whatever order the ``SomeOf`` block drew (the reference applies the picked augmenters in a random order).
+border handling of each on its own), and there is no 8-bit rounding between F and the edge filter E either (G = E * F is one
+filter); the masks are value noise where the reference has simplex noise; and the stages of a sample run in the fixed order
+warp, median, filter / edge blend, colour matrix (or the two blended), hue-saturation, noise, dropout, whatever order the
+``SomeOf`` block drew (the reference applies the picked augmenters in a random order).
 """
 import numpy as np
 import torch
@@ -102,7 +138,14 @@ WARP_ROW = 252                   # PSEG_AUGMENT_WARP_ROW; the offsets below are 
 WARP_H2, WARP_ALPHA, WARP_GRID_ON, WARP_GRID = 212, 215, 216, 220
 WARP_NODES = 4                   # the displacement grid is 4 x 4 nodes of (dx, dy)
 _WARP_OPS = ('elastic', 'piecewise', 'perspective')                  # slots 10..12
-PERSPECTIVE_CLIP = 0.4           # a corner moves inward by less than half a side and stays in its own quadrant (that alone
+BLEND_ROW = 1012                 # PSEG_AUGMENT_BLEND_ROW; the offsets below are PSEG_AUGMENT_BLEND_* of include/pseg_amd.h
+BLEND_KMEDMAX, BLEND_K2MAX = 11, 15
+BLEND_KMED, BLEND_K2, BLEND_COLOUR_ON, BLEND_HUE, BLEND_MB, BLEND_WEIGHTS2 = 252, 253, 254, 255, 260, 272
+BLEND_T1, BLEND_T2, BLEND_TABLE = 500, 756, 16                       # two 16 x 16 mask tables
+_BLEND_OPS = ('edge_blend', 'hue_sat')                               # slots 13, 14 (slot 15, Superpixels, is not built)
+_BLEND_KEYS = ('median', 'edge', 'hue_sat', 'colour_mask')           # recipe keys that send a batch to pseg_augment_batch_blend
+SIGMOID_GAIN = 10.0              # the masks' optional sigmoid: 1 / (1 + exp(-10 (m - 0.5)))
+PERSPECTIVE_CLIP = 0.4          # a corner moves inward by less than half a side and stays in its own quadrant (that alone
                                  # does not keep the quad convex: quad_is_convex)
 
 
@@ -321,9 +364,131 @@ def make_warp_row(base=None, h2=None, alpha=None, grid=None):
     return row
 
 
+def edge_detect_kernel(alpha):
+    """EdgeDetect(alpha): (1 - alpha) delta + alpha [[0,1,0],[1,-4,1],[0,1,0]]"""
+    return _blend_with_identity(alpha, [[0, 1, 0], [1, -4, 1], [0, 1, 0]])
+
+
+def directed_edge_kernel(alpha, direction):
+    """DirectedEdgeDetect(alpha, direction in turns, 0 = up, clockwise): centre 1, each of the eight neighbours weighted by
+    the squared clipped cosine between its direction and the drawn one, normalised to sum to -1; blended with delta"""
+    a = 2.0 * np.pi * float(direction)
+    d = np.array([np.sin(a), -np.cos(a)])                                 # (x, y), y down
+    m = np.zeros((3, 3), dtype=np.float64)
+    for j in range(3):
+        for i in range(3):
+            if (j, i) != (1, 1):
+                c = np.array([i - 1.0, j - 1.0])
+                m[j, i] = max(float(c @ d) / float(np.linalg.norm(c)), 0.0) ** 2
+    m *= -1.0 / m.sum()
+    m[1, 1] = 1.0
+    return _blend_with_identity(alpha, m)
+
+
+def edge_kernel(alpha, direction=None):
+    return edge_detect_kernel(alpha) if direction is None else directed_edge_kernel(alpha, direction)
+
+
+def _unit_range(m, sigmoid):
+    """a mask normalised to [0, 1] (a flat one becomes 0.5), optionally through the sigmoid; fp32"""
+    m = np.asarray(m, dtype=np.float64)
+    span = m.max() - m.min()
+    m = (m - m.min()) / span if span > 0 else np.full_like(m, 0.5)
+    if sigmoid:
+        m = 1.0 / (1.0 + np.exp(-SIGMOID_GAIN * (m - 0.5)))
+    return np.clip(m, 0.0, 1.0).astype(np.float32)
+
+
+def resize_to_table(grid, linear):
+    """a g x g grid -> BLEND_TABLE x BLEND_TABLE, pixel centres aligned: nearest, or bilinear with the border clamped"""
+    grid = np.asarray(grid, dtype=np.float64)
+    g, n = grid.shape[0], BLEND_TABLE
+    c = (np.arange(n) + 0.5) * g / n - 0.5
+    if not linear:
+        i = np.clip(np.floor(c + 0.5).astype(np.int64), 0, g - 1)
+        return grid[i][:, i]
+    c = np.clip(c, 0.0, g - 1.0)
+    i0 = np.minimum(c.astype(np.int64), max(g - 2, 0))
+    i1, f = np.minimum(i0 + 1, g - 1), c - i0
+    rows = grid[i0] * (1.0 - f)[:, None] + grid[i1] * f[:, None]
+    return rows[:, i0] * (1.0 - f)[None] + rows[:, i1] * f[None]
+
+
+def value_noise_table(rng):
+    """T1, the edge blend's mask: the sum of 1..3 octaves of VALUE noise (a random g x g grid, g in 2..16, resized to the table
+    with the sample's draw of nearest or linear), normalised, through the sigmoid half of the time.  Not simplex noise."""
+    linear = bool(rng.integers(2))
+    total = np.zeros((BLEND_TABLE, BLEND_TABLE), dtype=np.float64)
+    for _ in range(int(rng.integers(1, 4))):
+        g = int(rng.integers(2, BLEND_TABLE + 1))
+        total += resize_to_table(rng.random((g, g)), linear)
+    return _unit_range(total, bool(rng.random() < 0.5))
+
+
+def frequency_noise_table(rng):
+    """T2, the colour blend's mask: a random-phase spectrum weighted by |f|^exponent, exponent ~ U(-4, 0) (no mean term),
+    back through numpy.fft.irfft2, normalised, through the sigmoid half of the time"""
+    n = BLEND_TABLE
+    exponent = float(rng.uniform(-4.0, 0.0))
+    f = np.hypot(np.fft.fftfreq(n)[:, None], np.fft.rfftfreq(n)[None])
+    weight = np.zeros_like(f)
+    weight[f > 0] = f[f > 0] ** exponent
+    spectrum = weight * np.exp(2j * np.pi * rng.random(f.shape))
+    return _unit_range(np.fft.irfft2(spectrum, s=(n, n)), bool(rng.random() < 0.5))
+
+
+def hue_sat_shift(v):
+    """AddToHueAndSaturation's one integer v -> (dh in sixths of the colour circle, ds as a fraction): imgaug applies the one
+    value to cv2's 8-bit HSV, v / 255 of the hue's range and v / 255 of the saturation's: dh = 6 v / 255, ds = v / 255"""
+    return 6.0 * float(v) / 255.0, float(v) / 255.0
+
+
+def _check_table(name, t):
+    t = np.asarray(t, dtype=np.float32)
+    if t.shape != (BLEND_TABLE, BLEND_TABLE) or not np.isfinite(t).all() or t.min() < 0.0 or t.max() > 1.0:
+        raise ValueError('%s is a finite %d x %d table in [0, 1]' % (name, BLEND_TABLE, BLEND_TABLE))
+    return t
+
+
+def make_blend_row(base=None, kmed=0, kernel2=None, colour2=None, t1=None, t2=None, hue_sat=None):
+    """one row of pseg_augment_batch_blend's table from a make_warp_row() row, the median window kmed (0, or odd 3..11), the
+    second filter G (K2 x K2, K2 odd, 3..15) with its mask table t1, the second colour matrix Mb (3x4) with its mask table t2
+    (colour2 switches the colour blend on), and hue_sat = (dh, ds).  ValueError outside the ranges."""
+    row = np.zeros(BLEND_ROW, dtype=np.float32)
+    base = np.ascontiguousarray(make_warp_row() if base is None else base, dtype=np.float32)
+    row.view(np.uint32)[:WARP_ROW] = base.view(np.uint32)                # (the seed's bits)
+    kmed = int(kmed)
+    if kmed != 0 and (kmed < 3 or kmed > BLEND_KMEDMAX or kmed % 2 == 0):
+        raise ValueError('a median window is 0 or odd, 3..%d, not %d' % (BLEND_KMEDMAX, kmed))
+    row[BLEND_KMED] = kmed
+    if kernel2 is not None:
+        kernel2 = np.asarray(kernel2, dtype=np.float64)
+        K2 = kernel2.shape[0]
+        if kernel2.shape != (K2, K2) or K2 % 2 == 0 or K2 < 3 or K2 > BLEND_K2MAX:
+            raise ValueError('a second filter is K2 x K2 with K2 odd, 3..%d, not %s' % (BLEND_K2MAX, kernel2.shape))
+        row[BLEND_K2] = K2
+        row[BLEND_WEIGHTS2:BLEND_WEIGHTS2 + K2 * K2] = kernel2.reshape(-1)
+    if t1 is not None:
+        row[BLEND_T1:BLEND_T1 + BLEND_TABLE ** 2] = _check_table('t1', t1).reshape(-1)
+    row[BLEND_MB:BLEND_MB + 12] = np.eye(4)[:3].reshape(12)
+    if colour2 is not None:
+        row[BLEND_COLOUR_ON] = 1.0
+        row[BLEND_MB:BLEND_MB + 12] = np.asarray(colour2, dtype=np.float64).reshape(12)
+    if t2 is not None:
+        row[BLEND_T2:BLEND_T2 + BLEND_TABLE ** 2] = _check_table('t2', t2).reshape(-1)
+    if hue_sat is not None:
+        if not np.isfinite(hue_sat).all():
+            raise ValueError('hue_sat = (dh, ds) is finite, not %s' % (tuple(hue_sat),))
+        row[BLEND_HUE], row[BLEND_HUE + 1] = hue_sat
+    return row
+
+
 def row_shapes(table):
-    """int32 [B, 3] = {K, mh, mw} of each row: what pseg_augment_batch_nbhd / _warp validate on the host"""
-    return np.ascontiguousarray(np.asarray(table)[:, [NBHD_K, NBHD_DROP + 2, NBHD_DROP + 3]].astype(np.int32))
+    """int32 [B, 3] = {K, mh, mw} of each row: what pseg_augment_batch_nbhd / _warp validate on the host; for rows of
+    BLEND_ROW floats [B, 5] = {K, mh, mw, kmed, K2}, pseg_augment_batch_blend's"""
+    table = np.asarray(table)
+    cols = [NBHD_K, NBHD_DROP + 2, NBHD_DROP + 3] + ([BLEND_KMED, BLEND_K2] if table.shape[1] == BLEND_ROW else [])
+    return np.ascontiguousarray(table[:, cols].astype(np.int32))
 
 
 def _range(v):
@@ -340,7 +505,8 @@ class DeviceAugment:
                  gaussian_blur=None, average_blur=None, sharpen_alpha=None, sharpen_lightness=(0.75, 1.5), emboss_alpha=None,
                  emboss_strength=(0.0, 2.0), noise_scale=None, noise_per_channel=0.5, dropout_p=None, dropout_per_channel=0.5,
                  coarse_p=None, coarse_size=(0.02, 0.05), coarse_per_channel=0.2, elastic_alpha=None, elastic_p=None,
-                 piecewise_scale=None, piecewise_p=None, perspective_scale=None, perspective_p=None):
+                 piecewise_scale=None, piecewise_p=None, perspective_scale=None, perspective_p=None, median_blur=None,
+                 edge_blend=None, hue_sat=None, frequency_blend=False):
         self.fliplr, self.flipud = float(fliplr), float(flipud)
         self.crop_pad, self.crop_pad_p = _range(crop_pad), float(crop_pad_p if crop_pad is not None else 0.0)
         if self.crop_pad is not None and self.crop_pad[0] <= -0.45:
@@ -364,6 +530,9 @@ class DeviceAugment:
         self.elastic_alpha, self.elastic_p = _range(elastic_alpha), None if elastic_p is None else float(elastic_p)
         self.piecewise_scale, self.piecewise_p = _range(piecewise_scale), None if piecewise_p is None else float(piecewise_p)
         self.perspective_scale, self.perspective_p = _range(perspective_scale), None if perspective_p is None else float(perspective_p)
+        # the median blur, the two noise-masked blends and hue / saturation: None / False (the default) switches one off
+        self.median_blur, self.edge_blend, self.hue_sat = _range(median_blur), _range(edge_blend), _range(hue_sat)
+        self.frequency_blend = bool(frequency_blend)
         self._rng = None
 
     @classmethod
@@ -388,6 +557,15 @@ class DeviceAugment:
                   perspective_scale=(0.01, 0.1), perspective_p=0.5)
         on.update(kw)
         return cls.full(**on)
+
+    @classmethod
+    def blends(cls, **kw):
+        """warps() plus MedianBlur (the blur OneOf's third branch), the edge-detect blend, AddToHueAndSaturation and the
+        frequency-noise blend (the Multiply OneOf's other branch) at the reference's ranges: 15 of the 16 slots of the SomeOf
+        block, every OneOf complete"""
+        on = dict(median_blur=(3, 11), edge_blend=(0.5, 1.0), hue_sat=(-20, 20), frequency_blend=True)
+        on.update(kw)
+        return cls.warps(**on)
 
     @classmethod
     def identity(cls, order=0, **kw):
@@ -418,8 +596,8 @@ class DeviceAugment:
     def _draw_nbhd(self, rng, name, nbhd):
         """one picked slot of the five neighbourhood / per-pixel-random augmenters -> nbhd (an augmenter that is off draws
         nothing, so the default tables are those of the colour-only sampler)"""
-        if name == 'blur' and (self.gaussian_blur is not None or self.average_blur is not None):
-            which = int(rng.integers(3))                      # Gaussian, average, median (out of scope)
+        if name == 'blur' and (self.gaussian_blur is not None or self.average_blur is not None or self.median_blur is not None):
+            which = int(rng.integers(3))                      # Gaussian, average, median
             if which == 0 and self.gaussian_blur is not None:
                 sigma = float(rng.uniform(*self.gaussian_blur))
                 if sigma >= 0.001:
@@ -428,6 +606,9 @@ class DeviceAugment:
                 k = int(rng.integers(int(self.average_blur[0]), int(self.average_blur[1]) + 1))
                 if k > 1:
                     nbhd.setdefault('filters', []).append(('average', k))
+            elif which == 2 and self.median_blur is not None:
+                k = int(rng.integers(int(self.median_blur[0]), int(self.median_blur[1]) + 1))
+                nbhd['median'] = min(k + 1 - k % 2, BLEND_KMEDMAX)
         elif name == 'sharpen' and self.sharpen_alpha is not None:
             nbhd.setdefault('filters', []).append(('sharpen', float(rng.uniform(*self.sharpen_alpha)),
                                                    float(rng.uniform(*self.sharpen_lightness))))
@@ -461,6 +642,16 @@ class DeviceAugment:
             if quad_is_convex(f):                             # (several corners near the clip can fold the quad: nothing happens then)
                 nbhd['perspective'] = f
 
+    def _draw_blend(self, rng, name, nbhd):
+        """one picked slot of the edge-detect blend or hue / saturation -> nbhd (one that is off draws nothing)"""
+        if name == 'edge_blend' and self.edge_blend is not None:
+            alpha = float(rng.uniform(*self.edge_blend))
+            direction = None if rng.random() < 0.5 else float(rng.uniform(0.0, 1.0))     # EdgeDetect, DirectedEdgeDetect
+            nbhd['edge'] = {'alpha': alpha, 'direction': direction}
+            nbhd['edge_mask'] = value_noise_table(rng)
+        elif name == 'hue_sat' and self.hue_sat is not None:
+            nbhd['hue_sat'] = int(rng.integers(int(self.hue_sat[0]), int(self.hue_sat[1]) + 1))
+
     def _draw_colour(self, rng, nbhd=None):
         lo, hi = self.some_of
         n = int(rng.integers(lo, hi + 1)) if hi > 0 else 0
@@ -475,8 +666,11 @@ class DeviceAugment:
             elif name == 'add' and self.add is not None:
                 ops.append(('add', self._values(rng, self.add, integer=True)))
             elif name == 'multiply' and self.multiply is not None:
-                if rng.random() < 0.5:                        # the other branch of the reference's OneOf is out of scope
+                if rng.random() < 0.5:                        # the other branch of the reference's OneOf: the frequency-noise blend
                     ops.append(('multiply', self._values(rng, self.multiply)))
+                elif self.frequency_blend and nbhd is not None and self.contrast is not None:
+                    ops.append(('blend', (rng.uniform(self.multiply[0], self.multiply[1], 3), float(rng.uniform(*self.contrast)))))
+                    nbhd['colour_mask'] = frequency_noise_table(rng)
             elif name == 'contrast' and self.contrast is not None:
                 ops.append(('contrast', self._values(rng, self.contrast)))
             elif name == 'grayscale' and self.grayscale is not None:
@@ -485,6 +679,8 @@ class DeviceAugment:
                 self._draw_nbhd(rng, _NBHD_OPS[slot - len(_COLOUR_OPS)], nbhd)
             elif nbhd is not None and 0 <= slot - len(_COLOUR_OPS) - len(_NBHD_OPS) < len(_WARP_OPS):
                 self._draw_warp(rng, _WARP_OPS[slot - len(_COLOUR_OPS) - len(_NBHD_OPS)], nbhd)
+            elif nbhd is not None and 0 <= slot - len(_COLOUR_OPS) - len(_NBHD_OPS) - len(_WARP_OPS) < len(_BLEND_OPS):
+                self._draw_blend(rng, _BLEND_OPS[slot - len(_COLOUR_OPS) - len(_NBHD_OPS) - len(_WARP_OPS)], nbhd)
         if nbhd and ('noise' in nbhd or 'dropout' in nbhd or 'elastic' in nbhd):
             nbhd['seed'] = int(rng.integers(0, 2 ** 64, dtype=np.uint64))
         return ops
@@ -494,7 +690,9 @@ class DeviceAugment:
         arguments of affine_matrix) or None, order, cval, mode, colour [(name, value), ...]; and only where drawn: filters
         [(name, parameters of filter_kernel...), ...], noise (scale, per_channel), dropout {p, per_channel, size: the mask's
         fraction of the image or None}, elastic (alpha), piecewise ([4,4,2] node jitter as fractions of (W, H)), perspective
-        ([4,2] inward corner moves as fractions), seed (with noise, dropout or elastic)"""
+        ([4,2] inward corner moves as fractions), seed (with noise, dropout or elastic), median (the window k), edge {alpha,
+        direction: turns or None for EdgeDetect} with edge_mask (T1, fp32 [16,16]), hue_sat (the integer v), and colour_mask
+        (T2) next to a ('blend', (multiply[3], contrast)) entry of colour"""
         rng, out = self.rng, []
         for _ in range(B):
             r = {'fliplr': bool(rng.random() < self.fliplr), 'flipud': bool(rng.random() < self.flipud), 'crop_pad': None,
@@ -523,10 +721,13 @@ class DeviceAugment:
     def rows(recipes, H, W):
         """recipes -> the kernel's parameter table, numpy float32 (matrices and filters composed in fp64): [B, ROW], or
         [B, NBHD_ROW] when some recipe holds a filter, noise or dropout, or [B, WARP_ROW] when some recipe holds an elastic,
-        piecewise or perspective warp.  ValueError for a perspective whose inverse has no positive denominator on the grid."""
-        warp = any(r.get(k) is not None for r in recipes for k in _WARP_OPS)
+        piecewise or perspective warp, or [B, BLEND_ROW] when some recipe holds a median, an edge blend, a hue / saturation
+        shift or a colour blend.  ValueError for a perspective whose inverse has no positive denominator on the grid, a median
+        window or second filter outside its range, and a mask table that is not finite, 16 x 16 and in [0, 1]."""
+        blend = any(r.get(k) is not None for r in recipes for k in _BLEND_KEYS)
+        warp = blend or any(r.get(k) is not None for r in recipes for k in _WARP_OPS)
         wide = warp or any(r.get('filters') or r.get('noise') or r.get('dropout') for r in recipes)
-        table = np.zeros((len(recipes), WARP_ROW if warp else NBHD_ROW if wide else ROW), dtype=np.float32)
+        table = np.zeros((len(recipes), BLEND_ROW if blend else WARP_ROW if warp else NBHD_ROW if wide else ROW), dtype=np.float32)
         for i, r in enumerate(recipes):
             inv = np.linalg.inv(forward_matrix(r, H, W))
             if r.get('perspective') is not None:
@@ -536,7 +737,11 @@ class DeviceAugment:
                     raise ValueError('perspective %s: the inverse homography has no positive denominator on the %d x %d grid'
                                      % (np.asarray(r['perspective']).tolist(), H, W))
                 inv = inv / inv[2, 2]
-            row = make_row(inv, colour_matrix(r.get('colour', ())), r.get('cval', 0.0), r.get('order', 0), r.get('mode', 0))
+            colour, colour2 = list(r.get('colour', ())), None
+            if any(name == 'blend' for name, _ in colour):    # the two branches in the blend's place, the other ops on either side
+                colour2 = colour_matrix([('contrast', np.full(3, v[1])) if name == 'blend' else (name, v) for name, v in colour])
+                colour = [('multiply', v[0]) if name == 'blend' else (name, v) for name, v in colour]
+            row = make_row(inv, colour_matrix(colour), r.get('cval', 0.0), r.get('order', 0), r.get('mode', 0))
             if wide:
                 kernel = compose_filters([filter_kernel(*f) for f in r['filters']]) if r.get('filters') else None
                 d = r.get('dropout')
@@ -547,28 +752,35 @@ class DeviceAugment:
             if warp:
                 grid = None if r.get('piecewise') is None else -np.asarray(r['piecewise'], dtype=np.float64) * (W, H)
                 row = make_warp_row(row, inv[2] if r.get('perspective') is not None else None, r.get('elastic'), grid)
+            if blend:
+                kernel2 = None
+                if r.get('edge') is not None:                 # G = E * F, composed in fp64 as F itself; E alone without a filter
+                    kernel2 = compose_filters([filter_kernel(*f) for f in r.get('filters') or ()] + [edge_kernel(**r['edge'])])
+                row = make_blend_row(row, r.get('median') or 0, kernel2, colour2, r.get('edge_mask'), r.get('colour_mask'),
+                                     None if r.get('hue_sat') is None else hue_sat_shift(r['hue_sat']))
             table[i] = row
         return table
 
     def sample(self, B, H, W):
-        """-> numpy float32 [B, ROW], [B, NBHD_ROW] or [B, WARP_ROW]: one parameter row per sample of a B x 3 x H x W batch"""
+        """-> numpy float32 [B, ROW], [B, NBHD_ROW], [B, WARP_ROW] or [B, BLEND_ROW]: one parameter row per sample of a B x 3 x H x W batch"""
         return self.rows(self.draw(B), H, W)
 
     # ------------------------------------------------------------------ device side
     def apply(self, imgs, segs, params, out_hw=None, shapes=None):
-        """explicit rows (numpy or tensor [B, ROW], [B, NBHD_ROW] or [B, WARP_ROW]) -> (fp32 [B,3,oh,ow], int64 [B,H,W]);
-        out_hw=None keeps (H, W).  Rows of NBHD_ROW floats go through pseg_augment_batch_nbhd, rows of WARP_ROW floats through
-        pseg_augment_batch_warp; when they already live on the device, shapes (row_shapes() of the table) has to come with
+        """explicit rows (numpy or tensor [B, ROW], [B, NBHD_ROW], [B, WARP_ROW] or [B, BLEND_ROW]) -> (fp32 [B,3,oh,ow], int64
+        [B,H,W]); out_hw=None keeps (H, W).  Rows of NBHD_ROW floats go through pseg_augment_batch_nbhd, rows of WARP_ROW floats
+        through pseg_augment_batch_warp, rows of BLEND_ROW floats through pseg_augment_batch_blend; when they already live on the device, shapes (row_shapes() of the table) has to come with
         them."""
         from .. import ops
         assert ROW == ops.AUGMENT_ROW and NBHD_ROW == ops.AUGMENT_NBHD_ROW and WARP_ROW == ops.AUGMENT_WARP_ROW
+        assert BLEND_ROW == ops.AUGMENT_BLEND_ROW
         B, _, H, W = imgs.shape
         if not torch.is_tensor(params):
             params = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32))
-        wide = params.shape[1] in (NBHD_ROW, WARP_ROW)
+        wide = params.shape[1] in (NBHD_ROW, WARP_ROW, BLEND_ROW)
         if wide and shapes is None:
             if params.is_cuda:
-                raise ValueError('a device table of NBHD_ROW or WARP_ROW floats needs shapes=row_shapes(table) from the host')
+                raise ValueError('a device table of NBHD_ROW, WARP_ROW or BLEND_ROW floats needs shapes=row_shapes(table) from the host')
             shapes = row_shapes(params.numpy())
         if not params.is_cuda:
             # one pinned, non-blocking copy per batch (the pinned block stays alive until the copy ran: the caching
@@ -577,7 +789,7 @@ class DeviceAugment:
         oh, ow = (H, W) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
         if wide:
             shapes = torch.as_tensor(shapes, dtype=torch.int32).contiguous()
-            kernel = ops.augment_batch_warp if params.shape[1] == WARP_ROW else ops.augment_batch_nbhd
+            kernel = {WARP_ROW: ops.augment_batch_warp, BLEND_ROW: ops.augment_batch_blend}.get(params.shape[1], ops.augment_batch_nbhd)
             return kernel(imgs.contiguous(), segs.contiguous(), params.contiguous(), shapes, oh, ow, self.mean, self.std)
         return ops.augment_batch(imgs.contiguous(), segs.contiguous(), params.contiguous(), oh, ow, self.mean, self.std)
 

@@ -9,8 +9,9 @@ reference's mean/std normalisation (utils/datasets.py:199-205) and turns masks i
 
 ``augments=DeviceAugment(...)`` (utils/augment.py) turns ``post_fetch_fn`` into one augmenting kernel over the uint8 batch:
 the geometric (affine, and with ``DeviceAugment.warps()`` elastic, piecewise-affine and perspective), colour-affine, filter,
-noise and dropout part of the reference's imgaug pipeline: 13 of the 16 slots of its ``SomeOf`` block (SURVEY.md section 2,
-#9: partly built).
+noise and dropout part of the reference's imgaug pipeline and, with ``DeviceAugment.blends()``, its median blur, edge-detect
+and frequency-noise blends and hue / saturation shift: 15 of the 16 slots of its ``SomeOf`` block (SURVEY.md section 2,
+#9: partly built; Superpixels is the one left).
 
 Out of scope: the rest of the imgaug pipeline, the random instance crop of CocoInstance and
 the --rect letterboxing; images are decoded with PIL and resized directly.

@@ -17,6 +17,12 @@ and the warp kernel (ops.augment_batch_warp: elastic jitter, displacement grid, 
   * `warp ..., fields off`: the same rows with h2 = (0, 0, 1), no jitter, no grid (the output is the nbhd kernel's);
   * `warp ..., all three on`: the same rows with a mild perspective, a grid of N(0, 0.05) of the size and alpha = 3.5 on
     every sample.
+and the blend kernel (ops.augment_batch_blend: median, edge and colour blends, hue / saturation) on the first batch of
+DeviceAugment.blends(seed=0), tables on the device:
+  * `blend batch: warp kernel (baseline)`: the batch's rows without the four new stages, through ops.augment_batch_warp;
+  * `blend kernel, fields off`: the same rows through the blend kernel (the output is the warp kernel's);
+  * `blend kernel, median k=11` / `edge blend` / `colour blend` / `hue / saturation`: one new stage on every sample;
+  * `blend kernel, all on`: the four together; each with its ratio to the baseline of the same loop.
 Each figure is the median over --iters (>= 50) single calls, each between its own pair of events, after warm-up; the
 variants alternate inside one loop so that they see the same machine.  Algorithmic bytes = every input byte once + the fp32
 output + the int64 targets; fractions of the roof are over 6.3 TB/s HBM.
@@ -136,6 +142,57 @@ def nbhd_rows_for(B, H, W, iters):
     return out
 
 
+def blend_rows_for(B, H, W, iters):
+    """the blend kernel (ops.augment_batch_blend) on the first batch of DeviceAugment.blends(seed=0): the batch's own warp rows
+    through pseg_augment_batch_warp (the baseline: that kernel is the parent commit's), then the same rows through the blend
+    kernel with the new fields off, with each of the four on alone on every sample (the median at k = 11), and with all on"""
+    import numpy as np
+    from pytorch_segmentation_amd.utils import augment as aug
+    g = torch.Generator().manual_seed(B * H)
+    imgs = torch.randint(0, 256, (B, 3, H, W), dtype=torch.uint8, generator=g).cuda()
+    segs = torch.randint(0, 21, (B, H, W), dtype=torch.uint8, generator=g).cuda()
+    recipes = DeviceAugment.blends(seed=0).draw(B)
+    plain = [dict({k: v for k, v in r.items() if k not in aug._BLEND_KEYS + ('edge_mask',)},
+                  colour=[('multiply', v[0]) if n == 'blend' else (n, v) for n, v in r['colour']]) for r in recipes]
+    base = DeviceAugment.rows(plain, H, W)
+    if base.shape[1] == aug.ROW:
+        base = np.stack([aug.make_nbhd_row(r) for r in base])
+    if base.shape[1] == aug.NBHD_ROW:
+        base = np.stack([aug.make_warp_row(r) for r in base])
+    rng = np.random.default_rng(0)
+    t1, t2 = aug.value_noise_table(rng), aug.frequency_noise_table(rng)
+    mb = aug.colour_matrix([('contrast', np.full(3, 1.5))])
+
+    def second(row):                                        # G = E * F of the sample's own F
+        K = int(row[aug.NBHD_K])
+        F = row[aug.NBHD_WEIGHTS:aug.NBHD_WEIGHTS + K * K].astype(np.float64).reshape(K, K) if K > 1 else np.ones((1, 1))
+        return aug.compose_filters([F, aug.edge_kernel(0.75)])
+    on = {'median k=11': lambda r: dict(kmed=11), 'edge blend': lambda r: dict(kernel2=second(r), t1=t1),
+          'colour blend': lambda r: dict(colour2=mb, t2=t2), 'hue / saturation': lambda r: dict(hue_sat=aug.hue_sat_shift(20))}
+    tables = {'blend batch: warp kernel (baseline)': base, 'blend kernel, fields off': np.stack([aug.make_blend_row(r) for r in base])}
+    for name, kw in on.items():
+        tables['blend kernel, %s' % name] = np.stack([aug.make_blend_row(r, **kw(r)) for r in base])
+    tables['blend kernel, all on'] = np.stack([aug.make_blend_row(r, **{k: v for kw in on.values() for k, v in kw(r).items()}) for r in base])
+    fns = {}
+    for name, t in tables.items():
+        dev, shapes = torch.from_numpy(t).cuda(), torch.from_numpy(aug.row_shapes(t))
+        kernel = ops.augment_batch_blend if t.shape[1] == aug.BLEND_ROW else ops.augment_batch_warp
+        fns[name] = lambda kernel=kernel, dev=dev, shapes=shapes: kernel(imgs, segs, dev, shapes, H, W, MEAN, STD)
+    a, b = fns['blend batch: warp kernel (baseline)'](), fns['blend kernel, fields off']()
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), 'rows without blend fields must reproduce augment_batch_warp'
+    ms = timed_median(fns, iters)
+    ref = ms['blend batch: warp kernel (baseline)']
+    out = []
+    for k, v in ms.items():
+        r = {'name': k, 'B': B, 'in': [H, W], 'out': [H, W], 'median_ms': round(v, 4), 'iters': iters, 'section': 'blend',
+             'ratio_to_warp': round(v / ref, 3)}
+        if k.endswith('(baseline)'):
+            r['K'] = aug.row_shapes(base)[:, 0].tolist()
+        print(json.dumps(r), flush=True)
+        out.append(r)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='')
@@ -147,6 +204,7 @@ def main():
     rows = rows_for(16, 512, 512, None, opt.iters) + rows_for(8, 256, 256, None, opt.iters)
     rows += rows_for(16, 512, 512, (384, 384), opt.iters)          # one multi-scale size: the torch path adds its interpolate
     rows += nbhd_rows_for(16, 512, 512, opt.iters)
+    rows += blend_rows_for(16, 512, 512, opt.iters)
     if opt.out:
         with open(opt.out, 'w') as f:
             json.dump(rows, f, indent=1)

@@ -3,7 +3,8 @@
 on the MI355X HIP path.
 
     python3 train.py data/<custom> [--epochs N] [-s W H] [-bs N] [-a ACC] [--lr LR] [--adam] [--resume]
-                     [--weights F] [--notest] [--nosave] [--model unet|deeplabv3plus] [--augment | --augment-full | --augment-warps]
+                     [--weights F] [--notest] [--nosave] [--model unet|deeplabv3plus] [--augment | --augment-full | --augment-warps |
+                     --augment-blends]
                      [--loss ce|lovasz|ce+lovasz|tversky|ce+tversky|ce+surface|tversky+surface|ce+tversky+surface]
                      [--class-weights W0 W1 ...] [--label-smoothing E] [--focal-gamma G] [--ohem-keep R]
                      [--tversky-alpha A] [--tversky-beta B] [--tversky-smooth S] [--tversky-power P] [--tversky-per-image]
@@ -78,7 +79,7 @@ def train(data_dir, epochs=100, img_size=(320, 320), batch_size=32, accumulate=2
           model_name='unet', augment=False):
     # --augment: the training batches (never the validation ones) go through the on-device augmentation kernel; True =
     # the reference's values, or a DeviceAugment of the caller's own (seeded, other ranges; --augment-full: DeviceAugment.full(),
-    # --augment-warps: DeviceAugment.warps())
+    # --augment-warps: DeviceAugment.warps(), --augment-blends: DeviceAugment.blends())
     if augment and not isinstance(augment, DeviceAugment):
         augment = DeviceAugment.reference()
     train_data = CocoInstance(osp.join(data_dir, 'train.json'), img_size=list(img_size), multi_scale=multi_scale,
@@ -147,6 +148,9 @@ def build_parser():
     ap.add_argument('--augment-warps', action='store_true',
                     help='--augment-full plus elastic, piecewise-affine and perspective warps of images and labels: '
                          'DeviceAugment.warps()')
+    ap.add_argument('--augment-blends', action='store_true',
+                    help='--augment-warps plus the median blur, the edge-detect and frequency-noise blends and hue / saturation: '
+                         'DeviceAugment.blends()')
     ap.add_argument('--loss', choices=['ce', 'lovasz', 'ce+lovasz', 'tversky', 'ce+tversky', 'ce+surface', 'tversky+surface',
                                        'ce+tversky+surface'], default='ce',
                     help='training objective: per-pixel cross-entropy, the Lovasz-softmax surrogate of the mean IoU '
@@ -294,7 +298,7 @@ def main():
     print(opt)
     train(opt.data, opt.epochs, opt.img_size, opt.batch_size, opt.accumulate, opt.lr, opt.adam, opt.resume, opt.weights,
           opt.num_workers, opt.multi_scale, opt.rect, opt.mix_precision, opt.notest, opt.nosave, opt.model,
-          DeviceAugment.warps() if opt.augment_warps else DeviceAugment.full() if opt.augment_full else opt.augment)
+          DeviceAugment.blends() if opt.augment_blends else DeviceAugment.warps() if opt.augment_warps else DeviceAugment.full() if opt.augment_full else opt.augment)
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()
 
